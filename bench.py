@@ -14,13 +14,18 @@ waits.  Inputs are resident in HBM before the timed region starts.
     python bench.py --gpus N --steps K --warmup W          (no launcher: spawns its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full   (every leg below as well)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
 
 `value` is the time from calling generate_report() to holding the flagged-straggler set: every timed step keeps its
 Report and calls identify_stragglers() on it (rank 0), which waits for and copies the scores / flags out of the result
 block; `report_read` adds what building the six dict mappings of that report costs on the host, and
 `us_per_report_fully_read` is the sum (the reference's generate_report returns populated dicts, reporting.py:535-545).
 
-Prints ONE JSON line on rank 0 (see the driver contract); extra objects:
+A plain run sets up, warms up, times the K steps and prints the headline fields of the line; `--dump-outputs DIR` writes
+what the last timed step returned (see _dump_outputs).  Everything else below runs only with `--full`.
+
+Prints ONE JSON line on rank 0 (see the driver contract); extra objects (--full):
   roofline     -- the statistics kernel (k_row_stats) against the HBM roofline: algorithmic bytes =
                   local_ranks * 64 * 10000 * 4 per launch, duration from hipEvent pairs recorded
                   around every launch on the launch stream during a second, instrumented pass of the
@@ -973,6 +978,40 @@ def _routes_table(world: int, rank: int, steps: int, warmup: int, headline_route
     return table, clean
 
 
+def _dump_outputs(out_dir: str, rep, found, section_names, total_ranks: int = TOTAL_RANKS) -> list:
+    """``--dump-outputs DIR``: what a caller of the timed step holds after the last one -- the Report's score mappings and its
+    local section statistics (float64, the exact values of the f32 results) and the flagged sets identify_stragglers()
+    returned (float32 0/1 tables) -- as DIR/<name>.npy, rows in section order, columns in rank order.  A GPU score mapping is
+    written only when it holds a finite score: the benchmark's job times no GPU work, so both are NaN for every rank by
+    construction and carry no result (their flagged sets, always empty then, are written).  A few KB in all; the inputs are
+    seeded (synth.stress_samples), so two builds can be compared file by file."""
+    from nvrx_straggler import Statistic
+
+    os.makedirs(out_dir, exist_ok=True)
+    ranks = range(total_ranks)
+    arrays = {}
+    for field in ("gpu_relative_perf_scores", "gpu_individual_perf_scores"):
+        m = getattr(rep, field)
+        scores = np.array([m.get(r, np.nan) for r in ranks], dtype=np.float64)
+        if np.isfinite(scores).any():
+            arrays[field] = scores
+    for field in ("section_relative_perf_scores", "section_individual_perf_scores"):
+        m = getattr(rep, field)
+        arrays[field] = np.array([[m.get(n, {}).get(r, np.nan) for r in ranks] for n in section_names], dtype=np.float64)
+    summ = rep.local_section_summaries
+    arrays["local_section_summaries"] = np.array([[summ[n][s] if n in summ else np.nan for s in Statistic] for n in section_names],
+                                                 dtype=np.float64)
+    for key in ("straggler_gpus_relative", "straggler_gpus_individual"):
+        flagged = {s.rank for s in found[key]}
+        arrays[key] = np.array([r in flagged for r in ranks], dtype=np.float32)
+    for key in ("straggler_sections_relative", "straggler_sections_individual"):
+        flagged = {n: {s.rank for s in v} for n, v in found[key].items()}
+        arrays[key] = np.array([[r in flagged.get(n, ()) for r in ranks] for n in section_names], dtype=np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 _SIDECAR_SRC = r"""
 import sys, signal
 for s in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
@@ -1044,6 +1083,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="also run every leg besides the headline (roofline, report read, exchange "
+                    "and routes, cold / N=8-shape / Detector legs, host inputs, cadence, per-kernel mode, per-step overhead, CPU "
+                    "baseline); the --no-* options below pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--cpu-reps", type=int, default=60)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="process-group backend for N > 1 (nccl = RCCL; gloo lets the N > 1 flow "
@@ -1063,6 +1106,8 @@ def main():
     args = ap.parse_args()
     if args.child in ("kernels_mode", "stamp_mode"):
         return _kernels_mode_child(args.child.split("_")[0])
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         if TOTAL_RANKS % args.gpus:
@@ -1162,10 +1207,12 @@ def main():
     call_us_median = float(np.median(call_ns[: args.steps])) / 1e3
     if rank == 0:
         check_flagged(found)  # the last timed report
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, rep, found, job.section_names)
 
     # what READING the rest of a report costs on the host (rank 0): the six dict mappings, built on first access
     report_read = None
-    if rank == 0:
+    if args.full and rank == 0:
         t_ident, t_maps = [], []
         for _ in range(min(args.steps, 50)):
             job.rearm(SAMPLES)
@@ -1201,31 +1248,33 @@ def main():
                                "statistics; not part of `value`).  all_six_mappings_us: the caller has dropped the previous "
                                "report, as a training loop does -- its dicts are refilled in place (nvrx_pyread.c, recycling); "
                                "..._previous_report_held_us: it still holds it, every dict is built anew"}
-    elif world > 1:
+    elif args.full and world > 1:
         for _ in range(min(args.steps, 50) + min(args.steps, 30)):  # collective: the other ranks take part in rank 0's reports (both loops)
             job.rearm(SAMPLES)
             job.report()
 
     # instrumented pass: hipEvent pair around every statistics-kernel launch, on its launch stream
-    job.rings.timing_enable(True)
-    sync_all()
-    t1 = time.perf_counter()
+    elapsed_instr = 0.0
     score_wait, score_tail, score_staged = [], [], []
-    for _ in range(args.steps):
-        step()
-        plan = job.reporter._ring_plan
-        if plan is not None:  # the score kernel's own clocks (10 ns ticks of the constant-rate wall clock), see nvrx_score
-            score_wait.append(int(plan.ws.meta[6]))
-            score_tail.append(int(plan.ws.meta[7]) & 0xFFFF)
-            score_staged.append(int(plan.ws.meta[7]) >> 16)
-    sync_all()
-    elapsed_instr = time.perf_counter() - t1
-    kern_total_us, kern_launches = job.rings.timing_read(reset=True)
-    job.rings.timing_enable(False)
+    if args.full:
+        job.rings.timing_enable(True)
+        sync_all()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+            plan = job.reporter._ring_plan
+            if plan is not None:  # the score kernel's own clocks (10 ns ticks of the constant-rate wall clock), see nvrx_score
+                score_wait.append(int(plan.ws.meta[6]))
+                score_tail.append(int(plan.ws.meta[7]) & 0xFFFF)
+                score_staged.append(int(plan.ws.meta[7]) >> 16)
+        sync_all()
+        elapsed_instr = time.perf_counter() - t1
+        kern_total_us, kern_launches = job.rings.timing_read(reset=True)
+        job.rings.timing_enable(False)
 
     # the report's one collective on its own (N > 1): enqueue on the detector's stream, wait for that stream
     exchange = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             ws = job.reporter._ring_plan.ws
             for _ in range(10):
@@ -1290,7 +1339,7 @@ def main():
     cold = None
     n8 = None
     detector_leg = section_entry = None
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         sweep = torch.zeros(1 << 28, dtype=torch.float32, device="cuda")
         cold_us, cold_n = _kernel_leg(job, min(args.steps, 30), SAMPLES, cold=True, sweep=sweep)
         del sweep
@@ -1302,7 +1351,7 @@ def main():
         section_entry = _side_leg(_section_entry_leg)
 
     host_inputs = None
-    if world == 1 and not args.no_host_inputs:
+    if args.full and world == 1 and not args.no_host_inputs:
         try:
             host = [synth.stress_samples(r, SECTIONS, SAMPLES, slow_rank=3, slow_factor=1.5) for r in job.logical_ranks()]
             t_host = []
@@ -1322,18 +1371,18 @@ def main():
             host_inputs = {"error": f"{type(e).__name__}: {str(e)[-300:]}"}
 
     cadence = None
-    if world == 1 and not args.no_cadence:
+    if args.full and world == 1 and not args.no_cadence:
         cadence = {"headline_workload": _side_leg(_cadence_leg, args.cadence_reports, job)}
         job.backend.synchronize()
         cadence.update(_side_leg(_cadence_leg, args.cadence_reports))
 
     per_kernel = None
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         job.backend.synchronize()
         per_kernel = _side_leg(_per_kernel_leg)
 
     kernels_mode = None
-    if world == 1 and not args.no_kernels_mode and not args.no_overhead:
+    if args.full and world == 1 and not args.no_kernels_mode and not args.no_overhead:
         job.backend.synchronize()
         torch.cuda.synchronize()
         kernels_mode = _side_leg(_kernels_mode_leg)
@@ -1344,7 +1393,7 @@ def main():
                                                               ("per_step_overhead_kernels", "report_at_cadence_kernels", "error") if k in stamp_twin}
 
     overhead = overhead_async = None
-    if not args.no_overhead:
+    if args.full and not args.no_overhead:
         job.backend.synchronize()
         # (collective at N > 1: every rank runs it and a failure is a failure of the job; at N = 1 it is a side leg)
         if world == 1:
@@ -1359,9 +1408,6 @@ def main():
 
     if rank == 0:
         us_per_report = elapsed / args.steps * 1e6
-        kern_us = kern_total_us / max(kern_launches, 1)
-        alg_bytes = job.local_ranks * SECTIONS * SAMPLES * 4
-        achieved = alg_bytes / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
         out = {
             "metric": "generate_report_latency_us",
             "value": round(us_per_report, 2),
@@ -1399,8 +1445,13 @@ def main():
             # stream even when its work is long done), both divided by K
             "timed_region": {"first_step_us": round(per_step[0] / 1e3, 2), "closing_synchronize_us": round(closing_sync_us, 2),
                              "sum_of_steps_us": round(sum(per_step) / 1e3, 2), "region_us": round(elapsed * 1e6, 2)},
-            "instrumented_ms_per_step": round(elapsed_instr / args.steps * 1e3, 5),
-            "roofline": {
+        }
+        if args.full:
+            kern_us = kern_total_us / max(kern_launches, 1)
+            alg_bytes = job.local_ranks * SECTIONS * SAMPLES * 4
+            achieved = alg_bytes / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
+            out["instrumented_ms_per_step"] = round(elapsed_instr / args.steps * 1e3, 5)
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_row_stats",
                 "achieved": round(achieved, 1),
@@ -1416,8 +1467,7 @@ def main():
                         "stream k_row_stats has no queued neighbour; under rocprofv3 the same launches read ~1 us longer, "
                         "because the profiler's own packets behind every dispatch are queued successors (DESIGN.md 3.5, "
                         "kbench between-launch modes)",
-            },
-        }
+            }
         if score_tail:
             out["score_kernel"] = {
                 "waited_for_rows_us": round(float(np.median(score_wait)) / 100.0, 2),
@@ -1468,7 +1518,7 @@ def main():
             exchange["us_median"] = round(ex_us, 2) if "us_median" in exchange else None
             exchange["note"] = "enqueue + stream wait of one all-gather of the exchange rows, max over ranks; latency-bound"
             out["exchange"] = exchange
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (at N > 1 the other ranks wait at the barrier below meanwhile: the baseline runs on rank 0's host cores)
             out["cpu_baseline"] = _side_leg(_cpu_baseline, args.cpu_reps)
     else:
@@ -1481,7 +1531,7 @@ def main():
 
     printed = threading.Lock()
     sidecar = None
-    if rank == 0 and world > 1 and not args.no_routes:
+    if args.full and rank == 0 and world > 1 and not args.no_routes:
         sidecar = _headline_sidecar(out, job.reporter.exchange_info.get("mode", "c10d"))
 
     def emit(routes=None):
@@ -1505,7 +1555,7 @@ def main():
             print(json.dumps(out), flush=True)
 
     clean = True
-    if world > 1 and not args.no_routes:
+    if args.full and world > 1 and not args.no_routes:
         dist.barrier()  # (rank 0 comes from its CPU baseline: the legs' deadlines start together)
         headline_mode = job.reporter.exchange_info.get("mode", "c10d") if job.reporter._direct is None else job.reporter.exchange_info.get("mode", "rccl")
         routes, clean = _routes_table(world, rank, min(args.steps, 100), min(args.warmup, 10), headline_mode, args.route_timeout, emit)

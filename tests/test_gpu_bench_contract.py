@@ -9,7 +9,9 @@ import sys
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAST = ["--no-cpu-baseline", "--no-overhead", "--no-host-inputs", "--no-extra-legs", "--no-cadence"]
+# the legs these tests read (roofline, report_read, exchange, routes, cpu_baseline, ...) run only under --full; the --no-* flags
+# leave out the slow ones
+FAST = ["--full", "--no-cpu-baseline", "--no-overhead", "--no-host-inputs", "--no-extra-legs", "--no-cadence"]
 
 
 def _run(args, env=None, timeout=240):
@@ -41,6 +43,41 @@ def test_single_gpu_line_has_the_contract_fields_and_the_round3_legs():
     assert d["report_read"]["identify_stragglers_us"] > 0 and d["us_per_report_fully_read"] > d["value"] and 0 < d["us_per_call_median"] < d["us_per_report_median"]
     tr = d["timed_region"]
     assert tr["region_us"] >= tr["sum_of_steps_us"] and abs(tr["region_us"] / 6 - d["value"]) < 0.5
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_alone_and_dumps_what_its_last_step_returned(tmp_path):
+    """Without --full: set-up, warm-up, --steps timed steps, the headline fields; --dump-outputs writes the last timed report's
+    arrays, the same from run to run (the inputs are seeded)."""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        r, lines = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / str(k))])
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-1500:])
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["metric"] == "generate_report_latency_us" and d["unit"] == "us" and d["higher_is_better"] is False and d["dtype"] == "f32"
+    assert d["steps"] == 7 and d["warmup"] == 2 and abs(d["value"] - d["ms_per_step"] * 1e3) < 0.02
+    assert abs(d["timed_region"]["region_us"] / 7 - d["value"]) < 0.5 and d["value"] > 0
+    for k in ("roofline", "instrumented_ms_per_step", "report_read", "report_at_cadence", "per_step_overhead", "host_inputs",
+              "cpu_baseline", "roofline_n8_shape", "detector_report", "per_kernel_mode", "exchange", "routes"):
+        assert k not in d, k
+    names = sorted(os.listdir(tmp_path / "0"))
+    assert names == sorted(os.listdir(tmp_path / "1")) and len(names) == 7, names
+    assert "gpu_relative_perf_scores.npy" not in names     # NaN for every rank by construction: no GPU work is timed
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "0" / n), np.load(tmp_path / "1" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total < 64 << 20
+    rel = np.load(tmp_path / "0" / "section_relative_perf_scores.npy")
+    flagged = np.load(tmp_path / "0" / "straggler_sections_relative.npy")
+    stats = np.load(tmp_path / "0" / "local_section_summaries.npy")
+    assert rel.shape == flagged.shape == (64, 8) and stats.shape == (64, 6)
+    assert np.all(np.abs(rel[:, 3] - 1 / 1.5) < 0.02) and np.all(np.delete(rel, 3, axis=1) > 0.97)
+    assert np.all(flagged[:, 3] == 1) and flagged.sum() == 64 and np.all(stats[:, 5] == 10_000)
 
 
 @pytest.mark.gpu
