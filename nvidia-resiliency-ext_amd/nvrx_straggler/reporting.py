@@ -849,8 +849,7 @@ class ReportGenerator:
         # that ``name_mapper`` is untouched, as the reference guarantees
         self._private_mapper = NameMapper(pg=pg)
         self.rank_to_node: Dict[int, str] = collections.defaultdict(lambda: "<unk>")
-        self._ring_gid_state = None
-        self._ring_plan = None
+        self._rank_to_node_folded = False  # rank_to_node already names every LOGICAL rank of a folded job (local_ranks > 1)
         # the per-report all-gather straight into RCCL on our own stream (rccl_direct.py); created
         # collectively on the first multi-rank report, None = stay on torch.distributed
         self._direct = None
@@ -858,13 +857,16 @@ class ReportGenerator:
         # asynchronous reports (ring path only): generate_report_from_rings enqueues the report and returns a Report
         # that waits for the device on first read; the block in flight is settled before the next report starts
         self.asynchronous = bool(asynchronous)
-        self._inflight: Optional[_PendingBlock] = None
         self.exchange_info: Dict[str, Any] = {}
-        self._unreported_rows: list = []  # see take_unreported_rows
+        # ---- when ranks sync names and which collectives a ring report issues (transition table: DESIGN.md section 4).  Written
+        # by this class alone; Detector's lane reads them, and mirrors two writes on its hot path (straggler._Lane.run) ----
+        self._ring_plan = None        # the cached steady-state plan (_RingPlan); None: the next ring report takes the general path
+        self._ring_gid_state = None   # (mapper, version, rows, workspace) the GENERAL path last pointed the ring rows at; None: stale
+        self._inflight: Optional[_PendingBlock] = None  # the asynchronous report that was enqueued and nobody has seen complete
         self._prev_async_settled = True  # no asynchronous report of this generator is unaccounted for (see _settle_inflight)
-        self._resync_pending = False  # the next ring report starts with the name sync (see Detector's lane)
-        self._ring_reports = 0        # ring reports of this generator so far (collective: the same on every rank)
-        self._may_defer_sync = False  # inside a ring report that is not the first (see _score_round)
+        self._resync_pending = False  # some rank's table said "ids missing": no plan, no lane; the general path syncs names first
+        self._had_ring_report = False  # a ring report has reached its score round (collective: the same on every rank)
+        self._unreported_rows: list = []  # see take_unreported_rows
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
     # ---- pieces kept from the reference's host logic ----------------------------------------------
@@ -996,18 +998,21 @@ class ReportGenerator:
             self._direct = None
 
     def _score_round(self, kernel_names: List[str], section_names: List[str], fill_send, local_ranks: int = 1,
-                     stats_rows: int = 0, stats_rows_used: Optional[int] = None, resync_first: bool = False):
+                     stats_rows: int = 0, stats_rows_used: Optional[int] = None, sync_first: bool = False,
+                     may_defer_sync: bool = False):
         """pack -> all-gather -> score, repeated once after a name sync if any rank met a new name.
 
         ``fill_send(ws, mapper, names_ok)`` must leave this rank's exchange rows in ``ws.send``.
+        ``sync_first``: an earlier exchange already showed "ids missing" (``_take_resync``).  ``may_defer_sync``: a ring report
+        that is not the generator's first -- one that meets ANOTHER rank's "ids missing" may have to leave the sync to the next.
         Returns ``(workspace, mapper)`` with the results in ``ws.scores / flags / meta / stats``.
         """
         be = _backend_mod.get_backend()
         exchanged = self._exchanged()
         mapper = self.name_mapper if exchanged else self._private_mapper
-        if resync_first and exchanged and self.world_size > 1:
-            # the planned path already ran this report's first exchange and saw an incomplete flag:
-            # every rank is now heading for the name sync, so join it before exchanging rows again.
+        if sync_first and exchanged and self.world_size > 1:
+            # an exchange of this generator (the planned path's or the lane's, in this report or an asynchronous one before
+            # it) carried an incomplete flag: every rank is now heading for the name sync, so join it before exchanging rows again.
             # (Only where rows ARE exchanged: a generator that scores this rank alone -- individual scores, no gather -- has
             # nobody heading anywhere; its own new names get their ids in the loop below.  An asynchronous generator of that
             # kind used to call the collective here, alone, the report after one of ITS sections first appeared: the rank hung
@@ -1016,11 +1021,7 @@ class ReportGenerator:
         while True:
             names_ok = mapper.has_all_names(kernel_names, section_names)
             if not names_ok and (not exchanged or self.world_size == 1):
-                # nobody to agree with: extend the tables locally (same order as a 1-rank gather)
-                for s in section_names:
-                    mapper._assign_section_id(s)
-                for k in kernel_names:
-                    mapper._assign_kernel_id(k)
+                self._assign_ids_locally(mapper, kernel_names, section_names)
                 names_ok = True
             K, S = mapper.kernel_counter, mapper.section_counter
             world = self.world_size if exchanged else 1
@@ -1038,7 +1039,7 @@ class ReportGenerator:
                 self._check_exchange()
             if ws.meta[0] == 1:
                 return ws, mapper
-            if names_ok and world > 1 and self._may_defer_sync and self.enqueue_only():
+            if names_ok and world > 1 and may_defer_sync and self.enqueue_only():
                 # Asynchronous reports on an in-stream route, and the names without ids are ANOTHER rank's: that rank only
                 # enqueued this report (on its old tables, the flag in its row) and joins the name sync at the START of its next
                 # report, when it settles this one -- it is not waiting inside this report, so neither a sync nor a second
@@ -1047,7 +1048,8 @@ class ReportGenerator:
                 # time.  (It used to sync alone and exchange again: from then on its exchanges were paired with its peers'
                 # NEXT ones, the last one with nobody -- tools/soak_mp.py, profiles/r06af_soak_mp.txt.)
                 # (Not in a generator's FIRST ring report: no rank has a plan then, whoever flags is inside this report too.)
-                self._resync_pending = True
+                # (The caller still ends by caching a plan for its new tables; the pending resync keeps it from ever running.)
+                self._sync_names_first()
                 return ws, mapper
             # some rank (maybe this one) has names without ids: cold path, then go again
             mapper.sync_names(kernel_names, section_names)
@@ -1058,26 +1060,10 @@ class ReportGenerator:
         """Report of the general (name-syncing / dict-input) path.  ``section_summaries`` / ``kernel_summaries``
         are either the caller's dicts (handed on as they are, reporting.py:541-542) or name -> ring row
         tables to be resolved against ``stats``."""
-        S = ws.S
-        if self.gather_on_rank0:
-            if self.rank != 0:
-                return None
-            lo, hi = 0, ws.R
-            ranks = range(ws.R)
-            names = [mapper.get_section_name(i) for i in range(S)]
-            cols = {n: i for i, n in enumerate(names)}
-        else:
-            lo = self.rank * local_ranks if self._exchanged() else 0
-            hi = lo + local_ranks
-            ranks = range(self.rank * local_ranks, (self.rank + 1) * local_ranks)
-            names = list(local_section_names)
-            cols = {n: mapper.get_section_id(n) for n in names}
-        view = _View()
-        view.S, view.ranks, view.names, view.cols = S, ranks, names, cols
-        view.has_rel, view.has_indiv = self.is_computing_rel_scores, self.is_computing_indiv_scores
-        view.section_rows = section_summaries if stats is not None else None
-        view.kernel_rows = kernel_summaries if stats is not None else None
-        view.layout, view.thresholds = None, self.thresholds
+        if self.gather_on_rank0 and self.rank != 0:
+            return None
+        rows = (section_summaries, kernel_summaries) if stats is not None else (None, None)
+        view, lo, hi = self._view(ws, mapper, local_section_names, local_ranks, *rows)
         src = _ScoreSource(view)
         src.scores = ws.scores[lo:hi].copy()
         src.flags = ws.flags[lo:hi].copy()
@@ -1090,12 +1076,63 @@ class ReportGenerator:
             report.__dict__["local_kernel_summaries"] = kernel_summaries
         return report
 
+    def _view(self, ws, mapper, local_section_names: Sequence[str], local_ranks: int, section_rows, kernel_rows,
+              stats_needed: Optional[int] = None):
+        """What a report shows of the table in ``ws``: rank 0 of a gathering generator sees every rank's rows and every section
+        that has an id, any other generator its own rows and its own sections.  Returns ``(view, first row, end row)``.
+        ``stats_needed`` (a plan's reports, read lazily from the result block): also where those rows sit in the block."""
+        if self.gather_on_rank0:
+            lo, hi = 0, ws.R
+            ranks = range(ws.R)
+            names = [mapper.get_section_name(i) for i in range(ws.S)]
+        else:
+            lo = self.rank * local_ranks if self._exchanged() else 0
+            hi = lo + local_ranks
+            ranks = range(self.rank * local_ranks, (self.rank + 1) * local_ranks)
+            names = list(local_section_names)
+        v = _View()
+        v.S, v.ranks, v.names, v.cols = ws.S, ranks, names, {n: mapper.get_section_id(n) for n in names}
+        v.has_rel, v.has_indiv = self.is_computing_rel_scores, self.is_computing_indiv_scores
+        v.section_rows, v.kernel_rows = section_rows, kernel_rows
+        v.layout = None if stats_needed is None else (ws._off_scores, ws._off_flags, ws._off_stats, ws.R, ws.W, lo, hi, stats_needed)
+        v.thresholds = self.thresholds
+        return v, lo, hi
+
+    @staticmethod
+    def _assign_ids_locally(mapper, kernel_names, section_names) -> None:
+        """Nobody to agree with (one rank, or a generator that exchanges nothing): extend the tables locally, in the order a
+        1-rank name sync would."""
+        for s in section_names:
+            mapper._assign_section_id(s)
+        for k in kernel_names:
+            mapper._assign_kernel_id(k)
+
+    @staticmethod
+    def _point_ring_rows(rings, mapper, ws) -> None:
+        """Point every ring row at its slot of the exchange row (cold: ids or workspace changed)."""
+        for name, row in rings.kernel_row_names.items():
+            g = mapper.kernel_name_to_id.get(name, -1) if not is_collective_kernel(name) else -1
+            rings.configure(row, 1, g)
+        for name, row in rings.section_row_names.items():
+            g = mapper.section_name_to_id.get(name)
+            rings.configure(row, 0, ws.K + g if g is not None else -1)
+        ws.send_initialised = False
+
     # ---- steady-state plan of the ring path ---------------------------------------------------------
     class _RingPlan:
         """Everything about a ring report that only changes when names, ids or topology change."""
 
-        __slots__ = ("key", "ws", "mapper", "snames", "knames", "names", "cols", "ranks", "row_lo", "row_hi",
-                     "rows_used", "stats_needed", "section_rows", "kernel_rows", "fused", "view")
+        __slots__ = ("key", "topology", "ws", "mapper", "rows_used", "stats_needed", "section_rows", "kernel_rows", "fused", "view")
+
+    def _plan_key(self, rings, section_rows, kernel_rows, local_ranks):
+        """A cached plan serves a report whose key equals the plan's: same name tables (the caller hands the same dicts while
+        the occupied rows stay the same), same ids, same topology."""
+        return (id(section_rows), len(section_rows), id(kernel_rows), len(kernel_rows), self.name_mapper.version,
+                self._private_mapper.version, self.world_size, self.rank, rings.rows_used, local_ranks, id(rings))
+
+    def _plan_topology(self, rings, local_ranks):
+        """What names and ids have no say in (cold; kept on the plan: the asynchronous "new name" branch asks whether it still holds)."""
+        return (self.world_size, self.rank, local_ranks, id(rings))
 
     def _build_ring_plan(self, key, rings, section_rows, kernel_rows, local_ranks):
         be = _backend_mod.get_backend()
@@ -1105,50 +1142,33 @@ class ReportGenerator:
         if not mapper.has_all_names(knames, snames):
             if exchanged and self.world_size > 1:
                 return None  # ids must be agreed with the other ranks first: general path
-            for s in snames:
-                mapper._assign_section_id(s)
-            for k in knames:
-                mapper._assign_kernel_id(k)
+            self._assign_ids_locally(mapper, knames, snames)
         K, S = mapper.kernel_counter, mapper.section_counter
         world = self.world_size if exchanged else 1
         total_rows = rings.local_ranks * rings.rows_per_rank
         plan = self._RingPlan()
         plan.key = key
+        plan.topology = self._plan_topology(rings, local_ranks)
         plan.mapper = mapper
         plan.ws = be.workspace(world * local_ranks, K, S, local_ranks, total_rows)
-        plan.snames, plan.knames = snames, knames
         plan.rows_used = rings.rows_used
         # the report's local summaries are those of this process' FIRST logical rank (rank 0 of a folded job): its rows are
         # the first rows_used statistics rows, whatever the number of logical ranks -- nothing else is forwarded or copied
         plan.stats_needed = rings.rows_used
         plan.section_rows, plan.kernel_rows = section_rows, kernel_rows
         plan.fused = hasattr(rings, "report_fused")  # the HIP engine; the CPU test backend takes the stepwise route
-        if self.gather_on_rank0:
-            plan.ranks = range(plan.ws.R)
-            plan.names = [mapper.get_section_name(i) for i in range(S)]
-            plan.row_lo, plan.row_hi = 0, plan.ws.R
-        else:
-            me = self.rank * local_ranks if exchanged else 0
-            plan.ranks = range(self.rank * local_ranks, (self.rank + 1) * local_ranks)
-            plan.names = snames
-            plan.row_lo, plan.row_hi = me, me + local_ranks
-        plan.cols = {n: mapper.get_section_id(n) for n in plan.names}
-        # point every ring row at its slot of the exchange row (cold)
-        for name, row in rings.kernel_row_names.items():
-            g = mapper.kernel_name_to_id.get(name, -1) if not is_collective_kernel(name) else -1
-            rings.configure(row, 1, g)
-        for name, row in rings.section_row_names.items():
-            g = mapper.section_name_to_id.get(name)
-            rings.configure(row, 0, K + g if g is not None else -1)
-        plan.ws.send_initialised = False
-        plan.view = self._view_of(plan)
+        self._point_ring_rows(rings, mapper, plan.ws)
+        # the part of a report that every report of the plan shares (built once per plan)
+        plan.view = self._view(plan.ws, mapper, snames, local_ranks, section_rows, kernel_rows, plan.stats_needed)[0]
         self._ring_gid_state = None  # the general path must re-derive its own view if it runs next
         return plan
 
+    # ---- name-sync and in-flight state: every transition of DESIGN.md section 4's table, once -------------
     def _settle_inflight(self) -> bool:
         """Wait for the asynchronous report still in flight (if any) before its workspace is touched again.
         Returns True when that report's exchange showed a rank with names that have no id yet: every rank sees the
-        same table, so every rank learns it here, at the same point of the program, and goes through the name sync."""
+        same table, so every rank learns it here, at the same point of the program, and goes through the name sync
+        (the caller says so with ``_sync_names_first``; the dict-input path checks names in its score round anyway)."""
         pend = self._inflight
         if pend is None:
             return False
@@ -1158,21 +1178,26 @@ class ReportGenerator:
         self._check_exchange()
         return names_word != 1
 
+    def _drop_plan(self) -> None:
+        """The cached plan never runs again (a planned or lane report raised: e.g. a timed-out wait retired its workspace)."""
+        self._ring_plan = None
+
+    def _sync_names_first(self) -> None:
+        """Some rank's table said "ids missing": every rank is heading for the name sync, at the start of its next pass
+        through the general path -- in this very ``generate_report_from_rings`` call when a settled or synchronous report
+        showed it.  Until then neither a cached plan nor Detector's lane runs."""
+        self._ring_plan = None
+        self._resync_pending = True
+
+    def _take_resync(self) -> bool:
+        """The general path of a ring report, about to enter its score round: whether that starts with the name sync."""
+        pending, self._resync_pending = self._resync_pending, False
+        return pending
+
     def _check_exchange(self) -> None:
         check = getattr(self._direct, "check", None)  # the peer-window route reports peers that never arrived
         if check is not None:
             check()
-
-    def _view_of(self, plan) -> _View:
-        """The part of a report that every report of ``plan`` shares (built once per plan)."""
-        ws = plan.ws
-        v = _View()
-        v.S, v.ranks, v.names, v.cols = ws.S, plan.ranks, plan.names, plan.cols
-        v.has_rel, v.has_indiv = self.is_computing_rel_scores, self.is_computing_indiv_scores
-        v.section_rows, v.kernel_rows = plan.section_rows, plan.kernel_rows
-        v.layout = (ws._off_scores, ws._off_flags, ws._off_stats, ws.R, ws.W, plan.row_lo, plan.row_hi, plan.stats_needed)
-        v.thresholds = self.thresholds
-        return v
 
     def _report_from_plan(self, plan, rings, t0, order_after=None, names_ok: bool = True):
         """The steady-state report: ONE C call (statistics kernel, the collective, score kernel, wait), one host
@@ -1191,6 +1216,7 @@ class ReportGenerator:
                                                    and os.environ.get("NVRX_DEBUG_RESIDENT_SHARED_OK", "0") in ("", "0")),
                                      prev_settled=self._prev_async_settled)
             if not wait:
+                # the report is only enqueued (the lane's hot path mirrors these two writes: straggler._Lane.run)
                 self._prev_async_settled = False  # until somebody has seen THIS report complete
                 pend = self._inflight = _PendingBlock(be, ws, seq)
                 if self.gather_on_rank0 and self.rank != 0:
@@ -1199,14 +1225,10 @@ class ReportGenerator:
                     _ScoreSource(plan.view, pend),
                     self._shared_rank_to_node(),
                     (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
-        elif multi:
-            rings.report_local(ws, True, rows_active=plan.rows_used)
-            table = self._exchange(be, ws)
-            be.score(ws, table, self.is_computing_indiv_scores, self.is_computing_rel_scores, self.thresholds,
-                     wait=True, stats_rows=plan.stats_needed)
         else:
             rings.report_local(ws, True, rows_active=plan.rows_used)
-            be.score(ws, ws.send, self.is_computing_indiv_scores, self.is_computing_rel_scores, self.thresholds,
+            table = self._exchange(be, ws) if multi else ws.send
+            be.score(ws, table, self.is_computing_indiv_scores, self.is_computing_rel_scores, self.thresholds,
                      wait=True, stats_rows=plan.stats_needed)
         if fused:
             # a resident score kernel forwards the statistics rows AFTER the scores: whatever this call returns or
@@ -1246,7 +1268,7 @@ class ReportGenerator:
         self.world_size = dist_utils.get_world_size(self.group)
         self.rank = dist_utils.get_rank(self.group)
         if self._inflight is not None:
-            self._settle_inflight()
+            self._settle_inflight()  # ("ids missing" in that report's table is not acted on: the score round below checks names anyway)
         if not self._direct_tried:
             self._maybe_create_direct_exchange()
         kernel_summaries = self._filter_out_nccl_kernels(kernel_summaries)
@@ -1292,32 +1314,27 @@ class ReportGenerator:
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
-        if not self._direct_tried:
+        if not self._direct_tried and self.world_size != 1:  # (a single process has no route to build)
             self._maybe_create_direct_exchange()
-        # steady state: same name tables as last time -> run the cached plan
-        key = (id(section_rows), len(section_rows), id(kernel_rows), len(kernel_rows), self.name_mapper.version,
-               self._private_mapper.version, self.world_size, self.rank, rings.rows_used, local_ranks, id(rings))
-        first_ring_report = self._ring_reports == 0
-        self._ring_reports += 1
-        resync_first, self._resync_pending = self._resync_pending, False  # (left by a report that saw an "ids missing" table)
-        if resync_first:
-            self._ring_plan = None  # every rank is heading for the name sync: no cached plan runs before it
-        plan = self._ring_plan
         if self._inflight is not None and self._settle_inflight():
             # the previous (asynchronous) report's exchange carried an "ids missing" flag: every rank is here now
-            self._ring_plan = plan = None
-            resync_first = True
-        if plan is not None and plan.key == key:
+            self._sync_names_first()
+        if self._resync_pending:
+            # every rank is heading for the name sync: no cached plan runs before it -- neither the one dropped when the flag
+            # was seen nor the one that the report which DEFERRED its sync (see _score_round) cached on its way out
+            self._ring_plan = None
+        # steady state: same name tables as last time -> run the cached plan
+        plan = self._ring_plan
+        if plan is not None and plan.key == self._plan_key(rings, section_rows, kernel_rows, local_ranks):
             try:
                 out = self._report_from_plan(plan, rings, t0, order_after)
             except Exception:
-                self._ring_plan = None  # e.g. a timed-out wait retired the plan's workspace: never run it again
+                self._drop_plan()
                 raise
             if out is not False:
                 return out
-            self._ring_plan = None
-            resync_first = True  # some OTHER rank met a new name during this report's exchange
-        elif (plan is not None and self.enqueue_only() and plan.fused and plan.key[6:8] == key[6:8] and plan.key[9:] == key[9:]
+            self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
+        elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
               and not plan.mapper.has_all_names(list(kernel_rows.keys()), list(section_rows.keys()))):
             # asynchronous + a name this rank has no id for: the other ranks will not wait inside this report, so the
             # name exchange cannot happen now.  Run the OLD plan (the new rows are not exchanged yet) with the
@@ -1331,7 +1348,7 @@ class ReportGenerator:
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
         self._maybe_gather_rank_to_node()
-        if local_ranks > 1 and not getattr(self, "_rank_to_node_folded", False):
+        if local_ranks > 1 and not self._rank_to_node_folded:
             # folded runs: every logical rank inherits the node of the process that holds it
             per_proc = dict(self.rank_to_node)
             self.rank_to_node = {p * local_ranks + q: node for p, node in per_proc.items() for q in range(local_ranks)}
@@ -1344,28 +1361,16 @@ class ReportGenerator:
         def fill_send(ws, mapper, names_ok):
             state = (id(mapper), mapper.version, rows_used, id(ws))
             if self._ring_gid_state != state:
-                # ids changed (cold): re-point every ring row at its slot of the exchange row
-                K = ws.K
-                for name, row in rings.kernel_row_names.items():
-                    g = mapper.kernel_name_to_id.get(name, -1) if not is_collective_kernel(name) else -1
-                    rings.configure(row, 1, g)
-                for name, row in rings.section_row_names.items():
-                    g = mapper.section_name_to_id.get(name)
-                    rings.configure(row, 0, K + g if g is not None else -1)
-                ws.send_initialised = False
+                self._point_ring_rows(rings, mapper, ws)  # (ids changed)
                 self._ring_gid_state = state
             rings.report_local(ws, names_ok, rows_active=rows_used)
 
-        self._may_defer_sync = not first_ring_report
-        try:
-            ws, mapper = self._score_round(knames, snames, fill_send, local_ranks=local_ranks, stats_rows=total_rows,
-                                           stats_rows_used=stats_needed, resync_first=resync_first)
-        finally:
-            self._may_defer_sync = False
+        not_the_first, self._had_ring_report = self._had_ring_report, True
+        ws, mapper = self._score_round(knames, snames, fill_send, local_ranks=local_ranks, stats_rows=total_rows,
+                                       stats_rows_used=stats_needed, sync_first=self._take_resync(), may_defer_sync=not_the_first)
         report = self._assemble(ws, mapper, snames, dict(section_rows), dict(kernel_rows), t0, local_ranks=local_ranks,
                                 stats=ws.stats[:stats_needed].copy())
         # names are settled now: the next report with the same tables takes the planned path
-        key = (id(section_rows), len(section_rows), id(kernel_rows), len(kernel_rows), self.name_mapper.version,
-               self._private_mapper.version, self.world_size, self.rank, rings.rows_used, local_ranks, id(rings))
-        self._ring_plan = self._build_ring_plan(key, rings, section_rows, kernel_rows, local_ranks)
+        self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
+                                                section_rows, kernel_rows, local_ranks)
         return report

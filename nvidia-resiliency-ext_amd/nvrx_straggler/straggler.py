@@ -134,7 +134,9 @@ class _Lane:
     code: ~100 interpreter-level calls cost 150-190 us around a C call of 45 (profiles/r06a/r06c_kernels_mode_breakdown.txt).
     A lane is built after a report that took the cached plan; it holds everything that report looked up, checks with a few
     attribute reads that nothing it depends on has changed, and otherwise says ``_MISS`` BEFORE anything has happened, so the
-    general path -- which stays the specification -- runs as if the lane did not exist."""
+    general path -- which stays the specification -- runs as if the lane did not exist.  The generator's name-sync and
+    in-flight state is read here and written by the generator's own methods; the two marked spots of
+    the asynchronous hot path do a method's writes inline, in its order."""
 
     trace = None
 
@@ -212,6 +214,7 @@ class _Lane:
                 blk = pend.blk
                 words = getattr(blk, "meta_words", None)
                 if words is not None and pend.blob is None and words[4] == pend.seq:
+                    # (the writes of ReportGenerator._settle_inflight, in its order, kept inline: this is the lane's hot path)
                     reporter._inflight = None
                     reporter._prev_async_settled = True
                     if self.multi:
@@ -220,8 +223,9 @@ class _Lane:
                 else:
                     names_missing = reporter._settle_inflight()
                 if names_missing:
-                    reporter._ring_plan = None       # that report's table carried an "ids missing" flag: every rank is
-                    reporter._resync_pending = True  # heading for the name sync now, at the start of its general path
+                    # that report's table carried an "ids missing" flag: every rank is heading for the name sync now, at the
+                    # start of its general path
+                    reporter._sync_names_first()
                     return _MISS
         if tr is not None:
             tr.append(("checks", time.perf_counter_ns() - t0))
@@ -250,11 +254,12 @@ class _Lane:
             ws._cur, ws.block = cur, ws.blocks[cur]  # nothing ran on the block: it is not the current one
             return _MISS
         if rc < 0:
-            reporter._ring_plan = None
+            reporter._drop_plan()
             if rc == _native.ERR_TIMEOUT:
                 self.be.retire_workspace(ws)
             _native.check(rc)
         if self.enqueue_only:
+            # (the writes of ReportGenerator._report_from_plan for a report that is only enqueued, in its order, kept inline)
             reporter._prev_async_settled = False  # until somebody has seen THIS report complete
             pend = reporter._inflight = _PendingBlock(self.be, ws, seq)
             if self.returns_none:
@@ -266,8 +271,7 @@ class _Lane:
             reporter._check_exchange()
         if rc == _native.WINDOW_NAMES:
             # some rank met a new name during this report's exchange: the rings still hold the window -- sync names, report again
-            reporter._ring_plan = None
-            reporter._resync_pending = True
+            reporter._sync_names_first()
             return det._report_and_reset(rings, reporter)
         if self.returns_none:
             return None
