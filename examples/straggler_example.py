@@ -23,6 +23,9 @@ step ``--slow-from`` on (root and a writable sysfs needed).  Where the driver re
 GPU, ``--slow-by simulated`` puts a stand-in for "a kernel that takes longer on a slower GPU" into every rank's section:
 a spin kernel whose duration is its argument, 1.5x longer on the slow rank -- the report then reads as it would with a
 GPU at two thirds of its speed.
+
+With ``NVRX_KERNEL_ATTRIBUTION=5`` in the environment the report also names, for every flagged rank, the five kernels that
+carry most of its score's deficit (``Report.explain_gpu_scores()``).
 """
 import argparse
 import os
@@ -98,9 +101,18 @@ def train(args) -> None:
                 print(f"step {step}: GPUs relative perf: { {r: round(s, 3) for r, s in report.gpu_relative_perf_scores.items()} }")
                 print(f"step {step}: GPUs individual perf: { {r: round(s, 3) for r, s in report.gpu_individual_perf_scores.items()} }")
                 found = report.identify_stragglers(gpu_rel_threshold=args.threshold, gpu_indiv_threshold=args.threshold)
-                for kind in ("straggler_gpus_relative", "straggler_gpus_individual"):
+                explained = report.explain_gpu_scores()  # {} unless NVRX_KERNEL_ATTRIBUTION=N asks for the top-N kernels
+                for kind, family in (("straggler_gpus_relative", "relative"), ("straggler_gpus_individual", "individual")):
                     if found[kind]:
                         print(f"step {step}: {kind}: {sorted((s.rank, s.node) for s in found[kind])}")
+                    for s in sorted(found[kind], key=lambda s: s.rank):
+                        why = explained.get(family, {}).get(s.rank)
+                        if why:
+                            print(f"step {step}:   rank {s.rank}: {why['deficit']:.3f} of its {family} score is missing, "
+                                  f"{why['explained']:.3f} of it in:")
+                            for k in why["kernels"]:
+                                print(f"step {step}:     {k['kernel']}: share {k['share']:.3f}, score {k['score']:.3f}, "
+                                      f"{k['lost_us']:.0f} us above the reference pace")
                 print(f"step {step}: {straggler.Detector.gpu_telemetry_line()}", flush=True)
     if slow_ctx is not None:
         slow_ctx.__exit__(None, None, None)

@@ -117,6 +117,26 @@ int nvrx_score(const float *d_table, int R, int K, int S, int do_indiv, int do_r
                uint32_t *d_done_counter, uint32_t seq, const float *d_stats_src, float *d_stats_dst,
                int stats_rows, void *stream);
 
+/* Kernel attribution: which kernels carry each rank's GPU score deficit.  Extends _compute_gpu_perf_score
+ * (reporting.py:219-253), whose weighted mean g = sum_k(w_k * ref_k / med_k) / W keeps no per-kernel term: with
+ * s_k = ref_k / med_k and n_k = w_k * (1 - s_k) ("lost microseconds": time above the reference pace), 1 - g = sum_k(n_k) / W.
+ * Per reported rank and family (0 individual: ref_k = hmin; 1 relative: ref_k = column minimum of MED, NaN if any rank lacks
+ * the kernel) the top_n eligible kernels by n_k, descending, ties to the lower kernel id.  Eligible = what nvrx_score sums.
+ *   d_table [R][L] as for nvrx_score; ranks [first_rank, first_rank + n_ranks) are reported;
+ *   top_n in [1, NVRX_ATTR_MAX_TOP];
+ *   d_minmed_scratch  NVRX_ATTR_SCRATCH_FLOATS(K) floats of device memory (column minima), may be NULL when do_rel == 0;
+ *   d_out [n_ranks][2][1 + top_n] records of four 32-bit words, 16-byte aligned (NVRX_ATTR_WORDS(n_ranks, top_n) words):
+ *      header {f32 deficit = sum(n_k)/W, f32 explained = sum of the listed shares, u32 eligible kernels, f32 W}
+ *      entry  {i32 kernel id, f32 share = n_k/W, f32 score = s_k, f32 lost_us = n_k}
+ *      no eligible kernel / family not computed: header {NaN, NaN, 0, 0}, every id -1; fewer than top_n eligible kernels:
+ *      the remaining ids are -1 (their floats NaN).  s_k and n_k are the f64 formula rounded to f32.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_ATTR_MAX_TOP 16
+#define NVRX_ATTR_SCRATCH_FLOATS(K) (33 * (size_t)(K))
+#define NVRX_ATTR_WORDS(n_ranks, top_n) ((size_t)(n_ranks) * 2 * (1 + (size_t)(top_n)) * 4)
+int nvrx_attribute(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int top_n, int do_indiv,
+                   int do_rel, float *d_minmed_scratch, void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -274,6 +294,14 @@ typedef struct nvrx_report_desc {
                                  report's statistics kernel */
 } nvrx_report_desc;
 int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *desc, void *stream);
+/* nvrx_attribute (reporting.py:219-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or
+ * d_send without an exchange; shape and families from the descriptor).  The library orders the kernel behind that report's
+ * kernels itself: it is enqueued on the context's stream (nvrx_ctx_set_stream), behind an event of the stream the report's
+ * last kernel went to when that was another one (a re-homed report, the resident score kernel).  The host does not wait;
+ * copy d_out with a D2H on the context's stream.  The caller must not let a later report rewrite the table before this
+ * kernel has run (the Python package waits for it at the start of the next report on the same buffers).
+ * NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_attribute(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int top_n, void *d_out);
 /* One report WINDOW in one call: what straggler.py:228-244 does around the report in the steady state -- wait for the
  * window's GPU measurements (torch.cuda.synchronize() + the profiler's get_stats there; here the kernel tracer's sync, or a
  * harvest of the region events), check that the set of rows holding samples is the one the caller's name tables were built

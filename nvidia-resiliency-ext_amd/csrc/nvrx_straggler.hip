@@ -2050,6 +2050,14 @@ struct nvrx_ctx {
     };
     std::vector<StreamEpoch> stream_epochs;
 
+    // kernel attribution (nvrx_report_attribute, nvrx_attribute.inl): the descriptor of the last report and the stream its
+    // LAST kernel was enqueued on -- what an attribution of that report's table has to be ordered behind
+    const nvrx_report_desc *attr_desc = nullptr;
+    hipStream_t attr_stream = nullptr;
+    hipEvent_t attr_ev = nullptr;
+    float *attr_scratch = nullptr;  // column minima of the kernel medians, grown on demand
+    size_t attr_scratch_elems = 0;
+
     std::mutex mu;
 };
 
@@ -2554,6 +2562,8 @@ int nvrx_ctx_destroy(nvrx_ctx *ctx) {
     if (ctx->stamp_ev) (void)hipEventDestroy(ctx->stamp_ev);
     if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
     if (ctx->report_ev) (void)hipEventDestroy(ctx->report_ev);
+    if (ctx->attr_ev) (void)hipEventDestroy(ctx->attr_ev);
+    if (ctx->attr_scratch) (void)hipFree(ctx->attr_scratch);
     {
         // score scratch of the streams this context's reports ran on (its own, the resident scorer's, every user stream
         // a report was re-homed onto): the device is idle, nothing reads it any more
@@ -3431,6 +3441,7 @@ int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
                            d->d_scores, d->d_flags, d->d_meta, d->d_done_counter, d->seq, nullptr, nullptr, 0,
                            ctx->score_stream, peer_route ? &pa : nullptr, &ga);
         if (rc2) return rc2;
+        ctx->attr_desc = d, ctx->attr_stream = ctx->score_stream;  // (for nvrx_report_attribute)
         report_clk(4);
         report_clk(5);
         rc2 = nvrx_poll_u32(d->h_seq_word, d->seq, d->timeout_s > 0.0 ? d->timeout_s : 1e30);
@@ -3489,6 +3500,7 @@ int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
                       d->d_scores, d->d_flags, d->d_meta, d->d_done_counter, d->seq, d->d_stats, d->d_stats_dst,
                       d->stats_rows, stream, prologue ? &pa : nullptr);
     if (rc) return rc;
+    ctx->attr_desc = d, ctx->attr_stream = as_stream(stream);  // (for nvrx_report_attribute)
     report_clk(5);
     if (d->h_seq_word) {
         rc = nvrx_poll_u32(d->h_seq_word, d->seq, d->timeout_s > 0.0 ? d->timeout_s : 1e30);
@@ -3857,3 +3869,5 @@ int nvrx_wait(nvrx_ctx *ctx) {
 }
 
 }  // extern "C"
+
+#include "nvrx_attribute.inl"

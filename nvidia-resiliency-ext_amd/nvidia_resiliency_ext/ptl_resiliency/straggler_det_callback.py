@@ -137,6 +137,7 @@ class StragglerDetectionCallback(Callback):
         for text, ranks in hits:
             self.logger.warning(f"STRAGGLER DETECTION WARNING: {text} Affected ranks: {ranks}")
         if hits:
+            self._name_the_kernels(report, flagged)
             self._telemetry_of_a_flagged_reporter(ranks for _, ranks in hits)
         enabled = [f for f in self._FAMILIES if getattr(self, f[0])]
         n = self.num_gpu_perf_scores_to_print
@@ -147,6 +148,24 @@ class StragglerDetectionCallback(Callback):
             for _, field, _, _, prefix, _ in enabled:
                 self._log_extremes(pl_module, getattr(report, field), prefix)
         return bool(hits)
+
+    def _name_the_kernels(self, report, flagged) -> None:
+        """Kernel attribution (``NVRX_KERNEL_ATTRIBUTION=N``, off by default: nothing is logged then): for every flagged GPU the
+        kernels that carry its score's deficit, by name, with their share of it and the microseconds lost."""
+        explain = getattr(report, "explain_gpu_scores", None)
+        explained = explain() if explain is not None else {}
+        if not explained:
+            return
+        for family, key in (("relative", "straggler_gpus_relative"), ("individual", "straggler_gpus_individual")):
+            per_rank = explained.get(family, {})
+            for rank in sorted(getattr(s, "rank", s) for s in flagged[key]):
+                entry = per_rank.get(rank)
+                if not entry or not entry["kernels"]:
+                    continue
+                top = ", ".join(f"{k['kernel']} (share {k['share']:.2f}, score {k['score']:.2f}, lost {k['lost_us']:.0f} us)"
+                                for k in entry["kernels"] if k["lost_us"] > 0)
+                self.logger.warning(f"STRAGGLER DETECTION WARNING: rank {rank} {family} GPU score deficit {entry['deficit']:.2f}, "
+                                    f"top kernels: {top or 'none above the reference pace'}")
 
     def _telemetry_of_a_flagged_reporter(self, groups) -> None:
         # MI355X extra: when the reporting rank itself is flagged, say what ROCm SMI sees on its GPU (clock below

@@ -25,6 +25,8 @@ MAX_RING_CAP = 65536
 META_WORDS = 8
 ERR_TIMEOUT = -62
 ERR_RANGE = -34
+ERR_INVALID = -22
+ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
 
 
 
@@ -63,6 +65,7 @@ SYMBOLS = [
     ("nvrx_row_stats", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p,
                            c_void_p, c_uint32, c_void_p, c_void_p, c_int, c_void_p]),
+    ("nvrx_attribute", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -95,6 +98,7 @@ SYMBOLS = [
     ("nvrx_stamp_end", c_int, [c_void_p, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_local", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report", c_int, [c_void_p, POINTER(ReportDesc), c_void_p]),
+    ("nvrx_report_attribute", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
     ("nvrx_peer_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -179,3 +183,8 @@ def table_len(K: int, S: int) -> int:
 
 def score_len(S: int) -> int:
     return 2 + 2 * S
+
+
+def attr_words(n_ranks: int, top_n: int) -> int:
+    """NVRX_ATTR_WORDS: 32-bit words of an attribution block ``[n_ranks][2][1 + top_n][4]``."""
+    return n_ranks * 2 * (1 + top_n) * 4

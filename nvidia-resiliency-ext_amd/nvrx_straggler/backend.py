@@ -213,6 +213,32 @@ class ResultBlock:
         return self.stats[:rows].copy()
 
 
+class Attribution:
+    """Kernel attribution of one report (``nvrx_attribute`` / ``nvrx_report_attribute``), enqueued and not waited for: the
+    records -- ``[n_ranks][2 families][1 + top_n][4]`` 32-bit words, include/nvrx_straggler.h -- are in the workspace's device
+    buffer once the kernel has run.  ``records()`` waits for it and takes the private host copy (one ordered D2H on the
+    backend's stream): when a ``Report`` first asks, or -- ``Workspace.attr_settle`` -- before the next report on the same
+    workspace rewrites the table the kernel reads and the buffer it writes."""
+
+    __slots__ = ("backend", "d_ptr", "first_rank", "n_ranks", "top_n", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, first_rank: int, n_ranks: int, top_n: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.first_rank, self.n_ranks, self.top_n = first_rank, n_ranks, top_n
+        self._host: Optional[np.ndarray] = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self) -> np.ndarray:
+        """``[n_ranks, 2, 1 + top_n, 4]`` uint32 (private copy); the first call waits for the kernel."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.attribution_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -296,6 +322,30 @@ class Workspace:
 
     def host_stats(self, rows: int) -> np.ndarray:
         return self.block.host_stats(rows)
+
+    # ---- kernel attribution (off unless a ReportGenerator asks: nothing is allocated before) -------------------
+    _attr_buf = None      # device: the records of the last attribution of this workspace's table
+    _attr_scratch = None  # device: column minima for the stateless operator
+    _attr_last = None     # the Attribution whose kernel may still be reading the table / writing _attr_buf
+
+    def attr_buffers(self, n_ranks: int, top_n: int, scratch: bool):
+        """``(records buffer, scratch or None)`` for an attribution of ``n_ranks`` ranks (cold: allocated once per shape)."""
+        words = _native.attr_words(n_ranks, top_n)
+        dev = self._backend.device
+        if self._attr_buf is None or self._attr_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._attr_buf = torch.empty(max(words, 64), dtype=torch.int32, device=dev)
+        if scratch and self._attr_scratch is None:
+            with torch.cuda.stream(self._backend.stream):
+                self._attr_scratch = torch.empty(max(33 * self.K, 64), dtype=torch.float32, device=dev)
+        return self._attr_buf, (self._attr_scratch if scratch else None)
+
+    def attr_settle(self) -> None:
+        """Before anything rewrites this workspace's table: the last attribution's kernel has run and its records are on the
+        host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._attr_last = self._attr_last, None
+        if last is not None:
+            last.records()
 
     def set_send_row(self, lr: int, row: np.ndarray) -> None:
         """Host-packed exchange row (dict-input path)."""
@@ -413,6 +463,27 @@ class HipBackend:
             if ws is not None:
                 self.retire_workspace(ws)
             _native.check(rc)
+
+    def attribute(self, ws: Workspace, table: torch.Tensor, top_n: int, do_indiv: bool, do_rel: bool,
+                  first_rank: int = 0, n_ranks: Optional[int] = None) -> Attribution:
+        """Kernel attribution of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank +
+        n_ranks)``: ``nvrx_attribute`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        ws.attr_settle()
+        buf, scratch = ws.attr_buffers(n_ranks, top_n, bool(do_rel))
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_attribute(table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks, top_n, int(do_indiv), int(do_rel),
+                                     scratch.data_ptr() if scratch is not None else None, buf.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._attr_last = Attribution(self, buf, first_rank, n_ranks, top_n)
+        return out
+
+    def attribution_copy_out(self, attr: Attribution) -> np.ndarray:
+        """The one wait of an attribution: a D2H of its records on the backend's stream, behind its kernel."""
+        host = np.empty((attr.n_ranks, 2, 1 + attr.top_n, 4), dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, attr.d_ptr, host.nbytes, self._stream_handle))
+        return host
 
     def retire_workspace(self, ws: Workspace) -> None:
         """After a timed-out wait the kernels of ``ws`` may still be queued behind a collective: the workspace
@@ -691,6 +762,18 @@ class HipRings:
                 self.backend.retire_workspace(ws)
             _native.check(rc)
         return ws.seq
+
+    def report_attribute(self, ws: Workspace, top_n: int, first_rank: int = 0, n_ranks: Optional[int] = None) -> Attribution:
+        """Kernel attribution of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_attribute``):
+        enqueued behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        ws.attr_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
+        buf, _ = ws.attr_buffers(n_ranks, top_n, False)
+        rc = self.lib.nvrx_report_attribute(self.ctx, ws.block.desc_ref, first_rank, n_ranks, top_n, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._attr_last = Attribution(self.backend, buf, first_rank, n_ranks, top_n)
+        return out
 
     def peek_stats(self) -> np.ndarray:
         """Statistics of every used row right now ([rows_used, 8] on the host); exchanges nothing and

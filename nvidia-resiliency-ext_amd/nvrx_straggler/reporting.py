@@ -588,6 +588,43 @@ class _ScoreSource:
         return dict(zip(v.names, map(dict, map(zip, itertools.repeat(v.rank_list()), block.tolist()))))
 
 
+class _AttrSource:
+    """What a report keeps of its kernel attribution: the backend's handle (``records()`` waits for the kernel and copies the
+    records out on first use), the ranks its rows stand for, which families were computed, and the kernel names by id as
+    the report's mapper had them at report time (ids are never reassigned)."""
+
+    __slots__ = ("handle", "ranks", "names", "has_rel", "has_indiv", "_built")
+
+    def __init__(self, handle, ranks, names, has_rel: bool, has_indiv: bool):
+        self.handle, self.ranks, self.names = handle, tuple(ranks), names
+        self.has_rel, self.has_indiv = has_rel, has_indiv
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            rec = np.ascontiguousarray(self.handle.records(), dtype=np.uint32)
+            f32 = rec.view(np.float32)
+            ids = rec.view(np.int32)[:, :, 1:, 0]
+            out: Dict[str, Dict[int, Any]] = {}
+            for fam, key, on in ((1, "relative", self.has_rel), (0, "individual", self.has_indiv)):
+                if not on:
+                    continue
+                per_rank = out[key] = {}
+                for i, rank in enumerate(self.ranks):
+                    head = f32[i, fam, 0]
+                    kernels = [{"kernel": self.names[k], "share": float(e[1]), "score": float(e[2]), "lost_us": float(e[3])}
+                               for k, e in zip(ids[i, fam].tolist(), f32[i, fam, 1:]) if k >= 0]
+                    per_rank[rank] = {"deficit": float(head[0]), "explained": float(head[1]),
+                                      "num_kernels": int(rec[i, fam, 0, 2]), "kernels": kernels}
+            self._built = out
+            self.handle = None
+        return self._built
+
+
+def _copy_explanation(d: dict) -> dict:
+    return {fam: {r: dict(v, kernels=[dict(k) for k in v["kernels"]]) for r, v in ranks.items()} for fam, ranks in d.items()}
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -674,10 +711,31 @@ class Report:
         flags = self._flags()
         if flags is not None:
             state["_device_flags"] = flags
+        attr = self.__dict__.get("_attr")
+        if attr is not None:
+            state["_attr"] = attr.build() if isinstance(attr, _AttrSource) else attr  # plain dicts travel
         return state
 
     def __setstate__(self, state) -> None:
         self.__dict__.update(state)
+
+    def explain_gpu_scores(self) -> Dict[str, Dict[int, Dict[str, Any]]]:
+        """The kernels behind each rank's GPU score (``ReportGenerator(kernel_attribution=N)``; ``{}`` when the report carries
+        no attribution).  A GPU score is the weighted mean of per-kernel scores ``s_k = ref_k / med_k`` with the microseconds
+        ``w_k`` spent in kernel k as weights, so its deficit ``1 - score`` splits into per-kernel shares ``w_k * (1 - s_k) / W``.
+
+        ``{"relative": {rank: {"deficit": 1 - score, "explained": sum of the listed shares, "num_kernels": kernels the score
+        covers, "kernels": [{"kernel": name, "share", "score": s_k, "lost_us": w_k * (1 - s_k)}, ...]}}, "individual":
+        {...}}`` -- the N kernels with the largest ``lost_us``, largest first (ties: the kernel that got its id first);
+        families that were not computed are absent; ranks as in the score mappings.  Where the score is NaN the deficit is
+        NaN and the list is empty.  Plain dicts, lists, floats and strings.  The first call waits for the attribution
+        kernel; ``generate_report`` never does."""
+        attr = self.__dict__.get("_attr")
+        if attr is None:
+            return {}
+        if isinstance(attr, _AttrSource):
+            attr = self.__dict__["_attr"] = attr.build()
+        return _copy_explanation(attr)
 
     def _ids(self, ranks) -> set:
         return {StragglerId(rank=r, node=self.rank_to_node[r]) for r in ranks}
@@ -829,7 +887,8 @@ class ReportGenerator:
     """
 
     def __init__(self, scores_to_compute, gather_on_rank0=True, pg=None, node_name="<notset>",
-                 thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False) -> None:
+                 thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
+                 kernel_attribution: int = 0) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -867,6 +926,19 @@ class ReportGenerator:
         self._resync_pending = False  # some rank's table said "ids missing": no plan, no lane; the general path syncs names first
         self._had_ring_report = False  # a ring report has reached its score round (collective: the same on every rank)
         self._unreported_rows: list = []  # see take_unreported_rows
+        # kernel attribution: every report also names the top-N kernels behind each GPU score (Report.explain_gpu_scores); 0 = off:
+        # no buffer, no launch, no backend call.  Every rank should pass the same value (it changes no collective, so a
+        # mismatch cannot hang anything: a rank's own reports simply carry what that rank asked for)
+        n = int(kernel_attribution)
+        if not 0 <= n <= 16:
+            raise ValueError(f"kernel_attribution must be 0 (off) or 1..16 kernels per GPU score, got {kernel_attribution!r}")
+        self.kernel_attribution = n
+        if n:
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "attribute"):
+                raise RuntimeError(f"kernel_attribution={n}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no kernel attribution (backend.attribute)")
+        self._attr_names_cache = (None, 0, ())  # (mapper, kernel ids covered, names by id)
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
     # ---- pieces kept from the reference's host logic ----------------------------------------------
@@ -901,6 +973,20 @@ class ReportGenerator:
         for name, summ in section_summaries.items():
             if summ[Statistic.MED] < self.min_local_section_times[name]:
                 self.min_local_section_times[name] = summ[Statistic.MED]
+
+    # ---- kernel attribution ------------------------------------------------------------------------
+    def _attr_names(self, mapper, K: int) -> tuple:
+        """Kernel names by id, as ``mapper`` has them now (ids are only ever appended: cached until K grows)."""
+        owner, n, names = self._attr_names_cache
+        if owner is not mapper or n != K:
+            names = tuple(mapper.id_to_kernel_name[i] for i in range(K))
+            self._attr_names_cache = (mapper, K, names)
+        return names
+
+    def _attr_source(self, handle, ws, mapper, lo: int, hi: int, ranks) -> _AttrSource:
+        assert handle.first_rank == lo and handle.n_ranks == hi - lo
+        return _AttrSource(handle, ranks, self._attr_names(mapper, ws.K), self.is_computing_rel_scores,
+                           self.is_computing_indiv_scores)
 
     # ---- the shared score round -------------------------------------------------------------------
     def _exchanged(self) -> bool:
@@ -1026,6 +1112,8 @@ class ReportGenerator:
             K, S = mapper.kernel_counter, mapper.section_counter
             world = self.world_size if exchanged else 1
             ws = be.workspace(world * local_ranks, K, S, local_ranks, stats_rows)
+            if getattr(ws, "_attr_last", None) is not None:
+                ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1070,6 +1158,11 @@ class ReportGenerator:
         src.stats = stats
         report = Report._from_device(src, self._shared_rank_to_node(), (time.perf_counter_ns() - t_start_ns) * 1e-6,
                                      self.gather_on_rank0, self.rank)
+        if self.kernel_attribution:
+            # enqueued behind the score kernel on the backend's stream; waited for when the report is first asked
+            handle = _backend_mod.get_backend().attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
+                                                          self.is_computing_rel_scores, lo, hi - lo)
+            report.__dict__["_attr"] = self._attr_source(handle, ws, mapper, lo, hi, view.ranks)
         if stats is None:
             # the caller's own summaries travel with the report, untouched
             report.__dict__["local_section_summaries"] = section_summaries
@@ -1206,6 +1299,11 @@ class ReportGenerator:
         ws = plan.ws
         multi = self.world_size > 1 and self._exchanged()
         fused = plan.fused and (not multi or self._direct is not None)
+        attr_n = self.kernel_attribution
+        if getattr(ws, "_attr_last", None) is not None:
+            ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
+        if fused and attr_n and not hasattr(rings, "report_attribute"):
+            raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
         if fused:
             # ONE C call: flush -> statistics kernel -> [ncclAllGather] -> score kernel -> completion word
             wait = not self.asynchronous
@@ -1221,10 +1319,13 @@ class ReportGenerator:
                 pend = self._inflight = _PendingBlock(be, ws, seq)
                 if self.gather_on_rank0 and self.rank != 0:
                     return None
-                return Report._from_device(
+                report = Report._from_device(
                     _ScoreSource(plan.view, pend),
                     self._shared_rank_to_node(),
                     (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
+                if attr_n:
+                    self._attach_plan_attribution(report, plan, rings, True)
+                return report
         else:
             rings.report_local(ws, True, rows_active=plan.rows_used)
             table = self._exchange(be, ws) if multi else ws.send
@@ -1250,10 +1351,26 @@ class ReportGenerator:
             ws.attach(pending)  # the workspace collects it (if still held) before the block is reused by anybody
         else:
             pending = ws.host_block()
-        return Report._from_device(
+        report = Report._from_device(
             _ScoreSource(plan.view, pending),
             self._shared_rank_to_node(),
             (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
+        if attr_n:
+            self._attach_plan_attribution(report, plan, rings, fused)
+        return report
+
+    def _attach_plan_attribution(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the attribution of the planned report that was just issued (the one-call report: ordered behind its
+        kernels by the library; the stepwise one: behind the score kernel on the backend's stream) and hang it on
+        ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        lo, hi = plan.view.layout[5], plan.view.layout[6]
+        if fused:
+            handle = rings.report_attribute(ws, self.kernel_attribution, lo, hi - lo)
+        else:
+            handle = _backend_mod.get_backend().attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
+                                                          self.is_computing_rel_scores, lo, hi - lo)
+        report.__dict__["_attr"] = self._attr_source(handle, ws, plan.mapper, lo, hi, plan.view.ranks)
 
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],

@@ -156,6 +156,8 @@ class _Lane:
             return None  # (a host-driven exchange: the report is three calls with a collective between them)
         if reporter.asynchronous and not reporter.enqueue_only():
             return None
+        if reporter.kernel_attribution:
+            return None  # (the attribution launch follows the report in the generator's planned path: DESIGN.md, "Kernel attribution")
         ext = manager.cupti_ext
         ws = plan.ws
         if ws.block.desc_key is None or not ws.send_initialised:
@@ -377,6 +379,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         max_rows: int = 256,
         asynchronous: Optional[bool] = None,
         kernel_trace_budget_pct: Optional[float] = None,
+        kernel_attribution: Optional[int] = None,
     ):
         """
         Args:
@@ -401,6 +404,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 still recorded at ``profiling_interval``.  Default: ``NVRX_KTRACE_BUDGET_PCT``, else 1.0; 0 = trace at
                 ``profiling_interval`` whatever it costs (the reference's behaviour).  Jobs that call ``generate_report``
                 themselves never calibrate.
+            kernel_attribution: 0 = off; N in 1..16: every report also carries, per rank and GPU score, the N kernels with the
+                largest share of the score's deficit (``Report.explain_gpu_scores()``).  Default: ``NVRX_KERNEL_ATTRIBUTION``,
+                else 0.  Pass the same value on every rank (no collective depends on it).
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -436,8 +442,14 @@ class Detector(metaclass=_DeviceSideOnDemand):
         # host side: who scores, and when
         if asynchronous is None:
             asynchronous = os.environ.get("NVRX_ASYNC_REPORT", "0") not in ("", "0")
+        if kernel_attribution is None:
+            try:
+                kernel_attribution = int(os.environ.get("NVRX_KERNEL_ATTRIBUTION", "0") or 0)
+            except ValueError:
+                raise ValueError("NVRX_KERNEL_ATTRIBUTION must be an integer: 0 (off) or 1..16") from None
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
-                                       node_name=node_name or socket.gethostname(), asynchronous=asynchronous)
+                                       node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
+                                       kernel_attribution=kernel_attribution)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
