@@ -26,6 +26,11 @@ GPU at two thirds of its speed.
 
 With ``NVRX_KERNEL_ATTRIBUTION=5`` in the environment the report also names, for every flagged rank, the five kernels that
 carry most of its score's deficit (``Report.explain_gpu_scores()``).
+
+A GPU that is slow only SOME of the time does not move a median: ``--slow-by intermittent`` applies the simulated slowdown
+on every ``--slow-every``-th step of the slow rank only, and the lines above stay quiet.  With ``NVRX_TAIL_QUANTILE=0.9`` in
+the environment the report also compares the 0.9 quantile of every timing row across ranks (``Report.tail_scores()``) and
+the example prints whoever ``identify_tail_stragglers`` flags underneath.
 """
 import argparse
 import os
@@ -88,8 +93,10 @@ def train(args) -> None:
                 print(f"[rank {rank}] ROCm SMI refused to slow the GPU down ({e}); use --slow-by simulated", flush=True)
         with straggler.Detector.detection_section("fwd", profile_cuda=True):
             output = net(data)
-            if args.slow_by == "simulated":   # one kernel whose duration says how fast "this GPU" is
+            if args.slow_by in ("simulated", "intermittent"):   # one kernel whose duration says how fast "this GPU" is
                 slow = rank == args.slow_rank and step >= args.slow_from
+                if args.slow_by == "intermittent":
+                    slow = slow and step % args.slow_every == 0
                 torch.cuda._sleep(int(args.simulated_cycles * (1.5 if slow else 1.0)))
         loss = loss_fn(output, target)
         optim.zero_grad()
@@ -113,6 +120,14 @@ def train(args) -> None:
                             for k in why["kernels"]:
                                 print(f"step {step}:     {k['kernel']}: share {k['share']:.3f}, score {k['score']:.3f}, "
                                       f"{k['lost_us']:.0f} us above the reference pace")
+                tails = report.tail_scores()  # {} unless NVRX_TAIL_QUANTILE=q asks for tail scores
+                if tails:
+                    print(f"step {step}: GPUs relative tail perf (q={tails['quantile']:g}): "
+                          f"{ {r: round(s, 3) for r, s in tails['gpu_relative'].items()} }")
+                    tail_found = report.identify_tail_stragglers(gpu_rel_threshold=args.threshold)
+                    if tail_found["straggler_gpus_relative"]:
+                        print(f"step {step}: tail straggler_gpus_relative: "
+                              f"{sorted((s.rank, s.node) for s in tail_found['straggler_gpus_relative'])}")
                 print(f"step {step}: {straggler.Detector.gpu_telemetry_line()}", flush=True)
     if slow_ctx is not None:
         slow_ctx.__exit__(None, None, None)
@@ -136,7 +151,10 @@ def main() -> None:
     ap.add_argument("--threshold", type=float, default=0.75)
     ap.add_argument("--slow-rank", type=int, default=-1)
     ap.add_argument("--slow-from", type=int, default=300)
-    ap.add_argument("--slow-by", choices=["clock", "simulated"], default="clock")
+    ap.add_argument("--slow-by", choices=["clock", "simulated", "intermittent"], default="clock")
+    ap.add_argument("--slow-every", type=int, default=5,
+                    help="--slow-by intermittent: the slow rank's stand-in kernel is 1.5x longer on every N-th step only (with one "
+                         "step in ten slow, a 0.9 quantile would sit on the last FAST sample)")
     ap.add_argument("--simulated-cycles", type=float, default=3e6, help="--slow-by simulated: spin cycles of the stand-in kernel")
     args = ap.parse_args()
     if "RANK" in os.environ or args.num_processes == 1:

@@ -137,6 +137,28 @@ int nvrx_score(const float *d_table, int R, int K, int S, int do_indiv, int do_r
 int nvrx_attribute(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int top_n, int do_indiv,
                    int do_rel, float *d_minmed_scratch, void *d_out, void *stream);
 
+/* Tail quantile of timing rows.  Extends the statistics of straggler.py:172-197, whose only order statistic is the median:
+ * per row the nearest-rank q-quantile, q = q_ppm / 1e6 with q_ppm in [500000, 999999] -- the element of rank
+ * k = (q_ppm * n + 999999) / 1000000 - 1 (64-bit integers) of the row's n valid samples sorted ascending by their raw bit
+ * patterns (-inf < negatives < -0.0 < +0.0 < positives < +inf < NaN with a clear sign bit): always an actual sample, for
+ * section and kernel rows alike.  At q_ppm = 500000 that is the lower median, the MED of a section row.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_out [rows]: -1.0 where the row holds no sample.  Stateless: caller-owned buffers, like nvrx_row_stats.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+int nvrx_row_quantile(const float *d_samples, const uint32_t *d_counts, int rows, int row_stride, uint32_t q_ppm,
+                      float *d_out, void *stream);
+/* Relative tail scores.  Extends _compute_section_relative_scores / _compute_gpu_perf_score (reporting.py:196-253) from
+ * medians to tails: d_tails [R][K+S] holds every rank's tail per kernel id and section id (-1.0: none).  Reference per
+ * column = the minimum over all R ranks, NaN if any rank has none.  Per reported rank [first_rank, first_rank + n_ranks):
+ *   d_out [n_ranks][1 + S] = {GPU tail score, section tail score[S]}
+ *   section s: f32 of the f64 quotient ref / tail, NaN where either is missing;
+ *   GPU: f32 of sum_k w_k * (ref_k / tail_k) / sum_k w_k in f64 over the kernels with a tail and a reference, w_k the
+ *   weights NUM*AVG of that rank in d_table [R][L] (the table nvrx_score reads); NaN when no kernel is eligible.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(K+S) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+int nvrx_tail_score(const float *d_tails, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                    float *d_colmin_scratch, float *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -302,6 +324,16 @@ int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *desc, void *stream);
  * kernel has run (the Python package waits for it at the start of the next report on the same buffers).
  * NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_attribute(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int top_n, void *d_out);
+/* nvrx_row_quantile (straggler.py:172-197, above) on the rings as the report just issued saw them, packed by gid into
+ * d_tail_send [local_ranks][K+S]: kernel ids first, then section ids; every slot is written, -1.0 where no row with samples
+ * has that gid.  Staged samples are NOT flushed (the window is the one the report's statistics kernel read) and the history
+ * minima are not touched.  desc != NULL: the report went through nvrx_report; the kernel is enqueued on the context's stream
+ * behind that report's last kernel, as nvrx_report_attribute orders itself (NVRX_ERR_STATE: no report was issued through
+ * this descriptor).  desc == NULL: the stepwise path; it runs on `stream`, where nvrx_report_local ran.  rows_active as for
+ * nvrx_report_local.  The host does not wait -- but the caller must: the rings are emptied by count, and the next window's
+ * device-side writers on other streams may overwrite slots as soon as they are told to. */
+int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm, float *d_tail_send, int K, int S,
+                    int rows_active, void *stream);
 /* One report WINDOW in one call: what straggler.py:228-244 does around the report in the steady state -- wait for the
  * window's GPU measurements (torch.cuda.synchronize() + the profiler's get_stats there; here the kernel tracer's sync, or a
  * harvest of the region events), check that the set of rows holding samples is the one the caller's name tables were built

@@ -2058,6 +2058,10 @@ struct nvrx_ctx {
     float *attr_scratch = nullptr;  // column minima of the kernel medians, grown on demand
     size_t attr_scratch_elems = 0;
 
+    // tail scores (nvrx_tail_local, nvrx_tail.inl): the sample count the last report's statistics kernel was handed as an
+    // argument (-1: it read d_counts) -- the quantile kernel of that report must see the same window
+    int tail_uniform_n = -1;
+
     std::mutex mu;
 };
 
@@ -3213,6 +3217,7 @@ static int report_local_impl(nvrx_ctx *ctx, float *d_stats, float *d_send, int K
     int uniform_n = -1;
     rc = flush_locked(ctx, st, &uniform_n, rows_active);
     if (rc) return rc;
+    if (d_send) ctx->tail_uniform_n = uniform_n;  // (for nvrx_tail_local)
     report_clk(2);
     Epilogue ep{};
     ep.gid = ctx->d_gid;
@@ -3871,3 +3876,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 }  // extern "C"
 
 #include "nvrx_attribute.inl"
+#include "nvrx_tail.inl"

@@ -27,6 +27,7 @@ ERR_TIMEOUT = -62
 ERR_RANGE = -34
 ERR_INVALID = -22
 ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
+TAIL_Q_PPM_MIN, TAIL_Q_PPM_MAX = 500000, 999999  # the accepted range of a tail quantile, in parts per million
 
 
 
@@ -66,6 +67,8 @@ SYMBOLS = [
     ("nvrx_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p,
                            c_void_p, c_uint32, c_void_p, c_void_p, c_int, c_void_p]),
     ("nvrx_attribute", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_quantile", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_tail_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -99,6 +102,7 @@ SYMBOLS = [
     ("nvrx_report_local", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report", c_int, [c_void_p, POINTER(ReportDesc), c_void_p]),
     ("nvrx_report_attribute", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
+    ("nvrx_tail_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
     ("nvrx_peer_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -188,3 +192,23 @@ def score_len(S: int) -> int:
 def attr_words(n_ranks: int, top_n: int) -> int:
     """NVRX_ATTR_WORDS: 32-bit words of an attribution block ``[n_ranks][2][1 + top_n][4]``."""
     return n_ranks * 2 * (1 + top_n) * 4
+
+
+def tail_q_ppm(q) -> int:
+    """A tail quantile as the library carries it: ``round(q * 1e6)``; 0 / None = off, else within [0.5, 0.999999].
+    ``ValueError`` for anything else."""
+    if q is None:
+        return 0
+    try:
+        ppm = int(round(float(q) * 1e6))
+    except (TypeError, ValueError):
+        raise ValueError(f"tail_quantile must be a number: 0 (off) or within [0.5, 0.999999], got {q!r}") from None
+    if ppm != 0 and not TAIL_Q_PPM_MIN <= ppm <= TAIL_Q_PPM_MAX:
+        raise ValueError(f"tail_quantile must be 0 (off) or within [0.5, 0.999999], got {q!r}")
+    return ppm
+
+
+def tail_rank(q_ppm: int, n: int) -> int:
+    """Index, in the row sorted ascending, of the nearest-rank ``q_ppm / 1e6`` quantile of ``n >= 1`` samples:
+    ``ceil(q * n) - 1`` in integers, exactly as k_row_quantile computes it."""
+    return (q_ppm * n + 999999) // 1000000 - 1

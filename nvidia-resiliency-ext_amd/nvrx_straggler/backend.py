@@ -239,6 +239,35 @@ class Attribution:
         return self._host
 
 
+class Tails:
+    """Tail scores of one report (``nvrx_tail_local`` -> exchange -> ``nvrx_tail_score``), enqueued and not waited for: once
+    the score kernel has run, the workspace's tail buffer holds the gathered tail table ``[R][K+S]`` and, behind it, the
+    scores ``[n_ranks][1 + S]`` of the reported ranks.  ``records()`` waits for it and takes the private host copy (one
+    ordered D2H on the backend's stream): when a ``Report`` first asks, or -- ``Workspace.tail_settle`` -- before the next
+    report on the same workspace rewrites the table the kernel reads and the buffers it writes."""
+
+    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "q_ppm", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int,
+                 q_ppm: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.R, self.K, self.S = R, K, S
+        self.first_rank, self.n_ranks, self.q_ppm = first_rank, n_ranks, q_ppm
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(tails [n_ranks, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first call
+        waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.tails_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -344,6 +373,33 @@ class Workspace:
         """Before anything rewrites this workspace's table: the last attribution's kernel has run and its records are on the
         host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
         last, self._attr_last = self._attr_last, None
+        if last is not None:
+            last.records()
+
+    # ---- tail scores (off unless a ReportGenerator asks: nothing is allocated before) ----------------------------
+    _tail_buf = None      # device: tail table [R][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
+    _tail_send = None     # device: this process' tail rows [local_ranks][K+S] (the table's own rows without an exchange)
+    _tail_table = None    # ... the table part of _tail_buf as [R][K+S]
+    _tail_scratch = None  # device: column minima
+    _tail_last = None     # the Tails whose kernels may still be reading the table / writing the buffers
+
+    def tail_buffers(self):
+        """``(tail_send, tail_table, scores, scratch)`` (cold: allocated on first use)."""
+        if self._tail_buf is None:
+            KS, R = self.K + self.S, self.R
+            dev = self._backend.device
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._tail_buf = torch.empty(max(R * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
+                self._tail_table = self._tail_buf[: R * KS].view(R, KS)
+                self._tail_send = (self._tail_table if R == self.local_ranks
+                                   else torch.empty((self.local_ranks, KS), dtype=torch.float32, device=dev))
+                self._tail_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
+        return self._tail_send, self._tail_table, self._tail_buf[self.R * (self.K + self.S):], self._tail_scratch
+
+    def tail_settle(self) -> None:
+        """Before anything rewrites this workspace's table or tail buffers: the last tail step's kernels have run and
+        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        last, self._tail_last = self._tail_last, None
         if last is not None:
             last.records()
 
@@ -484,6 +540,44 @@ class HipBackend:
         host = np.empty((attr.n_ranks, 2, 1 + attr.top_n, 4), dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, attr.d_ptr, host.nbytes, self._stream_handle))
         return host
+
+    def tail_score(self, ws: Workspace, tails: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
+                   n_ranks: Optional[int] = None, q_ppm: int = 0) -> Tails:
+        """Relative tail scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered tail table ``tails``
+        ([R, K+S], ``Rings.tail_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
+        ``nvrx_tail_score`` enqueued on the backend's stream.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        _, tail_table, scores, scratch = ws.tail_buffers()
+        assert tails is tail_table or (tails.data_ptr() == tail_table.data_ptr())
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_tail_score(tail_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
+                                      scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._tail_last = Tails(self, ws._tail_buf, ws.R, ws.K, ws.S, first_rank, n_ranks, q_ppm)
+        return out
+
+    def tails_copy_out(self, t: Tails):
+        """The one wait of a report's tails: a D2H of the tail table and the scores on the backend's stream, behind the kernels."""
+        KS = t.K + t.S
+        n = t.R * KS + t.n_ranks * (1 + t.S)
+        host = np.empty(max(n, 1), dtype=np.float32)
+        if n:
+            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        tails = host[: t.R * KS].reshape(t.R, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        return tails, host[t.R * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+
+    def row_quantile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm: int) -> torch.Tensor:
+        """Stateless nearest-rank quantile on caller tensors ([rows, stride] f32, [rows] u32/i32) -> [rows] f32, -1.0 where
+        a row holds no sample (``nvrx_row_quantile``)."""
+        rows, stride = samples.shape
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(max(rows, 1), dtype=torch.float32, device=samples.device)
+            _native.check(self.lib.nvrx_row_quantile(samples.data_ptr(), counts.data_ptr(), rows, stride, int(q_ppm),
+                                                     out.data_ptr(), self.stream_handle))
+        self.stream.synchronize()
+        return out[:rows]
 
     def retire_workspace(self, ws: Workspace) -> None:
         """After a timed-out wait the kernels of ``ws`` may still be queued behind a collective: the workspace
@@ -774,6 +868,21 @@ class HipRings:
             _native.check(rc)
         out = ws._attr_last = Attribution(self.backend, buf, first_rank, n_ranks, top_n)
         return out
+
+    def tail_local(self, ws: Workspace, q_ppm: int, rows_active: int = 0, fused: bool = False):
+        """The ``q_ppm / 1e6`` quantile of every ring row as the report just issued on ``ws`` saw it, packed by gid into the
+        workspace's tail rows (``nvrx_tail_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s).
+        Returns ``(tail_send [local_ranks, K+S], tail_table [R, K+S])`` -- the same rows when nothing is exchanged.
+        Waits for the quantile kernel: the rings are emptied by count, and the next window's device-side writers on other
+        streams may overwrite slots as soon as the report call returns."""
+        ws.tail_settle()
+        send, table, _, _ = ws.tail_buffers()
+        rc = self.lib.nvrx_tail_local(self.ctx, ws.block.desc_ref if fused else None, int(q_ppm), send.data_ptr(), ws.K, ws.S,
+                                      rows_active, self.backend._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        self.backend.stream.synchronize()
+        return send, table
 
     def peek_stats(self) -> np.ndarray:
         """Statistics of every used row right now ([rows_used, 8] on the host); exchanges nothing and

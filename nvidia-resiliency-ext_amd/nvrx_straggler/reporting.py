@@ -625,6 +625,46 @@ def _copy_explanation(d: dict) -> dict:
     return {fam: {r: dict(v, kernels=[dict(k) for k in v["kernels"]]) for r, v in ranks.items()} for fam, ranks in d.items()}
 
 
+class _TailSource:
+    """What a report keeps of its tail scores: the backend's handle (``records()`` waits for the kernels and copies the tails
+    and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the kernel names
+    by id as the report's mapper had them at report time."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "q_ppm", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, q_ppm: int):
+        self.handle, self.ranks, self.kernels, self.q_ppm = handle, tuple(ranks), kernels, q_ppm
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            tails, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks = self.ranks
+            t, sc = tails.tolist(), scores.tolist()
+
+            def present(col):
+                return {r: t[i][col] for i, r in enumerate(ranks) if not t[i][col] == -1.0}
+
+            kernel_tails = {name: present(k) for k, name in enumerate(self.kernels)}
+            section_tails = {name: present(K + g) for name, g in self.sections.items()}
+            self._built = {
+                "quantile": self.q_ppm / 1e6,
+                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
+                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_tails": {n: v for n, v in section_tails.items() if v},
+                "kernel_tails": {n: v for n, v in kernel_tails.items() if v},
+            }
+            self.handle = None
+        return self._built
+
+
+def _copy_tails(d: dict) -> dict:
+    return {k: ({n: dict(v) if isinstance(v, dict) else v for n, v in val.items()} if isinstance(val, dict) else val)
+            for k, val in d.items()}
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -714,6 +754,9 @@ class Report:
         attr = self.__dict__.get("_attr")
         if attr is not None:
             state["_attr"] = attr.build() if isinstance(attr, _AttrSource) else attr  # plain dicts travel
+        tail = self.__dict__.get("_tail")
+        if tail is not None:
+            state["_tail"] = tail.build() if isinstance(tail, _TailSource) else tail
         return state
 
     def __setstate__(self, state) -> None:
@@ -736,6 +779,33 @@ class Report:
         if isinstance(attr, _AttrSource):
             attr = self.__dict__["_attr"] = attr.build()
         return _copy_explanation(attr)
+
+    def tail_scores(self) -> Dict[str, Any]:
+        """Tail scores (``ReportGenerator(tail_quantile=q)``; ``{}`` when the report carries none).  Every score of a report
+        compares medians and cannot see a rank that is slow on SOME iterations; these compare, the same way, the q-quantile
+        of every timing row (nearest rank: an actual sample).
+
+        ``{"quantile": q, "gpu_relative": {rank: score}, "section_relative": {section: {rank: score}}, "section_tails":
+        {section: {rank: the row's q-quantile, in the row's own unit}}, "kernel_tails": {kernel: {rank: microseconds}}}`` --
+        scores are the fastest rank's tail over this rank's (NaN where a rank lacks the row), ranks and sections as in the
+        score mappings, rows without samples are left out of the tails.  Plain dicts and floats.  The first call waits for
+        the tail kernels and copies their results; ``generate_report`` does not."""
+        tail = self.__dict__.get("_tail")
+        if tail is None:
+            return {}
+        if isinstance(tail, _TailSource):
+            tail = self.__dict__["_tail"] = tail.build()
+        return _copy_tails(tail)
+
+    def identify_tail_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose TAIL scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no tail scores."""
+        t = self.tail_scores()
+        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
+        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
+        return {"straggler_gpus_relative": self._ids(gr),
+                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
 
     def _ids(self, ranks) -> set:
         return {StragglerId(rank=r, node=self.rank_to_node[r]) for r in ranks}
@@ -888,7 +958,7 @@ class ReportGenerator:
 
     def __init__(self, scores_to_compute, gather_on_rank0=True, pg=None, node_name="<notset>",
                  thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
-                 kernel_attribution: int = 0) -> None:
+                 kernel_attribution: int = 0, tail_quantile: float = 0.0) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -939,6 +1009,19 @@ class ReportGenerator:
                 raise RuntimeError(f"kernel_attribution={n}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no kernel attribution (backend.attribute)")
         self._attr_names_cache = (None, 0, ())  # (mapper, kernel ids covered, names by id)
+        # tail scores: every ring report also carries the q-quantile of every row and relative scores built from them
+        # (Report.tail_scores); 0 = off: no buffer, no launch, no collective, no backend call.  The step adds one collective
+        # per report, so EVERY rank must pass the same value.
+        self.tail_q_ppm = _backend_mod._native.tail_q_ppm(tail_quantile)
+        if self.tail_q_ppm:
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"tail_quantile={tail_quantile!r} needs relative_perf_scores among scores_to_compute "
+                                 f"(got {scores_to_compute!r}): tail scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "tail_score"):
+                raise RuntimeError(f"tail_quantile={tail_quantile!r}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no tail scores (backend.tail_score)")
+        self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
     # ---- pieces kept from the reference's host logic ----------------------------------------------
@@ -1003,6 +1086,16 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
+        if self.tail_q_ppm:
+            # the tail step's collective is a torch.distributed call between two kernels: reports with tails stay on that
+            # route as a whole (the option has the same value on every rank, so every rank decides alike -- no collective here)
+            self._direct = None
+            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (tail_quantile is "
+                                           "set: reports with tail scores do not use the in-stream routes)", "mode": "c10d"}
+            if mode != "c10d":
+                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while tail_quantile is set: reports with tail scores "
+                             "run on torch.distributed's route (c10d)", mode)
+            return
         # c10d (the default) on ANY rank keeps every rank on torch.distributed (the decision has to be the same everywhere:
         # building a communicator is collective)
         if not dist_utils.is_all_true(mode != "c10d", self.group):
@@ -1114,6 +1207,8 @@ class ReportGenerator:
             ws = be.workspace(world * local_ranks, K, S, local_ranks, stats_rows)
             if getattr(ws, "_attr_last", None) is not None:
                 ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
+            if getattr(ws, "_tail_last", None) is not None:
+                ws.tail_settle()  # ... or a tail score kernel
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1302,6 +1397,9 @@ class ReportGenerator:
         attr_n = self.kernel_attribution
         if getattr(ws, "_attr_last", None) is not None:
             ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
+        if getattr(ws, "_tail_last", None) is not None:
+            ws.tail_settle()  # ... or a tail score kernel
+        self._last_plan_fused = fused
         if fused and attr_n and not hasattr(rings, "report_attribute"):
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
         if fused:
@@ -1372,6 +1470,32 @@ class ReportGenerator:
                                                           self.is_computing_rel_scores, lo, hi - lo)
         report.__dict__["_attr"] = self._attr_source(handle, ws, plan.mapper, lo, hi, plan.view.ranks)
 
+    # ---- tail scores --------------------------------------------------------------------------------
+    def _tail_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The tail step of a ring report, once per ``generate_report_from_rings`` call behind its last score round, on that
+        round's workspace: quantile kernel on the window the report saw -> [one all-gather of the tail rows] -> tail score
+        kernel for the ranks the report covers, hung on ``report`` unread.  Every rank issues it at every report, whatever
+        the report found and whether or not it holds a report (a gathering generator's other ranks): same collectives
+        everywhere."""
+        be = _backend_mod.get_backend()
+        if not hasattr(rings, "tail_local") or not hasattr(be, "tail_score"):
+            raise RuntimeError(f"tail_quantile={self.tail_q_ppm / 1e6}: the active backend has no tail scores "
+                               "(rings.tail_local / backend.tail_score)")
+        send, table = rings.tail_local(ws, self.tail_q_ppm, rows_active, fused)
+        if self.world_size > 1:
+            with be.stream_context():  # (behind the quantile kernel)
+                table = dist_utils.all_gather_rows(send, table, self.group)
+        if report is None or report is False:
+            return
+        if self.gather_on_rank0:
+            lo, hi = 0, ws.R
+        else:
+            lo = self.rank * local_ranks
+            hi = lo + local_ranks
+        view = report.__dict__["_src"].view
+        handle = be.tail_score(ws, table, ws.table, lo, hi - lo, self.tail_q_ppm)
+        report.__dict__["_tail"] = _TailSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), self.tail_q_ppm)
+
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],
                         kernel_summaries: Mapping[str, _SummaryType]):
@@ -1379,7 +1503,8 @@ class ReportGenerator:
 
         Collective.  Returns a :class:`Report`, or ``None`` on ranks other than 0 when
         ``gather_on_rank0`` is set.  The summaries are packed into this rank's exchange row on the
-        host; exchange and scoring run on the device exactly as in the ring path.
+        host; exchange and scoring run on the device exactly as in the ring path.  Summaries hold no samples: a report
+        of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``).
         """
         t0 = time.perf_counter_ns()
         self.world_size = dist_utils.get_world_size(self.group)
@@ -1449,6 +1574,8 @@ class ReportGenerator:
                 self._drop_plan()
                 raise
             if out is not False:
+                if self.tail_q_ppm:
+                    self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 return out
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
@@ -1461,7 +1588,10 @@ class ReportGenerator:
             known_k, known_s = plan.kernel_rows, plan.section_rows
             self._unreported_rows = ([r for n, r in kernel_rows.items() if n not in known_k and not is_collective_kernel(n)]
                                      + [r for n, r in section_rows.items() if n not in known_s])
-            return self._report_from_plan(plan, rings, t0, order_after, names_ok=False)
+            out = self._report_from_plan(plan, rings, t0, order_after, names_ok=False)
+            if self.tail_q_ppm:
+                self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+            return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
         self._maybe_gather_rank_to_node()
@@ -1487,6 +1617,8 @@ class ReportGenerator:
                                        stats_rows_used=stats_needed, sync_first=self._take_resync(), may_defer_sync=not_the_first)
         report = self._assemble(ws, mapper, snames, dict(section_rows), dict(kernel_rows), t0, local_ranks=local_ranks,
                                 stats=ws.stats[:stats_needed].copy())
+        if self.tail_q_ppm:  # (before the plan below re-points the ring rows)
+            self._tail_step(report, rings, ws, mapper, rows_used, False, local_ranks)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

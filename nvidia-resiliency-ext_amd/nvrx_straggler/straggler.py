@@ -158,6 +158,8 @@ class _Lane:
             return None
         if reporter.kernel_attribution:
             return None  # (the attribution launch follows the report in the generator's planned path: DESIGN.md, "Kernel attribution")
+        if reporter.tail_q_ppm:
+            return None  # (the tail step follows the report in the generator's paths: DESIGN.md, "Tail scores")
         ext = manager.cupti_ext
         ws = plan.ws
         if ws.block.desc_key is None or not ws.send_initialised:
@@ -380,6 +382,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         asynchronous: Optional[bool] = None,
         kernel_trace_budget_pct: Optional[float] = None,
         kernel_attribution: Optional[int] = None,
+        tail_quantile: Optional[float] = None,
     ):
         """
         Args:
@@ -407,6 +410,11 @@ class Detector(metaclass=_DeviceSideOnDemand):
             kernel_attribution: 0 = off; N in 1..16: every report also carries, per rank and GPU score, the N kernels with the
                 largest share of the score's deficit (``Report.explain_gpu_scores()``).  Default: ``NVRX_KERNEL_ATTRIBUTION``,
                 else 0.  Pass the same value on every rank (no collective depends on it).
+            tail_quantile: 0 = off; q in [0.5, 0.999999]: every report also carries the q-quantile of every section and kernel
+                row and relative scores built from them (``Report.tail_scores()``, ``Report.identify_tail_stragglers()``):
+                they show a rank that is slow on some iterations only, which median-based scores cannot.  Needs
+                ``relative_perf_scores``.  Default: ``NVRX_TAIL_QUANTILE``, else 0.  Pass the same value on EVERY rank (the
+                step adds one collective per report).
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -447,9 +455,11 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 kernel_attribution = int(os.environ.get("NVRX_KERNEL_ATTRIBUTION", "0") or 0)
             except ValueError:
                 raise ValueError("NVRX_KERNEL_ATTRIBUTION must be an integer: 0 (off) or 1..16") from None
+        if tail_quantile is None:
+            tail_quantile = os.environ.get("NVRX_TAIL_QUANTILE", "") or 0.0
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
-                                       kernel_attribution=kernel_attribution)
+                                       kernel_attribution=kernel_attribution, tail_quantile=tail_quantile)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
