@@ -31,6 +31,9 @@ A GPU that is slow only SOME of the time does not move a median: ``--slow-by int
 on every ``--slow-every``-th step of the slow rank only, and the lines above stay quiet.  With ``NVRX_TAIL_QUANTILE=0.9`` in
 the environment the report also compares the 0.9 quantile of every timing row across ranks (``Report.tail_scores()``) and
 the example prints whoever ``identify_tail_stragglers`` flags underneath.
+
+With ``NVRX_ROBUST_SCORES=1`` the report also rates every rank against the job's median and spread
+(``Report.robust_scores()``) and the example prints each GPU's z-score and whoever ``identify_robust_stragglers`` flags.
 """
 import argparse
 import os
@@ -128,6 +131,13 @@ def train(args) -> None:
                     if tail_found["straggler_gpus_relative"]:
                         print(f"step {step}: tail straggler_gpus_relative: "
                               f"{sorted((s.rank, s.node) for s in tail_found['straggler_gpus_relative'])}")
+                robust = report.robust_scores()  # {} unless NVRX_ROBUST_SCORES=1 asks for robust scores
+                if robust:
+                    print(f"step {step}: GPUs z against the job's median: { {r: round(z, 2) for r, z in robust['gpu_z'].items()} }")
+                    robust_found = report.identify_robust_stragglers()
+                    if robust_found["straggler_gpus_relative"]:
+                        print(f"step {step}: robust straggler_gpus_relative: "
+                              f"{sorted((s.rank, s.node) for s in robust_found['straggler_gpus_relative'])}")
                 print(f"step {step}: {straggler.Detector.gpu_telemetry_line()}", flush=True)
     if slow_ctx is not None:
         slow_ctx.__exit__(None, None, None)

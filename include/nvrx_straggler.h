@@ -159,6 +159,34 @@ int nvrx_row_quantile(const float *d_samples, const uint32_t *d_counts, int rows
 int nvrx_tail_score(const float *d_tails, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                     float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Robust scores: every rank against the job's median and spread.  Extends _compute_section_relative_scores /
+ * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
+ * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
+ *   d_table [R][L] as for nvrx_score.  Column c in [0, K+S) of its med part: v = table[r][c] is PRESENT iff v >= 0 (the -1
+ *   sentinel and NaN are absent).  Per column:
+ *      n      present values;
+ *      ctr    their LOWER median: the element of rank (n-1) >> 1 sorted by raw bit pattern (-0.0 < +0.0 < ... < +inf),
+ *             always an actual value;
+ *      mad    the lower median of the n deviations fabsf(v - ctr) (f32; a NaN deviation orders above +inf);
+ *      scale  fmaxf(1.4826f * mad, floor_rel * ctr): two f32 products and a maximum;
+ *      a column with n < min_ranks has no reference.
+ *   Per reported rank r in [first_rank, first_rank + n_ranks), two planes of 1 + S floats:
+ *      ratio, section s: f32 of the f64 quotient ctr / v (above 1: faster than the median);
+ *      z,     section s: f32 of the f64 (v - ctr) / scale;
+ *      NaN where v is absent or the column has no reference;
+ *      slot 0 (GPU): f32 of sum_k w_k * x_k / sum_k w_k in f64 over the kernels k < K with v present and a reference, x_k
+ *      the f64 ratio / z before rounding, w_k that rank's weights NUM*AVG in the table; NaN when no kernel is eligible.
+ *   Zero scales and infinities give IEEE results, never an error.
+ *   min_ranks >= 1; floor_rel finite, in [0, 1]: it keeps a column whose ranks agree to the last bit from turning a 0.1 %
+ *   difference into z = inf.
+ *   d_out  16-byte aligned, NVRX_ROBUST_WORDS(n_ranks, K, S) 32-bit words: K+S column records {f32 ctr, f32 mad, f32 scale,
+ *      u32 n} (the floats NaN where there is no reference; n is always written), then [n_ranks][2][1 + S] f32 {ratio, z}.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_ROBUST_MAX_RANKS 65536
+#define NVRX_ROBUST_WORDS(n_ranks, K, S) (4 * ((size_t)(K) + (S)) + (size_t)(n_ranks) * 2 * (1 + (size_t)(S)))
+int nvrx_robust_score(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks,
+                      float floor_rel, void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -334,6 +362,13 @@ int nvrx_report_attribute(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first
  * device-side writers on other streams may overwrite slots as soon as they are told to. */
 int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm, float *d_tail_send, int K, int S,
                     int rows_active, void *stream);
+/* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
+ * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
+ * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The
+ * host does not wait; copy d_out with a D2H on the context's stream, and do not let a later report rewrite the table before
+ * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_robust(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int min_ranks,
+                       float floor_rel, void *d_out);
 /* One report WINDOW in one call: what straggler.py:228-244 does around the report in the steady state -- wait for the
  * window's GPU measurements (torch.cuda.synchronize() + the profiler's get_stats there; here the kernel tracer's sync, or a
  * harvest of the region events), check that the set of rows holding samples is the one the caller's name tables were built

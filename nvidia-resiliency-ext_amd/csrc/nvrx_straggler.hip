@@ -3877,3 +3877,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 
 #include "nvrx_attribute.inl"
 #include "nvrx_tail.inl"
+#include "nvrx_robust.inl"

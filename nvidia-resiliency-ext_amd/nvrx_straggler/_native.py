@@ -28,6 +28,7 @@ ERR_RANGE = -34
 ERR_INVALID = -22
 ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
 TAIL_Q_PPM_MIN, TAIL_Q_PPM_MAX = 500000, 999999  # the accepted range of a tail quantile, in parts per million
+ROBUST_MAX_RANKS = 65536  # NVRX_ROBUST_MAX_RANKS
 
 
 
@@ -69,6 +70,7 @@ SYMBOLS = [
     ("nvrx_attribute", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_quantile", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_tail_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -103,6 +105,7 @@ SYMBOLS = [
     ("nvrx_report", c_int, [c_void_p, POINTER(ReportDesc), c_void_p]),
     ("nvrx_report_attribute", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_tail_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
     ("nvrx_peer_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -192,6 +195,11 @@ def score_len(S: int) -> int:
 def attr_words(n_ranks: int, top_n: int) -> int:
     """NVRX_ATTR_WORDS: 32-bit words of an attribution block ``[n_ranks][2][1 + top_n][4]``."""
     return n_ranks * 2 * (1 + top_n) * 4
+
+
+def robust_words(n_ranks: int, K: int, S: int) -> int:
+    """NVRX_ROBUST_WORDS: 32-bit words of a robust-score block: ``[K+S][4]`` column records, then ``[n_ranks][2][1 + S]``."""
+    return 4 * (K + S) + n_ranks * 2 * (1 + S)
 
 
 def tail_q_ppm(q) -> int:

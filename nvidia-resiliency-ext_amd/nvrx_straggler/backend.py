@@ -268,6 +268,37 @@ class Tails:
         return self._host
 
 
+class Robust:
+    """Robust scores of one report (``nvrx_robust_score`` / ``nvrx_report_robust``), enqueued and not waited for: once the
+    kernels have run, the workspace's device buffer holds the ``K+S`` column records ``{ctr, mad, scale, n}`` and, behind
+    them, ``[n_ranks][2][1 + S]`` f32 ``{ratio, z}`` of the reported ranks (include/nvrx_straggler.h).  ``records()`` waits
+    for them and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report`` first asks, or
+    -- ``Workspace.robust_settle`` -- before the next report on the same workspace rewrites the table the kernels read and
+    the buffer they write."""
+
+    __slots__ = ("backend", "d_ptr", "K", "S", "first_rank", "n_ranks", "min_ranks", "floor_rel", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, K: int, S: int, first_rank: int, n_ranks: int,
+                 min_ranks: int, floor_rel: float):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.K, self.S = K, S
+        self.first_rank, self.n_ranks = first_rank, n_ranks
+        self.min_ranks, self.floor_rel = min_ranks, floor_rel
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(cols [K+S, 4] uint32, scores [n_ranks, 2, 1 + S] f32)`` (private copies); the first call waits for the
+        kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.robust_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -400,6 +431,25 @@ class Workspace:
         """Before anything rewrites this workspace's table or tail buffers: the last tail step's kernels have run and
         their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
         last, self._tail_last = self._tail_last, None
+        if last is not None:
+            last.records()
+
+    # ---- robust scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
+    _robust_buf = None   # device: column records, then the scores of the last robust step of this workspace's table
+    _robust_last = None  # the Robust whose kernels may still be reading the table / writing _robust_buf
+
+    def robust_buffers(self, n_ranks: int):
+        """The records buffer for robust scores of ``n_ranks`` ranks (cold: allocated once per shape)."""
+        words = _native.robust_words(n_ranks, self.K, self.S)
+        if self._robust_buf is None or self._robust_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._robust_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return self._robust_buf
+
+    def robust_settle(self) -> None:
+        """Before anything rewrites this workspace's table: the last robust step's kernels have run and their results are
+        on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._robust_last = self._robust_last, None
         if last is not None:
             last.records()
 
@@ -566,6 +616,30 @@ class HipBackend:
             _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
         tails = host[: t.R * KS].reshape(t.R, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
         return tails, host[t.R * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+
+    def robust_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
+                     min_ranks: int = 4, floor_rel: float = 0.02) -> Robust:
+        """Robust scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank +
+        n_ranks)``: ``nvrx_robust_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        ws.robust_settle()
+        buf = ws.robust_buffers(n_ranks)
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_robust_score(table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel,
+                                        buf.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._robust_last = Robust(self, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
+        return out
+
+    def robust_copy_out(self, rb: Robust):
+        """The one wait of a report's robust scores: a D2H of the records on the backend's stream, behind the kernels."""
+        KS = rb.K + rb.S
+        n = _native.robust_words(rb.n_ranks, rb.K, rb.S)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, rb.d_ptr, n * 4, self._stream_handle))
+        cols = host[: 4 * KS].reshape(KS, 4).copy()
+        return cols, host[4 * KS :].view(np.float32).reshape(rb.n_ranks, 2, 1 + rb.S).copy()
 
     def row_quantile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm: int) -> torch.Tensor:
         """Stateless nearest-rank quantile on caller tensors ([rows, stride] f32, [rows] u32/i32) -> [rows] f32, -1.0 where
@@ -867,6 +941,19 @@ class HipRings:
         if rc < 0:
             _native.check(rc)
         out = ws._attr_last = Attribution(self.backend, buf, first_rank, n_ranks, top_n)
+        return out
+
+    def report_robust(self, ws: Workspace, first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 4,
+                      floor_rel: float = 0.02) -> Robust:
+        """Robust scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_robust``): enqueued
+        behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        ws.robust_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
+        buf = ws.robust_buffers(n_ranks)
+        rc = self.lib.nvrx_report_robust(self.ctx, ws.block.desc_ref, first_rank, n_ranks, min_ranks, floor_rel, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._robust_last = Robust(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
         return out
 
     def tail_local(self, ws: Workspace, q_ppm: int, rows_active: int = 0, fused: bool = False):

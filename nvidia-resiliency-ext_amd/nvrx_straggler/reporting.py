@@ -665,6 +665,45 @@ def _copy_tails(d: dict) -> dict:
             for k, val in d.items()}
 
 
+class _RobustSource:
+    """What a report keeps of its robust scores: the backend's handle (``records()`` waits for the kernels and copies the
+    column records and the scores out on first use), the ranks its rows stand for, the sections it shows with their ids,
+    and the kernel names by id as the report's mapper had them at report time."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "min_ranks", "floor", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, min_ranks: int, floor: float):
+        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
+        self.min_ranks, self.floor = min_ranks, floor
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            cols, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks = self.ranks
+            f = np.ascontiguousarray(cols).view(np.float32)[:, :3].tolist()
+            n = cols[:, 3].tolist()
+            sc = scores.tolist()
+            with_data = {name: n[k] for k, name in enumerate(self.kernels)}
+            with_data.update((name, n[K + g]) for name, g in self.sections.items())
+            self._built = {
+                "gpu_ratio": {r: sc[i][0][0] for i, r in enumerate(ranks)},
+                "gpu_z": {r: sc[i][1][0] for i, r in enumerate(ranks)},
+                "section_ratio": {name: {r: sc[i][0][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_z": {name: {r: sc[i][1][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_center": {name: f[K + g][0] for name, g in self.sections.items()},
+                "section_spread": {name: f[K + g][2] for name, g in self.sections.items()},
+                "kernel_center": {name: f[k][0] for k, name in enumerate(self.kernels)},
+                "ranks_with_data": with_data,
+                "min_ranks": self.min_ranks,
+                "floor": self.floor,
+            }
+            self.handle = None
+        return self._built
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -757,6 +796,9 @@ class Report:
         tail = self.__dict__.get("_tail")
         if tail is not None:
             state["_tail"] = tail.build() if isinstance(tail, _TailSource) else tail
+        robust = self.__dict__.get("_robust")
+        if robust is not None:
+            state["_robust"] = robust.build() if isinstance(robust, _RobustSource) else robust
         return state
 
     def __setstate__(self, state) -> None:
@@ -804,6 +846,37 @@ class Report:
         t = self.tail_scores()
         gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
         sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
+        return {"straggler_gpus_relative": self._ids(gr),
+                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def robust_scores(self) -> Dict[str, Any]:
+        """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
+        of a report divides the FASTEST rank's median by this rank's; these rate a rank against the job's own middle and
+        spread instead: per section and kernel the lower median ``ctr`` of the ranks that have the row, the median absolute
+        deviation ``mad`` around it, ``scale = max(1.4826 * mad, floor * ctr)``.
+
+        ``{"gpu_ratio": {rank: x}, "gpu_z": {rank: x}, "section_ratio": {section: {rank: ctr / median}}, "section_z":
+        {section: {rank: (median - ctr) / scale}}, "section_center": {section: ctr}, "section_spread": {section: scale},
+        "kernel_center": {kernel: microseconds}, "ranks_with_data": {section or kernel: ranks that have the row}, "min_ranks":
+        n, "floor": x}`` -- a ratio above 1 is faster than the median, a positive z slower; the GPU entries are the means of
+        the per-kernel ratios and z weighted by the microseconds spent in each kernel; NaN where a rank lacks the row or
+        fewer than ``min_ranks`` ranks have it.  Ranks and sections as in the score mappings.  Plain dicts and floats.  The
+        first call waits for the robust kernels and copies their results; ``generate_report`` does not."""
+        robust = self.__dict__.get("_robust")
+        if robust is None:
+            return {}
+        if isinstance(robust, _RobustSource):
+            robust = self.__dict__["_robust"] = robust.build()
+        return _copy_tails(robust)
+
+    def identify_robust_stragglers(self, gpu_z_threshold: float = 3.5, section_z_threshold: float = 3.5) -> Dict[str, Any]:
+        """Ranks whose robust z-scores lie strictly ABOVE the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  3.5 is the conventional cut-off for modified z-scores (Iglewicz and Hoaglin): a default, not a measurement.
+        Empty sets when the report carries no robust scores."""
+        t = self.robust_scores()
+        gr = [r for r, z in t.get("gpu_z", {}).items() if z > gpu_z_threshold]
+        sr = {n: [r for r, z in v.items() if z > section_z_threshold] for n, v in t.get("section_z", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
                 "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
 
@@ -958,7 +1031,8 @@ class ReportGenerator:
 
     def __init__(self, scores_to_compute, gather_on_rank0=True, pg=None, node_name="<notset>",
                  thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
-                 kernel_attribution: int = 0, tail_quantile: float = 0.0) -> None:
+                 kernel_attribution: int = 0, tail_quantile: float = 0.0, robust_scores: bool = False,
+                 robust_min_ranks: int = 4, robust_floor: float = 0.02) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1021,6 +1095,27 @@ class ReportGenerator:
             if be is not None and not hasattr(be, "tail_score"):
                 raise RuntimeError(f"tail_quantile={tail_quantile!r}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no tail scores (backend.tail_score)")
+        # robust scores: every report also rates each rank against the job's median and spread (Report.robust_scores); off: no
+        # buffer, no launch, no backend call.  They read the exchanged table only: no collective, so a mismatch between ranks
+        # cannot hang anything -- but every rank should pass the same value.
+        self.robust_scores = bool(robust_scores)
+        if self.robust_scores:
+            if isinstance(robust_min_ranks, bool) or not isinstance(robust_min_ranks, (int, np.integer)) or robust_min_ranks < 1:
+                raise ValueError(f"robust_min_ranks must be an integer >= 1, got {robust_min_ranks!r}")
+            try:
+                floor = float(robust_floor)
+            except (TypeError, ValueError):
+                raise ValueError(f"robust_floor must be a number within [0, 1], got {robust_floor!r}") from None
+            if not 0.0 <= floor <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"robust_floor must be within [0, 1], got {robust_floor!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"robust_scores needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "robust scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "robust_score"):
+                raise RuntimeError(f"robust_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no robust scores (backend.robust_score)")
+            self.robust_min_ranks, self.robust_floor = int(robust_min_ranks), floor
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -1209,6 +1304,8 @@ class ReportGenerator:
                 ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
             if getattr(ws, "_tail_last", None) is not None:
                 ws.tail_settle()  # ... or a tail score kernel
+            if getattr(ws, "_robust_last", None) is not None:
+                ws.robust_settle()  # ... or the robust kernels
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1258,6 +1355,10 @@ class ReportGenerator:
             handle = _backend_mod.get_backend().attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
                                                           self.is_computing_rel_scores, lo, hi - lo)
             report.__dict__["_attr"] = self._attr_source(handle, ws, mapper, lo, hi, view.ranks)
+        if self.robust_scores:
+            # likewise: enqueued behind the score kernel, waited for when the report is first asked
+            self._attach_robust(report, _backend_mod.get_backend().robust_score(
+                ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor), ws, mapper, view)
         if stats is None:
             # the caller's own summaries travel with the report, untouched
             report.__dict__["local_section_summaries"] = section_summaries
@@ -1399,9 +1500,13 @@ class ReportGenerator:
             ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
         if getattr(ws, "_tail_last", None) is not None:
             ws.tail_settle()  # ... or a tail score kernel
+        if getattr(ws, "_robust_last", None) is not None:
+            ws.robust_settle()  # ... or the robust kernels
         self._last_plan_fused = fused
         if fused and attr_n and not hasattr(rings, "report_attribute"):
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
+        if fused and self.robust_scores and not hasattr(rings, "report_robust"):
+            raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
         if fused:
             # ONE C call: flush -> statistics kernel -> [ncclAllGather] -> score kernel -> completion word
             wait = not self.asynchronous
@@ -1423,6 +1528,8 @@ class ReportGenerator:
                     (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
                 if attr_n:
                     self._attach_plan_attribution(report, plan, rings, True)
+                if self.robust_scores:
+                    self._attach_plan_robust(report, plan, rings, True)
                 return report
         else:
             rings.report_local(ws, True, rows_active=plan.rows_used)
@@ -1455,6 +1562,8 @@ class ReportGenerator:
             (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
         if attr_n:
             self._attach_plan_attribution(report, plan, rings, fused)
+        if self.robust_scores:
+            self._attach_plan_robust(report, plan, rings, fused)
         return report
 
     def _attach_plan_attribution(self, report, plan, rings, fused: bool) -> None:
@@ -1469,6 +1578,27 @@ class ReportGenerator:
             handle = _backend_mod.get_backend().attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
                                                           self.is_computing_rel_scores, lo, hi - lo)
         report.__dict__["_attr"] = self._attr_source(handle, ws, plan.mapper, lo, hi, plan.view.ranks)
+
+    # ---- robust scores ------------------------------------------------------------------------------
+    def _robust_min(self, ws) -> int:
+        """``robust_min_ranks``, but never more than the ranks the table has: a job smaller than that is rated against its own
+        median all the same (one rank: ratio 1, z 0)."""
+        return min(self.robust_min_ranks, ws.R)
+
+    def _attach_robust(self, report, handle, ws, mapper, view) -> None:
+        report.__dict__["_robust"] = _RobustSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
+                                                   self._robust_min(ws), self.robust_floor)
+
+    def _attach_plan_robust(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the robust scores of the planned report that was just issued, as ``_attach_plan_attribution`` does, for the
+        ranks the report covers, and hang them on ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        lo, hi = plan.view.layout[5], plan.view.layout[6]
+        if fused:
+            handle = rings.report_robust(ws, lo, hi - lo, self._robust_min(ws), self.robust_floor)
+        else:
+            handle = _backend_mod.get_backend().robust_score(ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor)
+        self._attach_robust(report, handle, ws, plan.mapper, plan.view)
 
     # ---- tail scores --------------------------------------------------------------------------------
     def _tail_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:

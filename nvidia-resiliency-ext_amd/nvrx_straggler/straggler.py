@@ -160,6 +160,8 @@ class _Lane:
             return None  # (the attribution launch follows the report in the generator's planned path: DESIGN.md, "Kernel attribution")
         if reporter.tail_q_ppm:
             return None  # (the tail step follows the report in the generator's paths: DESIGN.md, "Tail scores")
+        if getattr(reporter, "robust_scores", False):
+            return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         ext = manager.cupti_ext
         ws = plan.ws
         if ws.block.desc_key is None or not ws.send_initialised:
@@ -383,6 +385,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         kernel_trace_budget_pct: Optional[float] = None,
         kernel_attribution: Optional[int] = None,
         tail_quantile: Optional[float] = None,
+        robust_scores: Optional[bool] = None,
     ):
         """
         Args:
@@ -415,6 +418,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 they show a rank that is slow on some iterations only, which median-based scores cannot.  Needs
                 ``relative_perf_scores``.  Default: ``NVRX_TAIL_QUANTILE``, else 0.  Pass the same value on EVERY rank (the
                 step adds one collective per report).
+            robust_scores: every report also rates each rank against the job's MEDIAN and spread instead of its fastest rank
+                (``Report.robust_scores()``, ``Report.identify_robust_stragglers()``): one anomalously fast rank no longer
+                flags everybody else, and the cut-off follows the job's own scatter.  Needs ``relative_perf_scores``.
+                Default: ``NVRX_ROBUST_SCORES``, else off.  Pass the same value on every rank (no collective depends on it).
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -457,9 +464,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 raise ValueError("NVRX_KERNEL_ATTRIBUTION must be an integer: 0 (off) or 1..16") from None
         if tail_quantile is None:
             tail_quantile = os.environ.get("NVRX_TAIL_QUANTILE", "") or 0.0
+        if robust_scores is None:
+            robust_scores = os.environ.get("NVRX_ROBUST_SCORES", "0") not in ("", "0")
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
-                                       kernel_attribution=kernel_attribution, tail_quantile=tail_quantile)
+                                       kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
+                                       robust_scores=robust_scores)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
