@@ -34,6 +34,11 @@ the example prints whoever ``identify_tail_stragglers`` flags underneath.
 
 With ``NVRX_ROBUST_SCORES=1`` the report also rates every rank against the job's median and spread
 (``Report.robust_scores()``) and the example prints each GPU's z-score and whoever ``identify_robust_stragglers`` flags.
+
+A GPU that BECOMES slow late in a window does not move a median either: ``--slow-by onset`` makes the slow rank's stand-in
+kernel 1.5x longer from 70 % of every report window on.  With ``NVRX_ONSET_DETECTION=1`` the report also looks for the one
+step in every timing row that explains most of its variance (``Report.onset_scores()``) and the example prints whoever
+``identify_onset_stragglers`` flags, with how many samples ago the rank's largest shift happened.
 """
 import argparse
 import os
@@ -96,10 +101,12 @@ def train(args) -> None:
                 print(f"[rank {rank}] ROCm SMI refused to slow the GPU down ({e}); use --slow-by simulated", flush=True)
         with straggler.Detector.detection_section("fwd", profile_cuda=True):
             output = net(data)
-            if args.slow_by in ("simulated", "intermittent"):   # one kernel whose duration says how fast "this GPU" is
+            if args.slow_by in ("simulated", "intermittent", "onset"):   # one kernel whose duration says how fast "this GPU" is
                 slow = rank == args.slow_rank and step >= args.slow_from
                 if args.slow_by == "intermittent":
                     slow = slow and step % args.slow_every == 0
+                if args.slow_by == "onset":  # (a window: the steps behind one report up to and including the next one's)
+                    slow = slow and (step - 1) % args.report_interval >= 0.7 * args.report_interval
                 torch.cuda._sleep(int(args.simulated_cycles * (1.5 if slow else 1.0)))
         loss = loss_fn(output, target)
         optim.zero_grad()
@@ -138,6 +145,19 @@ def train(args) -> None:
                     if robust_found["straggler_gpus_relative"]:
                         print(f"step {step}: robust straggler_gpus_relative: "
                               f"{sorted((s.rank, s.node) for s in robust_found['straggler_gpus_relative'])}")
+                onsets = report.onset_scores()  # {} unless NVRX_ONSET_DETECTION=1 asks for onset scores
+                if onsets:
+                    print(f"step {step}: GPUs relative onset perf: { {r: round(s, 3) for r, s in onsets['gpu_relative'].items()} }")
+                    onset_found = report.identify_onset_stragglers(gpu_rel_threshold=args.threshold)
+                    if onset_found["straggler_gpus_relative"]:
+                        print(f"step {step}: onset straggler_gpus_relative: "
+                              f"{sorted((s.rank, s.node) for s in onset_found['straggler_gpus_relative'])}")
+                    for s in sorted(onset_found["straggler_gpus_relative"], key=lambda s: s.rank):
+                        rows = [(per[s.rank], name) for name, per in onsets["kernel_onsets"].items() if s.rank in per]
+                        if rows:
+                            rec, name = max(rows, key=lambda x: x[0]["shift"])
+                            print(f"step {step}:   rank {s.rank}: {name} became {rec['shift']:.2f}x slower {rec['samples_ago']} "
+                                  f"samples ago (of {rec['window']}; the step explains {rec['strength']:.2f} of the row's variance)")
                 print(f"step {step}: {straggler.Detector.gpu_telemetry_line()}", flush=True)
     if slow_ctx is not None:
         slow_ctx.__exit__(None, None, None)
@@ -161,7 +181,7 @@ def main() -> None:
     ap.add_argument("--threshold", type=float, default=0.75)
     ap.add_argument("--slow-rank", type=int, default=-1)
     ap.add_argument("--slow-from", type=int, default=300)
-    ap.add_argument("--slow-by", choices=["clock", "simulated", "intermittent"], default="clock")
+    ap.add_argument("--slow-by", choices=["clock", "simulated", "intermittent", "onset"], default="clock")
     ap.add_argument("--slow-every", type=int, default=5,
                     help="--slow-by intermittent: the slow rank's stand-in kernel is 1.5x longer on every N-th step only (with one "
                          "step in ten slow, a 0.9 quantile would sit on the last FAST sample)")

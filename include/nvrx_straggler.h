@@ -159,6 +159,43 @@ int nvrx_row_quantile(const float *d_samples, const uint32_t *d_counts, int rows
 int nvrx_tail_score(const float *d_tails, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                     float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Onset of a change in timing rows: SINCE WHEN a row is slow.  Extends the statistics of straggler.py:172-197, which are
+ * order statistics and do not look at the order of the samples.  Per row with n valid samples:
+ *   time order  sample i lives in slot (start + i) mod n, 0 <= start < n (a larger start is taken modulo n): start is 0 for a
+ *               ring that has not wrapped since its last reset, total % ring_cap for a wrapped one (then n == ring_cap);
+ *   pivoting    d_i = (f64)x_i - (f64)x_0; all sums below are f64 sums of d; T = sum of all d_i, C_t = sum of d_0 .. d_(t-1);
+ *   m           max(8, (min_seg_ppm * n + 999999) / 1000000) (64-bit integers), min_seg_ppm in [1, 500000];
+ *   D_t         t * (n - t) / n * (after_t - before_t)^2 for every split t in [m, n - m], before_t = C_t / t and
+ *               after_t = (T - C_t) / (n - t) the pivoted means of x[0..t) and x[t..n): the least-squares single change point;
+ *   t*          the split with the largest D_t, the lowest t on ties;
+ *   strength    D_t* / SST, SST = sum of (d_i - T / n)^2: the share of the row's variance that one step explains, in [0, 1].
+ * Row record, 16 bytes: {u32 ago = n - t*, f32 before = x_0 + before_t*, f32 after = x_0 + after_t*, f32 strength} -- "the
+ * change happened `ago` samples ago".
+ *   n == 0 (an absent row)      {0, -1, -1, -1};
+ *   T or SST not finite         {0, NaN, NaN, NaN};
+ *   0 < n < 2m (no onset)       {0, mean, mean, 0}, mean = x_0 + T / n;
+ *   SST == 0 (a constant row)   {n - m, x_0, x_0, 0}: t* = m.
+ * Effective shift of a record: e = f32 of the f64 quotient after / before (the record's f32 values) where
+ * strength >= min_strength and after > before > 0; 1.0 otherwise ("did not shift"); -1.0 for an absent row.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_starts [rows] or NULL (0 everywhere); d_out [rows] records, 16-byte aligned.  Stateless, like nvrx_row_quantile.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+int nvrx_row_onset(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride,
+                   uint32_t min_seg_ppm, void *d_out, void *stream);
+/* Relative onset scores.  d_onset [R][NVRX_ONSET_PLANES][K+S]: per rank six planes {e, before, after, strength, ago as f32,
+ * n as f32} per kernel id and section id (-1.0: none; n, the row's sample count, travels along so that "ago" can be read
+ * against the window of a rank other than one's own); only plane 0 is read.  Reference per column = the minimum of e over all R ranks, NaN if any
+ * rank has none.  Per reported rank [first_rank, first_rank + n_ranks), nvrx_tail_score's arithmetic on e:
+ *   d_out [n_ranks][1 + S] = {GPU onset score, section onset score[S]}
+ *   section s: f32 of the f64 quotient ref / e, NaN where either is missing;
+ *   GPU: f32 of sum_k w_k * (ref_k / e_k) / sum_k w_k in f64, w_k the weights NUM*AVG of that rank in d_table [R][L].
+ * Scores are in (0, 1]: 1 = "shifted no more than the steadiest rank"; a phase change of the whole job flags nobody.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(K+S) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_ONSET_PLANES 6
+int nvrx_onset_score(const float *d_onset, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                     float *d_colmin_scratch, float *d_out, void *stream);
+
 /* Robust scores: every rank against the job's median and spread.  Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
@@ -362,6 +399,17 @@ int nvrx_report_attribute(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first
  * device-side writers on other streams may overwrite slots as soon as they are told to. */
 int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm, float *d_tail_send, int K, int S,
                     int rows_active, void *stream);
+/* Onset scores on the rings.  nvrx_onset_enable(ctx, 1): from now on every report (nvrx_report_local with a d_send,
+ * nvrx_report, nvrx_window_report) snapshots, right after it has flushed the staged samples, the slot of every ring's oldest
+ * sample; 0 switches that off again.  With the switch off a report does nothing it did not do before.
+ * nvrx_onset_local: nvrx_row_onset on the rings as the report just issued saw them -- its counts, its ring starts, whatever
+ * has been pushed since -- packed by gid into d_onset_send [local_ranks][NVRX_ONSET_PLANES][K+S] (planes {e, before, after,
+ * strength, ago as f32, n as f32}; kernel ids first, then section ids; every slot is written, -1.0 where no row with samples has that gid).  min_strength
+ * in [0, 1].  Ordering, desc, rows_active and the caller's duty to wait are those of nvrx_tail_local.
+ * NVRX_ERR_STATE: not enabled, or no report was issued through this descriptor. */
+int nvrx_onset_enable(nvrx_ctx *ctx, int on);
+int nvrx_onset_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_seg_ppm, float min_strength,
+                     float *d_onset_send, int K, int S, int rows_active, void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

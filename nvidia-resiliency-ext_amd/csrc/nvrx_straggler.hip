@@ -156,6 +156,29 @@ __device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {
     v += dpp<DPP_BCAST31, 0xc>(0u, v);
     return v;
 }
+// one step of the f64 scan: both halves through the same DPP move, +0.0 in the lanes the step does not write
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ double dpp_f64_masked(double src) {
+    const uint64_t u = (uint64_t)__double_as_longlong(src);
+    const uint32_t lo = dpp<CTRL, ROW_MASK>(0u, (uint32_t)u), hi = dpp<CTRL, ROW_MASK>(0u, (uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+// inclusive prefix sum across the wave in f64, the steps of wave_scan_u32
+__device__ __forceinline__ double wave_scan_f64(double v) {
+    v += dpp_f64_masked<DPP_ROW_SHR1>(v);
+    v += dpp_f64_masked<DPP_ROW_SHR2>(v);
+    v += dpp_f64_masked<DPP_ROW_SHR4>(v);
+    v += dpp_f64_masked<DPP_ROW_SHR8>(v);
+    v += dpp_f64_masked<DPP_BCAST15, 0xa>(v);
+    v += dpp_f64_masked<DPP_BCAST31, 0xc>(v);
+    return v;
+}
+__device__ __forceinline__ double wave_last_f64(double v) {  // lane 63's value, in every lane
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 63);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 63);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
 
 struct Epilogue {
     const int32_t *gid;  // [rows] position in the exchange row, -1 = not exchanged; may be null
@@ -2062,6 +2085,14 @@ struct nvrx_ctx {
     // argument (-1: it read d_counts) -- the quantile kernel of that report must see the same window
     int tail_uniform_n = -1;
 
+    // onset scores (nvrx_onset_local, nvrx_onset.inl): while enabled, every report snapshots the slot of each ring's oldest
+    // sample (0 unless the window was longer than the ring) -- the onset kernel of that report walks the window in time order
+    bool onset_on = false;
+    bool onset_wrapped = false;           // the snapshot holds a start other than 0
+    int onset_rows = 0;                   // rows the snapshot covers (rows_hi at the report)
+    uint32_t *h_onset_starts = nullptr;   // pinned [rows]
+    uint32_t *d_onset_starts = nullptr;   // device [rows]
+
     std::mutex mu;
 };
 
@@ -2568,6 +2599,8 @@ int nvrx_ctx_destroy(nvrx_ctx *ctx) {
     if (ctx->report_ev) (void)hipEventDestroy(ctx->report_ev);
     if (ctx->attr_ev) (void)hipEventDestroy(ctx->attr_ev);
     if (ctx->attr_scratch) (void)hipFree(ctx->attr_scratch);
+    if (ctx->h_onset_starts) (void)hipHostFree(ctx->h_onset_starts);
+    if (ctx->d_onset_starts) (void)hipFree(ctx->d_onset_starts);
     {
         // score scratch of the streams this context's reports ran on (its own, the resident scorer's, every user stream
         // a report was re-homed onto): the device is idle, nothing reads it any more
@@ -3195,6 +3228,20 @@ int nvrx_stamp_end(nvrx_ctx *ctx, int row, int cpu_row, float cpu_value, void *s
 static int report_local_impl(nvrx_ctx *ctx, float *d_stats, float *d_send, int K, int S, int names_ok, int rows_active,
                              void *stream, unsigned long long *rowg, uint32_t epoch);
 
+// where every ring's oldest sample lives, as of this report (the lock is held)
+static void onset_snapshot_locked(nvrx_ctx *ctx) {
+    const uint64_t cap = (uint64_t)ctx->ring_cap;
+    bool any = false;
+    for (int r = 0; r < ctx->rows_hi; r++) {
+        const uint64_t total = ctx->total[(size_t)r];
+        const uint32_t s = total > cap ? (uint32_t)(total % cap) : 0u;
+        ctx->h_onset_starts[r] = s;
+        any = any || s != 0;
+    }
+    ctx->onset_rows = ctx->rows_hi;
+    ctx->onset_wrapped = any;
+}
+
 int nvrx_report_local(nvrx_ctx *ctx, float *d_stats, float *d_send, int K, int S, int names_ok, int rows_active,
                       void *stream) {
     if (ctx) {
@@ -3218,6 +3265,7 @@ static int report_local_impl(nvrx_ctx *ctx, float *d_stats, float *d_send, int K
     rc = flush_locked(ctx, st, &uniform_n, rows_active);
     if (rc) return rc;
     if (d_send) ctx->tail_uniform_n = uniform_n;  // (for nvrx_tail_local)
+    if (ctx->onset_on && d_send) onset_snapshot_locked(ctx);  // (for nvrx_onset_local)
     report_clk(2);
     Epilogue ep{};
     ep.gid = ctx->d_gid;
@@ -3877,4 +3925,5 @@ int nvrx_wait(nvrx_ctx *ctx) {
 
 #include "nvrx_attribute.inl"
 #include "nvrx_tail.inl"
+#include "nvrx_onset.inl"
 #include "nvrx_robust.inl"

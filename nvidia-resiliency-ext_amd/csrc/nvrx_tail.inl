@@ -146,7 +146,8 @@ __global__ __launch_bounds__(THREADS) void k_row_quantile(QuantArgs a) {
 }
 
 struct TailScoreArgs {
-    const float *tails;   // [R][KS]
+    const float *tails;   // [R][KS] with a pitch of ld floats
+    int ld;
     const float *table;   // [R][L]: the weights
     const float *colmin;  // [KS]
     int R, K, S;
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(TAIL_SCORE_THREADS) void k_tail_score(TailScoreArgs
     const int K = a.K, S = a.S, KS = K + S;
     const int L = NVRX_TABLE_LEN(K, S);
     const int r = a.first_rank + (int)blockIdx.x;
-    const float *__restrict__ tail = a.tails + (size_t)r * KS;
+    const float *__restrict__ tail = a.tails + (size_t)r * (size_t)a.ld;
     const float *__restrict__ wrow = a.table + (size_t)r * L + 2 * KS;
     float *__restrict__ out = a.out + (size_t)blockIdx.x * (size_t)(1 + S);
     const float NaN = __builtin_nanf("");
@@ -217,6 +218,32 @@ int quantile_launch(const QuantArgs &a, int blocks, hipStream_t st) {
     return NVRX_OK;
 }
 
+// column minima of a [R][KS] table whose rows are ld floats apart, then k_tail_score (arguments checked by the caller)
+int tail_score_launch(const float *d_tails, int ld, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                      float *d_colmin_scratch, float *d_out, hipStream_t st) {
+    const int KS = K + S;
+    if (KS > 0) {
+        // attr_colmin with the tail table's own pitch: every column of a [R][KS] table
+        if (R > 64) {
+            const int chunks = std::max(1, std::min(COLMIN_MAX_CHUNKS, (R + 63) / 64));
+            const int rows_per_chunk = (R + chunks - 1) / chunks;
+            float *part = d_colmin_scratch + KS;
+            hipLaunchKernelGGL(k_colmin_part, dim3((KS + 63) / 64, chunks), dim3(256), 0, st, d_tails, R, KS, ld, rows_per_chunk, part);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_colmin_finish, dim3((KS + 255) / 256), dim3(256), 0, st, part, chunks, KS, d_colmin_scratch);
+        } else {
+            hipLaunchKernelGGL(k_colmin, dim3((KS + 255) / 256), dim3(256), 0, st, d_tails, R, KS, ld, d_colmin_scratch);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    TailScoreArgs a{};
+    a.tails = d_tails, a.ld = ld, a.table = d_table, a.colmin = d_colmin_scratch;
+    a.R = R, a.K = K, a.S = S, a.first_rank = first_rank, a.out = d_out;
+    hipLaunchKernelGGL(k_tail_score, dim3(n_ranks), dim3(TAIL_SCORE_THREADS), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return NVRX_OK;
+}
+
 int tail_q_check(uint32_t q_ppm) {
     if (q_ppm < TAIL_Q_MIN || q_ppm > TAIL_Q_MAX)
         return fail(NVRX_ERR_RANGE, "q_ppm=%u outside [%u,%u]", q_ppm, TAIL_Q_MIN, TAIL_Q_MAX);
@@ -250,29 +277,8 @@ int nvrx_tail_score(const float *d_tails, const float *d_table, int R, int K, in
     if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
         return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
     if (!d_tails || !d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    const int KS = K + S;
-    if (KS > 0 && !d_colmin_scratch) return fail(NVRX_ERR_INVALID, "d_colmin_scratch is null");
-    hipStream_t st = as_stream(stream);
-    if (KS > 0) {
-        // attr_colmin with the tail table's own pitch: every column of a [R][KS] table
-        if (R > 64) {
-            const int chunks = std::max(1, std::min(COLMIN_MAX_CHUNKS, (R + 63) / 64));
-            const int rows_per_chunk = (R + chunks - 1) / chunks;
-            float *part = d_colmin_scratch + KS;
-            hipLaunchKernelGGL(k_colmin_part, dim3((KS + 63) / 64, chunks), dim3(256), 0, st, d_tails, R, KS, KS, rows_per_chunk, part);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_colmin_finish, dim3((KS + 255) / 256), dim3(256), 0, st, part, chunks, KS, d_colmin_scratch);
-        } else {
-            hipLaunchKernelGGL(k_colmin, dim3((KS + 255) / 256), dim3(256), 0, st, d_tails, R, KS, KS, d_colmin_scratch);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    TailScoreArgs a{};
-    a.tails = d_tails, a.table = d_table, a.colmin = d_colmin_scratch;
-    a.R = R, a.K = K, a.S = S, a.first_rank = first_rank, a.out = d_out;
-    hipLaunchKernelGGL(k_tail_score, dim3(n_ranks), dim3(TAIL_SCORE_THREADS), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return NVRX_OK;
+    if (K + S > 0 && !d_colmin_scratch) return fail(NVRX_ERR_INVALID, "d_colmin_scratch is null");
+    return tail_score_launch(d_tails, K + S, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out, as_stream(stream));
 }
 
 int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm, float *d_tail_send, int K, int S,

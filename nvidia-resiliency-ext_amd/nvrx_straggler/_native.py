@@ -29,6 +29,9 @@ ERR_INVALID = -22
 ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
 TAIL_Q_PPM_MIN, TAIL_Q_PPM_MAX = 500000, 999999  # the accepted range of a tail quantile, in parts per million
 ROBUST_MAX_RANKS = 65536  # NVRX_ROBUST_MAX_RANKS
+ONSET_SEG_PPM_MIN, ONSET_SEG_PPM_MAX = 1, 500000  # the accepted range of an onset's minimum segment, in parts per million
+ONSET_MIN_SEG_SAMPLES = 8  # ... and the segment's floor in samples
+ONSET_PLANES = 6  # NVRX_ONSET_PLANES: {e, before, after, strength, ago, n} per kernel id and section id
 
 
 
@@ -70,6 +73,8 @@ SYMBOLS = [
     ("nvrx_attribute", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_quantile", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_tail_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_onset", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_onset_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
@@ -105,6 +110,8 @@ SYMBOLS = [
     ("nvrx_report", c_int, [c_void_p, POINTER(ReportDesc), c_void_p]),
     ("nvrx_report_attribute", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_tail_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_onset_enable", c_int, [c_void_p, c_int]),
+    ("nvrx_onset_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
@@ -220,3 +227,21 @@ def tail_rank(q_ppm: int, n: int) -> int:
     """Index, in the row sorted ascending, of the nearest-rank ``q_ppm / 1e6`` quantile of ``n >= 1`` samples:
     ``ceil(q * n) - 1`` in integers, exactly as k_row_quantile computes it."""
     return (q_ppm * n + 999999) // 1000000 - 1
+
+
+def onset_seg_ppm(frac) -> int:
+    """An onset's minimum segment as the library carries it: ``round(frac * 1e6)``, within [0.000001, 0.5].  ``ValueError``
+    for anything else."""
+    try:
+        ppm = int(round(float(frac) * 1e6))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"onset_min_segment must be a number within [0.000001, 0.5], got {frac!r}") from None
+    if not ONSET_SEG_PPM_MIN <= ppm <= ONSET_SEG_PPM_MAX:
+        raise ValueError(f"onset_min_segment must be within [0.000001, 0.5], got {frac!r}")
+    return ppm
+
+
+def onset_min_segment(seg_ppm: int, n: int) -> int:
+    """Samples either side of an onset in a row of ``n``: ``max(8, ceil(seg_ppm * n / 1e6))`` in integers, exactly as
+    k_row_onset computes it.  A row shorter than twice that has no onset."""
+    return max(ONSET_MIN_SEG_SAMPLES, (seg_ppm * n + 999999) // 1000000)

@@ -268,6 +268,35 @@ class Tails:
         return self._host
 
 
+class Onsets:
+    """Onset scores of one report (``nvrx_onset_local`` -> exchange -> ``nvrx_onset_score``), enqueued and not waited for: once
+    the score kernel has run, the workspace's onset buffer holds the gathered onset table ``[R][6][K+S]`` (planes ``{e,
+    before, after, strength, ago, n}``) and, behind it, the scores ``[n_ranks][1 + S]`` of the reported ranks.  ``records()``
+    waits for it and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report`` first asks,
+    or -- ``Workspace.onset_settle`` -- before the next report on the same workspace rewrites the table the kernel reads
+    and the buffers it writes."""
+
+    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.R, self.K, self.S = R, K, S
+        self.first_rank, self.n_ranks = first_rank, n_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(onsets [n_ranks, 6, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first
+        call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.onsets_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Robust:
     """Robust scores of one report (``nvrx_robust_score`` / ``nvrx_report_robust``), enqueued and not waited for: once the
     kernels have run, the workspace's device buffer holds the ``K+S`` column records ``{ctr, mad, scale, n}`` and, behind
@@ -431,6 +460,35 @@ class Workspace:
         """Before anything rewrites this workspace's table or tail buffers: the last tail step's kernels have run and
         their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
         last, self._tail_last = self._tail_last, None
+        if last is not None:
+            last.records()
+
+    # ---- onset scores (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------
+    _onset_buf = None      # device: onset table [R][6][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
+    _onset_send = None     # device: this process' onset rows [local_ranks][6][K+S] (the table's own rows without an exchange)
+    _onset_table = None    # ... the table part of _onset_buf as [R][6 * (K+S)]
+    _onset_scratch = None  # device: column minima
+    _onset_last = None     # the Onsets whose kernels may still be reading the table / writing the buffers
+
+    def onset_buffers(self):
+        """``(onset_send, onset_table, scores, scratch)`` (cold: allocated on first use)."""
+        if self._onset_buf is None:
+            KS, R = self.K + self.S, self.R
+            P = _native.ONSET_PLANES
+            dev = self._backend.device
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._onset_buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
+                self._onset_table = self._onset_buf[: R * P * KS].view(R, P * KS)
+                self._onset_send = (self._onset_table if R == self.local_ranks
+                                    else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
+                self._onset_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
+        return (self._onset_send, self._onset_table, self._onset_buf[self.R * _native.ONSET_PLANES * (self.K + self.S):],
+                self._onset_scratch)
+
+    def onset_settle(self) -> None:
+        """Before anything rewrites this workspace's table or onset buffers: the last onset step's kernels have run and
+        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        last, self._onset_last = self._onset_last, None
         if last is not None:
             last.records()
 
@@ -616,6 +674,46 @@ class HipBackend:
             _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
         tails = host[: t.R * KS].reshape(t.R, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
         return tails, host[t.R * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+
+    def onset_score(self, ws: Workspace, onsets: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
+                    n_ranks: Optional[int] = None) -> Onsets:
+        """Relative onset scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered onset table ``onsets``
+        ([R, 6 * (K+S)], ``Rings.onset_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
+        ``nvrx_onset_score`` enqueued on the backend's stream.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        _, onset_table, scores, scratch = ws.onset_buffers()
+        assert onsets is onset_table or (onsets.data_ptr() == onset_table.data_ptr())
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_onset_score(onset_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
+                                       scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._onset_last = Onsets(self, ws._onset_buf, ws.R, ws.K, ws.S, first_rank, n_ranks)
+        return out
+
+    def onsets_copy_out(self, t: Onsets):
+        """The one wait of a report's onsets: a D2H of the onset table and the scores on the backend's stream, behind the kernels."""
+        KS, P = t.K + t.S, _native.ONSET_PLANES
+        n = t.R * P * KS + t.n_ranks * (1 + t.S)
+        host = np.empty(max(n, 1), dtype=np.float32)
+        if n:
+            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        onsets = host[: t.R * P * KS].reshape(t.R, P, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        return onsets, host[t.R * P * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+
+    def row_onset(self, samples: torch.Tensor, counts: torch.Tensor, min_seg_ppm: int,
+                  starts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Stateless onset operator on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) -> [rows, 4]
+        int32 records ``{ago, before, after, strength}`` (the last three are f32 bit patterns; ``nvrx_row_onset``)."""
+        rows, stride = samples.shape
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=samples.device)
+            _native.check(self.lib.nvrx_row_onset(samples.data_ptr(), counts.data_ptr(),
+                                                  starts.data_ptr() if starts is not None else None, rows, stride,
+                                                  int(min_seg_ppm), out.data_ptr(), self.stream_handle))
+        self.stream.synchronize()
+        return out[:rows]
 
     def robust_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
                      min_ranks: int = 4, floor_rel: float = 0.02) -> Robust:
@@ -966,6 +1064,29 @@ class HipRings:
         send, table, _, _ = ws.tail_buffers()
         rc = self.lib.nvrx_tail_local(self.ctx, ws.block.desc_ref if fused else None, int(q_ppm), send.data_ptr(), ws.K, ws.S,
                                       rows_active, self.backend._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        self.backend.stream.synchronize()
+        return send, table
+
+    onset_enabled = False
+
+    def onset_enable(self, on: bool = True) -> None:
+        """From now on every report also notes where each ring's oldest sample lives (``nvrx_onset_enable``): what
+        ``onset_local`` needs to walk the report's window in time order."""
+        _native.check(self.lib.nvrx_onset_enable(self.ctx, int(on)))
+        self.onset_enabled = bool(on)
+
+    def onset_local(self, ws: Workspace, min_seg_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
+        """The onset of every ring row as the report just issued on ``ws`` saw it, packed by gid into the workspace's onset
+        rows (``nvrx_onset_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s).  Returns
+        ``(onset_send [local_ranks, 6 * (K+S)], onset_table [R, 6 * (K+S)])`` -- the same rows when nothing is exchanged.
+        Waits for the onset kernel, for the reason ``tail_local`` waits for its own: the rings are emptied by count, and the
+        next window's device-side writers on other streams may overwrite slots as soon as the report call returns."""
+        ws.onset_settle()
+        send, table, _, _ = ws.onset_buffers()
+        rc = self.lib.nvrx_onset_local(self.ctx, ws.block.desc_ref if fused else None, int(min_seg_ppm), float(min_strength),
+                                       send.data_ptr(), ws.K, ws.S, rows_active, self.backend._stream_handle)
         if rc < 0:
             _native.check(rc)
         self.backend.stream.synchronize()

@@ -665,6 +665,56 @@ def _copy_tails(d: dict) -> dict:
             for k, val in d.items()}
 
 
+class _OnsetSource:
+    """What a report keeps of its onset scores: the backend's handle (``records()`` waits for the kernels and copies the onset
+    planes and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the kernel
+    names by id as the report's mapper had them at report time."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "seg_ppm", "min_strength", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, seg_ppm: int, min_strength: float):
+        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
+        self.seg_ppm, self.min_strength = seg_ppm, min_strength
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            onsets, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks = self.ranks
+            o, sc = onsets.tolist(), scores.tolist()
+
+            def present(col):
+                out = {}
+                for i, r in enumerate(ranks):
+                    e, before, after, strength, ago, n = (o[i][p][col] for p in range(6))
+                    if e != -1.0:  # (-1: the rank has no samples in this row)
+                        out[r] = {"shift": e, "before": before, "after": after, "strength": strength,
+                                  "samples_ago": int(ago), "window": int(n)}
+                return out
+
+            kernel_onsets = {name: present(k) for k, name in enumerate(self.kernels)}
+            section_onsets = {name: present(K + g) for name, g in self.sections.items()}
+            self._built = {
+                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
+                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_onsets": {n: v for n, v in section_onsets.items() if v},
+                "kernel_onsets": {n: v for n, v in kernel_onsets.items() if v},
+                "min_segment": self.seg_ppm / 1e6,
+                "min_strength": self.min_strength,
+            }
+            self.handle = None
+        return self._built
+
+
+def _copy_onsets(d: dict) -> dict:
+    def deep(v):
+        return {k: deep(x) for k, x in v.items()} if isinstance(v, dict) else v
+
+    return deep(d)
+
+
 class _RobustSource:
     """What a report keeps of its robust scores: the backend's handle (``records()`` waits for the kernels and copies the
     column records and the scores out on first use), the ranks its rows stand for, the sections it shows with their ids,
@@ -799,6 +849,9 @@ class Report:
         robust = self.__dict__.get("_robust")
         if robust is not None:
             state["_robust"] = robust.build() if isinstance(robust, _RobustSource) else robust
+        onset = self.__dict__.get("_onset")
+        if onset is not None:
+            state["_onset"] = onset.build() if isinstance(onset, _OnsetSource) else onset
         return state
 
     def __setstate__(self, state) -> None:
@@ -844,6 +897,37 @@ class Report:
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no tail scores."""
         t = self.tail_scores()
+        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
+        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
+        return {"straggler_gpus_relative": self._ids(gr),
+                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def onset_scores(self) -> Dict[str, Any]:
+        """Onset scores (``ReportGenerator(onset_detection=True)``; ``{}`` when the report carries none).  Medians, tails and
+        robust scores are order statistics; these look at the ORDER of a window's samples: per timing row the single split of
+        the time axis that explains most of the row's variance by one step (least squares), the means either side of it and
+        the share of the variance it explains.
+
+        ``{"gpu_relative": {rank: score}, "section_relative": {section: {rank: score}}, "section_onsets": {section: {rank:
+        {"shift", "before", "after", "strength", "samples_ago", "window"}}}, "kernel_onsets": {kernel: {rank: {...}}},
+        "min_segment": x, "min_strength": x}`` -- ``shift`` is ``after / before`` where the step is a slow-down that explains
+        at least ``min_strength`` of the row's variance, 1.0 otherwise; ``samples_ago`` of the row's ``window`` samples lie
+        behind the step; scores are the steadiest rank's shift over this rank's (NaN where a rank lacks the row): 1 = shifted
+        no more than the steadiest rank, so a phase change of the whole job flags nobody.  Ranks and sections as in the score
+        mappings, rows without samples are left out of the onsets.  Plain dicts and floats.  The first call waits for the
+        onset kernels and copies their results; ``generate_report`` does not."""
+        onset = self.__dict__.get("_onset")
+        if onset is None:
+            return {}
+        if isinstance(onset, _OnsetSource):
+            onset = self.__dict__["_onset"] = onset.build()
+        return _copy_onsets(onset)
+
+    def identify_onset_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose ONSET scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no onset scores."""
+        t = self.onset_scores()
         gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
         sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
@@ -1032,7 +1116,8 @@ class ReportGenerator:
     def __init__(self, scores_to_compute, gather_on_rank0=True, pg=None, node_name="<notset>",
                  thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
                  kernel_attribution: int = 0, tail_quantile: float = 0.0, robust_scores: bool = False,
-                 robust_min_ranks: int = 4, robust_floor: float = 0.02) -> None:
+                 robust_min_ranks: int = 4, robust_floor: float = 0.02, onset_detection: bool = False,
+                 onset_min_segment: float = 0.05, onset_min_strength: float = 0.5) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1116,6 +1201,26 @@ class ReportGenerator:
                 raise RuntimeError(f"robust_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no robust scores (backend.robust_score)")
             self.robust_min_ranks, self.robust_floor = int(robust_min_ranks), floor
+        # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
+        # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
+        # call.  The step adds one collective per report, so EVERY rank must pass the same value.
+        self.onset_seg_ppm = 0  # (0 = off)
+        if onset_detection:
+            seg_ppm = _backend_mod._native.onset_seg_ppm(onset_min_segment)
+            try:
+                strength = float(onset_min_strength)
+            except (TypeError, ValueError):
+                raise ValueError(f"onset_min_strength must be a number within [0, 1], got {onset_min_strength!r}") from None
+            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"onset_min_strength must be within [0, 1], got {onset_min_strength!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"onset_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "onset scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "onset_score"):
+                raise RuntimeError(f"onset_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no onset scores (backend.onset_score)")
+            self.onset_seg_ppm, self.onset_min_strength = seg_ppm, strength
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -1181,6 +1286,16 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
+        if self.onset_seg_ppm and not self.tail_q_ppm:
+            # the onset step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
+            # onsets stay on that route as a whole (the option has the same value on every rank: no collective here)
+            self._direct = None
+            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (onset_detection is "
+                                           "set: reports with onset scores do not use the in-stream routes)", "mode": "c10d"}
+            if mode != "c10d":
+                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while onset_detection is set: reports with onset scores "
+                             "run on torch.distributed's route (c10d)", mode)
+            return
         if self.tail_q_ppm:
             # the tail step's collective is a torch.distributed call between two kernels: reports with tails stay on that
             # route as a whole (the option has the same value on every rank, so every rank decides alike -- no collective here)
@@ -1306,6 +1421,8 @@ class ReportGenerator:
                 ws.tail_settle()  # ... or a tail score kernel
             if getattr(ws, "_robust_last", None) is not None:
                 ws.robust_settle()  # ... or the robust kernels
+            if getattr(ws, "_onset_last", None) is not None:
+                ws.onset_settle()  # ... or an onset score kernel
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1502,6 +1619,8 @@ class ReportGenerator:
             ws.tail_settle()  # ... or a tail score kernel
         if getattr(ws, "_robust_last", None) is not None:
             ws.robust_settle()  # ... or the robust kernels
+        if getattr(ws, "_onset_last", None) is not None:
+            ws.onset_settle()  # ... or an onset score kernel
         self._last_plan_fused = fused
         if fused and attr_n and not hasattr(rings, "report_attribute"):
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
@@ -1626,6 +1745,32 @@ class ReportGenerator:
         handle = be.tail_score(ws, table, ws.table, lo, hi - lo, self.tail_q_ppm)
         report.__dict__["_tail"] = _TailSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), self.tail_q_ppm)
 
+    # ---- onset scores -------------------------------------------------------------------------------
+    def _onset_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The onset step of a ring report, once per ``generate_report_from_rings`` call behind its last score round (and
+        behind the tail step, when both are on), on that round's workspace: onset kernel on the window the report saw -> [one
+        all-gather of the onset rows] -> onset score kernel for the ranks the report covers, hung on ``report`` unread.
+        Every rank issues it at every report, whatever the report found and whether or not it holds a report (a gathering
+        generator's other ranks): same collectives everywhere."""
+        be = _backend_mod.get_backend()
+        if not hasattr(rings, "onset_local") or not hasattr(be, "onset_score"):
+            raise RuntimeError("onset_detection: the active backend has no onset scores (rings.onset_local / backend.onset_score)")
+        send, table = rings.onset_local(ws, self.onset_seg_ppm, self.onset_min_strength, rows_active, fused)
+        if self.world_size > 1:
+            with be.stream_context():  # (behind the onset kernel)
+                table = dist_utils.all_gather_rows(send, table, self.group)
+        if report is None or report is False:
+            return
+        if self.gather_on_rank0:
+            lo, hi = 0, ws.R
+        else:
+            lo = self.rank * local_ranks
+            hi = lo + local_ranks
+        view = report.__dict__["_src"].view
+        handle = be.onset_score(ws, table, ws.table, lo, hi - lo)
+        report.__dict__["_onset"] = _OnsetSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
+                                                 self.onset_seg_ppm, self.onset_min_strength)
+
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],
                         kernel_summaries: Mapping[str, _SummaryType]):
@@ -1634,7 +1779,8 @@ class ReportGenerator:
         Collective.  Returns a :class:`Report`, or ``None`` on ranks other than 0 when
         ``gather_on_rank0`` is set.  The summaries are packed into this rank's exchange row on the
         host; exchange and scoring run on the device exactly as in the ring path.  Summaries hold no samples: a report
-        of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``).
+        of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``) and no onset scores
+        (``onset_detection``; ``Report.onset_scores()`` is ``{}``).
         """
         t0 = time.perf_counter_ns()
         self.world_size = dist_utils.get_world_size(self.group)
@@ -1686,6 +1832,10 @@ class ReportGenerator:
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
+        if self.onset_seg_ppm and not getattr(rings, "onset_enabled", False):
+            if not hasattr(rings, "onset_enable"):
+                raise RuntimeError("onset_detection: the active backend has no onset scores (rings.onset_enable)")
+            rings.onset_enable(True)  # (before this window's report: it notes where every ring's oldest sample lives)
         if not self._direct_tried and self.world_size != 1:  # (a single process has no route to build)
             self._maybe_create_direct_exchange()
         if self._inflight is not None and self._settle_inflight():
@@ -1706,6 +1856,8 @@ class ReportGenerator:
             if out is not False:
                 if self.tail_q_ppm:
                     self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+                if self.onset_seg_ppm:
+                    self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 return out
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
@@ -1721,6 +1873,8 @@ class ReportGenerator:
             out = self._report_from_plan(plan, rings, t0, order_after, names_ok=False)
             if self.tail_q_ppm:
                 self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+            if self.onset_seg_ppm:
+                self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
@@ -1749,6 +1903,8 @@ class ReportGenerator:
                                 stats=ws.stats[:stats_needed].copy())
         if self.tail_q_ppm:  # (before the plan below re-points the ring rows)
             self._tail_step(report, rings, ws, mapper, rows_used, False, local_ranks)
+        if self.onset_seg_ppm:
+            self._onset_step(report, rings, ws, mapper, rows_used, False, local_ranks)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

@@ -160,6 +160,8 @@ class _Lane:
             return None  # (the attribution launch follows the report in the generator's planned path: DESIGN.md, "Kernel attribution")
         if reporter.tail_q_ppm:
             return None  # (the tail step follows the report in the generator's paths: DESIGN.md, "Tail scores")
+        if getattr(reporter, "onset_seg_ppm", 0):
+            return None  # (the onset step follows the report in the generator's paths: DESIGN.md, "Onset scores")
         if getattr(reporter, "robust_scores", False):
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         ext = manager.cupti_ext
@@ -386,6 +388,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
         kernel_attribution: Optional[int] = None,
         tail_quantile: Optional[float] = None,
         robust_scores: Optional[bool] = None,
+        onset_detection: Optional[bool] = None,
+        onset_min_segment: float = 0.05,
+        onset_min_strength: float = 0.5,
     ):
         """
         Args:
@@ -422,6 +427,16 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 (``Report.robust_scores()``, ``Report.identify_robust_stragglers()``): one anomalously fast rank no longer
                 flags everybody else, and the cut-off follows the job's own scatter.  Needs ``relative_perf_scores``.
                 Default: ``NVRX_ROBUST_SCORES``, else off.  Pass the same value on every rank (no collective depends on it).
+            onset_detection: every report also says SINCE WHEN a rank is slow: per section and kernel row the single step in
+                the window's samples, in time order, that explains most of their variance, and relative scores built from the
+                shifts (``Report.onset_scores()``, ``Report.identify_onset_stragglers()``).  A rank that became 1.5 x slower
+                70 % of the way through a window leaves the median where it was; here it shows with the number of samples
+                since the change.  Needs ``relative_perf_scores``.  Default: ``NVRX_ONSET_DETECTION``, else off.  Pass the
+                same values on EVERY rank (the step adds one collective per report).
+            onset_min_segment: the shortest stretch either side of a step, as a share of the row's samples, within
+                [0.000001, 0.5]; never fewer than 8 samples.
+            onset_min_strength: a step counts as a shift when it explains at least this share of the row's variance, within
+                [0, 1].  0.5 is a default, not a measurement.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -466,10 +481,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
             tail_quantile = os.environ.get("NVRX_TAIL_QUANTILE", "") or 0.0
         if robust_scores is None:
             robust_scores = os.environ.get("NVRX_ROBUST_SCORES", "0") not in ("", "0")
+        if onset_detection is None:
+            onset_detection = os.environ.get("NVRX_ONSET_DETECTION", "0") not in ("", "0")
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
-                                       robust_scores=robust_scores)
+                                       robust_scores=robust_scores, onset_detection=onset_detection,
+                                       onset_min_segment=onset_min_segment, onset_min_strength=onset_min_strength)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
