@@ -39,6 +39,11 @@ A GPU that BECOMES slow late in a window does not move a median either: ``--slow
 kernel 1.5x longer from 70 % of every report window on.  With ``NVRX_ONSET_DETECTION=1`` the report also looks for the one
 step in every timing row that explains most of its variance (``Report.onset_scores()``) and the example prints whoever
 ``identify_onset_stragglers`` flags, with how many samples ago the rank's largest shift happened.
+
+``--slow-by intermittent --slow-every N`` is also a BEAT: the slow rank stalls on every N-th step.  With
+``NVRX_PERIOD_DETECTION=1`` the report folds every timing row over every period up to a quarter of its samples
+(``Report.period_scores()``) and the example prints whoever ``identify_period_stragglers`` flags, with the period of the
+rank's largest excess and how many samples ago its slow phase last occurred.
 """
 import argparse
 import os
@@ -158,6 +163,20 @@ def train(args) -> None:
                             rec, name = max(rows, key=lambda x: x[0]["shift"])
                             print(f"step {step}:   rank {s.rank}: {name} became {rec['shift']:.2f}x slower {rec['samples_ago']} "
                                   f"samples ago (of {rec['window']}; the step explains {rec['strength']:.2f} of the row's variance)")
+                periods = report.period_scores()  # {} unless NVRX_PERIOD_DETECTION=1 asks for period scores
+                if periods:
+                    print(f"step {step}: GPUs relative period perf: { {r: round(s, 3) for r, s in periods['gpu_relative'].items()} }")
+                    period_found = report.identify_period_stragglers(gpu_rel_threshold=args.threshold)
+                    if period_found["straggler_gpus_relative"]:
+                        print(f"step {step}: period straggler_gpus_relative: "
+                              f"{sorted((s.rank, s.node) for s in period_found['straggler_gpus_relative'])}")
+                    for s in sorted(period_found["straggler_gpus_relative"], key=lambda s: s.rank):
+                        rows = [(per[s.rank], name) for name, per in periods["kernel_periods"].items() if s.rank in per]
+                        if rows:
+                            rec, name = max(rows, key=lambda x: x[0]["excess"])
+                            print(f"step {step}:   rank {s.rank}: {name} is {rec['excess']:.2f}x slower every {rec['period']} samples, "
+                                  f"last {rec['samples_ago']} samples ago (of {rec['window']}; the beat explains {rec['strength']:.2f} "
+                                  f"of the row's variance)")
                 print(f"step {step}: {straggler.Detector.gpu_telemetry_line()}", flush=True)
     if slow_ctx is not None:
         slow_ctx.__exit__(None, None, None)

@@ -196,7 +196,54 @@ int nvrx_row_onset(const float *d_samples, const uint32_t *d_counts, const uint3
 int nvrx_onset_score(const float *d_onset, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                      float *d_colmin_scratch, float *d_out, void *stream);
 
-/* Robust scores: every rank against the job's median and spread.  Extends _compute_section_relative_scores /
+/* Period of timing rows: whether a row is slow ON A BEAT -- a stall every P-th sample (a data-loader refill, a host-side GC, a
+ * log flush, a per-rank checkpoint shard).  Medians, tails, robust scores and onsets cannot see it: one slow sample in fifty
+ * moves no median and no 0.95-quantile, and a spike train is no step.  Per row with n valid samples:
+ *   time order  as for nvrx_row_onset: sample i lives in slot (start + i) mod n;
+ *   pivoting    d_i = (f64)x_i - (f64)x_0; all sums below are f64 sums of d; T = sum of all d_i, SST = sum of (d_i - T / n)^2;
+ *   candidates  P in [2, Pmax], Pmax = min(max_period, n / NVRX_PERIOD_MIN_CYCLES) (integer division; fewer than four
+ *               repetitions are not a beat), max_period in [2, NVRX_PERIOD_MAX];
+ *   fold at P   the phase of sample i is i mod P; S_f = the sum of the d_i of phase f, n_f their count;
+ *               B_P = sum_f S_f^2 / n_f - T^2 / n; eta2_P = B_P / SST, the share of the row's variance that the P phase
+ *               means explain; a_P = 1 - (1 - eta2_P) * (n - 1) / (n - P), the adjusted R^2 (unadjusted, pure noise explains
+ *               (P - 1) / (n - 1));
+ *   P*          a_max = the largest a_P; no period if a_max <= 0; else the SMALLEST P with a_P >= NVRX_PERIOD_BAR * a_max (a
+ *               fold at any multiple of the true period explains as much as the true one, a divisor P / k at most 1 / k:
+ *               the rule lands on the fundamental.  0.95 is a rule, not a measurement);
+ *   at P*       f* = the phase with the largest mean S_f / n_f (the lowest f on ties); peak = x_0 + S_f* / n_f*;
+ *               rest = x_0 + (T - S_f*) / (n - n_f*); ago = (n - 1 - f*) mod P*, the samples since the slow phase last occurred;
+ *               strength = a_P*.
+ * Row record, 16 bytes: {u32 period | ago << 16, f32 peak, f32 rest, f32 strength}.
+ *   n == 0 (an absent row)        {0, -1, -1, -1};
+ *   T or SST not finite           {0, NaN, NaN, NaN};
+ *   Pmax < 2, or a_max <= 0       {0, mean, mean, 0}, mean = x_0 + T / n;
+ *   SST == 0 (a constant row)     {0, x_0, x_0, 0}.
+ * Effective excess of a record: e = f32 of the f64 quotient peak / rest (the record's f32 values) where period > 0,
+ * strength >= min_strength and peak > rest > 0; 1.0 otherwise ("no beat"); -1.0 for an absent row.
+ * Periods are counted in samples of that row: report-window samples, traced entries with a thinned tracer.  Only the
+ * strongest beat of a row is reported, and a row that also stepped has an SST the step dominates: its beat reads weak.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_starts [rows] or NULL (0 everywhere); d_out [rows] records, 16-byte aligned.  Stateless, like nvrx_row_onset.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_PERIOD_MIN_CYCLES 4
+#define NVRX_PERIOD_MAX 4096
+#define NVRX_PERIOD_BAR 0.95
+int nvrx_row_period(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride,
+                    int max_period, void *d_out, void *stream);
+/* Relative period scores.  d_period [R][NVRX_PERIOD_PLANES][K+S]: per rank seven planes {e, peak, rest, strength, period as
+ * f32, ago as f32, n as f32} per kernel id and section id (-1.0: none); only plane 0 is read.  Reference per column = the
+ * minimum of e over all R ranks, NaN if any rank has none.  Per reported rank [first_rank, first_rank + n_ranks),
+ * nvrx_tail_score's arithmetic on e, exactly as nvrx_onset_score:
+ *   d_out [n_ranks][1 + S] = {GPU period score, section period score[S]}
+ * Scores are in (0, 1]: 1 = "stalls no more than the steadiest rank"; a beat of the whole job (an eval, a checkpoint every
+ * rank takes) flags nobody.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(K+S) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_PERIOD_PLANES 7
+int nvrx_period_score(const float *d_period, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                      float *d_colmin_scratch, float *d_out, void *stream);
+
+/* Robust scores: every rank against the job's median and spread. Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
  *   d_table [R][L] as for nvrx_score.  Column c in [0, K+S) of its med part: v = table[r][c] is PRESENT iff v >= 0 (the -1
@@ -406,10 +453,20 @@ int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm,
  * has been pushed since -- packed by gid into d_onset_send [local_ranks][NVRX_ONSET_PLANES][K+S] (planes {e, before, after,
  * strength, ago as f32, n as f32}; kernel ids first, then section ids; every slot is written, -1.0 where no row with samples has that gid).  min_strength
  * in [0, 1].  Ordering, desc, rows_active and the caller's duty to wait are those of nvrx_tail_local.
- * NVRX_ERR_STATE: not enabled, or no report was issued through this descriptor. */
+ * NVRX_ERR_STATE: not enabled, or no report was issued through this descriptor.
+ * The snapshot nvrx_onset_enable switches on is also what nvrx_period_local walks its windows by: a caller that wants period
+ * scores enables it whether or not it wants onsets. */
 int nvrx_onset_enable(nvrx_ctx *ctx, int on);
 int nvrx_onset_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_seg_ppm, float min_strength,
                      float *d_onset_send, int K, int S, int rows_active, void *stream);
+/* Period scores on the rings: nvrx_row_period on the rings as the report just issued saw them -- its counts, its ring starts
+ * (the snapshot of nvrx_onset_enable), whatever has been pushed since -- packed by gid into d_period_send
+ * [local_ranks][NVRX_PERIOD_PLANES][K+S] (planes {e, peak, rest, strength, period as f32, ago as f32, n as f32}; kernel ids
+ * first, then section ids; every slot is written, -1.0 where no row with samples has that gid).  max_period in
+ * [2, NVRX_PERIOD_MAX], min_strength in [0, 1].  Ordering, desc, rows_active and the caller's duty to wait are those of
+ * nvrx_onset_local.  NVRX_ERR_STATE: the snapshot is not enabled, or no report was issued through this descriptor. */
+int nvrx_period_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, int max_period, float min_strength,
+                      float *d_period_send, int K, int S, int rows_active, void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

@@ -3927,3 +3927,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_tail.inl"
 #include "nvrx_onset.inl"
 #include "nvrx_robust.inl"
+#include "nvrx_period.inl"

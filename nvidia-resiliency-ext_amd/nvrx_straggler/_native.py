@@ -32,6 +32,9 @@ ROBUST_MAX_RANKS = 65536  # NVRX_ROBUST_MAX_RANKS
 ONSET_SEG_PPM_MIN, ONSET_SEG_PPM_MAX = 1, 500000  # the accepted range of an onset's minimum segment, in parts per million
 ONSET_MIN_SEG_SAMPLES = 8  # ... and the segment's floor in samples
 ONSET_PLANES = 6  # NVRX_ONSET_PLANES: {e, before, after, strength, ago, n} per kernel id and section id
+PERIOD_MAX = 4096  # NVRX_PERIOD_MAX: the largest max_period
+PERIOD_MIN_CYCLES = 4  # NVRX_PERIOD_MIN_CYCLES: a period repeats at least that often within its row
+PERIOD_PLANES = 7  # NVRX_PERIOD_PLANES: {e, peak, rest, strength, period, ago, n} per kernel id and section id
 
 
 
@@ -75,6 +78,8 @@ SYMBOLS = [
     ("nvrx_tail_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_onset", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_onset_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_period", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("nvrx_period_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
@@ -112,6 +117,7 @@ SYMBOLS = [
     ("nvrx_tail_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_onset_enable", c_int, [c_void_p, c_int]),
     ("nvrx_onset_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_period_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
@@ -245,3 +251,17 @@ def onset_min_segment(seg_ppm: int, n: int) -> int:
     """Samples either side of an onset in a row of ``n``: ``max(8, ceil(seg_ppm * n / 1e6))`` in integers, exactly as
     k_row_onset computes it.  A row shorter than twice that has no onset."""
     return max(ONSET_MIN_SEG_SAMPLES, (seg_ppm * n + 999999) // 1000000)
+
+
+def period_max(value) -> int:
+    """A report's largest candidate period as the library carries it: an integer within [2, 4096].  ``ValueError`` for
+    anything else."""
+    try:
+        p = int(value)
+        if p != value:
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"period_max must be an integer within [2, {PERIOD_MAX}], got {value!r}") from None
+    if not 2 <= p <= PERIOD_MAX:
+        raise ValueError(f"period_max must be within [2, {PERIOD_MAX}], got {value!r}")
+    return p

@@ -25,7 +25,8 @@ class FoldedJob:
                  ring_cap: int = 8192, scores_to_compute=("relative_perf_scores", "individual_perf_scores"),
                  gather_on_rank0: bool = True, pg=None, node_name: str = "node", kernel_attribution: int = 0,
                  tail_quantile: float = 0.0, robust_scores: bool = False, asynchronous: bool = False,
-                 onset_detection: bool = False, onset_min_segment: float = 0.05, onset_min_strength: float = 0.5):
+                 onset_detection: bool = False, onset_min_segment: float = 0.05, onset_min_strength: float = 0.5,
+                 period_detection: bool = False, period_max: int = 1024, period_min_strength: float = 0.5):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -40,7 +41,8 @@ class FoldedJob:
                                         kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
                                         robust_scores=robust_scores, asynchronous=asynchronous,
                                         onset_detection=onset_detection, onset_min_segment=onset_min_segment,
-                                        onset_min_strength=onset_min_strength)
+                                        onset_min_strength=onset_min_strength, period_detection=period_detection,
+                                        period_max=period_max, period_min_strength=period_min_strength)
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         self._no_kernel_rows = {}  # same object every report so the reporter's cached plan stays valid
 

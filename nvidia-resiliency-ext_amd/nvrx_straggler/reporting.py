@@ -715,6 +715,49 @@ def _copy_onsets(d: dict) -> dict:
     return deep(d)
 
 
+class _PeriodSource:
+    """What a report keeps of its period scores: the backend's handle (``records()`` waits for the kernels and copies the
+    period planes and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the
+    kernel names by id as the report's mapper had them at report time."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "max_period", "min_strength", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, max_period: int, min_strength: float):
+        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
+        self.max_period, self.min_strength = max_period, min_strength
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            periods, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks = self.ranks
+            o, sc = periods.tolist(), scores.tolist()
+
+            def present(col):
+                out = {}
+                for i, r in enumerate(ranks):
+                    e, peak, rest, strength, period, ago, n = (o[i][p][col] for p in range(7))
+                    if e != -1.0:  # (-1: the rank has no samples in this row)
+                        out[r] = {"period": int(period), "samples_ago": int(ago), "peak": peak, "rest": rest, "excess": e,
+                                  "strength": strength, "window": int(n)}
+                return out
+
+            kernel_periods = {name: present(k) for k, name in enumerate(self.kernels)}
+            section_periods = {name: present(K + g) for name, g in self.sections.items()}
+            self._built = {
+                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
+                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_periods": {n: v for n, v in section_periods.items() if v},
+                "kernel_periods": {n: v for n, v in kernel_periods.items() if v},
+                "max_period": self.max_period,
+                "min_strength": self.min_strength,
+            }
+            self.handle = None
+        return self._built
+
+
 class _RobustSource:
     """What a report keeps of its robust scores: the backend's handle (``records()`` waits for the kernels and copies the
     column records and the scores out on first use), the ranks its rows stand for, the sections it shows with their ids,
@@ -852,6 +895,9 @@ class Report:
         onset = self.__dict__.get("_onset")
         if onset is not None:
             state["_onset"] = onset.build() if isinstance(onset, _OnsetSource) else onset
+        period = self.__dict__.get("_period")
+        if period is not None:
+            state["_period"] = period.build() if isinstance(period, _PeriodSource) else period
         return state
 
     def __setstate__(self, state) -> None:
@@ -928,6 +974,38 @@ class Report:
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no onset scores."""
         t = self.onset_scores()
+        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
+        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
+        return {"straggler_gpus_relative": self._ids(gr),
+                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def period_scores(self) -> Dict[str, Any]:
+        """Period scores (``ReportGenerator(period_detection=True)``; ``{}`` when the report carries none).  Whether a rank is
+        slow ON A BEAT -- a stall every P-th sample, which moves no median and no quantile and is no step: per timing row the
+        samples, in time order, are folded over every period up to ``max_period`` (and a quarter of the row), and the
+        smallest period whose phase means explain (adjusted R^2) at least 0.95 of what the best period explains is kept.
+
+        ``{"gpu_relative": {rank: score}, "section_relative": {section: {rank: score}}, "section_periods": {section: {rank:
+        {"period", "samples_ago", "peak", "rest", "excess", "strength", "window"}}}, "kernel_periods": {kernel: {rank:
+        {...}}}, "max_period": P, "min_strength": x}`` -- ``period`` is counted in samples of that row (0: none found), the
+        slow phase last occurred ``samples_ago`` samples before the end of the row's ``window`` samples, ``peak`` is the mean of
+        the slow phase and ``rest`` that of all others, ``excess`` is ``peak / rest`` where the beat explains at least
+        ``min_strength`` of the row's variance, 1.0 otherwise; scores are the steadiest rank's excess over this rank's (NaN
+        where a rank lacks the row): 1 = stalls no more than the steadiest rank, so a beat of the whole job flags nobody.
+        Ranks and sections as in the score mappings, rows without samples are left out.  Plain dicts and floats.  The first
+        call waits for the period kernels and copies their results; ``generate_report`` does not."""
+        period = self.__dict__.get("_period")
+        if period is None:
+            return {}
+        if isinstance(period, _PeriodSource):
+            period = self.__dict__["_period"] = period.build()
+        return _copy_onsets(period)
+
+    def identify_period_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose PERIOD scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no period scores."""
+        t = self.period_scores()
         gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
         sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
@@ -1117,7 +1195,8 @@ class ReportGenerator:
                  thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
                  kernel_attribution: int = 0, tail_quantile: float = 0.0, robust_scores: bool = False,
                  robust_min_ranks: int = 4, robust_floor: float = 0.02, onset_detection: bool = False,
-                 onset_min_segment: float = 0.05, onset_min_strength: float = 0.5) -> None:
+                 onset_min_segment: float = 0.05, onset_min_strength: float = 0.5, period_detection: bool = False,
+                 period_max: int = 1024, period_min_strength: float = 0.5) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1221,6 +1300,26 @@ class ReportGenerator:
                 raise RuntimeError(f"onset_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no onset scores (backend.onset_score)")
             self.onset_seg_ppm, self.onset_min_strength = seg_ppm, strength
+        # period scores: every ring report also carries, per row, the period on which the row stalls, if any, and relative
+        # scores built from the excesses (Report.period_scores); off: no buffer, no launch, no collective, no backend call.
+        # The step adds one collective per report, so EVERY rank must pass the same value.
+        self.period_max = 0  # (0 = off)
+        if period_detection:
+            pmax = _backend_mod._native.period_max(period_max)
+            try:
+                strength = float(period_min_strength)
+            except (TypeError, ValueError):
+                raise ValueError(f"period_min_strength must be a number within [0, 1], got {period_min_strength!r}") from None
+            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"period_min_strength must be within [0, 1], got {period_min_strength!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"period_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "period scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "period_score"):
+                raise RuntimeError(f"period_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no period scores (backend.period_score)")
+            self.period_max, self.period_min_strength = pmax, strength
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -1286,6 +1385,16 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
+        if self.period_max and not self.tail_q_ppm and not self.onset_seg_ppm:
+            # the period step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
+            # periods stay on that route as a whole (the option has the same value on every rank: no collective here)
+            self._direct = None
+            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (period_detection is "
+                                           "set: reports with period scores do not use the in-stream routes)", "mode": "c10d"}
+            if mode != "c10d":
+                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while period_detection is set: reports with period "
+                             "scores run on torch.distributed's route (c10d)", mode)
+            return
         if self.onset_seg_ppm and not self.tail_q_ppm:
             # the onset step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
             # onsets stay on that route as a whole (the option has the same value on every rank: no collective here)
@@ -1423,6 +1532,8 @@ class ReportGenerator:
                 ws.robust_settle()  # ... or the robust kernels
             if getattr(ws, "_onset_last", None) is not None:
                 ws.onset_settle()  # ... or an onset score kernel
+            if getattr(ws, "_period_last", None) is not None:
+                ws.period_settle()  # ... or a period score kernel
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1621,6 +1732,8 @@ class ReportGenerator:
             ws.robust_settle()  # ... or the robust kernels
         if getattr(ws, "_onset_last", None) is not None:
             ws.onset_settle()  # ... or an onset score kernel
+        if getattr(ws, "_period_last", None) is not None:
+            ws.period_settle()  # ... or a period score kernel
         self._last_plan_fused = fused
         if fused and attr_n and not hasattr(rings, "report_attribute"):
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
@@ -1771,6 +1884,32 @@ class ReportGenerator:
         report.__dict__["_onset"] = _OnsetSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
                                                  self.onset_seg_ppm, self.onset_min_strength)
 
+    # ---- period scores ------------------------------------------------------------------------------
+    def _period_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The period step of a ring report, once per ``generate_report_from_rings`` call behind its last score round (and
+        behind the tail and onset steps, when they are on), on that round's workspace: period kernel on the window the report
+        saw -> [one all-gather of the period rows] -> period score kernel for the ranks the report covers, hung on ``report``
+        unread.  Every rank issues it at every report, whatever the report found and whether or not it holds a report (a
+        gathering generator's other ranks): same collectives everywhere."""
+        be = _backend_mod.get_backend()
+        if not hasattr(rings, "period_local") or not hasattr(be, "period_score"):
+            raise RuntimeError("period_detection: the active backend has no period scores (rings.period_local / backend.period_score)")
+        send, table = rings.period_local(ws, self.period_max, self.period_min_strength, rows_active, fused)
+        if self.world_size > 1:
+            with be.stream_context():  # (behind the period kernel)
+                table = dist_utils.all_gather_rows(send, table, self.group)
+        if report is None or report is False:
+            return
+        if self.gather_on_rank0:
+            lo, hi = 0, ws.R
+        else:
+            lo = self.rank * local_ranks
+            hi = lo + local_ranks
+        view = report.__dict__["_src"].view
+        handle = be.period_score(ws, table, ws.table, lo, hi - lo)
+        report.__dict__["_period"] = _PeriodSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
+                                                   self.period_max, self.period_min_strength)
+
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],
                         kernel_summaries: Mapping[str, _SummaryType]):
@@ -1779,8 +1918,9 @@ class ReportGenerator:
         Collective.  Returns a :class:`Report`, or ``None`` on ranks other than 0 when
         ``gather_on_rank0`` is set.  The summaries are packed into this rank's exchange row on the
         host; exchange and scoring run on the device exactly as in the ring path.  Summaries hold no samples: a report
-        of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``) and no onset scores
-        (``onset_detection``; ``Report.onset_scores()`` is ``{}``).
+        of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``), no onset scores
+        (``onset_detection``; ``Report.onset_scores()`` is ``{}``) and no period scores (``period_detection``;
+        ``Report.period_scores()`` is ``{}``).
         """
         t0 = time.perf_counter_ns()
         self.world_size = dist_utils.get_world_size(self.group)
@@ -1832,9 +1972,10 @@ class ReportGenerator:
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
-        if self.onset_seg_ppm and not getattr(rings, "onset_enabled", False):
+        if (self.onset_seg_ppm or self.period_max) and not getattr(rings, "onset_enabled", False):
             if not hasattr(rings, "onset_enable"):
-                raise RuntimeError("onset_detection: the active backend has no onset scores (rings.onset_enable)")
+                raise RuntimeError(f"{'onset' if self.onset_seg_ppm else 'period'}_detection: the active backend has no ring-start "
+                                   "snapshot (rings.onset_enable)")
             rings.onset_enable(True)  # (before this window's report: it notes where every ring's oldest sample lives)
         if not self._direct_tried and self.world_size != 1:  # (a single process has no route to build)
             self._maybe_create_direct_exchange()
@@ -1858,6 +1999,8 @@ class ReportGenerator:
                     self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 if self.onset_seg_ppm:
                     self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+                if self.period_max:
+                    self._period_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 return out
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
@@ -1875,6 +2018,8 @@ class ReportGenerator:
                 self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             if self.onset_seg_ppm:
                 self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+            if self.period_max:
+                self._period_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
@@ -1905,6 +2050,8 @@ class ReportGenerator:
             self._tail_step(report, rings, ws, mapper, rows_used, False, local_ranks)
         if self.onset_seg_ppm:
             self._onset_step(report, rings, ws, mapper, rows_used, False, local_ranks)
+        if self.period_max:
+            self._period_step(report, rings, ws, mapper, rows_used, False, local_ranks)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

@@ -162,6 +162,8 @@ class _Lane:
             return None  # (the tail step follows the report in the generator's paths: DESIGN.md, "Tail scores")
         if getattr(reporter, "onset_seg_ppm", 0):
             return None  # (the onset step follows the report in the generator's paths: DESIGN.md, "Onset scores")
+        if getattr(reporter, "period_max", 0):
+            return None  # (the period step follows the report in the generator's paths: DESIGN.md, "Period scores")
         if getattr(reporter, "robust_scores", False):
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         ext = manager.cupti_ext
@@ -391,6 +393,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
         onset_detection: Optional[bool] = None,
         onset_min_segment: float = 0.05,
         onset_min_strength: float = 0.5,
+        period_detection: Optional[bool] = None,
+        period_max: int = 1024,
+        period_min_strength: float = 0.5,
     ):
         """
         Args:
@@ -437,6 +442,17 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 [0.000001, 0.5]; never fewer than 8 samples.
             onset_min_strength: a step counts as a shift when it explains at least this share of the row's variance, within
                 [0, 1].  0.5 is a default, not a measurement.
+            period_detection: every report also says whether a rank is slow ON A BEAT: per section and kernel row the period,
+                counted in samples of that row, on which the row stalls, the samples since the slow phase last occurred, and
+                relative scores built from the excess of the slow phase over the rest (``Report.period_scores()``,
+                ``Report.identify_period_stragglers()``).  A rank that is 1.5 x slower on every 50th sample moves neither its
+                median nor its 0.95-quantile; here it shows as "every 50 samples, last seen 36 samples ago".  Needs
+                ``relative_perf_scores``.  Default: ``NVRX_PERIOD_DETECTION``, else off.  Pass the same values on EVERY rank
+                (the step adds one collective per report).
+            period_max: the largest period looked for, an integer within [2, 4096]; never more than a quarter of a row's
+                samples (fewer than four repetitions are not a beat).
+            period_min_strength: a beat counts when its phase means explain (adjusted R^2) at least this share of the row's
+                variance, within [0, 1].  0.5 is a default, not a measurement.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -483,11 +499,15 @@ class Detector(metaclass=_DeviceSideOnDemand):
             robust_scores = os.environ.get("NVRX_ROBUST_SCORES", "0") not in ("", "0")
         if onset_detection is None:
             onset_detection = os.environ.get("NVRX_ONSET_DETECTION", "0") not in ("", "0")
+        if period_detection is None:
+            period_detection = os.environ.get("NVRX_PERIOD_DETECTION", "0") not in ("", "0")
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
                                        robust_scores=robust_scores, onset_detection=onset_detection,
-                                       onset_min_segment=onset_min_segment, onset_min_strength=onset_min_strength)
+                                       onset_min_segment=onset_min_segment, onset_min_strength=onset_min_strength,
+                                       period_detection=period_detection, period_max=period_max,
+                                       period_min_strength=period_min_strength)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
