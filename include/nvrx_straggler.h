@@ -117,6 +117,22 @@ int nvrx_score(const float *d_table, int R, int K, int S, int do_indiv, int do_r
                uint32_t *d_done_counter, uint32_t seq, const float *d_stats_src, float *d_stats_dst,
                int stats_rows, void *stream);
 
+/* Which kernels nvrx_score / a report would launch for this shape and these result arrays; touches no device.  This IS the
+ * dispatch (nvrx_score switches on it), so a test can assert the route it believes it covers:
+ *   SINGLE    R <= 64, staged results + column minima within 60 KB of LDS, both arrays 16-byte aligned: one workgroup;
+ *   ROWS      otherwise R <= 64 and (K+S)*4 <= 48 KB: one workgroup per rank, column minima in its own LDS;
+ *   ROWS_PRE  (K+S)*4 > 48 KB at R <= 64, or R > 64 where no tile fits or an array is unaligned: column minima in a
+ *             two-level pass of their own, then one workgroup per rank;
+ *   TILE16    R > 64, aligned arrays, 16 score rows fit 48 KB of LDS (S <= 306): that pass, then 16 ranks per workgroup;
+ *   TILE8     R > 64, aligned arrays, only 8 rows fit (307 <= S <= 613): the same with 8 ranks per workgroup.
+ * NVRX_ERR_INVALID for R <= 0, K < 0 or S < 0. */
+#define NVRX_SCORE_ROUTE_SINGLE 1
+#define NVRX_SCORE_ROUTE_ROWS 2
+#define NVRX_SCORE_ROUTE_ROWS_PRE 3
+#define NVRX_SCORE_ROUTE_TILE16 4
+#define NVRX_SCORE_ROUTE_TILE8 5
+int nvrx_score_route(int R, int K, int S, const void *d_scores, const void *d_flags);
+
 /* Kernel attribution: which kernels carry each rank's GPU score deficit.  Extends _compute_gpu_perf_score
  * (reporting.py:219-253), whose weighted mean g = sum_k(w_k * ref_k / med_k) / W keeps no per-kernel term: with
  * s_k = ref_k / med_k and n_k = w_k * (1 - s_k) ("lost microseconds": time above the reference pace), 1 - g = sum_k(n_k) / W.

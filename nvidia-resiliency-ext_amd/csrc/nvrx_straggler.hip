@@ -2336,6 +2336,26 @@ static bool score_fits_single_wg(int R, int K, int S, const float *d_scores, con
            score_single_wg_enabled();
 }
 
+// The dispatch of the score kernels (nvrx_score_route is this function behind an argument check): which kernels turn a
+// table of this shape into these result arrays.  score_launch switches on the result and decides nothing itself.
+constexpr size_t SCORE_ROWS_MAX_LDS = 48 * 1024;  // k_score's column minima in LDS, KS floats
+
+static int score_route(int R, int K, int S, const float *d_scores, const uint8_t *d_flags) {
+    // One workgroup does it all when the staged results fit in LDS.  The result arrays are then written in 16-byte
+    // units: the caller's buffers must be 16-byte aligned and padded to a multiple of 16 bytes (the workspace is).
+    if (score_fits_single_wg(R, K, S, d_scores, d_flags)) return NVRX_SCORE_ROUTE_SINGLE;
+    if (R <= 64 && (size_t)(K + S) * sizeof(float) <= SCORE_ROWS_MAX_LDS) return NVRX_SCORE_ROUTE_ROWS;
+    // large jobs: column minima in their own two-level pass, then a tile of 16 (or 8) ranks per workgroup when its staged
+    // results fit in LDS and the result arrays can be written in 16-byte units (every tile then starts on a 16-byte
+    // boundary of both arrays: the score row is an even number of floats / bytes)
+    const bool aligned = ((reinterpret_cast<uintptr_t>(d_scores) | reinterpret_cast<uintptr_t>(d_flags)) & 15u) == 0;
+    if (aligned && R > 64) {
+        if (score_tile_lds_bytes(16, S) <= TILE_MAX_LDS) return NVRX_SCORE_ROUTE_TILE16;
+        if (score_tile_lds_bytes(8, S) <= TILE_MAX_LDS) return NVRX_SCORE_ROUTE_TILE8;
+    }
+    return NVRX_SCORE_ROUTE_ROWS_PRE;
+}
+
 static int score_launch(const float *d_table, int R, int K, int S, int do_indiv, int do_rel, const double *thresholds,
                         float *d_scores, uint8_t *d_flags, uint32_t *d_meta, uint32_t *d_done_counter, uint32_t seq,
                         const float *d_stats_src, float *d_stats_dst, int stats_rows, void *stream, const PeerArgs *pa,
@@ -2362,9 +2382,8 @@ static int score_launch(const float *d_table, int R, int K, int S, int do_indiv,
         a.stats_n4 = stats_rows * (NVRX_STATS_STRIDE / 4);
     }
     const int KS = K + S;
-    // One workgroup does it all when the staged results fit in LDS.  The result arrays are then written in 16-byte
-    // units: the caller's buffers must be 16-byte aligned and padded to a multiple of 16 bytes (the workspace is).
-    if (score_fits_single_wg(R, K, S, d_scores, d_flags)) {
+    const int route = score_route(R, K, S, d_scores, d_flags);
+    if (route == NVRX_SCORE_ROUTE_SINGLE) {
         PeerArgs none{};
         GatherArgs nog{};
         size_t lds1 = score1_lds_bytes(R, K, S);
@@ -2391,10 +2410,8 @@ static int score_launch(const float *d_table, int R, int K, int S, int do_indiv,
     }
     if (ga) return fail(NVRX_ERR_STATE, "the resident scorer needs the single-workgroup score kernel");
     if (pa) return fail(NVRX_ERR_STATE, "the exchange prologue needs the single-workgroup score kernel");
-    size_t lds = (size_t)KS * sizeof(float);
-    int tile_ranks = 0;
-    if (R > 64 || lds > 48 * 1024) {
-        // large jobs: column minima in their own two-level pass over a coalesced grid
+    if (route != NVRX_SCORE_ROUTE_ROWS) {
+        // column minima in their own two-level pass over a coalesced grid
         const int chunks = std::max(1, std::min(COLMIN_MAX_CHUNKS, (R + 63) / 64));
         const int rows_per_chunk = (R + chunks - 1) / chunks;
         const size_t need = (size_t)KS * (size_t)(chunks + 1);
@@ -2419,23 +2436,31 @@ static int score_launch(const float *d_table, int R, int K, int S, int do_indiv,
             HIP_TRY(hipGetLastError());
         }
         a.minmed_pre = scratch;
-        lds = 0;
-        // a tile of 16 (or 8) ranks per workgroup when its staged results fit in LDS and the result arrays can be
-        // written in 16-byte units (every tile then starts on a 16-byte boundary of both arrays: the score row is an
-        // even number of floats / bytes)
-        const bool aligned = ((reinterpret_cast<uintptr_t>(d_scores) | reinterpret_cast<uintptr_t>(d_flags)) & 15u) == 0;
-        if (aligned && R > 64)
-            for (int t : {16, 8})
-                if (!tile_ranks && score_tile_lds_bytes(t, S) <= TILE_MAX_LDS) tile_ranks = t;
     }
-    if (tile_ranks) {
+    switch (route) {
+    case NVRX_SCORE_ROUTE_ROWS:
+        hipLaunchKernelGGL(k_score, dim3(R), dim3(SCORE_THREADS), (size_t)KS * sizeof(float), st, a);
+        break;
+    case NVRX_SCORE_ROUTE_ROWS_PRE:
+        hipLaunchKernelGGL(k_score, dim3(R), dim3(SCORE_THREADS), 0, st, a);
+        break;
+    case NVRX_SCORE_ROUTE_TILE16:
+    case NVRX_SCORE_ROUTE_TILE8: {
+        const int tile_ranks = route == NVRX_SCORE_ROUTE_TILE16 ? 16 : 8;
         hipLaunchKernelGGL(k_score_tile, dim3((R + tile_ranks - 1) / tile_ranks), dim3(TILE_THREADS),
                            score_tile_lds_bytes(tile_ranks, S), st, a, tile_ranks);
-    } else {
-        hipLaunchKernelGGL(k_score, dim3(R), dim3(SCORE_THREADS), lds, st, a);
+        break;
+    }
+    default:
+        return fail(NVRX_ERR_STATE, "no score kernel for route %d", route);
     }
     HIP_TRY(hipGetLastError());
     return NVRX_OK;
+}
+
+int nvrx_score_route(int R, int K, int S, const void *d_scores, const void *d_flags) {
+    if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
+    return score_route(R, K, S, static_cast<const float *>(d_scores), static_cast<const uint8_t *>(d_flags));
 }
 
 int nvrx_score(const float *d_table, int R, int K, int S, int do_indiv, int do_rel, const double *thresholds,

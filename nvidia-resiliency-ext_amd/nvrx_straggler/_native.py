@@ -28,6 +28,7 @@ ERR_RANGE = -34
 ERR_INVALID = -22
 ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
 TAIL_Q_PPM_MIN, TAIL_Q_PPM_MAX = 500000, 999999  # the accepted range of a tail quantile, in parts per million
+ROUTE_SINGLE, ROUTE_ROWS, ROUTE_ROWS_PRE, ROUTE_TILE16, ROUTE_TILE8 = 1, 2, 3, 4, 5  # NVRX_SCORE_ROUTE_*: what nvrx_score_route returns
 ROBUST_MAX_RANKS = 65536  # NVRX_ROBUST_MAX_RANKS
 ONSET_SEG_PPM_MIN, ONSET_SEG_PPM_MAX = 1, 500000  # the accepted range of an onset's minimum segment, in parts per million
 ONSET_MIN_SEG_SAMPLES = 8  # ... and the segment's floor in samples
@@ -73,6 +74,7 @@ SYMBOLS = [
     ("nvrx_row_stats", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p,
                            c_void_p, c_uint32, c_void_p, c_void_p, c_int, c_void_p]),
+    ("nvrx_score_route", c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_attribute", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_quantile", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_tail_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -85,10 +85,12 @@ def test_stress_capacity_10000_vs_oracle():
 
 @pytest.mark.parametrize("R", [65, 96, 512])
 def test_one_call_report_beyond_the_single_workgroup_scorer(R):
-    """More ranks than `k_score1` takes (64): the one-call report goes through `k_colmin` + `k_score` (one workgroup
-    per rank), non-resident.  R logical ranks x 8 sections folded onto one GPU, two reports (the second one's
-    individual scores use the minima of both), every score against the oracle, flagged sets against the scores."""
-    from nvrx_straggler import Statistic
+    """More ranks than `k_score1` takes (64): the one-call report goes through `k_colmin_part` + `k_colmin_finish` +
+    `k_score_tile` (16 ranks per workgroup; route TILE16 of `nvrx_score_route`), non-resident.  The routes on
+    `k_score`, one workgroup per rank: tests/test_gpu_score_routes.py.  R logical ranks x 8 sections folded onto one
+    GPU, two reports (the second one's individual scores use the minima of both), every score against the oracle,
+    flagged sets against the scores."""
+    from nvrx_straggler import Statistic, _native
     from nvrx_straggler.folded import FoldedJob
 
     S, n = 8, 301
@@ -120,7 +122,10 @@ def test_one_call_report_beyond_the_single_workgroup_scorer(R):
             assert {k: {x.rank for x in v} for k, v in got["straggler_sections_individual"].items()} == \
                 {k: v for k, v in exp_ind.items() if v}
             assert rep.local_section_summaries[names[0]][Statistic.NUM] == n
-            assert job.reporter._ring_plan.ws.meta[0] == 1
+            ws = job.reporter._ring_plan.ws
+            assert ws.meta[0] == 1
+            assert (ws.R, ws.K, ws.S) == (R, 0, S)
+            assert _native.load().nvrx_score_route(R, 0, 8, ws.d_scores, ws.d_flags) == _native.ROUTE_TILE16
     finally:
         job.close()
 

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import oracle
+from score_cases import SINGLE, TILE16, random_table as _random_table
 from util import close, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -16,24 +17,6 @@ def be():
     return get_backend()
 
 
-def _random_table(rng, R, K, S, p_missing=0.15):
-    L = oracle.table_len(K, S)
-    KS = K + S
-    T = np.zeros((R, L), dtype=np.float32)
-    med = rng.lognormal(1.0, 0.5, (R, KS)).astype(np.float32)
-    hmin = (med * rng.uniform(0.5, 1.0, (R, KS))).astype(np.float32)
-    missing = rng.random((R, KS)) < p_missing
-    med[missing] = -1.0
-    hmin[missing] = np.nan
-    T[:, :KS] = med
-    T[:, KS : 2 * KS] = hmin
-    w = rng.uniform(1, 1000, (R, K)).astype(np.float32)
-    w[missing[:, :K]] = 0.0
-    T[:, 2 * KS : 2 * KS + K] = w
-    T[:, L - 1] = 1.0
-    return T
-
-
 def _score(be, T, K, S, do_indiv=True, do_rel=True, thr=(0.75, 0.75, 0.75, 0.75)):
     R = T.shape[0]
     ws = be.workspace(R, K, S, R, 0)
@@ -42,9 +25,18 @@ def _score(be, T, K, S, do_indiv=True, do_rel=True, thr=(0.75, 0.75, 0.75, 0.75)
     return ws.scores.copy(), ws.flags.copy(), ws.meta.copy()
 
 
+# the route of every shape below (nvrx_score_route); the other three routes: tests/test_gpu_score_routes.py
+_ROUTES = {(1, 0, 1): SINGLE, (1, 3, 0): SINGLE, (2, 2, 2): SINGLE, (8, 0, 64): SINGLE, (8, 5, 6): SINGLE, (8, 4096, 8): SINGLE,
+           (64, 17, 33): SINGLE, (100, 7, 9): TILE16, (3, 0, 0): SINGLE, (16, 13000, 40): SINGLE, (65, 0, 64): TILE16,
+           (1024, 0, 64): TILE16, (4096, 32, 16): TILE16}
+
+
 @pytest.mark.parametrize("R,K,S", [(1, 0, 1), (1, 3, 0), (2, 2, 2), (8, 0, 64), (8, 5, 6), (8, 4096, 8), (64, 17, 33),
                                    (100, 7, 9), (3, 0, 0), (16, 13000, 40), (65, 0, 64), (1024, 0, 64), (4096, 32, 16)])
 def test_score_kernel_matches_oracle(be, R, K, S):
+    ws = be.workspace(R, K, S, R, 0)
+    for blk in ws.blocks:
+        assert be.lib.nvrx_score_route(R, K, S, blk.d_scores, blk.d_flags) == _ROUTES[(R, K, S)]
     rng = np.random.default_rng(R * 1000 + K + S)
     T = _random_table(rng, R, K, S)
     for do_indiv, do_rel in ((True, True), (True, False), (False, True)):
@@ -145,6 +137,7 @@ def test_completion_word_never_precedes_the_results(be, R, K, S):
     exp = [oracle.score_table(t, K, S, True, True) for t in tabs]
     dev = [torch.from_numpy(t).cuda() for t in tabs]
     ws = be.workspace(R, K, S, R, 0)
+    assert be.lib.nvrx_score_route(R, K, S, ws.d_scores, ws.d_flags) == SINGLE
     torch.cuda.synchronize()
     W = 2 + 2 * S
     for i in range(20_000):
