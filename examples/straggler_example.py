@@ -44,6 +44,12 @@ step in every timing row that explains most of its variance (``Report.onset_scor
 ``NVRX_PERIOD_DETECTION=1`` the report folds every timing row over every period up to a quarter of its samples
 (``Report.period_scores()``) and the example prints whoever ``identify_period_stragglers`` flags, with the period of the
 rank's largest excess and how many samples ago its slow phase last occurred.
+
+``--slow-by stretch`` makes the slow rank's GPU kernel 1.5x longer for ONE stretch of every report window (from 60 % to 70 %
+of it) and normal again afterwards: no median, no 0.95-quantile, no step and no beat shows it.  With
+``NVRX_EPISODE_DETECTION=1`` the report also looks for the one interval of every timing row that spent most time above the
+row's mean (``Report.episode_scores()``) and the example prints whoever ``identify_episode_stragglers`` flags, with how long
+the rank's strongest episode lasted and how many samples ago it ended.
 """
 import argparse
 import os
@@ -106,12 +112,14 @@ def train(args) -> None:
                 print(f"[rank {rank}] ROCm SMI refused to slow the GPU down ({e}); use --slow-by simulated", flush=True)
         with straggler.Detector.detection_section("fwd", profile_cuda=True):
             output = net(data)
-            if args.slow_by in ("simulated", "intermittent", "onset"):   # one kernel whose duration says how fast "this GPU" is
+            if args.slow_by in ("simulated", "intermittent", "onset", "stretch"):   # one kernel whose duration says how fast "this GPU" is
                 slow = rank == args.slow_rank and step >= args.slow_from
                 if args.slow_by == "intermittent":
                     slow = slow and step % args.slow_every == 0
                 if args.slow_by == "onset":  # (a window: the steps behind one report up to and including the next one's)
                     slow = slow and (step - 1) % args.report_interval >= 0.7 * args.report_interval
+                if args.slow_by == "stretch":  # (one stretch of every window, and normal again behind it)
+                    slow = slow and 0.6 * args.report_interval <= (step - 1) % args.report_interval < 0.7 * args.report_interval
                 torch.cuda._sleep(int(args.simulated_cycles * (1.5 if slow else 1.0)))
         loss = loss_fn(output, target)
         optim.zero_grad()
@@ -177,6 +185,20 @@ def train(args) -> None:
                             print(f"step {step}:   rank {s.rank}: {name} is {rec['excess']:.2f}x slower every {rec['period']} samples, "
                                   f"last {rec['samples_ago']} samples ago (of {rec['window']}; the beat explains {rec['strength']:.2f} "
                                   f"of the row's variance)")
+                episodes = report.episode_scores()  # {} unless NVRX_EPISODE_DETECTION=1 asks for episode scores
+                if episodes:
+                    print(f"step {step}: GPUs relative episode perf: { {r: round(s, 3) for r, s in episodes['gpu_scores'].items()} }")
+                    episode_found = report.identify_episode_stragglers(gpu_rel_threshold=args.threshold)
+                    if episode_found["straggler_gpus_relative"]:
+                        print(f"step {step}: episode straggler_gpus_relative: "
+                              f"{sorted((s.rank, s.node) for s in episode_found['straggler_gpus_relative'])}")
+                    for s in sorted(episode_found["straggler_gpus_relative"], key=lambda s: s.rank):
+                        rows = [(per[s.rank], name) for name, per in episodes["kernel_episodes"].items() if s.rank in per]
+                        if rows:
+                            rec, name = max(rows, key=lambda x: x[0]["excess"])
+                            print(f"step {step}:   rank {s.rank}: {name} was {rec['excess']:.2f}x slower for {rec['length']} samples "
+                                  f"that ended {rec['samples_ago']} samples ago (of {rec['window']}; the stretch explains "
+                                  f"{rec['strength']:.2f} of the row's variance{', and has not ended' if rec['open_ended'] else ''})")
                 print(f"step {step}: {straggler.Detector.gpu_telemetry_line()}", flush=True)
     if slow_ctx is not None:
         slow_ctx.__exit__(None, None, None)
@@ -200,7 +222,7 @@ def main() -> None:
     ap.add_argument("--threshold", type=float, default=0.75)
     ap.add_argument("--slow-rank", type=int, default=-1)
     ap.add_argument("--slow-from", type=int, default=300)
-    ap.add_argument("--slow-by", choices=["clock", "simulated", "intermittent", "onset"], default="clock")
+    ap.add_argument("--slow-by", choices=["clock", "simulated", "intermittent", "onset", "stretch"], default="clock")
     ap.add_argument("--slow-every", type=int, default=5,
                     help="--slow-by intermittent: the slow rank's stand-in kernel is 1.5x longer on every N-th step only (with one "
                          "step in ten slow, a 0.9 quantile would sit on the last FAST sample)")

@@ -259,6 +259,52 @@ int nvrx_row_period(const float *d_samples, const uint32_t *d_counts, const uint
 int nvrx_period_score(const float *d_period, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                       float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Episode of timing rows: whether a row was slow FOR ONE STRETCH of its window and then recovered -- a thermal excursion, a
+ * neighbour's checkpoint saturating the host, a link that flapped, an ECC-retry storm.  Extends the statistics of
+ * straggler.py:172-197: a stretch of 3 % of a window moves no median and no 0.95-quantile, a pulse is no step and no beat.
+ * Per row with n valid samples:
+ *   time order  as for nvrx_row_onset: sample i lives in slot (start + i) mod n;
+ *   pivoting    d_i = (f64)x_i - (f64)x_0; all sums below are f64 sums of d; T = sum of all d_i, C_t = sum of d_0 .. d_(t-1),
+ *               SST = sum of (d_i - T / n)^2;
+ *   m           max(8, (min_len_ppm * n + 999999) / 1000000) (64-bit integers), min_len_ppm in [1, 333333];
+ *   candidates  every interval [a, b) with a >= m, b <= n - m and b - a >= m: the episode began and ended inside the window,
+ *               with at least m samples of "normal" either side (needs n >= 3m; a stretch that runs to the window's end is an
+ *               onset);
+ *   excess      H_t = n * C_t - t * T, evaluated in this form (two rounded products, one rounded difference);
+ *               E_(a,b) = (H_b - H_a) / n: the time the interval spent above the row's mean (the Levin-Kline statistic for an
+ *               "epidemic" change);
+ *   (a*, b*)    the candidate with the largest E; ties go to the lowest b, then the lowest a; no episode if the largest E <= 0;
+ *   at (a*, b*) L = b* - a*; inside = x_0 + (C_b* - C_a*) / L; outside = x_0 + (T - (C_b* - C_a*)) / (n - L);
+ *               strength = E^2 * n / (L * (n - L)) / SST, the share of the row's variance that the two-level pulse explains,
+ *               in [0, 1]; ago = n - b*, the samples since the episode ended (it began ago + L samples ago).
+ * Row record, 16 bytes: {u32 ago | L << 16, f32 inside, f32 outside, f32 strength} (both halves fit 16 bits at
+ * NVRX_MAX_RING_CAP).
+ *   n == 0 (an absent row)              {0, -1, -1, -1};
+ *   T or SST not finite                 {0, NaN, NaN, NaN};
+ *   0 < n < 3m, or the largest E <= 0   {0, mean, mean, 0}, mean = x_0 + T / n;
+ *   SST == 0 (a constant row)           {0, x_0, x_0, 0}.
+ * Effective excess of a record: e = f32 of the f64 quotient inside / outside (the record's f32 values) where L > 0,
+ * strength >= min_strength and inside > outside > 0; 1.0 otherwise ("no episode"); -1.0 for an absent row.
+ * Rules, not defects: a row that STEPPED UP reads as a strong episode that runs to the last admissible sample (ago == m:
+ * "open-ended"; onset scores are the better reading there); a ramp reads as a weaker episode of its upper half (0.71 on a 30 %
+ * ramp over 2000 samples; a two-level fit of a ramp explains at most 0.75); a row on a beat reads as none.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_starts [rows] or NULL (0 everywhere); d_out [rows] records, 16-byte aligned.  Stateless, like nvrx_row_onset.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+int nvrx_row_episode(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride,
+                     uint32_t min_len_ppm, void *d_out, void *stream);
+/* Relative episode scores (reporting.py:196-253 on the excesses).  d_episode [R][NVRX_EPISODE_PLANES][K+S]: per rank seven
+ * planes {e, inside, outside, strength, length as f32, ago as f32, n as f32} per kernel id and section id (-1.0: none); only
+ * plane 0 is read.  Reference per column = the minimum of e over all R ranks, NaN if any rank has none.  Per reported rank
+ * [first_rank, first_rank + n_ranks), nvrx_tail_score's arithmetic on e, exactly as nvrx_onset_score and nvrx_period_score:
+ *   d_out [n_ranks][1 + S] = {GPU episode score, section episode score[S]}
+ * Scores are in (0, 1]: 1 = "no stretch slower than the steadiest rank's"; a stretch the whole job shares flags nobody.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(K+S) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_EPISODE_PLANES 7
+int nvrx_episode_score(const float *d_episode, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                       float *d_colmin_scratch, float *d_out, void *stream);
+
 /* Robust scores: every rank against the job's median and spread. Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
@@ -470,8 +516,8 @@ int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm,
  * strength, ago as f32, n as f32}; kernel ids first, then section ids; every slot is written, -1.0 where no row with samples has that gid).  min_strength
  * in [0, 1].  Ordering, desc, rows_active and the caller's duty to wait are those of nvrx_tail_local.
  * NVRX_ERR_STATE: not enabled, or no report was issued through this descriptor.
- * The snapshot nvrx_onset_enable switches on is also what nvrx_period_local walks its windows by: a caller that wants period
- * scores enables it whether or not it wants onsets. */
+ * The snapshot nvrx_onset_enable switches on is also what nvrx_period_local and nvrx_episode_local walk their windows by: a
+ * caller that wants period or episode scores enables it whether or not it wants onsets. */
 int nvrx_onset_enable(nvrx_ctx *ctx, int on);
 int nvrx_onset_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_seg_ppm, float min_strength,
                      float *d_onset_send, int K, int S, int rows_active, void *stream);
@@ -483,6 +529,15 @@ int nvrx_onset_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_s
  * nvrx_onset_local.  NVRX_ERR_STATE: the snapshot is not enabled, or no report was issued through this descriptor. */
 int nvrx_period_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, int max_period, float min_strength,
                       float *d_period_send, int K, int S, int rows_active, void *stream);
+/* Episode scores on the rings (straggler.py:172-197 on the window in time order; reporting.py:196-253 follows with
+ * nvrx_episode_score): nvrx_row_episode on the rings as the report just issued saw them -- its counts, its ring starts (the
+ * snapshot of nvrx_onset_enable), whatever has been pushed since -- packed by gid into d_episode_send
+ * [local_ranks][NVRX_EPISODE_PLANES][K+S] (planes {e, inside, outside, strength, length as f32, ago as f32, n as f32}; kernel
+ * ids first, then section ids; every slot is written, -1.0 where no row with samples has that gid).  min_len_ppm in
+ * [1, 333333], min_strength in [0, 1].  Ordering, desc, rows_active and the caller's duty to wait are those of
+ * nvrx_onset_local.  NVRX_ERR_STATE: the snapshot is not enabled, or no report was issued through this descriptor. */
+int nvrx_episode_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_len_ppm, float min_strength,
+                       float *d_episode_send, int K, int S, int rows_active, void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

@@ -3953,3 +3953,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_onset.inl"
 #include "nvrx_robust.inl"
 #include "nvrx_period.inl"
+#include "nvrx_episode.inl"

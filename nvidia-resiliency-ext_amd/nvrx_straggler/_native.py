@@ -36,6 +36,9 @@ ONSET_PLANES = 6  # NVRX_ONSET_PLANES: {e, before, after, strength, ago, n} per 
 PERIOD_MAX = 4096  # NVRX_PERIOD_MAX: the largest max_period
 PERIOD_MIN_CYCLES = 4  # NVRX_PERIOD_MIN_CYCLES: a period repeats at least that often within its row
 PERIOD_PLANES = 7  # NVRX_PERIOD_PLANES: {e, peak, rest, strength, period, ago, n} per kernel id and section id
+EPISODE_LEN_PPM_MIN, EPISODE_LEN_PPM_MAX = 1, 333333  # the accepted range of an episode's minimum length, in parts per million
+EPISODE_MIN_SAMPLES = 8  # ... and the length's floor in samples
+EPISODE_PLANES = 7  # NVRX_EPISODE_PLANES: {e, inside, outside, strength, length, ago, n} per kernel id and section id
 
 
 
@@ -82,6 +85,8 @@ SYMBOLS = [
     ("nvrx_onset_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_period", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_period_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_episode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_episode_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
@@ -120,6 +125,7 @@ SYMBOLS = [
     ("nvrx_onset_enable", c_int, [c_void_p, c_int]),
     ("nvrx_onset_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_period_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
@@ -267,3 +273,22 @@ def period_max(value) -> int:
     if not 2 <= p <= PERIOD_MAX:
         raise ValueError(f"period_max must be within [2, {PERIOD_MAX}], got {value!r}")
     return p
+
+
+def episode_len_ppm(frac) -> int:
+    """An episode's minimum length as the library carries it: ``round(frac * 1e6)``, within [0.000001, 0.333333] (an
+    episode needs that many samples of "normal" either side as well: three of them fill the row).  ``ValueError`` for
+    anything else."""
+    try:
+        ppm = int(round(float(frac) * 1e6))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"episode_min_length must be a number within [0.000001, 0.333333], got {frac!r}") from None
+    if not EPISODE_LEN_PPM_MIN <= ppm <= EPISODE_LEN_PPM_MAX:
+        raise ValueError(f"episode_min_length must be within [0.000001, 0.333333], got {frac!r}")
+    return ppm
+
+
+def episode_min_samples(len_ppm: int, n: int) -> int:
+    """Samples of an episode, and of the stretches either side of it, in a row of ``n``: ``max(8, ceil(len_ppm * n / 1e6))``
+    in integers, exactly as k_row_episode computes it.  A row shorter than three times that has no episode."""
+    return max(EPISODE_MIN_SAMPLES, (len_ppm * n + 999999) // 1000000)

@@ -326,6 +326,35 @@ class Periods:
         return self._host
 
 
+class Episodes:
+    """Episode scores of one report (``nvrx_episode_local`` -> exchange -> ``nvrx_episode_score``), enqueued and not waited for:
+    once the score kernel has run, the workspace's episode buffer holds the gathered episode table ``[R][7][K+S]`` (planes
+    ``{e, inside, outside, strength, length, ago, n}``) and, behind it, the scores ``[n_ranks][1 + S]`` of the reported ranks.
+    ``records()`` waits for it and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report``
+    first asks, or -- ``Workspace.episode_settle`` -- before the next report on the same workspace rewrites the table the
+    kernel reads and the buffers it writes."""
+
+    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.R, self.K, self.S = R, K, S
+        self.first_rank, self.n_ranks = first_rank, n_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(episodes [n_ranks, 7, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first
+        call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.episodes_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Robust:
     """Robust scores of one report (``nvrx_robust_score`` / ``nvrx_report_robust``), enqueued and not waited for: once the
     kernels have run, the workspace's device buffer holds the ``K+S`` column records ``{ctr, mad, scale, n}`` and, behind
@@ -547,6 +576,35 @@ class Workspace:
         """Before anything rewrites this workspace's table or period buffers: the last period step's kernels have run and
         their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
         last, self._period_last = self._period_last, None
+        if last is not None:
+            last.records()
+
+    # ---- episode scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
+    _episode_buf = None      # device: episode table [R][7][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
+    _episode_send = None     # device: this process' episode rows [local_ranks][7][K+S] (the table's own rows without an exchange)
+    _episode_table = None    # ... the table part of _episode_buf as [R][7 * (K+S)]
+    _episode_scratch = None  # device: column minima
+    _episode_last = None     # the Episodes whose kernels may still be reading the table / writing the buffers
+
+    def episode_buffers(self):
+        """``(episode_send, episode_table, scores, scratch)`` (cold: allocated on first use)."""
+        if self._episode_buf is None:
+            KS, R = self.K + self.S, self.R
+            P = _native.EPISODE_PLANES
+            dev = self._backend.device
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._episode_buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
+                self._episode_table = self._episode_buf[: R * P * KS].view(R, P * KS)
+                self._episode_send = (self._episode_table if R == self.local_ranks
+                                     else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
+                self._episode_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
+        return (self._episode_send, self._episode_table, self._episode_buf[self.R * _native.EPISODE_PLANES * (self.K + self.S):],
+                self._episode_scratch)
+
+    def episode_settle(self) -> None:
+        """Before anything rewrites this workspace's table or episode buffers: the last episode step's kernels have run and
+        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        last, self._episode_last = self._episode_last, None
         if last is not None:
             last.records()
 
@@ -811,6 +869,47 @@ class HipBackend:
             _native.check(self.lib.nvrx_row_period(samples.data_ptr(), counts.data_ptr(),
                                                    starts.data_ptr() if starts is not None else None, rows, stride,
                                                    int(max_period), out.data_ptr(), self.stream_handle))
+        self.stream.synchronize()
+        return out[:rows]
+
+    def episode_score(self, ws: Workspace, episodes: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
+                     n_ranks: Optional[int] = None) -> Episodes:
+        """Relative episode scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered episode table ``episodes``
+        ([R, 7 * (K+S)], ``Rings.episode_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
+        ``nvrx_episode_score`` enqueued on the backend's stream.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        _, episode_table, scores, scratch = ws.episode_buffers()
+        assert episodes is episode_table or (episodes.data_ptr() == episode_table.data_ptr())
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_episode_score(episode_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
+                                        scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._episode_last = Episodes(self, ws._episode_buf, ws.R, ws.K, ws.S, first_rank, n_ranks)
+        return out
+
+    def episodes_copy_out(self, t: Episodes):
+        """The one wait of a report's episodes: a D2H of the episode table and the scores on the backend's stream, behind the kernels."""
+        KS, P = t.K + t.S, _native.EPISODE_PLANES
+        n = t.R * P * KS + t.n_ranks * (1 + t.S)
+        host = np.empty(max(n, 1), dtype=np.float32)
+        if n:
+            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        episodes = host[: t.R * P * KS].reshape(t.R, P, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        return episodes, host[t.R * P * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+
+    def row_episode(self, samples: torch.Tensor, counts: torch.Tensor, min_len_ppm: int,
+                   starts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Stateless episode operator on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) -> [rows, 4]
+        int32 records ``{ago | length << 16, inside, outside, strength}`` (the last three are f32 bit patterns;
+        ``nvrx_row_episode``)."""
+        rows, stride = samples.shape
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=samples.device)
+            _native.check(self.lib.nvrx_row_episode(samples.data_ptr(), counts.data_ptr(),
+                                                   starts.data_ptr() if starts is not None else None, rows, stride,
+                                                   int(min_len_ppm), out.data_ptr(), self.stream_handle))
         self.stream.synchronize()
         return out[:rows]
 
@@ -1201,6 +1300,22 @@ class HipRings:
         ws.period_settle()
         send, table, _, _ = ws.period_buffers()
         rc = self.lib.nvrx_period_local(self.ctx, ws.block.desc_ref if fused else None, int(max_period), float(min_strength),
+                                        send.data_ptr(), ws.K, ws.S, rows_active, self.backend._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        self.backend.stream.synchronize()
+        return send, table
+
+    def episode_local(self, ws: Workspace, min_len_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
+        """The episode of every ring row as the report just issued on ``ws`` saw it, packed by gid into the workspace's episode
+        rows (``nvrx_episode_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s; needs
+        ``onset_enable``'s ring-start snapshot).  Returns ``(episode_send [local_ranks, 7 * (K+S)], episode_table [R, 7 *
+        (K+S)])`` -- the same rows when nothing is exchanged.  Waits for the episode kernel, for the reason ``onset_local``
+        waits for its own: the rings are emptied by count, and the next window's device-side writers on other streams may
+        overwrite slots as soon as the report call returns."""
+        ws.episode_settle()
+        send, table, _, _ = ws.episode_buffers()
+        rc = self.lib.nvrx_episode_local(self.ctx, ws.block.desc_ref if fused else None, int(min_len_ppm), float(min_strength),
                                         send.data_ptr(), ws.K, ws.S, rows_active, self.backend._stream_handle)
         if rc < 0:
             _native.check(rc)

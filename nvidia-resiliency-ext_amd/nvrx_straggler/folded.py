@@ -26,7 +26,8 @@ class FoldedJob:
                  gather_on_rank0: bool = True, pg=None, node_name: str = "node", kernel_attribution: int = 0,
                  tail_quantile: float = 0.0, robust_scores: bool = False, asynchronous: bool = False,
                  onset_detection: bool = False, onset_min_segment: float = 0.05, onset_min_strength: float = 0.5,
-                 period_detection: bool = False, period_max: int = 1024, period_min_strength: float = 0.5):
+                 period_detection: bool = False, period_max: int = 1024, period_min_strength: float = 0.5,
+                 episode_detection: bool = False, episode_min_length: float = 0.005, episode_min_strength: float = 0.5):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -42,7 +43,9 @@ class FoldedJob:
                                         robust_scores=robust_scores, asynchronous=asynchronous,
                                         onset_detection=onset_detection, onset_min_segment=onset_min_segment,
                                         onset_min_strength=onset_min_strength, period_detection=period_detection,
-                                        period_max=period_max, period_min_strength=period_min_strength)
+                                        period_max=period_max, period_min_strength=period_min_strength,
+                                        episode_detection=episode_detection, episode_min_length=episode_min_length,
+                                        episode_min_strength=episode_min_strength)
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         self._no_kernel_rows = {}  # same object every report so the reporter's cached plan stays valid
 

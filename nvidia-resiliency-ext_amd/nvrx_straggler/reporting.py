@@ -758,6 +758,59 @@ class _PeriodSource:
         return self._built
 
 
+class _EpisodeSource:
+    """What a report keeps of its episode scores: the backend's handle (``records()`` waits for the kernels and copies the
+    episode planes and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the
+    kernel names by id as the report's mapper had them at report time."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "len_ppm", "min_strength", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, len_ppm: int, min_strength: float):
+        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
+        self.len_ppm, self.min_strength = len_ppm, min_strength
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            episodes, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks = self.ranks
+            o, sc = episodes.tolist(), scores.tolist()
+            min_samples, len_ppm = _backend_mod._native.episode_min_samples, self.len_ppm
+
+            def present(col):
+                out = {}
+                for i, r in enumerate(ranks):
+                    e, inside, outside, strength, length, ago, n = (o[i][p][col] for p in range(7))
+                    if e != -1.0:  # (-1: the rank has no samples in this row)
+                        length, ago, n = int(length), int(ago), int(n)
+                        out[r] = {"length": length, "samples_ago": ago, "began_ago": ago + length if length else 0, "window": n,
+                                  "inside": inside, "outside": outside, "strength": strength, "excess": e,
+                                  "open_ended": bool(length) and ago == min_samples(len_ppm, n)}
+                return out
+
+            kernel_episodes = {name: present(k) for k, name in enumerate(self.kernels)}
+            section_episodes = {name: present(K + g) for name, g in self.sections.items()}
+            self._built = {
+                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
+                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_episodes": {n: v for n, v in section_episodes.items() if v},
+                "kernel_episodes": {n: v for n, v in kernel_episodes.items() if v},
+                "min_length": self.len_ppm / 1e6,
+                "min_strength": self.min_strength,
+            }
+            self._built["section_scores"] = self._built["section_relative"]
+            self._built["gpu_scores"] = self._built["gpu_relative"]
+            self.handle = None
+        return self._built
+
+
+def _copy_episodes(d: dict) -> dict:
+    """A private copy of a report's episode scores (plain dicts, floats, ints and bools all the way down)."""
+    return _copy_onsets(d)
+
+
 class _RobustSource:
     """What a report keeps of its robust scores: the backend's handle (``records()`` waits for the kernels and copies the
     column records and the scores out on first use), the ranks its rows stand for, the sections it shows with their ids,
@@ -898,6 +951,9 @@ class Report:
         period = self.__dict__.get("_period")
         if period is not None:
             state["_period"] = period.build() if isinstance(period, _PeriodSource) else period
+        episode = self.__dict__.get("_episode")
+        if episode is not None:
+            state["_episode"] = episode.build() if isinstance(episode, _EpisodeSource) else episode
         return state
 
     def __setstate__(self, state) -> None:
@@ -1006,6 +1062,44 @@ class Report:
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no period scores."""
         t = self.period_scores()
+        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
+        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
+        return {"straggler_gpus_relative": self._ids(gr),
+                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def episode_scores(self) -> Dict[str, Any]:
+        """Episode scores (``ReportGenerator(episode_detection=True)``; ``{}`` when the report carries none).  Whether a rank
+        was slow FOR ONE STRETCH of the window and then recovered -- which moves no median, is below what a quantile looks at
+        when it is short, is no step and no beat: per timing row the interval ``[a, b)`` of its samples, in time order, that
+        spent most time above the row's mean, with at least ``min_length`` of the row (never fewer than 8 samples) inside and
+        either side of it.
+
+        ``{"gpu_scores": {rank: score}, "section_scores": {section: {rank: score}}, "section_episodes": {section: {rank:
+        {"length", "samples_ago", "began_ago", "window", "inside", "outside", "strength", "excess", "open_ended"}}},
+        "kernel_episodes": {kernel: {rank: {...}}}, "min_length": f, "min_strength": x}`` (``gpu_relative`` and
+        ``section_relative`` name the two score mappings as well) -- the episode lasted ``length`` samples of that row (0:
+        none found), ended ``samples_ago`` and began ``began_ago`` samples before the end of the row's ``window`` samples;
+        ``inside`` is its mean and ``outside`` that of all other samples, ``strength`` the share of the row's variance the
+        two-level pulse explains, ``excess`` is ``inside / outside`` where the strength is at least ``min_strength``, 1.0
+        otherwise; ``open_ended`` says that the stretch runs to the last sample an episode may end at: the row stepped up and
+        has not recovered, and ``onset_scores()`` is the better reading.  Scores are the steadiest rank's excess over this
+        rank's (NaN where a rank lacks the row): 1 = no stretch slower than the steadiest rank's, so a stretch the whole job
+        shares flags nobody.  Ranks and sections as in the score mappings, rows without samples are left out.  Plain dicts
+        and floats.  The first call waits for the episode kernels and copies their results; ``generate_report`` does not."""
+        episode = self.__dict__.get("_episode")
+        if episode is None:
+            return {}
+        if isinstance(episode, _EpisodeSource):
+            episode = self.__dict__["_episode"] = episode.build()
+        out = _copy_episodes(episode)
+        out["section_scores"], out["gpu_scores"] = out["section_relative"], out["gpu_relative"]
+        return out
+
+    def identify_episode_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose EPISODE scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no episode scores."""
+        t = self.episode_scores()
         gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
         sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
@@ -1196,7 +1290,8 @@ class ReportGenerator:
                  kernel_attribution: int = 0, tail_quantile: float = 0.0, robust_scores: bool = False,
                  robust_min_ranks: int = 4, robust_floor: float = 0.02, onset_detection: bool = False,
                  onset_min_segment: float = 0.05, onset_min_strength: float = 0.5, period_detection: bool = False,
-                 period_max: int = 1024, period_min_strength: float = 0.5) -> None:
+                 period_max: int = 1024, period_min_strength: float = 0.5, episode_detection: bool = False,
+                 episode_min_length: float = 0.005, episode_min_strength: float = 0.5) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1320,6 +1415,27 @@ class ReportGenerator:
                 raise RuntimeError(f"period_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no period scores (backend.period_score)")
             self.period_max, self.period_min_strength = pmax, strength
+        # episode scores: every ring report also carries, per row, the one stretch of the window that spent most time above
+        # the row's mean, if any, and relative scores built from the excesses (Report.episode_scores); off: no buffer, no
+        # launch, no collective, no backend call.  The step adds one collective per report, so EVERY rank must pass the same
+        # value.
+        self.episode_len_ppm = 0  # (0 = off)
+        if episode_detection:
+            len_ppm = _backend_mod._native.episode_len_ppm(episode_min_length)
+            try:
+                strength = float(episode_min_strength)
+            except (TypeError, ValueError):
+                raise ValueError(f"episode_min_strength must be a number within [0, 1], got {episode_min_strength!r}") from None
+            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"episode_min_strength must be within [0, 1], got {episode_min_strength!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"episode_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "episode scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "episode_score"):
+                raise RuntimeError(f"episode_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no episode scores (backend.episode_score)")
+            self.episode_len_ppm, self.episode_min_strength = len_ppm, strength
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -1385,6 +1501,16 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
+        if self.episode_len_ppm and not self.tail_q_ppm and not self.onset_seg_ppm and not self.period_max:
+            # the episode step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
+            # episodes stay on that route as a whole (the option has the same value on every rank: no collective here)
+            self._direct = None
+            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (episode_detection is "
+                                           "set: reports with episode scores do not use the in-stream routes)", "mode": "c10d"}
+            if mode != "c10d":
+                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while episode_detection is set: reports with episode "
+                             "scores run on torch.distributed's route (c10d)", mode)
+            return
         if self.period_max and not self.tail_q_ppm and not self.onset_seg_ppm:
             # the period step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
             # periods stay on that route as a whole (the option has the same value on every rank: no collective here)
@@ -1534,6 +1660,8 @@ class ReportGenerator:
                 ws.onset_settle()  # ... or an onset score kernel
             if getattr(ws, "_period_last", None) is not None:
                 ws.period_settle()  # ... or a period score kernel
+            if getattr(ws, "_episode_last", None) is not None:
+                ws.episode_settle()  # ... or an episode score kernel
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1734,6 +1862,8 @@ class ReportGenerator:
             ws.onset_settle()  # ... or an onset score kernel
         if getattr(ws, "_period_last", None) is not None:
             ws.period_settle()  # ... or a period score kernel
+        if getattr(ws, "_episode_last", None) is not None:
+            ws.episode_settle()  # ... or an episode score kernel
         self._last_plan_fused = fused
         if fused and attr_n and not hasattr(rings, "report_attribute"):
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
@@ -1910,6 +2040,32 @@ class ReportGenerator:
         report.__dict__["_period"] = _PeriodSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
                                                    self.period_max, self.period_min_strength)
 
+    # ---- episode scores -----------------------------------------------------------------------------
+    def _episode_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The episode step of a ring report, once per ``generate_report_from_rings`` call behind its last score round (and
+        behind the tail, onset and period steps, when they are on), on that round's workspace: episode kernel on the window
+        the report saw -> [one all-gather of the episode rows] -> episode score kernel for the ranks the report covers, hung
+        on ``report`` unread.  Every rank issues it at every report, whatever the report found and whether or not it holds a
+        report (a gathering generator's other ranks): same collectives everywhere."""
+        be = _backend_mod.get_backend()
+        if not hasattr(rings, "episode_local") or not hasattr(be, "episode_score"):
+            raise RuntimeError("episode_detection: the active backend has no episode scores (rings.episode_local / backend.episode_score)")
+        send, table = rings.episode_local(ws, self.episode_len_ppm, self.episode_min_strength, rows_active, fused)
+        if self.world_size > 1:
+            with be.stream_context():  # (behind the episode kernel)
+                table = dist_utils.all_gather_rows(send, table, self.group)
+        if report is None or report is False:
+            return
+        if self.gather_on_rank0:
+            lo, hi = 0, ws.R
+        else:
+            lo = self.rank * local_ranks
+            hi = lo + local_ranks
+        view = report.__dict__["_src"].view
+        handle = be.episode_score(ws, table, ws.table, lo, hi - lo)
+        report.__dict__["_episode"] = _EpisodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
+                                                     self.episode_len_ppm, self.episode_min_strength)
+
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],
                         kernel_summaries: Mapping[str, _SummaryType]):
@@ -1919,8 +2075,9 @@ class ReportGenerator:
         ``gather_on_rank0`` is set.  The summaries are packed into this rank's exchange row on the
         host; exchange and scoring run on the device exactly as in the ring path.  Summaries hold no samples: a report
         of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``), no onset scores
-        (``onset_detection``; ``Report.onset_scores()`` is ``{}``) and no period scores (``period_detection``;
-        ``Report.period_scores()`` is ``{}``).
+        (``onset_detection``; ``Report.onset_scores()`` is ``{}``), no period scores (``period_detection``;
+        ``Report.period_scores()`` is ``{}``) and no episode scores (``episode_detection``; ``Report.episode_scores()`` is
+        ``{}``).
         """
         t0 = time.perf_counter_ns()
         self.world_size = dist_utils.get_world_size(self.group)
@@ -1972,9 +2129,9 @@ class ReportGenerator:
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
-        if (self.onset_seg_ppm or self.period_max) and not getattr(rings, "onset_enabled", False):
+        if (self.onset_seg_ppm or self.period_max or self.episode_len_ppm) and not getattr(rings, "onset_enabled", False):
             if not hasattr(rings, "onset_enable"):
-                raise RuntimeError(f"{'onset' if self.onset_seg_ppm else 'period'}_detection: the active backend has no ring-start "
+                raise RuntimeError(f"{'onset' if self.onset_seg_ppm else 'period' if self.period_max else 'episode'}_detection: the active backend has no ring-start "
                                    "snapshot (rings.onset_enable)")
             rings.onset_enable(True)  # (before this window's report: it notes where every ring's oldest sample lives)
         if not self._direct_tried and self.world_size != 1:  # (a single process has no route to build)
@@ -2001,6 +2158,8 @@ class ReportGenerator:
                     self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 if self.period_max:
                     self._period_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+                if self.episode_len_ppm:
+                    self._episode_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 return out
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
@@ -2020,6 +2179,8 @@ class ReportGenerator:
                 self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             if self.period_max:
                 self._period_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+            if self.episode_len_ppm:
+                self._episode_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
@@ -2052,6 +2213,8 @@ class ReportGenerator:
             self._onset_step(report, rings, ws, mapper, rows_used, False, local_ranks)
         if self.period_max:
             self._period_step(report, rings, ws, mapper, rows_used, False, local_ranks)
+        if self.episode_len_ppm:
+            self._episode_step(report, rings, ws, mapper, rows_used, False, local_ranks)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

@@ -164,6 +164,8 @@ class _Lane:
             return None  # (the onset step follows the report in the generator's paths: DESIGN.md, "Onset scores")
         if getattr(reporter, "period_max", 0):
             return None  # (the period step follows the report in the generator's paths: DESIGN.md, "Period scores")
+        if getattr(reporter, "episode_len_ppm", 0):
+            return None  # (the episode step follows the report in the generator's paths: DESIGN.md, "Episode scores")
         if getattr(reporter, "robust_scores", False):
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         ext = manager.cupti_ext
@@ -396,6 +398,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
         period_detection: Optional[bool] = None,
         period_max: int = 1024,
         period_min_strength: float = 0.5,
+        episode_detection: Optional[bool] = None,
+        episode_min_length: float = 0.005,
+        episode_min_strength: float = 0.5,
     ):
         """
         Args:
@@ -453,6 +458,18 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 samples (fewer than four repetitions are not a beat).
             period_min_strength: a beat counts when its phase means explain (adjusted R^2) at least this share of the row's
                 variance, within [0, 1].  0.5 is a default, not a measurement.
+            episode_detection: every report also says whether a rank was slow FOR ONE STRETCH of the window and then recovered
+                (a thermal excursion, a neighbour's checkpoint, a link that flapped): per section and kernel row the interval
+                of its samples, in time order, that spent most time above the row's mean, how long it lasted, how many samples
+                ago it ended, the means inside and outside, and relative scores built from their ratio
+                (``Report.episode_scores()``, ``Report.identify_episode_stragglers()``).  A rank that is 1.5 x slower on 300
+                consecutive samples of 10 000 moves neither its median nor its 0.95-quantile, and has no step and no beat;
+                here it scores 0.67.  Needs ``relative_perf_scores``.  Default: ``NVRX_EPISODE_DETECTION``, else off.  Pass
+                the same values on EVERY rank (the step adds one collective per report).
+            episode_min_length: an episode, and the stretch of "normal" either side of it, holds at least this share of the
+                row's samples, within [0.000001, 0.333333]; never fewer than 8 samples.
+            episode_min_strength: an episode counts when its two levels explain at least this share of the row's variance,
+                within [0, 1].  0.5 is a default, not a measurement.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -501,13 +518,16 @@ class Detector(metaclass=_DeviceSideOnDemand):
             onset_detection = os.environ.get("NVRX_ONSET_DETECTION", "0") not in ("", "0")
         if period_detection is None:
             period_detection = os.environ.get("NVRX_PERIOD_DETECTION", "0") not in ("", "0")
+        if episode_detection is None:
+            episode_detection = os.environ.get("NVRX_EPISODE_DETECTION", "0") not in ("", "0")
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
                                        robust_scores=robust_scores, onset_detection=onset_detection,
                                        onset_min_segment=onset_min_segment, onset_min_strength=onset_min_strength,
                                        period_detection=period_detection, period_max=period_max,
-                                       period_min_strength=period_min_strength)
+                                       period_min_strength=period_min_strength, episode_detection=episode_detection,
+                                       episode_min_length=episode_min_length, episode_min_strength=episode_min_strength)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
