@@ -224,15 +224,8 @@ extern "C" {
 
 int nvrx_row_onset(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride,
                    uint32_t min_seg_ppm, void *d_out, void *stream) {
-    if (rows < 0) return fail(NVRX_ERR_INVALID, "rows=%d is negative", rows);
-    if (row_stride <= 0 || row_stride % 4 != 0) return fail(NVRX_ERR_INVALID, "row_stride %d is not a positive multiple of 4", row_stride);
-    if (row_stride > NVRX_MAX_RING_CAP) return fail(NVRX_ERR_RANGE, "row_stride %d exceeds %d", row_stride, NVRX_MAX_RING_CAP);
-    const int rc = onset_seg_check(min_seg_ppm);
-    if (rc) return rc;
-    if (rows == 0) return NVRX_OK;
-    if (!d_samples || !d_counts || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_samples) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_samples is not 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    const int rc = row_op_check(rows, row_stride, d_samples, d_counts, d_out, true, [&] { return onset_seg_check(min_seg_ppm); });
+    if (rc || rows == 0) return rc;
     OnsetArgs a{};
     a.samples = d_samples, a.counts = d_counts, a.starts = d_starts, a.out = d_out;
     a.row_stride = row_stride, a.uniform_n = -1, a.min_seg_ppm = min_seg_ppm;
@@ -241,16 +234,8 @@ int nvrx_row_onset(const float *d_samples, const uint32_t *d_counts, const uint3
 
 int nvrx_onset_score(const float *d_onset, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                      float *d_colmin_scratch, float *d_out, void *stream) {
-    if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
-    if (K > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d kernel ids, at most %d", K, NVRX_MAX_ROWS);
-    if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
-        return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
-    if (!d_onset || !d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    const int KS = K + S;
-    if (KS > 0 && !d_colmin_scratch) return fail(NVRX_ERR_INVALID, "d_colmin_scratch is null");
-    // plane 0 (the effective shifts) of a [R][6][KS] table: a [R][KS] table with a pitch of 6 * KS
-    return tail_score_launch(d_onset, ONSET_PLANES * KS, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out,
-                             as_stream(stream));
+    // plane 0 (the effective shifts) of a [R][6][KS] table
+    return plane_score(d_onset, ONSET_PLANES, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out, stream);
 }
 
 int nvrx_onset_enable(nvrx_ctx *ctx, int on) {
@@ -269,53 +254,25 @@ int nvrx_onset_enable(nvrx_ctx *ctx, int on) {
 
 int nvrx_onset_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_seg_ppm, float min_strength,
                      float *d_onset_send, int K, int S, int rows_active, void *stream) {
-    if (!ctx || !d_onset_send) return fail(NVRX_ERR_INVALID, "null argument");
-    if (K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad K/S");
-    if (K > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d kernel ids, at most %d", K, NVRX_MAX_ROWS);
-    int rc = onset_seg_check(min_seg_ppm);
-    if (rc) return rc;
-    if (!(min_strength >= 0.0f && min_strength <= 1.0f)) return fail(NVRX_ERR_RANGE, "min_strength=%g outside [0,1]", (double)min_strength);
-    if (rows_active < 0 || rows_active > ctx->rows_per_rank)
-        return fail(NVRX_ERR_INVALID, "rows_active %d outside [0,%d]", rows_active, ctx->rows_per_rank);
-    if (rows_active == 0) rows_active = ctx->rows_per_rank;
     hipStream_t st = as_stream(stream);
+    LocalWindow w;
+    int rc = local_window(ctx, desc, d_onset_send, K, S, rows_active, [&] {
+        const int bad = onset_seg_check(min_seg_ppm);
+        return bad ? bad : min_strength_check(min_strength);
+    }, "onset scores are not enabled on this context (nvrx_onset_enable)", &st, &w);
+    if (rc) return rc;
     OnsetArgs a{};
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (!ctx->onset_on) return fail(NVRX_ERR_STATE, "onset scores are not enabled on this context (nvrx_onset_enable)");
-        if (desc && ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (desc) {
-            // behind the report's last kernel, as nvrx_report_attribute orders itself
-            st = ctx->default_stream;
-            if (ctx->attr_stream != st) {
-                if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(ctx->attr_ev, ctx->attr_stream));
-                HIP_TRY(hipStreamWaitEvent(st, ctx->attr_ev, 0));
-            }
-        }
-        // nothing is flushed: counts and ring starts are the ones of the window the report's statistics kernel read
-        a.uniform_n = ctx->tail_uniform_n;
-        a.samples = ctx->d_samples, a.counts = ctx->d_counts, a.gid = ctx->d_gid;
-        a.row_stride = ctx->row_stride;
-        a.rows_active = rows_active, a.rows_per_rank = ctx->rows_per_rank;
-        if (ctx->onset_wrapped) {  // (rare: a window longer than the ring)
-            HIP_TRY(hipMemcpyAsync(ctx->d_onset_starts, ctx->h_onset_starts, (size_t)ctx->onset_rows * sizeof(uint32_t),
-                                   hipMemcpyHostToDevice, st));
-            if (ctx->onset_rows < ctx->rows)
-                HIP_TRY(hipMemsetAsync(ctx->d_onset_starts + ctx->onset_rows, 0, (size_t)(ctx->rows - ctx->onset_rows) * sizeof(uint32_t), st));
-            a.starts = ctx->d_onset_starts;
-        }
-    }
+    window_args(w, &a);
+    a.starts = w.starts;
     a.out = d_onset_send;
     a.KS = K + S;
     a.min_seg_ppm = min_seg_ppm;
     a.min_strength = min_strength;
     const size_t slots = (size_t)ctx->local_ranks * ONSET_PLANES * (size_t)a.KS;
     if (slots == 0) return NVRX_OK;
-    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_onset_send, slots, -1.0f);
-    HIP_TRY(hipGetLastError());
-    return onset_launch(a, ctx->local_ranks * rows_active, st);
+    rc = fill_minus_one(d_onset_send, slots, st);
+    if (rc) return rc;
+    return onset_launch(a, ctx->local_ranks * w.rows_active, st);
 }
 
 }  // extern "C"

@@ -3949,6 +3949,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 }  // extern "C"
 
 #include "nvrx_attribute.inl"
+#include "nvrx_rowfam.inl"
 #include "nvrx_tail.inl"
 #include "nvrx_onset.inl"
 #include "nvrx_robust.inl"

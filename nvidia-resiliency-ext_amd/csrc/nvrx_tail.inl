@@ -256,14 +256,8 @@ extern "C" {
 
 int nvrx_row_quantile(const float *d_samples, const uint32_t *d_counts, int rows, int row_stride, uint32_t q_ppm,
                       float *d_out, void *stream) {
-    if (rows < 0) return fail(NVRX_ERR_INVALID, "rows=%d is negative", rows);
-    if (row_stride <= 0 || row_stride % 4 != 0) return fail(NVRX_ERR_INVALID, "row_stride %d is not a positive multiple of 4", row_stride);
-    if (row_stride > NVRX_MAX_RING_CAP) return fail(NVRX_ERR_RANGE, "row_stride %d exceeds %d", row_stride, NVRX_MAX_RING_CAP);
-    const int rc = tail_q_check(q_ppm);
-    if (rc) return rc;
-    if (rows == 0) return NVRX_OK;
-    if (!d_samples || !d_counts || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_samples) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_samples is not 16-byte aligned");
+    const int rc = row_op_check(rows, row_stride, d_samples, d_counts, d_out, false, [&] { return tail_q_check(q_ppm); });
+    if (rc || rows == 0) return rc;
     QuantArgs a{};
     a.samples = d_samples, a.counts = d_counts, a.out = d_out;
     a.row_stride = row_stride, a.uniform_n = -1, a.q_ppm = q_ppm;
@@ -272,54 +266,25 @@ int nvrx_row_quantile(const float *d_samples, const uint32_t *d_counts, int rows
 
 int nvrx_tail_score(const float *d_tails, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                     float *d_colmin_scratch, float *d_out, void *stream) {
-    if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
-    if (K > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d kernel ids, at most %d", K, NVRX_MAX_ROWS);
-    if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
-        return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
-    if (!d_tails || !d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if (K + S > 0 && !d_colmin_scratch) return fail(NVRX_ERR_INVALID, "d_colmin_scratch is null");
-    return tail_score_launch(d_tails, K + S, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out, as_stream(stream));
+    return plane_score(d_tails, 1, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out, stream);
 }
 
 int nvrx_tail_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t q_ppm, float *d_tail_send, int K, int S,
                     int rows_active, void *stream) {
-    if (!ctx || !d_tail_send) return fail(NVRX_ERR_INVALID, "null argument");
-    if (K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad K/S");
-    if (K > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d kernel ids, at most %d", K, NVRX_MAX_ROWS);
-    int rc = tail_q_check(q_ppm);
-    if (rc) return rc;
-    if (rows_active < 0 || rows_active > ctx->rows_per_rank)
-        return fail(NVRX_ERR_INVALID, "rows_active %d outside [0,%d]", rows_active, ctx->rows_per_rank);
-    if (rows_active == 0) rows_active = ctx->rows_per_rank;
     hipStream_t st = as_stream(stream);
+    LocalWindow w;
+    int rc = local_window(ctx, desc, d_tail_send, K, S, rows_active, [&] { return tail_q_check(q_ppm); }, nullptr, &st, &w);
+    if (rc) return rc;
     QuantArgs a{};
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (desc && ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (desc) {
-            // behind the report's last kernel, as nvrx_report_attribute orders itself
-            st = ctx->default_stream;
-            if (ctx->attr_stream != st) {
-                if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(ctx->attr_ev, ctx->attr_stream));
-                HIP_TRY(hipStreamWaitEvent(st, ctx->attr_ev, 0));
-            }
-        }
-        // nothing is flushed: the counts are the ones the report's statistics kernel was given
-        a.uniform_n = ctx->tail_uniform_n;
-        a.samples = ctx->d_samples, a.counts = ctx->d_counts, a.gid = ctx->d_gid;
-        a.row_stride = ctx->row_stride;
-        a.rows_active = rows_active, a.rows_per_rank = ctx->rows_per_rank;
-    }
+    window_args(w, &a);
     a.out = d_tail_send;
     a.KS = K + S;
     a.q_ppm = q_ppm;
     const size_t slots = (size_t)ctx->local_ranks * (size_t)a.KS;
     if (slots == 0) return NVRX_OK;
-    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_tail_send, slots, -1.0f);
-    HIP_TRY(hipGetLastError());
-    return quantile_launch(a, ctx->local_ranks * rows_active, st);
+    rc = fill_minus_one(d_tail_send, slots, st);
+    if (rc) return rc;
+    return quantile_launch(a, ctx->local_ranks * w.rows_active, st);
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .row_families import EPISODE, FAMILIES, ONSET, PERIOD, TAIL, RowFamily
 
 DEFAULT_THRESHOLDS = (0.75, 0.75, 0.75, 0.75)  # gpu_rel, section_rel, gpu_indiv, section_indiv
 
@@ -239,120 +240,40 @@ class Attribution:
         return self._host
 
 
-class Tails:
-    """Tail scores of one report (``nvrx_tail_local`` -> exchange -> ``nvrx_tail_score``), enqueued and not waited for: once
-    the score kernel has run, the workspace's tail buffer holds the gathered tail table ``[R][K+S]`` and, behind it, the
-    scores ``[n_ranks][1 + S]`` of the reported ranks.  ``records()`` waits for it and takes the private host copy (one
-    ordered D2H on the backend's stream): when a ``Report`` first asks, or -- ``Workspace.tail_settle`` -- before the next
-    report on the same workspace rewrites the table the kernel reads and the buffers it writes."""
+class RowScores:
+    """One row family's scores of one report (``nvrx_<family>_local`` -> exchange -> ``nvrx_<family>_score``;
+    row_families.py), enqueued and not waited for: once the score kernel has run, the workspace's buffer of that family
+    holds the gathered table ``[R][P][K+S]`` (``[R][K+S]`` for a family of one plane) and, behind it, the scores
+    ``[n_ranks][1 + S]`` of the reported ranks.  ``records()`` waits for it and takes the private host copy (one ordered D2H
+    on the backend's stream): when a ``Report`` first asks, or -- ``Workspace.family_settle`` -- before the next report on
+    the same workspace rewrites the table the kernel reads and the buffers it writes."""
 
-    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "q_ppm", "_host", "_lock", "_keep")
+    __slots__ = ("backend", "family", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "params", "_host", "_lock", "_keep")
 
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int,
-                 q_ppm: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
+    def __init__(self, backend: "HipBackend", family: RowFamily, buf: torch.Tensor, R: int, K: int, S: int, first_rank: int,
+                 n_ranks: int, params: tuple = ()):
+        self.backend, self.family, self.d_ptr = backend, family, buf.data_ptr()
         self.R, self.K, self.S = R, K, S
-        self.first_rank, self.n_ranks, self.q_ppm = first_rank, n_ranks, q_ppm
+        self.first_rank, self.n_ranks, self.params = first_rank, n_ranks, params
         self._host = None
         self._lock = threading.Lock()
         self._keep = buf  # the device buffer lives at least until the copy is taken
 
     def records(self):
-        """``(tails [n_ranks, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first call
-        waits for the kernels."""
+        """``(planes [n_ranks, P, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks -- ``[n_ranks, K+S]`` for a
+        family of one plane -- (private copies); the first call waits for the kernels."""
         if self._host is None:
             with self._lock:
                 if self._host is None:
-                    self._host = self.backend.tails_copy_out(self)
+                    self._host = getattr(self.backend, self.family.stem + "_copy_out")(self)
                     self.backend = self._keep = None
         return self._host
 
 
-class Onsets:
-    """Onset scores of one report (``nvrx_onset_local`` -> exchange -> ``nvrx_onset_score``), enqueued and not waited for: once
-    the score kernel has run, the workspace's onset buffer holds the gathered onset table ``[R][6][K+S]`` (planes ``{e,
-    before, after, strength, ago, n}``) and, behind it, the scores ``[n_ranks][1 + S]`` of the reported ranks.  ``records()``
-    waits for it and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report`` first asks,
-    or -- ``Workspace.onset_settle`` -- before the next report on the same workspace rewrites the table the kernel reads
-    and the buffers it writes."""
+class _FamilyBuffers:
+    """A workspace's device buffers of one row family, and the handle that may still be using them."""
 
-    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.R, self.K, self.S = R, K, S
-        self.first_rank, self.n_ranks = first_rank, n_ranks
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(onsets [n_ranks, 6, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first
-        call waits for the kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.onsets_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
-
-
-class Periods:
-    """Period scores of one report (``nvrx_period_local`` -> exchange -> ``nvrx_period_score``), enqueued and not waited for:
-    once the score kernel has run, the workspace's period buffer holds the gathered period table ``[R][7][K+S]`` (planes
-    ``{e, peak, rest, strength, period, ago, n}``) and, behind it, the scores ``[n_ranks][1 + S]`` of the reported ranks.
-    ``records()`` waits for it and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report``
-    first asks, or -- ``Workspace.period_settle`` -- before the next report on the same workspace rewrites the table the
-    kernel reads and the buffers it writes."""
-
-    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.R, self.K, self.S = R, K, S
-        self.first_rank, self.n_ranks = first_rank, n_ranks
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(periods [n_ranks, 7, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first
-        call waits for the kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.periods_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
-
-
-class Episodes:
-    """Episode scores of one report (``nvrx_episode_local`` -> exchange -> ``nvrx_episode_score``), enqueued and not waited for:
-    once the score kernel has run, the workspace's episode buffer holds the gathered episode table ``[R][7][K+S]`` (planes
-    ``{e, inside, outside, strength, length, ago, n}``) and, behind it, the scores ``[n_ranks][1 + S]`` of the reported ranks.
-    ``records()`` waits for it and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report``
-    first asks, or -- ``Workspace.episode_settle`` -- before the next report on the same workspace rewrites the table the
-    kernel reads and the buffers it writes."""
-
-    __slots__ = ("backend", "d_ptr", "R", "K", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, first_rank: int, n_ranks: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.R, self.K, self.S = R, K, S
-        self.first_rank, self.n_ranks = first_rank, n_ranks
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(episodes [n_ranks, 7, K+S], scores [n_ranks, 1 + S])`` f32 of the reported ranks (private copies); the first
-        call waits for the kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.episodes_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
+    __slots__ = ("buf", "send", "table", "scratch", "last")
 
 
 class Robust:
@@ -494,119 +415,74 @@ class Workspace:
         if last is not None:
             last.records()
 
-    # ---- tail scores (off unless a ReportGenerator asks: nothing is allocated before) ----------------------------
-    _tail_buf = None      # device: tail table [R][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
-    _tail_send = None     # device: this process' tail rows [local_ranks][K+S] (the table's own rows without an exchange)
-    _tail_table = None    # ... the table part of _tail_buf as [R][K+S]
-    _tail_scratch = None  # device: column minima
-    _tail_last = None     # the Tails whose kernels may still be reading the table / writing the buffers
+    # ---- row families: tail, onset, period, episode scores (off unless a ReportGenerator asks: nothing is allocated before) ----
+    _family_state = None  # family name -> _FamilyBuffers, once that family has run on this workspace
 
-    def tail_buffers(self):
-        """``(tail_send, tail_table, scores, scratch)`` (cold: allocated on first use)."""
-        if self._tail_buf is None:
-            KS, R = self.K + self.S, self.R
+    def family_buffers(self, fam: RowFamily):
+        """``(send, table, scores, scratch)`` of one row family (cold: allocated on first use): ONE buffer holds the gathered
+        table ``[R][P * (K+S)]`` and then the scores ``[R][1 + S]`` (one copy-out); ``send`` are this process' rows
+        ``[local_ranks][P * (K+S)]`` (the table's own rows without an exchange); ``scratch`` takes the column minima."""
+        if self._family_state is None:
+            self._family_state = {}
+        st = self._family_state.get(fam.name)
+        KS, R, P = self.K + self.S, self.R, fam.planes
+        if st is None:
+            st = self._family_state[fam.name] = _FamilyBuffers()
             dev = self._backend.device
             with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._tail_buf = torch.empty(max(R * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
-                self._tail_table = self._tail_buf[: R * KS].view(R, KS)
-                self._tail_send = (self._tail_table if R == self.local_ranks
-                                   else torch.empty((self.local_ranks, KS), dtype=torch.float32, device=dev))
-                self._tail_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
-        return self._tail_send, self._tail_table, self._tail_buf[self.R * (self.K + self.S):], self._tail_scratch
+                st.buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
+                st.table = st.buf[: R * P * KS].view(R, P * KS)
+                st.send = (st.table if R == self.local_ranks
+                           else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
+                st.scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
+            st.last = None  # the RowScores whose kernels may still be reading the table / writing the buffers
+        return st.send, st.table, st.buf[R * P * KS:], st.scratch
+
+    def family_settle(self, fam: RowFamily) -> None:
+        """Before anything rewrites this workspace's table or that family's buffers: the family's last step's kernels have
+        run and their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        st = self._family_state.get(fam.name) if self._family_state else None
+        if st is not None and st.last is not None:
+            last, st.last = st.last, None
+            last.records()
+
+    # (the families by name, as the backend and the rings have them: one-line delegations)
+    def tail_buffers(self):
+        return self.family_buffers(TAIL)
 
     def tail_settle(self) -> None:
-        """Before anything rewrites this workspace's table or tail buffers: the last tail step's kernels have run and
-        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
-        last, self._tail_last = self._tail_last, None
-        if last is not None:
-            last.records()
-
-    # ---- onset scores (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------
-    _onset_buf = None      # device: onset table [R][6][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
-    _onset_send = None     # device: this process' onset rows [local_ranks][6][K+S] (the table's own rows without an exchange)
-    _onset_table = None    # ... the table part of _onset_buf as [R][6 * (K+S)]
-    _onset_scratch = None  # device: column minima
-    _onset_last = None     # the Onsets whose kernels may still be reading the table / writing the buffers
+        self.family_settle(TAIL)
 
     def onset_buffers(self):
-        """``(onset_send, onset_table, scores, scratch)`` (cold: allocated on first use)."""
-        if self._onset_buf is None:
-            KS, R = self.K + self.S, self.R
-            P = _native.ONSET_PLANES
-            dev = self._backend.device
-            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._onset_buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
-                self._onset_table = self._onset_buf[: R * P * KS].view(R, P * KS)
-                self._onset_send = (self._onset_table if R == self.local_ranks
-                                    else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
-                self._onset_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
-        return (self._onset_send, self._onset_table, self._onset_buf[self.R * _native.ONSET_PLANES * (self.K + self.S):],
-                self._onset_scratch)
+        return self.family_buffers(ONSET)
 
     def onset_settle(self) -> None:
-        """Before anything rewrites this workspace's table or onset buffers: the last onset step's kernels have run and
-        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
-        last, self._onset_last = self._onset_last, None
-        if last is not None:
-            last.records()
-
-    # ---- period scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
-    _period_buf = None      # device: period table [R][7][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
-    _period_send = None     # device: this process' period rows [local_ranks][7][K+S] (the table's own rows without an exchange)
-    _period_table = None    # ... the table part of _period_buf as [R][7 * (K+S)]
-    _period_scratch = None  # device: column minima
-    _period_last = None     # the Periods whose kernels may still be reading the table / writing the buffers
+        self.family_settle(ONSET)
 
     def period_buffers(self):
-        """``(period_send, period_table, scores, scratch)`` (cold: allocated on first use)."""
-        if self._period_buf is None:
-            KS, R = self.K + self.S, self.R
-            P = _native.PERIOD_PLANES
-            dev = self._backend.device
-            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._period_buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
-                self._period_table = self._period_buf[: R * P * KS].view(R, P * KS)
-                self._period_send = (self._period_table if R == self.local_ranks
-                                     else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
-                self._period_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
-        return (self._period_send, self._period_table, self._period_buf[self.R * _native.PERIOD_PLANES * (self.K + self.S):],
-                self._period_scratch)
+        return self.family_buffers(PERIOD)
 
     def period_settle(self) -> None:
-        """Before anything rewrites this workspace's table or period buffers: the last period step's kernels have run and
-        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
-        last, self._period_last = self._period_last, None
-        if last is not None:
-            last.records()
-
-    # ---- episode scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
-    _episode_buf = None      # device: episode table [R][7][K+S], then the scores [R][1 + S] (one buffer: one copy-out)
-    _episode_send = None     # device: this process' episode rows [local_ranks][7][K+S] (the table's own rows without an exchange)
-    _episode_table = None    # ... the table part of _episode_buf as [R][7 * (K+S)]
-    _episode_scratch = None  # device: column minima
-    _episode_last = None     # the Episodes whose kernels may still be reading the table / writing the buffers
+        self.family_settle(PERIOD)
 
     def episode_buffers(self):
-        """``(episode_send, episode_table, scores, scratch)`` (cold: allocated on first use)."""
-        if self._episode_buf is None:
-            KS, R = self.K + self.S, self.R
-            P = _native.EPISODE_PLANES
-            dev = self._backend.device
-            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._episode_buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
-                self._episode_table = self._episode_buf[: R * P * KS].view(R, P * KS)
-                self._episode_send = (self._episode_table if R == self.local_ranks
-                                     else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
-                self._episode_scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
-        return (self._episode_send, self._episode_table, self._episode_buf[self.R * _native.EPISODE_PLANES * (self.K + self.S):],
-                self._episode_scratch)
+        return self.family_buffers(EPISODE)
 
     def episode_settle(self) -> None:
-        """Before anything rewrites this workspace's table or episode buffers: the last episode step's kernels have run and
-        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
-        last, self._episode_last = self._episode_last, None
-        if last is not None:
-            last.records()
+        self.family_settle(EPISODE)
+
+    def settle_readers(self) -> None:
+        """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
+        reading it -- attribution, tails, robust scores, onsets, periods, episodes -- has run and delivered."""
+        if self._attr_last is not None:
+            self.attr_settle()
+        if self._family_state:
+            self.family_settle(TAIL)
+        if self._robust_last is not None:
+            self.robust_settle()
+        if self._family_state:
+            for fam in FAMILIES[1:]:
+                self.family_settle(fam)
 
     # ---- robust scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
     _robust_buf = None   # device: column records, then the scores of the last robust step of this workspace's table
@@ -765,153 +641,83 @@ class HipBackend:
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, attr.d_ptr, host.nbytes, self._stream_handle))
         return host
 
-    def tail_score(self, ws: Workspace, tails: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
-                   n_ranks: Optional[int] = None, q_ppm: int = 0) -> Tails:
-        """Relative tail scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered tail table ``tails``
-        ([R, K+S], ``Rings.tail_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
-        ``nvrx_tail_score`` enqueued on the backend's stream.  Nothing is waited for."""
+    def _family_score(self, fam: RowFamily, ws: Workspace, planes: torch.Tensor, table: torch.Tensor, first_rank: int,
+                      n_ranks: Optional[int], params: tuple = ()) -> RowScores:
+        """Relative scores of one row family for ranks ``[first_rank, first_rank + n_ranks)`` from its gathered table
+        ``planes`` ([R, P * (K+S)], ``Rings.<family>_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was
+        given): ``nvrx_<family>_score`` enqueued on the backend's stream.  Nothing is waited for."""
         n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        _, tail_table, scores, scratch = ws.tail_buffers()
-        assert tails is tail_table or (tails.data_ptr() == tail_table.data_ptr())
+        _, fam_table, scores, scratch = ws.family_buffers(fam)
+        assert planes is fam_table or (planes.data_ptr() == fam_table.data_ptr())
         table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_tail_score(tail_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
-                                      scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
+        rc = getattr(self.lib, fam.c_score)(fam_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
+                                            scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
         if rc < 0:
             _native.check(rc)
-        out = ws._tail_last = Tails(self, ws._tail_buf, ws.R, ws.K, ws.S, first_rank, n_ranks, q_ppm)
+        st = ws._family_state[fam.name]
+        out = st.last = RowScores(self, fam, st.buf, ws.R, ws.K, ws.S, first_rank, n_ranks, params)
         return out
 
-    def tails_copy_out(self, t: Tails):
-        """The one wait of a report's tails: a D2H of the tail table and the scores on the backend's stream, behind the kernels."""
-        KS = t.K + t.S
-        n = t.R * KS + t.n_ranks * (1 + t.S)
-        host = np.empty(max(n, 1), dtype=np.float32)
-        if n:
-            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
-        tails = host[: t.R * KS].reshape(t.R, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
-        return tails, host[t.R * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
-
-    def onset_score(self, ws: Workspace, onsets: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
-                    n_ranks: Optional[int] = None) -> Onsets:
-        """Relative onset scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered onset table ``onsets``
-        ([R, 6 * (K+S)], ``Rings.onset_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
-        ``nvrx_onset_score`` enqueued on the backend's stream.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        _, onset_table, scores, scratch = ws.onset_buffers()
-        assert onsets is onset_table or (onsets.data_ptr() == onset_table.data_ptr())
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_onset_score(onset_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
-                                       scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._onset_last = Onsets(self, ws._onset_buf, ws.R, ws.K, ws.S, first_rank, n_ranks)
-        return out
-
-    def onsets_copy_out(self, t: Onsets):
-        """The one wait of a report's onsets: a D2H of the onset table and the scores on the backend's stream, behind the kernels."""
-        KS, P = t.K + t.S, _native.ONSET_PLANES
+    def family_copy_out(self, t: RowScores):
+        """The one wait of a report's row family: a D2H of its table and scores on the backend's stream, behind the kernels."""
+        KS, P = t.K + t.S, t.family.planes
         n = t.R * P * KS + t.n_ranks * (1 + t.S)
         host = np.empty(max(n, 1), dtype=np.float32)
         if n:
             _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
-        onsets = host[: t.R * P * KS].reshape(t.R, P, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
-        return onsets, host[t.R * P * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+        shape = (t.R, KS) if P == 1 else (t.R, P, KS)
+        planes = host[: t.R * P * KS].reshape(shape)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        return planes, host[t.R * P * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
 
-    def row_onset(self, samples: torch.Tensor, counts: torch.Tensor, min_seg_ppm: int,
-                  starts: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Stateless onset operator on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) -> [rows, 4]
-        int32 records ``{ago, before, after, strength}`` (the last three are f32 bit patterns; ``nvrx_row_onset``)."""
+    def tails_copy_out(self, t: RowScores):
+        return self.family_copy_out(t)
+
+    def onsets_copy_out(self, t: RowScores):
+        return self.family_copy_out(t)
+
+    def periods_copy_out(self, t: RowScores):
+        return self.family_copy_out(t)
+
+    def episodes_copy_out(self, t: RowScores):
+        return self.family_copy_out(t)
+
+    def tail_score(self, ws, tails, table, first_rank: int = 0, n_ranks: Optional[int] = None, q_ppm: int = 0) -> RowScores:
+        return self._family_score(TAIL, ws, tails, table, first_rank, n_ranks, (q_ppm,))
+
+    def onset_score(self, ws, onsets, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
+        return self._family_score(ONSET, ws, onsets, table, first_rank, n_ranks)
+
+    def period_score(self, ws, periods, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
+        return self._family_score(PERIOD, ws, periods, table, first_rank, n_ranks)
+
+    def episode_score(self, ws, episodes, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
+        return self._family_score(EPISODE, ws, episodes, table, first_rank, n_ranks)
+
+    def _row_op(self, fam: RowFamily, samples: torch.Tensor, counts: torch.Tensor, param: int,
+                starts: Optional[torch.Tensor]) -> torch.Tensor:
+        """A family's stateless operator on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) ->
+        [rows, 4] int32 records, the last three words f32 bit patterns (``nvrx_row_<family>``, include/nvrx_straggler.h)."""
         rows, stride = samples.shape
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(self.stream):
             out = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=samples.device)
-            _native.check(self.lib.nvrx_row_onset(samples.data_ptr(), counts.data_ptr(),
-                                                  starts.data_ptr() if starts is not None else None, rows, stride,
-                                                  int(min_seg_ppm), out.data_ptr(), self.stream_handle))
+            _native.check(getattr(self.lib, fam.c_row)(samples.data_ptr(), counts.data_ptr(),
+                                                       starts.data_ptr() if starts is not None else None, rows, stride,
+                                                       int(param), out.data_ptr(), self.stream_handle))
         self.stream.synchronize()
         return out[:rows]
 
-    def period_score(self, ws: Workspace, periods: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
-                     n_ranks: Optional[int] = None) -> Periods:
-        """Relative period scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered period table ``periods``
-        ([R, 7 * (K+S)], ``Rings.period_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
-        ``nvrx_period_score`` enqueued on the backend's stream.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        _, period_table, scores, scratch = ws.period_buffers()
-        assert periods is period_table or (periods.data_ptr() == period_table.data_ptr())
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_period_score(period_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
-                                        scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._period_last = Periods(self, ws._period_buf, ws.R, ws.K, ws.S, first_rank, n_ranks)
-        return out
+    def row_onset(self, samples, counts, min_seg_ppm: int, starts=None) -> torch.Tensor:
+        """Records ``{ago, before, after, strength}``."""
+        return self._row_op(ONSET, samples, counts, min_seg_ppm, starts)
 
-    def periods_copy_out(self, t: Periods):
-        """The one wait of a report's periods: a D2H of the period table and the scores on the backend's stream, behind the kernels."""
-        KS, P = t.K + t.S, _native.PERIOD_PLANES
-        n = t.R * P * KS + t.n_ranks * (1 + t.S)
-        host = np.empty(max(n, 1), dtype=np.float32)
-        if n:
-            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
-        periods = host[: t.R * P * KS].reshape(t.R, P, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
-        return periods, host[t.R * P * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
+    def row_period(self, samples, counts, max_period: int, starts=None) -> torch.Tensor:
+        """Records ``{period | ago << 16, peak, rest, strength}``."""
+        return self._row_op(PERIOD, samples, counts, max_period, starts)
 
-    def row_period(self, samples: torch.Tensor, counts: torch.Tensor, max_period: int,
-                   starts: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Stateless period operator on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) -> [rows, 4]
-        int32 records ``{period | ago << 16, peak, rest, strength}`` (the last three are f32 bit patterns;
-        ``nvrx_row_period``)."""
-        rows, stride = samples.shape
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.stream):
-            out = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=samples.device)
-            _native.check(self.lib.nvrx_row_period(samples.data_ptr(), counts.data_ptr(),
-                                                   starts.data_ptr() if starts is not None else None, rows, stride,
-                                                   int(max_period), out.data_ptr(), self.stream_handle))
-        self.stream.synchronize()
-        return out[:rows]
-
-    def episode_score(self, ws: Workspace, episodes: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
-                     n_ranks: Optional[int] = None) -> Episodes:
-        """Relative episode scores of ranks ``[first_rank, first_rank + n_ranks)`` from the gathered episode table ``episodes``
-        ([R, 7 * (K+S)], ``Rings.episode_local``'s) and the weights in ``table`` ([R, L], the table ``score`` was given):
-        ``nvrx_episode_score`` enqueued on the backend's stream.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        _, episode_table, scores, scratch = ws.episode_buffers()
-        assert episodes is episode_table or (episodes.data_ptr() == episode_table.data_ptr())
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_episode_score(episode_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
-                                        scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._episode_last = Episodes(self, ws._episode_buf, ws.R, ws.K, ws.S, first_rank, n_ranks)
-        return out
-
-    def episodes_copy_out(self, t: Episodes):
-        """The one wait of a report's episodes: a D2H of the episode table and the scores on the backend's stream, behind the kernels."""
-        KS, P = t.K + t.S, _native.EPISODE_PLANES
-        n = t.R * P * KS + t.n_ranks * (1 + t.S)
-        host = np.empty(max(n, 1), dtype=np.float32)
-        if n:
-            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
-        episodes = host[: t.R * P * KS].reshape(t.R, P, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
-        return episodes, host[t.R * P * KS : n].reshape(t.n_ranks, 1 + t.S).copy()
-
-    def row_episode(self, samples: torch.Tensor, counts: torch.Tensor, min_len_ppm: int,
-                   starts: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Stateless episode operator on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) -> [rows, 4]
-        int32 records ``{ago | length << 16, inside, outside, strength}`` (the last three are f32 bit patterns;
-        ``nvrx_row_episode``)."""
-        rows, stride = samples.shape
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.stream):
-            out = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=samples.device)
-            _native.check(self.lib.nvrx_row_episode(samples.data_ptr(), counts.data_ptr(),
-                                                   starts.data_ptr() if starts is not None else None, rows, stride,
-                                                   int(min_len_ppm), out.data_ptr(), self.stream_handle))
-        self.stream.synchronize()
-        return out[:rows]
+    def row_episode(self, samples, counts, min_len_ppm: int, starts=None) -> torch.Tensor:
+        """Records ``{ago | length << 16, inside, outside, strength}``."""
+        return self._row_op(EPISODE, samples, counts, min_len_ppm, starts)
 
     def robust_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
                      min_ranks: int = 4, floor_rel: float = 0.02) -> Robust:
@@ -1252,75 +1058,43 @@ class HipRings:
         out = ws._robust_last = Robust(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
         return out
 
-    def tail_local(self, ws: Workspace, q_ppm: int, rows_active: int = 0, fused: bool = False):
-        """The ``q_ppm / 1e6`` quantile of every ring row as the report just issued on ``ws`` saw it, packed by gid into the
-        workspace's tail rows (``nvrx_tail_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s).
-        Returns ``(tail_send [local_ranks, K+S], tail_table [R, K+S])`` -- the same rows when nothing is exchanged.
-        Waits for the quantile kernel: the rings are emptied by count, and the next window's device-side writers on other
-        streams may overwrite slots as soon as the report call returns."""
-        ws.tail_settle()
-        send, table, _, _ = ws.tail_buffers()
-        rc = self.lib.nvrx_tail_local(self.ctx, ws.block.desc_ref if fused else None, int(q_ppm), send.data_ptr(), ws.K, ws.S,
-                                      rows_active, self.backend._stream_handle)
+    def _family_local(self, fam: RowFamily, ws: Workspace, params: tuple, rows_active: int, fused: bool):
+        """A row family's ring kernel over every ring row as the report just issued on ``ws`` saw it, packed by gid into the
+        workspace's rows of that family (``nvrx_<family>_local``; ``fused``: that report was ``report_fused``'s, else
+        ``report_local``'s; every family but tail needs ``onset_enable``'s ring-start snapshot).  Returns ``(send
+        [local_ranks, P * (K+S)], table [R, P * (K+S)])`` -- the same rows when nothing is exchanged.  Waits for the kernel:
+        the rings are emptied by count, and the next window's device-side writers on other streams may overwrite slots as
+        soon as the report call returns."""
+        assert self.onset_enabled or not fam.needs_starts, f"{fam.name}_local() before onset_enable(): no ring-start snapshot"
+        ws.family_settle(fam)
+        send, table, _, _ = ws.family_buffers(fam)
+        rc = getattr(self.lib, fam.c_local)(self.ctx, ws.block.desc_ref if fused else None, int(params[0]),
+                                            *map(float, params[1:]), send.data_ptr(), ws.K, ws.S, rows_active,
+                                            self.backend._stream_handle)
         if rc < 0:
             _native.check(rc)
         self.backend.stream.synchronize()
         return send, table
+
+    def tail_local(self, ws: Workspace, q_ppm: int, rows_active: int = 0, fused: bool = False):
+        return self._family_local(TAIL, ws, (q_ppm,), rows_active, fused)
 
     onset_enabled = False
 
     def onset_enable(self, on: bool = True) -> None:
-        """From now on every report also notes where each ring's oldest sample lives (``nvrx_onset_enable``): what
-        ``onset_local`` needs to walk the report's window in time order."""
+        """From now on every report also notes where each ring's oldest sample lives (``nvrx_onset_enable``): what the
+        families that walk the report's window in time order need."""
         _native.check(self.lib.nvrx_onset_enable(self.ctx, int(on)))
         self.onset_enabled = bool(on)
 
     def onset_local(self, ws: Workspace, min_seg_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
-        """The onset of every ring row as the report just issued on ``ws`` saw it, packed by gid into the workspace's onset
-        rows (``nvrx_onset_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s).  Returns
-        ``(onset_send [local_ranks, 6 * (K+S)], onset_table [R, 6 * (K+S)])`` -- the same rows when nothing is exchanged.
-        Waits for the onset kernel, for the reason ``tail_local`` waits for its own: the rings are emptied by count, and the
-        next window's device-side writers on other streams may overwrite slots as soon as the report call returns."""
-        ws.onset_settle()
-        send, table, _, _ = ws.onset_buffers()
-        rc = self.lib.nvrx_onset_local(self.ctx, ws.block.desc_ref if fused else None, int(min_seg_ppm), float(min_strength),
-                                       send.data_ptr(), ws.K, ws.S, rows_active, self.backend._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        self.backend.stream.synchronize()
-        return send, table
+        return self._family_local(ONSET, ws, (min_seg_ppm, min_strength), rows_active, fused)
 
     def period_local(self, ws: Workspace, max_period: int, min_strength: float, rows_active: int = 0, fused: bool = False):
-        """The period of every ring row as the report just issued on ``ws`` saw it, packed by gid into the workspace's period
-        rows (``nvrx_period_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s; needs
-        ``onset_enable``'s ring-start snapshot).  Returns ``(period_send [local_ranks, 7 * (K+S)], period_table [R, 7 *
-        (K+S)])`` -- the same rows when nothing is exchanged.  Waits for the period kernel, for the reason ``onset_local``
-        waits for its own: the rings are emptied by count, and the next window's device-side writers on other streams may
-        overwrite slots as soon as the report call returns."""
-        ws.period_settle()
-        send, table, _, _ = ws.period_buffers()
-        rc = self.lib.nvrx_period_local(self.ctx, ws.block.desc_ref if fused else None, int(max_period), float(min_strength),
-                                        send.data_ptr(), ws.K, ws.S, rows_active, self.backend._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        self.backend.stream.synchronize()
-        return send, table
+        return self._family_local(PERIOD, ws, (max_period, min_strength), rows_active, fused)
 
     def episode_local(self, ws: Workspace, min_len_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
-        """The episode of every ring row as the report just issued on ``ws`` saw it, packed by gid into the workspace's episode
-        rows (``nvrx_episode_local``; ``fused``: that report was ``report_fused``'s, else ``report_local``'s; needs
-        ``onset_enable``'s ring-start snapshot).  Returns ``(episode_send [local_ranks, 7 * (K+S)], episode_table [R, 7 *
-        (K+S)])`` -- the same rows when nothing is exchanged.  Waits for the episode kernel, for the reason ``onset_local``
-        waits for its own: the rings are emptied by count, and the next window's device-side writers on other streams may
-        overwrite slots as soon as the report call returns."""
-        ws.episode_settle()
-        send, table, _, _ = ws.episode_buffers()
-        rc = self.lib.nvrx_episode_local(self.ctx, ws.block.desc_ref if fused else None, int(min_len_ppm), float(min_strength),
-                                        send.data_ptr(), ws.K, ws.S, rows_active, self.backend._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        self.backend.stream.synchronize()
-        return send, table
+        return self._family_local(EPISODE, ws, (min_len_ppm, min_strength), rows_active, fused)
 
     def peek_stats(self) -> np.ndarray:
         """Statistics of every used row right now ([rows_used, 8] on the host); exchanges nothing and

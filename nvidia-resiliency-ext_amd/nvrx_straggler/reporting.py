@@ -32,7 +32,7 @@ from typing import Any, Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import backend as _backend_mod
-from . import dist_utils
+from . import dist_utils, row_families
 from .name_mapper import NameMapper
 from .statistics import NUM_COLUMN, STAT_KEYS, Statistic
 
@@ -625,190 +625,55 @@ def _copy_explanation(d: dict) -> dict:
     return {fam: {r: dict(v, kernels=[dict(k) for k in v["kernels"]]) for r, v in ranks.items()} for fam, ranks in d.items()}
 
 
-class _TailSource:
-    """What a report keeps of its tail scores: the backend's handle (``records()`` waits for the kernels and copies the tails
-    and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the kernel names
-    by id as the report's mapper had them at report time."""
+class _RowFamilySource:
+    """What a report keeps of one row family's scores (row_families.py: tail, onset, period, episode): the backend's handle
+    (``records()`` waits for the kernels and copies the planes and scores out on first use), the ranks its rows stand for,
+    the sections it shows with their ids, the kernel names by id as the report's mapper had them at report time, and the
+    family's parameters."""
 
-    __slots__ = ("handle", "ranks", "sections", "kernels", "q_ppm", "_built")
+    __slots__ = ("family", "handle", "ranks", "sections", "kernels", "params", "_built")
 
-    def __init__(self, handle, ranks, sections, kernels, q_ppm: int):
-        self.handle, self.ranks, self.kernels, self.q_ppm = handle, tuple(ranks), kernels, q_ppm
+    def __init__(self, family, handle, ranks, sections, kernels, params: tuple):
+        self.family, self.handle, self.ranks, self.kernels, self.params = family, handle, tuple(ranks), kernels, params
         self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
         self._built: Optional[dict] = None
 
     def build(self) -> dict:
         if self._built is None:
-            tails, scores = self.handle.records()
-            K = len(self.kernels)
-            ranks = self.ranks
-            t, sc = tails.tolist(), scores.tolist()
-
-            def present(col):
-                return {r: t[i][col] for i, r in enumerate(ranks) if not t[i][col] == -1.0}
-
-            kernel_tails = {name: present(k) for k, name in enumerate(self.kernels)}
-            section_tails = {name: present(K + g) for name, g in self.sections.items()}
-            self._built = {
-                "quantile": self.q_ppm / 1e6,
-                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
-                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
-                "section_tails": {n: v for n, v in section_tails.items() if v},
-                "kernel_tails": {n: v for n, v in kernel_tails.items() if v},
-            }
-            self.handle = None
-        return self._built
-
-
-def _copy_tails(d: dict) -> dict:
-    return {k: ({n: dict(v) if isinstance(v, dict) else v for n, v in val.items()} if isinstance(val, dict) else val)
-            for k, val in d.items()}
-
-
-class _OnsetSource:
-    """What a report keeps of its onset scores: the backend's handle (``records()`` waits for the kernels and copies the onset
-    planes and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the kernel
-    names by id as the report's mapper had them at report time."""
-
-    __slots__ = ("handle", "ranks", "sections", "kernels", "seg_ppm", "min_strength", "_built")
-
-    def __init__(self, handle, ranks, sections, kernels, seg_ppm: int, min_strength: float):
-        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
-        self.seg_ppm, self.min_strength = seg_ppm, min_strength
-        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
-        self._built: Optional[dict] = None
-
-    def build(self) -> dict:
-        if self._built is None:
-            onsets, scores = self.handle.records()
-            K = len(self.kernels)
-            ranks = self.ranks
-            o, sc = onsets.tolist(), scores.tolist()
+            fam, params, ranks = self.family, self.params, self.ranks
+            planes, scores = self.handle.records()
+            K, P, record = len(self.kernels), fam.planes, fam.record
+            o, sc = planes.reshape(len(ranks), P, -1).tolist(), scores.tolist()
 
             def present(col):
                 out = {}
                 for i, r in enumerate(ranks):
-                    e, before, after, strength, ago, n = (o[i][p][col] for p in range(6))
-                    if e != -1.0:  # (-1: the rank has no samples in this row)
-                        out[r] = {"shift": e, "before": before, "after": after, "strength": strength,
-                                  "samples_ago": int(ago), "window": int(n)}
+                    rec = record([o[i][p][col] for p in range(P)], params)
+                    if rec is not None:
+                        out[r] = rec
                 return out
 
-            kernel_onsets = {name: present(k) for k, name in enumerate(self.kernels)}
-            section_onsets = {name: present(K + g) for name, g in self.sections.items()}
-            self._built = {
+            kernel_records = {name: present(k) for k, name in enumerate(self.kernels)}
+            section_records = {name: present(K + g) for name, g in self.sections.items()}
+            built = fam.footer(params) if fam.footer_first else {}
+            built.update({
                 "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
                 "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
-                "section_onsets": {n: v for n, v in section_onsets.items() if v},
-                "kernel_onsets": {n: v for n, v in kernel_onsets.items() if v},
-                "min_segment": self.seg_ppm / 1e6,
-                "min_strength": self.min_strength,
-            }
+                "section_" + fam.stem: {n: v for n, v in section_records.items() if v},
+                "kernel_" + fam.stem: {n: v for n, v in kernel_records.items() if v},
+            })
+            if not fam.footer_first:
+                built.update(fam.footer(params))
+            for alias, key in fam.aliases:
+                built[alias] = built[key]
+            self._built = built
             self.handle = None
         return self._built
 
 
-def _copy_onsets(d: dict) -> dict:
-    def deep(v):
-        return {k: deep(x) for k, x in v.items()} if isinstance(v, dict) else v
-
-    return deep(d)
-
-
-class _PeriodSource:
-    """What a report keeps of its period scores: the backend's handle (``records()`` waits for the kernels and copies the
-    period planes and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the
-    kernel names by id as the report's mapper had them at report time."""
-
-    __slots__ = ("handle", "ranks", "sections", "kernels", "max_period", "min_strength", "_built")
-
-    def __init__(self, handle, ranks, sections, kernels, max_period: int, min_strength: float):
-        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
-        self.max_period, self.min_strength = max_period, min_strength
-        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
-        self._built: Optional[dict] = None
-
-    def build(self) -> dict:
-        if self._built is None:
-            periods, scores = self.handle.records()
-            K = len(self.kernels)
-            ranks = self.ranks
-            o, sc = periods.tolist(), scores.tolist()
-
-            def present(col):
-                out = {}
-                for i, r in enumerate(ranks):
-                    e, peak, rest, strength, period, ago, n = (o[i][p][col] for p in range(7))
-                    if e != -1.0:  # (-1: the rank has no samples in this row)
-                        out[r] = {"period": int(period), "samples_ago": int(ago), "peak": peak, "rest": rest, "excess": e,
-                                  "strength": strength, "window": int(n)}
-                return out
-
-            kernel_periods = {name: present(k) for k, name in enumerate(self.kernels)}
-            section_periods = {name: present(K + g) for name, g in self.sections.items()}
-            self._built = {
-                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
-                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
-                "section_periods": {n: v for n, v in section_periods.items() if v},
-                "kernel_periods": {n: v for n, v in kernel_periods.items() if v},
-                "max_period": self.max_period,
-                "min_strength": self.min_strength,
-            }
-            self.handle = None
-        return self._built
-
-
-class _EpisodeSource:
-    """What a report keeps of its episode scores: the backend's handle (``records()`` waits for the kernels and copies the
-    episode planes and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, and the
-    kernel names by id as the report's mapper had them at report time."""
-
-    __slots__ = ("handle", "ranks", "sections", "kernels", "len_ppm", "min_strength", "_built")
-
-    def __init__(self, handle, ranks, sections, kernels, len_ppm: int, min_strength: float):
-        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
-        self.len_ppm, self.min_strength = len_ppm, min_strength
-        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
-        self._built: Optional[dict] = None
-
-    def build(self) -> dict:
-        if self._built is None:
-            episodes, scores = self.handle.records()
-            K = len(self.kernels)
-            ranks = self.ranks
-            o, sc = episodes.tolist(), scores.tolist()
-            min_samples, len_ppm = _backend_mod._native.episode_min_samples, self.len_ppm
-
-            def present(col):
-                out = {}
-                for i, r in enumerate(ranks):
-                    e, inside, outside, strength, length, ago, n = (o[i][p][col] for p in range(7))
-                    if e != -1.0:  # (-1: the rank has no samples in this row)
-                        length, ago, n = int(length), int(ago), int(n)
-                        out[r] = {"length": length, "samples_ago": ago, "began_ago": ago + length if length else 0, "window": n,
-                                  "inside": inside, "outside": outside, "strength": strength, "excess": e,
-                                  "open_ended": bool(length) and ago == min_samples(len_ppm, n)}
-                return out
-
-            kernel_episodes = {name: present(k) for k, name in enumerate(self.kernels)}
-            section_episodes = {name: present(K + g) for name, g in self.sections.items()}
-            self._built = {
-                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
-                "section_relative": {name: {r: sc[i][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
-                "section_episodes": {n: v for n, v in section_episodes.items() if v},
-                "kernel_episodes": {n: v for n, v in kernel_episodes.items() if v},
-                "min_length": self.len_ppm / 1e6,
-                "min_strength": self.min_strength,
-            }
-            self._built["section_scores"] = self._built["section_relative"]
-            self._built["gpu_scores"] = self._built["gpu_relative"]
-            self.handle = None
-        return self._built
-
-
-def _copy_episodes(d: dict) -> dict:
-    """A private copy of a report's episode scores (plain dicts, floats, ints and bools all the way down)."""
-    return _copy_onsets(d)
+def _copy_scores(d: dict) -> dict:
+    """A private copy of a report's follow-up scores (plain dicts, floats, ints and bools all the way down)."""
+    return {k: _copy_scores(x) if isinstance(x, dict) else x for k, x in d.items()}
 
 
 class _RobustSource:
@@ -939,21 +804,13 @@ class Report:
         attr = self.__dict__.get("_attr")
         if attr is not None:
             state["_attr"] = attr.build() if isinstance(attr, _AttrSource) else attr  # plain dicts travel
-        tail = self.__dict__.get("_tail")
-        if tail is not None:
-            state["_tail"] = tail.build() if isinstance(tail, _TailSource) else tail
         robust = self.__dict__.get("_robust")
         if robust is not None:
             state["_robust"] = robust.build() if isinstance(robust, _RobustSource) else robust
-        onset = self.__dict__.get("_onset")
-        if onset is not None:
-            state["_onset"] = onset.build() if isinstance(onset, _OnsetSource) else onset
-        period = self.__dict__.get("_period")
-        if period is not None:
-            state["_period"] = period.build() if isinstance(period, _PeriodSource) else period
-        episode = self.__dict__.get("_episode")
-        if episode is not None:
-            state["_episode"] = episode.build() if isinstance(episode, _EpisodeSource) else episode
+        for fam in row_families.FAMILIES:
+            scores = self.__dict__.get(fam.slot)
+            if scores is not None:
+                state[fam.slot] = scores.build() if isinstance(scores, _RowFamilySource) else scores
         return state
 
     def __setstate__(self, state) -> None:
@@ -987,22 +844,13 @@ class Report:
         scores are the fastest rank's tail over this rank's (NaN where a rank lacks the row), ranks and sections as in the
         score mappings, rows without samples are left out of the tails.  Plain dicts and floats.  The first call waits for
         the tail kernels and copies their results; ``generate_report`` does not."""
-        tail = self.__dict__.get("_tail")
-        if tail is None:
-            return {}
-        if isinstance(tail, _TailSource):
-            tail = self.__dict__["_tail"] = tail.build()
-        return _copy_tails(tail)
+        return self._family_scores("tail")
 
     def identify_tail_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
         """Ranks whose TAIL scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no tail scores."""
-        t = self.tail_scores()
-        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
-        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
-        return {"straggler_gpus_relative": self._ids(gr),
-                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+        return self._identify_relative(self.tail_scores(), gpu_rel_threshold, section_rel_threshold)
 
     def onset_scores(self) -> Dict[str, Any]:
         """Onset scores (``ReportGenerator(onset_detection=True)``; ``{}`` when the report carries none).  Medians, tails and
@@ -1018,22 +866,13 @@ class Report:
         no more than the steadiest rank, so a phase change of the whole job flags nobody.  Ranks and sections as in the score
         mappings, rows without samples are left out of the onsets.  Plain dicts and floats.  The first call waits for the
         onset kernels and copies their results; ``generate_report`` does not."""
-        onset = self.__dict__.get("_onset")
-        if onset is None:
-            return {}
-        if isinstance(onset, _OnsetSource):
-            onset = self.__dict__["_onset"] = onset.build()
-        return _copy_onsets(onset)
+        return self._family_scores("onset")
 
     def identify_onset_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
         """Ranks whose ONSET scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no onset scores."""
-        t = self.onset_scores()
-        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
-        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
-        return {"straggler_gpus_relative": self._ids(gr),
-                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+        return self._identify_relative(self.onset_scores(), gpu_rel_threshold, section_rel_threshold)
 
     def period_scores(self) -> Dict[str, Any]:
         """Period scores (``ReportGenerator(period_detection=True)``; ``{}`` when the report carries none).  Whether a rank is
@@ -1050,22 +889,13 @@ class Report:
         where a rank lacks the row): 1 = stalls no more than the steadiest rank, so a beat of the whole job flags nobody.
         Ranks and sections as in the score mappings, rows without samples are left out.  Plain dicts and floats.  The first
         call waits for the period kernels and copies their results; ``generate_report`` does not."""
-        period = self.__dict__.get("_period")
-        if period is None:
-            return {}
-        if isinstance(period, _PeriodSource):
-            period = self.__dict__["_period"] = period.build()
-        return _copy_onsets(period)
+        return self._family_scores("period")
 
     def identify_period_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
         """Ranks whose PERIOD scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no period scores."""
-        t = self.period_scores()
-        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
-        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
-        return {"straggler_gpus_relative": self._ids(gr),
-                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+        return self._identify_relative(self.period_scores(), gpu_rel_threshold, section_rel_threshold)
 
     def episode_scores(self) -> Dict[str, Any]:
         """Episode scores (``ReportGenerator(episode_detection=True)``; ``{}`` when the report carries none).  Whether a rank
@@ -1086,24 +916,13 @@ class Report:
         rank's (NaN where a rank lacks the row): 1 = no stretch slower than the steadiest rank's, so a stretch the whole job
         shares flags nobody.  Ranks and sections as in the score mappings, rows without samples are left out.  Plain dicts
         and floats.  The first call waits for the episode kernels and copies their results; ``generate_report`` does not."""
-        episode = self.__dict__.get("_episode")
-        if episode is None:
-            return {}
-        if isinstance(episode, _EpisodeSource):
-            episode = self.__dict__["_episode"] = episode.build()
-        out = _copy_episodes(episode)
-        out["section_scores"], out["gpu_scores"] = out["section_relative"], out["gpu_relative"]
-        return out
+        return self._family_scores("episode")
 
     def identify_episode_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
         """Ranks whose EPISODE scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no episode scores."""
-        t = self.episode_scores()
-        gr = self._below(t.get("gpu_relative", {}), gpu_rel_threshold)
-        sr = {n: self._below(v, section_rel_threshold) for n, v in t.get("section_relative", {}).items()}
-        return {"straggler_gpus_relative": self._ids(gr),
-                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+        return self._identify_relative(self.episode_scores(), gpu_rel_threshold, section_rel_threshold)
 
     def robust_scores(self) -> Dict[str, Any]:
         """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
@@ -1123,7 +942,7 @@ class Report:
             return {}
         if isinstance(robust, _RobustSource):
             robust = self.__dict__["_robust"] = robust.build()
-        return _copy_tails(robust)
+        return _copy_scores(robust)
 
     def identify_robust_stragglers(self, gpu_z_threshold: float = 3.5, section_z_threshold: float = 3.5) -> Dict[str, Any]:
         """Ranks whose robust z-scores lie strictly ABOVE the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
@@ -1133,6 +952,25 @@ class Report:
         t = self.robust_scores()
         gr = [r for r, z in t.get("gpu_z", {}).items() if z > gpu_z_threshold]
         sr = {n: [r for r, z in v.items() if z > section_z_threshold] for n, v in t.get("section_z", {}).items()}
+        return {"straggler_gpus_relative": self._ids(gr),
+                "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def _family_scores(self, name: str) -> Dict[str, Any]:
+        """A private copy of one row family's scores (built from the device's planes on first use); ``{}`` without them."""
+        fam = row_families.BY_NAME[name]
+        scores = self.__dict__.get(fam.slot)
+        if scores is None:
+            return {}
+        if isinstance(scores, _RowFamilySource):
+            scores = self.__dict__[fam.slot] = scores.build()
+        out = _copy_scores(scores)
+        for alias, key in fam.aliases:
+            out[alias] = out[key]
+        return out
+
+    def _identify_relative(self, scores: Mapping[str, Any], gpu_thr: float, sec_thr: float) -> Dict[str, Any]:
+        gr = self._below(scores.get("gpu_relative", {}), gpu_thr)
+        sr = {n: self._below(v, sec_thr) for n, v in scores.get("section_relative", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
                 "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
 
@@ -1436,6 +1274,10 @@ class ReportGenerator:
                 raise RuntimeError(f"episode_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no episode scores (backend.episode_score)")
             self.episode_len_ppm, self.episode_min_strength = len_ppm, strength
+        # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
+        # any, that needs the ring-start snapshot
+        self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
+        self._starts_family = next((f for f in self._row_families if f.needs_starts), None)
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -1501,45 +1343,16 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
-        if self.episode_len_ppm and not self.tail_q_ppm and not self.onset_seg_ppm and not self.period_max:
-            # the episode step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
-            # episodes stay on that route as a whole (the option has the same value on every rank: no collective here)
+        if self._row_families:
+            fam = self._row_families[0]
+            # a row family's collective is a torch.distributed call between two kernels: reports with one stay on that route
+            # as a whole (the option has the same value on every rank, so every rank decides alike -- no collective here)
             self._direct = None
-            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (episode_detection is "
-                                           "set: reports with episode scores do not use the in-stream routes)", "mode": "c10d"}
+            self.exchange_info = {"route": f"torch.distributed all-gather on the job's own process group ({fam.option} is "
+                                           f"set: reports with {fam.name} scores do not use the in-stream routes)", "mode": "c10d"}
             if mode != "c10d":
-                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while episode_detection is set: reports with episode "
-                             "scores run on torch.distributed's route (c10d)", mode)
-            return
-        if self.period_max and not self.tail_q_ppm and not self.onset_seg_ppm:
-            # the period step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
-            # periods stay on that route as a whole (the option has the same value on every rank: no collective here)
-            self._direct = None
-            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (period_detection is "
-                                           "set: reports with period scores do not use the in-stream routes)", "mode": "c10d"}
-            if mode != "c10d":
-                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while period_detection is set: reports with period "
-                             "scores run on torch.distributed's route (c10d)", mode)
-            return
-        if self.onset_seg_ppm and not self.tail_q_ppm:
-            # the onset step's collective is a torch.distributed call between two kernels, as the tail step's is: reports with
-            # onsets stay on that route as a whole (the option has the same value on every rank: no collective here)
-            self._direct = None
-            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (onset_detection is "
-                                           "set: reports with onset scores do not use the in-stream routes)", "mode": "c10d"}
-            if mode != "c10d":
-                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while onset_detection is set: reports with onset scores "
-                             "run on torch.distributed's route (c10d)", mode)
-            return
-        if self.tail_q_ppm:
-            # the tail step's collective is a torch.distributed call between two kernels: reports with tails stay on that
-            # route as a whole (the option has the same value on every rank, so every rank decides alike -- no collective here)
-            self._direct = None
-            self.exchange_info = {"route": "torch.distributed all-gather on the job's own process group (tail_quantile is "
-                                           "set: reports with tail scores do not use the in-stream routes)", "mode": "c10d"}
-            if mode != "c10d":
-                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while tail_quantile is set: reports with tail scores "
-                             "run on torch.distributed's route (c10d)", mode)
+                _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while %s is set: reports with %s scores "
+                             "run on torch.distributed's route (c10d)", mode, fam.option, fam.name)
             return
         # c10d (the default) on ANY rank keeps every rank on torch.distributed (the decision has to be the same everywhere:
         # building a communicator is collective)
@@ -1650,18 +1463,9 @@ class ReportGenerator:
             K, S = mapper.kernel_counter, mapper.section_counter
             world = self.world_size if exchanged else 1
             ws = be.workspace(world * local_ranks, K, S, local_ranks, stats_rows)
-            if getattr(ws, "_attr_last", None) is not None:
-                ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
-            if getattr(ws, "_tail_last", None) is not None:
-                ws.tail_settle()  # ... or a tail score kernel
-            if getattr(ws, "_robust_last", None) is not None:
-                ws.robust_settle()  # ... or the robust kernels
-            if getattr(ws, "_onset_last", None) is not None:
-                ws.onset_settle()  # ... or an onset score kernel
-            if getattr(ws, "_period_last", None) is not None:
-                ws.period_settle()  # ... or a period score kernel
-            if getattr(ws, "_episode_last", None) is not None:
-                ws.episode_settle()  # ... or an episode score kernel
+            settle = getattr(ws, "settle_readers", None)  # (the CPU checker backend of the tests has no deferred readers)
+            if settle is not None:
+                settle()  # a follow-up kernel of the last report may still be reading the table that is about to be rewritten
             if world > 1:
                 with be.stream_context():  # host-packed rows are copied on the stream the report runs on
                     fill_send(ws, mapper, names_ok)
@@ -1852,18 +1656,9 @@ class ReportGenerator:
         multi = self.world_size > 1 and self._exchanged()
         fused = plan.fused and (not multi or self._direct is not None)
         attr_n = self.kernel_attribution
-        if getattr(ws, "_attr_last", None) is not None:
-            ws.attr_settle()  # an attribution kernel may still be reading the table that is about to be rewritten
-        if getattr(ws, "_tail_last", None) is not None:
-            ws.tail_settle()  # ... or a tail score kernel
-        if getattr(ws, "_robust_last", None) is not None:
-            ws.robust_settle()  # ... or the robust kernels
-        if getattr(ws, "_onset_last", None) is not None:
-            ws.onset_settle()  # ... or an onset score kernel
-        if getattr(ws, "_period_last", None) is not None:
-            ws.period_settle()  # ... or a period score kernel
-        if getattr(ws, "_episode_last", None) is not None:
-            ws.episode_settle()  # ... or an episode score kernel
+        settle = getattr(ws, "settle_readers", None)  # (the CPU checker backend of the tests has no deferred readers)
+        if settle is not None:
+            settle()  # a follow-up kernel of the last report may still be reading the table that is about to be rewritten
         self._last_plan_fused = fused
         if fused and attr_n and not hasattr(rings, "report_attribute"):
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
@@ -1962,71 +1757,22 @@ class ReportGenerator:
             handle = _backend_mod.get_backend().robust_score(ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor)
         self._attach_robust(report, handle, ws, plan.mapper, plan.view)
 
-    # ---- tail scores --------------------------------------------------------------------------------
-    def _tail_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
-        """The tail step of a ring report, once per ``generate_report_from_rings`` call behind its last score round, on that
-        round's workspace: quantile kernel on the window the report saw -> [one all-gather of the tail rows] -> tail score
-        kernel for the ranks the report covers, hung on ``report`` unread.  Every rank issues it at every report, whatever
-        the report found and whether or not it holds a report (a gathering generator's other ranks): same collectives
-        everywhere."""
-        be = _backend_mod.get_backend()
-        if not hasattr(rings, "tail_local") or not hasattr(be, "tail_score"):
-            raise RuntimeError(f"tail_quantile={self.tail_q_ppm / 1e6}: the active backend has no tail scores "
-                               "(rings.tail_local / backend.tail_score)")
-        send, table = rings.tail_local(ws, self.tail_q_ppm, rows_active, fused)
-        if self.world_size > 1:
-            with be.stream_context():  # (behind the quantile kernel)
-                table = dist_utils.all_gather_rows(send, table, self.group)
-        if report is None or report is False:
-            return
-        if self.gather_on_rank0:
-            lo, hi = 0, ws.R
-        else:
-            lo = self.rank * local_ranks
-            hi = lo + local_ranks
-        view = report.__dict__["_src"].view
-        handle = be.tail_score(ws, table, ws.table, lo, hi - lo, self.tail_q_ppm)
-        report.__dict__["_tail"] = _TailSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), self.tail_q_ppm)
-
-    # ---- onset scores -------------------------------------------------------------------------------
-    def _onset_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
-        """The onset step of a ring report, once per ``generate_report_from_rings`` call behind its last score round (and
-        behind the tail step, when both are on), on that round's workspace: onset kernel on the window the report saw -> [one
-        all-gather of the onset rows] -> onset score kernel for the ranks the report covers, hung on ``report`` unread.
-        Every rank issues it at every report, whatever the report found and whether or not it holds a report (a gathering
-        generator's other ranks): same collectives everywhere."""
-        be = _backend_mod.get_backend()
-        if not hasattr(rings, "onset_local") or not hasattr(be, "onset_score"):
-            raise RuntimeError("onset_detection: the active backend has no onset scores (rings.onset_local / backend.onset_score)")
-        send, table = rings.onset_local(ws, self.onset_seg_ppm, self.onset_min_strength, rows_active, fused)
-        if self.world_size > 1:
-            with be.stream_context():  # (behind the onset kernel)
-                table = dist_utils.all_gather_rows(send, table, self.group)
-        if report is None or report is False:
-            return
-        if self.gather_on_rank0:
-            lo, hi = 0, ws.R
-        else:
-            lo = self.rank * local_ranks
-            hi = lo + local_ranks
-        view = report.__dict__["_src"].view
-        handle = be.onset_score(ws, table, ws.table, lo, hi - lo)
-        report.__dict__["_onset"] = _OnsetSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
-                                                 self.onset_seg_ppm, self.onset_min_strength)
-
-    # ---- period scores ------------------------------------------------------------------------------
-    def _period_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
-        """The period step of a ring report, once per ``generate_report_from_rings`` call behind its last score round (and
-        behind the tail and onset steps, when they are on), on that round's workspace: period kernel on the window the report
-        saw -> [one all-gather of the period rows] -> period score kernel for the ranks the report covers, hung on ``report``
+    # ---- row families: tail, onset, period, episode scores ------------------------------------------
+    def _family_step(self, fam, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """One row family's step of a ring report, once per ``generate_report_from_rings`` call behind its last score round
+        (and behind the steps of the families before it), on that round's workspace: the family's ring kernel on the window
+        the report saw -> [one all-gather of its rows] -> its score kernel for the ranks the report covers, hung on ``report``
         unread.  Every rank issues it at every report, whatever the report found and whether or not it holds a report (a
         gathering generator's other ranks): same collectives everywhere."""
         be = _backend_mod.get_backend()
-        if not hasattr(rings, "period_local") or not hasattr(be, "period_score"):
-            raise RuntimeError("period_detection: the active backend has no period scores (rings.period_local / backend.period_score)")
-        send, table = rings.period_local(ws, self.period_max, self.period_min_strength, rows_active, fused)
+        params = fam.params(self)
+        local, score = getattr(rings, fam.name + "_local", None), getattr(be, fam.name + "_score", None)
+        if local is None or score is None:
+            raise RuntimeError(f"{fam.label(params)}: the active backend has no {fam.name} scores "
+                               f"(rings.{fam.name}_local / backend.{fam.name}_score)")
+        send, table = local(ws, *params, rows_active, fused)
         if self.world_size > 1:
-            with be.stream_context():  # (behind the period kernel)
+            with be.stream_context():  # (behind the family's ring kernel)
                 table = dist_utils.all_gather_rows(send, table, self.group)
         if report is None or report is False:
             return
@@ -2036,35 +1782,13 @@ class ReportGenerator:
             lo = self.rank * local_ranks
             hi = lo + local_ranks
         view = report.__dict__["_src"].view
-        handle = be.period_score(ws, table, ws.table, lo, hi - lo)
-        report.__dict__["_period"] = _PeriodSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
-                                                   self.period_max, self.period_min_strength)
+        handle = score(ws, table, ws.table, lo, hi - lo, *params[:fam.score_params])
+        report.__dict__[fam.slot] = _RowFamilySource(fam, handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
 
-    # ---- episode scores -----------------------------------------------------------------------------
-    def _episode_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
-        """The episode step of a ring report, once per ``generate_report_from_rings`` call behind its last score round (and
-        behind the tail, onset and period steps, when they are on), on that round's workspace: episode kernel on the window
-        the report saw -> [one all-gather of the episode rows] -> episode score kernel for the ranks the report covers, hung
-        on ``report`` unread.  Every rank issues it at every report, whatever the report found and whether or not it holds a
-        report (a gathering generator's other ranks): same collectives everywhere."""
-        be = _backend_mod.get_backend()
-        if not hasattr(rings, "episode_local") or not hasattr(be, "episode_score"):
-            raise RuntimeError("episode_detection: the active backend has no episode scores (rings.episode_local / backend.episode_score)")
-        send, table = rings.episode_local(ws, self.episode_len_ppm, self.episode_min_strength, rows_active, fused)
-        if self.world_size > 1:
-            with be.stream_context():  # (behind the episode kernel)
-                table = dist_utils.all_gather_rows(send, table, self.group)
-        if report is None or report is False:
-            return
-        if self.gather_on_rank0:
-            lo, hi = 0, ws.R
-        else:
-            lo = self.rank * local_ranks
-            hi = lo + local_ranks
-        view = report.__dict__["_src"].view
-        handle = be.episode_score(ws, table, ws.table, lo, hi - lo)
-        report.__dict__["_episode"] = _EpisodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
-                                                     self.episode_len_ppm, self.episode_min_strength)
+    def _family_steps(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The steps of the families that are switched on, in the table's order: the order of their collectives."""
+        for fam in self._row_families:
+            self._family_step(fam, report, rings, ws, mapper, rows_active, fused, local_ranks)
 
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],
@@ -2129,10 +1853,9 @@ class ReportGenerator:
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
-        if (self.onset_seg_ppm or self.period_max or self.episode_len_ppm) and not getattr(rings, "onset_enabled", False):
+        if self._starts_family is not None and not getattr(rings, "onset_enabled", False):
             if not hasattr(rings, "onset_enable"):
-                raise RuntimeError(f"{'onset' if self.onset_seg_ppm else 'period' if self.period_max else 'episode'}_detection: the active backend has no ring-start "
-                                   "snapshot (rings.onset_enable)")
+                raise RuntimeError(f"{self._starts_family.option}: the active backend has no ring-start snapshot (rings.onset_enable)")
             rings.onset_enable(True)  # (before this window's report: it notes where every ring's oldest sample lives)
         if not self._direct_tried and self.world_size != 1:  # (a single process has no route to build)
             self._maybe_create_direct_exchange()
@@ -2152,14 +1875,7 @@ class ReportGenerator:
                 self._drop_plan()
                 raise
             if out is not False:
-                if self.tail_q_ppm:
-                    self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-                if self.onset_seg_ppm:
-                    self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-                if self.period_max:
-                    self._period_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-                if self.episode_len_ppm:
-                    self._episode_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+                self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 return out
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
@@ -2173,14 +1889,7 @@ class ReportGenerator:
             self._unreported_rows = ([r for n, r in kernel_rows.items() if n not in known_k and not is_collective_kernel(n)]
                                      + [r for n, r in section_rows.items() if n not in known_s])
             out = self._report_from_plan(plan, rings, t0, order_after, names_ok=False)
-            if self.tail_q_ppm:
-                self._tail_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-            if self.onset_seg_ppm:
-                self._onset_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-            if self.period_max:
-                self._period_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-            if self.episode_len_ppm:
-                self._episode_step(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+            self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
@@ -2207,14 +1916,7 @@ class ReportGenerator:
                                        stats_rows_used=stats_needed, sync_first=self._take_resync(), may_defer_sync=not_the_first)
         report = self._assemble(ws, mapper, snames, dict(section_rows), dict(kernel_rows), t0, local_ranks=local_ranks,
                                 stats=ws.stats[:stats_needed].copy())
-        if self.tail_q_ppm:  # (before the plan below re-points the ring rows)
-            self._tail_step(report, rings, ws, mapper, rows_used, False, local_ranks)
-        if self.onset_seg_ppm:
-            self._onset_step(report, rings, ws, mapper, rows_used, False, local_ranks)
-        if self.period_max:
-            self._period_step(report, rings, ws, mapper, rows_used, False, local_ranks)
-        if self.episode_len_ppm:
-            self._episode_step(report, rings, ws, mapper, rows_used, False, local_ranks)
+        self._family_steps(report, rings, ws, mapper, rows_used, False, local_ranks)  # (before the plan below re-points the ring rows)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

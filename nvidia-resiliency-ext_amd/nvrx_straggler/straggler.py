@@ -35,7 +35,7 @@ from collections.abc import Callable
 from contextlib import contextmanager
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Union
 
-from . import _native
+from . import _native, row_families
 from . import backend as _backend_mod
 from . import dist_utils as _dist_utils
 from . import ktrace as _ktrace
@@ -158,14 +158,8 @@ class _Lane:
             return None
         if reporter.kernel_attribution:
             return None  # (the attribution launch follows the report in the generator's planned path: DESIGN.md, "Kernel attribution")
-        if reporter.tail_q_ppm:
-            return None  # (the tail step follows the report in the generator's paths: DESIGN.md, "Tail scores")
-        if getattr(reporter, "onset_seg_ppm", 0):
-            return None  # (the onset step follows the report in the generator's paths: DESIGN.md, "Onset scores")
-        if getattr(reporter, "period_max", 0):
-            return None  # (the period step follows the report in the generator's paths: DESIGN.md, "Period scores")
-        if getattr(reporter, "episode_len_ppm", 0):
-            return None  # (the episode step follows the report in the generator's paths: DESIGN.md, "Episode scores")
+        if any(getattr(reporter, fam.param_attrs[0], 0) for fam in row_families.FAMILIES):
+            return None  # (a row family's step follows the report in the generator's paths: DESIGN.md, "Row families")
         if getattr(reporter, "robust_scores", False):
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         ext = manager.cupti_ext

@@ -243,7 +243,7 @@ def test_default_is_off_and_calls_nothing(emulate_fused, asynchronous):
             assert "_episode" not in rep.__dict__
         assert gen._ring_plan is not None
         for ws in (gen._ring_plan.ws,):  # no workspace grew an episode buffer
-            assert getattr(ws, "_episode_buf", None) is None and getattr(ws, "_episode_table", None) is None
+            assert "episode" not in (getattr(ws, "_family_state", None) or {}) and getattr(ws, "_episode_table", None) is None
         gen.close()
         # ... and through the Detector
         Detector.initialize(scores_to_compute="all", gather_on_rank0=True, node_name="n0", asynchronous=asynchronous)
