@@ -138,6 +138,8 @@ int nvrx_score_route(int R, int K, int S, const void *d_scores, const void *d_fl
  * s_k = ref_k / med_k and n_k = w_k * (1 - s_k) ("lost microseconds": time above the reference pace), 1 - g = sum_k(n_k) / W.
  * Per reported rank and family (0 individual: ref_k = hmin; 1 relative: ref_k = column minimum of MED, NaN if any rank lacks
  * the kernel) the top_n eligible kernels by n_k, descending, ties to the lower kernel id.  Eligible = what nvrx_score sums.
+ * The order is by VALUE: -0.0 and +0.0 tie (a zero n_k is recorded as +0.0), and a NaN n_k (0/0 from a zero median, 0 * inf
+ * under a zero weight) comes after -inf whatever its sign bit, NaN among themselves by kernel id.
  *   d_table [R][L] as for nvrx_score; ranks [first_rank, first_rank + n_ranks) are reported;
  *   top_n in [1, NVRX_ATTR_MAX_TOP];
  *   d_minmed_scratch  NVRX_ATTR_SCRATCH_FLOATS(K) floats of device memory (column minima), may be NULL when do_rel == 0;

@@ -4,12 +4,12 @@
 // The GPU score of rank r (reporting.py:219-253; score_rank above) is g = sum_k(w_k * ref_k / med_k) / sum_k(w_k) over
 // the eligible kernels.  Its deficit 1 - g = sum_k(n_k) / W with n_k = w_k * (1 - ref_k / med_k): the microseconds kernel k
 // spent above the reference pace this window.  k_attribute lists, per rank and score family, the N kernels with the
-// largest n_k (ties: the lower kernel id) as 16-byte records; the table is the one nvrx_score reads, nothing else is
-// exchanged.
+// largest n_k by value (ties, -0.0 against +0.0 among them: the lower kernel id; NaN after -inf) as 16-byte records; the
+// table is the one nvrx_score reads, nothing else is exchanged.
 //
 // One workgroup per (rank, family).  The selection needs no buffer proportional to K: N rounds of a block-wide arg-max
-// over the key (order-preserving bits of the f64 n_k, then ~id), each round admitting only keys that order strictly
-// after the previous winner.  A round is three 32-bit DPP wave maxima (high word, low word, ~id: a lexicographic
+// over the key (order-preserving bits of the canonical f64 n_k -- canon_nk, nk2key -- then ~id), each round admitting only
+// keys that order strictly after the previous winner.  A round is three 32-bit DPP wave maxima (high word, low word, ~id: a lexicographic
 // maximum), one LDS slot per wave and one barrier (the slots alternate between two banks by round parity).  The n_k are
 // recomputed every round: N * K f64 quotients per workgroup, spread over 256 or 1024 lanes.
 
@@ -30,6 +30,11 @@ __device__ __forceinline__ uint64_t d2key(double d) {
     const uint64_t u = (uint64_t)__double_as_longlong(d);
     return u ^ ((u >> 63) ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull);
 }
+
+// The n_k the order and the records see: the order is by VALUE, so -0.0 (a zero weight times a negative 1 - s_k) becomes
+// +0.0 and ties with it, and every NaN (0/0, 0 * inf) becomes the one NaN that nk2key puts after -inf
+__device__ __forceinline__ double canon_nk(double n) { return n != n ? (double)__builtin_nanf("") : (n == 0.0 ? 0.0 : n); }
+__device__ __forceinline__ uint64_t nk2key(double n) { return n != n ? 0ull : d2key(n); }  // (d2key(-inf) > 0)
 
 template <int NTHR>
 __global__ __launch_bounds__(NTHR) void k_attribute(AttrArgs a) {
@@ -100,8 +105,8 @@ __global__ __launch_bounds__(NTHR) void k_attribute(AttrArgs a) {
             if (!(medf >= 0.0f)) continue;
             const float rf = ref[k];
             if (fam && !(rf == rf)) continue;
-            const double n = (double)row[2 * KS + k] * (1.0 - (double)rf / (double)medf);
-            const uint64_t key = d2key(n);
+            const double n = canon_nk((double)row[2 * KS + k] * (1.0 - (double)rf / (double)medf));
+            const uint64_t key = nk2key(n);
             const uint32_t kh = (uint32_t)(key >> 32), kl = (uint32_t)key, ki = ~(uint32_t)k;
             // strictly after the previous winner ...
             if (j > 0 && !(kh < ph || (kh == ph && (kl < pl || (kl == pl && ki < pi))))) continue;
@@ -133,7 +138,7 @@ __global__ __launch_bounds__(NTHR) void k_attribute(AttrArgs a) {
             const int k = (int)~pi;
             const double w = (double)row[2 * KS + k];
             const double s = (double)ref[k] / (double)row[k];
-            const double n = w * (1.0 - s);
+            const double n = canon_nk(w * (1.0 - s));
             listed += n;
             out[1 + j] = make_uint4((uint32_t)k, __float_as_uint((float)(n / wsum)), __float_as_uint((float)s),
                                     __float_as_uint((float)n));

@@ -14,10 +14,40 @@ NAN32 = np.float32(np.nan)
 
 
 def rank_by_loss(ids, lost):
-    """Positions of ``ids`` ordered by descending ``lost``, ties by the lower id."""
+    """Positions of ``ids`` ordered by descending ``lost`` BY VALUE, ties by the lower id: ``-0.0`` and ``+0.0`` tie, a NaN
+    comes after -inf whatever its sign bit (the ordering rule of ``nvrx_attribute``, include/nvrx_straggler.h)."""
     ids = np.asarray(ids)
     lost = np.asarray(lost, dtype=np.float64)
     return np.lexsort((ids, -lost))
+
+
+def column_minima(med):
+    """``[K]`` f32 references of the relative family: the rule of ``k_colmin`` (``v < m``: a NaN median never wins, the -1 of
+    an absent entry does), NaN where some rank lacks the kernel -- as ``nvrx_score`` takes them."""
+    med = np.asarray(med, dtype=np.float32)
+    m = np.full(med.shape[1], np.inf, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        for r in range(med.shape[0]):
+            m = np.where(med[r] < m, med[r], m)
+        return np.where(m >= 0, m, NAN32).astype(np.float32)
+
+
+def loss_terms(T, K, S, r, fam, minmed=None):
+    """``(ids, s, n, w)`` of rank ``r``'s eligible kernels in family ``fam`` (0 individual, 1 relative), f64, unordered: the
+    scores s_k = ref_k / med_k and the lost microseconds n_k = w_k * (1 - s_k) exactly as the formula produces them (a zero
+    n_k keeps its sign here; the records report it as +0.0)."""
+    T = np.asarray(T, dtype=np.float32)
+    KS = K + S
+    med, hmin, w = T[:, :K], T[:, KS : KS + K], T[:, 2 * KS : 2 * KS + K]
+    ref = (column_minima(med) if minmed is None else minmed) if fam else hmin[r]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        elig = med[r] >= 0
+        if fam:
+            elig &= ~np.isnan(ref)
+        ids = np.flatnonzero(elig)
+        s = ref[ids].astype(np.float64) / med[r, ids].astype(np.float64)
+        wk = w[r, ids].astype(np.float64)
+        return ids, s, wk * (1.0 - s), wk
 
 
 def attribute_table(T, K, S, top_n, do_indiv, do_rel, first_rank=0, n_ranks=None):
@@ -26,10 +56,7 @@ def attribute_table(T, K, S, top_n, do_indiv, do_rel, first_rank=0, n_ranks=None
     R = T.shape[0]
     n_ranks = R - first_rank if n_ranks is None else n_ranks
     KS = K + S
-    med, hmin, w = T[:, :K], T[:, KS : KS + K], T[:, 2 * KS : 2 * KS + K]
-    with np.errstate(invalid="ignore"):
-        m = med.min(axis=0) if R and K else np.zeros(K, np.float32)
-        minmed = np.where(m >= 0, m, NAN32).astype(np.float32)
+    minmed = column_minima(T[:, :K])
     out = np.zeros((n_ranks, 2, 1 + top_n, 4), dtype=np.uint32)
     f32 = out.view(np.float32)
     i32 = out.view(np.int32)
@@ -42,19 +69,13 @@ def attribute_table(T, K, S, top_n, do_indiv, do_rel, first_rank=0, n_ranks=None
         for fam, on in ((0, do_indiv), (1, do_rel)):
             if not on:
                 continue
-            ref = minmed if fam else hmin[r]
-            elig = med[r] >= 0
-            if fam:
-                elig &= ~np.isnan(ref)
-            ids = np.flatnonzero(elig)
+            ids, s, n, wk = loss_terms(T, K, S, r, fam, minmed)
             if ids.size == 0:
                 continue
-            s = ref[ids].astype(np.float64) / med[r, ids].astype(np.float64)
-            wk = w[r, ids].astype(np.float64)
-            n = wk * (1.0 - s)
             W = wk.sum()
             order = rank_by_loss(ids, n)[:top_n]
             with np.errstate(invalid="ignore", divide="ignore"):
+                n = n + 0.0  # (a zero n_k is reported as +0.0; NaN stays NaN)
                 f32[i, fam, 0, 0] = n.sum() / W
                 f32[i, fam, 0, 1] = n[order].sum() / W
                 out[i, fam, 0, 2] = ids.size

@@ -13,14 +13,16 @@ import torch
 
 import robust_workers
 from mp_util import run_ranks
+from followup_cases import ROBUST_SHAPES
 from robust_oracle_backend import robust_scores_table
+from score_cases import case_table
 from test_gpu_score import _random_table
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 3, 0), (2, 2, 2), (3, 5, 6), (4, 0, 7), (5, 4, 4), (63, 17, 33), (64, 17, 33), (65, 0, 64), (100, 7, 9),
-          (4096, 32, 16), (8, 4096, 8)]
-SPECIALS = ("full", "single", "equal", "zero_inf", "repeated")
+          (4096, 32, 16), (8, 4096, 8)] + list(ROBUST_SHAPES)  # (the boundaries of k_robust_cols: tests/followup_cases.py)
+SPECIALS = ("full", "single", "equal", "zero_inf", "repeated", "mostly_inf")
 ALL_BUT_FAST = [0, 1, 2, 3, 4, 6, 7]
 
 
@@ -55,14 +57,18 @@ def _special(T, rng, c, kind, K, S):
         order = np.argsort(col, kind="stable")
         mid = (R - 1) >> 1
         col[order[max(0, mid - 2) : mid + 3]] = col[order[mid]]
+    elif kind == "mostly_inf":  # more than half the ranks hold +inf: ctr = inf, the deviations inf - inf = NaN and
+        col[:] = rng.lognormal(1.0, 0.5, R)  # |finite - inf| = inf; a NaN deviation orders above +inf, so mad = NaN
+        col[rng.permutation(R)[: R // 2 + 1]] = np.inf
     T[:, c] = col
     if c < K:
         T[:, 2 * KS + c] = np.where(col >= 0, rng.uniform(1, 1000, R), 0.0).astype(np.float32)
 
 
 def _tables(R, K, S):
-    """The tables of one case: ``_random_table`` with 15 % of the medians absent plus the five special columns, spread over
-    the columns (a case with fewer than five columns gets several tables, so that each special column is exercised)."""
+    """The tables of one case: ``_random_table`` with 15 % of the medians absent plus the six special columns, spread over
+    the columns (a case with fewer than six columns gets several tables, so that each special column is exercised), each
+    with the columns whose records hold NaN of the arithmetic's own making (``mostly_inf``)."""
     rng = np.random.default_rng(R * 1000 + K + S)
     KS = K + S
     todo = list(SPECIALS)
@@ -72,7 +78,7 @@ def _tables(R, K, S):
         cols = np.linspace(0, KS - 1, len(take)).astype(int) if len(take) > 1 else [KS // 2]
         for c, kind in zip(cols, take):
             _special(T, rng, int(c), kind, K, S)
-        yield T
+        yield T, [int(c) for c, kind in zip(cols, take) if kind == "mostly_inf"]
 
 
 def _run(be, T, K, S, first_rank, n_ranks, min_ranks, floor_rel):
@@ -84,10 +90,18 @@ def _run(be, T, K, S, first_rank, n_ranks, min_ranks, floor_rel):
     return be.robust_score(ws, ws.send, first_rank, n_ranks, min_ranks, floor_rel).records()
 
 
-def _compare(got, exp, tag):
+def _compare(got, exp, tag, nan_cols=()):
+    """``nan_cols``: columns whose mad / scale are NaN by arithmetic (inf - inf, 0 * inf), not the "no reference" NaN the
+    kernel writes itself: their float words are compared by NaN-ness, a NaN's sign and payload being nobody's contract.
+    Every other word of every record is compared bit for bit."""
     (gcols, gsc), (ecols, esc) = got, exp
     assert gcols.shape == ecols.shape and gsc.shape == esc.shape, tag
-    bad = np.flatnonzero((gcols != ecols).any(axis=1))
+    differ = gcols != ecols
+    for c in nan_cols:
+        gf, ef = gcols[c, :3].view(np.float32), ecols[c, :3].view(np.float32)
+        assert np.array_equal(np.isnan(gf), np.isnan(ef)), (tag, "column", c, gf, ef)
+        differ[c, :3] &= ~np.isnan(ef)
+    bad = np.flatnonzero(differ.any(axis=1))
     assert bad.size == 0, (tag, "columns", bad[:8].tolist(), gcols[bad[:4]], ecols[bad[:4]],
                            gcols[bad[:4]].view(np.float32), ecols[bad[:4]].view(np.float32))
     assert np.array_equal(np.isnan(gsc), np.isnan(esc)), (tag, "NaN masks", np.argwhere(np.isnan(gsc) != np.isnan(esc))[:8])
@@ -106,18 +120,38 @@ def _compare(got, exp, tag):
 
 @pytest.mark.parametrize("R,K,S", SHAPES)
 def test_robust_score_matches_numpy(be, R, K, S):
-    for t, T in enumerate(_tables(R, K, S)):
+    for t, (T, nan_cols) in enumerate(_tables(R, K, S)):
         for min_ranks in (1, 4):
             for floor_rel in (0.0, 0.02):
                 tag = (R, K, S, t, min_ranks, floor_rel)
                 got = _run(be, T, K, S, 0, R, min_ranks, floor_rel)
                 exp = robust_scores_table(T, K, S, 0, R, min_ranks, floor_rel)
-                _compare(got, exp, tag)
+                _compare(got, exp, tag, nan_cols)
+                for c in nan_cols:
+                    ctr, mad, _, n = exp[0][c]
+                    if n >= min_ranks:  # what the header defines for this column
+                        assert ctr == 0x7F800000 and np.isnan(np.uint32(mad).view(np.float32)), (tag, exp[0][c])
                 if min_ranks == 4 and floor_rel == 0.02:
                     # a sub-range of ranks equals the slice of the full result, bit for bit
                     lo, n = (R // 3, max(1, R // 2)) if R > 1 else (0, 1)
                     pcols, psc = _run(be, T, K, S, lo, n, min_ranks, floor_rel)
                     assert np.array_equal(pcols, got[0]) and np.array_equal(_bits(psc), _bits(got[1][lo : lo + n])), tag
+
+
+@pytest.mark.parametrize("R,K,S", [(2, 2, 2), (5, 8, 8), (64, 12, 3), (65, 12, 3), (100, 7, 9), (1025, 2, 2)])
+def test_robust_score_on_edge_tables(be, R, K, S):
+    """``score_cases.case_table("edge_common")``: NaN medians (absent by ``v >= 0``), a column of -1 only and a one-rank column
+    under both ``min_ranks``, zero and infinite medians, thirty orders of magnitude inside one column, a rank whose weights
+    are all zero."""
+    T = case_table("edge_common", R, K, S)
+    for min_ranks in (1, 4):
+        for floor_rel in (0.0, 0.02):
+            tag = ("edge_common", R, K, S, min_ranks, floor_rel)
+            got = _run(be, T, K, S, 0, R, min_ranks, floor_rel)
+            _compare(got, robust_scores_table(T, K, S, 0, R, min_ranks, floor_rel), tag)
+    lo, n = R // 3, max(1, R // 2)
+    pcols, psc = _run(be, T, K, S, lo, n, 4, 0.02)
+    assert np.array_equal(pcols, got[0]) and np.array_equal(_bits(psc), _bits(got[1][lo : lo + n]))
 
 
 def test_argument_errors_come_back_before_the_device_is_touched(be):
