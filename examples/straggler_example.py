@@ -50,6 +50,12 @@ of it) and normal again afterwards: no median, no 0.95-quantile, no step and no 
 ``NVRX_EPISODE_DETECTION=1`` the report also looks for the one interval of every timing row that spent most time above the
 row's mean (``Report.episode_scores()``) and the example prints whoever ``identify_episode_stragglers`` flags, with how long
 the rank's strongest episode lasted and how many samples ago it ended.
+
+``--persist`` needs no training loop: it plays 20 reports of a job of 8 ranks (folded onto one GPU, 1 % noise, seed 17) in which
+rank 2 is 1.6x slower in report 6 only and rank 5 is 1.45x slower from report 10 on, with a score history of 8 reports
+(``ReportGenerator(score_history=8, persistence_min_reports=3)``), and prints per report whom ``identify_stragglers`` flags and
+whom ``identify_persistent_stragglers`` does: rank 2 once and never persistently, rank 5 from report 10 and, persistently,
+from report 12 on.
 """
 import argparse
 import os
@@ -211,6 +217,39 @@ def train(args) -> None:
         dist.destroy_process_group()
 
 
+def persist(reports: int = 20, ranks: int = 8, sections: int = 4, samples: int = 33) -> None:
+    """One slow window against a rank that stays slow: what a report flags, and what the score history does."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=64, scores_to_compute=("relative_perf_scores",),
+                    score_history=8, persistence_min_reports=3)
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    try:
+        for i in range(reports):
+            x = 1000.0 * (1.0 + 0.01 * np.random.default_rng([17, i]).standard_normal((ranks, sections, samples)))
+            if i == 6:
+                x[2] *= 1.6
+            if i >= 10:
+                x[5] *= 1.45
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, x[r].astype(np.float32))
+            report = job.report()
+            history = report.score_history()
+            rec = history["section_relative"][job.section_names[0]]
+            print(f"report {i:2d}: flagged {named(report.identify_stragglers())}, for 3 reports in a row "
+                  f"{named(report.identify_persistent_stragglers())}; rank 5 on {job.section_names[0]}: latest "
+                  f"{rec[5]['latest']:.2f}, median of the last {history['depth']} {rec[5]['median']:.2f}, streak {rec[5]['streak']}, "
+                  f"below in {rec[5]['below']} of {rec[5]['present']}")
+    finally:
+        job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -227,7 +266,12 @@ def main() -> None:
                     help="--slow-by intermittent: the slow rank's stand-in kernel is 1.5x longer on every N-th step only (with one "
                          "step in ten slow, a 0.9 quantile would sit on the last FAST sample)")
     ap.add_argument("--simulated-cycles", type=float, default=3e6, help="--slow-by simulated: spin cycles of the stand-in kernel")
+    ap.add_argument("--persist", action="store_true",
+                    help="no training: play the score-history scenario (one slow window against a rank that stays slow) and exit")
     args = ap.parse_args()
+    if args.persist:
+        persist()
+        return
     if "RANK" in os.environ or args.num_processes == 1:
         train(args)
         return

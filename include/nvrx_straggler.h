@@ -335,6 +335,44 @@ int nvrx_episode_score(const float *d_episode, const float *d_table, int R, int 
 int nvrx_robust_score(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks,
                       float floor_rel, void *d_out, void *stream);
 
+/* Score history: how each score behaved over the last H reports.  Every score above looks inside one report window; the one
+ * thing a report carries over from its predecessors is the running minimum of MED.  Here a device ring keeps the last H
+ * reports' scores per reported rank, family f (0 individual, 1 relative: the parity of the score row's first two columns)
+ * and slot j (0 = the GPU score, 1 + s = section id s), and one step per report appends the report's scores and says, per
+ * (rank, f, j), how long the score has been below its threshold.  Nothing is exchanged: the step reads what nvrx_score wrote.
+ *   H       depth, in [2, NVRX_HISTORY_MAX_DEPTH]; Hs = NVRX_HISTORY_STRIDE(H): 16, 32 or 64, the smallest that is >= H;
+ *   d_hist  f32 [n_ranks][2][1 + S_cap][Hs], 16-byte aligned (NVRX_HISTORY_FLOATS).  Physical position i < H of a cell holds
+ *           the report with (number of that report) % H == i; positions [H, Hs) are never touched.  An ABSENT entry is a NaN:
+ *           the caller fills a fresh buffer with bytes 0xFF (a NaN in every word);
+ *   d_scores [R][NVRX_SCORE_LEN(S)] as nvrx_score wrote it (it may be the pinned, device-mapped result block); S <= S_cap;
+ *   ranks   [first_rank, first_rank + n_ranks) of the R score rows: row r of d_hist / d_out is rank first_rank + r;
+ *   n_before  reports appended so far; thresholds[4] in nvrx_score's order, NULL => 0.75 each (finite).
+ * The step, per (r, f, j) with j <= S (slots j > S are left alone):
+ *   x      = d_scores[first_rank + r][col], col = f for j == 0, else 2 + (j - 1) for f == 0 and 2 + S + (j - 1) for f == 1;
+ *   x is stored at position n_before % H; depth = min(n_before + 1, H); x_a, a in [0, depth), is the entry of AGE a -- the one
+ *   at position (n_before - a) mod H -- so x_0 = x;
+ *   thr    = thresholds[0] for (f, j) = (1, 0), [1] for (1, j > 0), [2] for (0, 0), [3] for (0, j > 0);
+ *   x_a is PRESENT iff it is no NaN and BELOW iff (double)x_a < thr -- the comparison behind nvrx_score's d_flags (strict; NaN
+ *   is never below; +inf and 0.0 are values);
+ *   record, 32 bytes: {f32 latest = x_0, f32 median, f32 worst, f32 best, u32 streak, u32 below, u32 present, u32 depth}
+ *      present  number of present entries, below  number of entries below;
+ *      streak   number of newest entries x_0, x_1, ... that are all below: 0 if x_0 is not; a NaN ends it, and so does depth;
+ *      median, worst, best  the elements of rank (present - 1) >> 1, 0 and present - 1 of the present entries sorted by raw
+ *               bit pattern (-0.0 < +0.0 < ... < +inf): the LOWER median, always actual scores; NaN when present == 0.
+ *   Every word is exact: no sum, no rounding.
+ *   d_out  16-byte aligned, NVRX_HISTORY_WORDS(n_ranks, S) 32-bit words: [n_ranks][2][1 + S][8].
+ * A rank is PERSISTENTLY slow on a column when streak >= min_reports; below / present serve "k of the last H".
+ * One launch; every (r, f, j) appends its own entry, so steps must only be ordered against each other (one stream).
+ * NVRX_ERR_RANGE for H outside [2, 64], S_cap above NVRX_MAX_ROWS, or more cells than one launch covers (n_ranks * 2 *
+ * ceil((1 + S) / (64 / Hs)) waves above 2^31 - 1); NVRX_ERR_INVALID for null or misaligned pointers, S > S_cap, a bad rank
+ * range or non-finite thresholds -- reported before any device is touched. */
+#define NVRX_HISTORY_MAX_DEPTH 64
+#define NVRX_HISTORY_STRIDE(H) ((H) <= 16 ? 16 : (H) <= 32 ? 32 : 64)
+#define NVRX_HISTORY_FLOATS(n_ranks, S_cap, H) ((size_t)(n_ranks) * 2 * (1 + (size_t)(S_cap)) * NVRX_HISTORY_STRIDE(H))
+#define NVRX_HISTORY_WORDS(n_ranks, S) ((size_t)(n_ranks) * 2 * (1 + (size_t)(S)) * 8)
+int nvrx_score_history(const float *d_scores, int R, int S, int first_rank, int n_ranks, float *d_hist, int S_cap, int H,
+                       uint64_t n_before, const double *thresholds, void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -547,6 +585,13 @@ int nvrx_episode_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min
  * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_robust(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int min_ranks,
                        float floor_rel, void *d_out);
+/* nvrx_score_history (above) on the result block of the report LAST issued through `desc` on `ctx` (desc->d_scores; R and S
+ * from the descriptor).  Ordered behind that report's last kernel exactly as nvrx_report_robust orders itself: the context's
+ * stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a D2H on the
+ * context's stream, and do not let a later report rewrite that block before the kernel has run.  NVRX_ERR_STATE: no report
+ * was issued through this descriptor. */
+int nvrx_report_history(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, float *d_hist, int S_cap,
+                        int H, uint64_t n_before, const double *thresholds, void *d_out);
 /* One report WINDOW in one call: what straggler.py:228-244 does around the report in the steady state -- wait for the
  * window's GPU measurements (torch.cuda.synchronize() + the profiler's get_stats there; here the kernel tracer's sync, or a
  * harvest of the region events), check that the set of rows holding samples is the one the caller's name tables were built

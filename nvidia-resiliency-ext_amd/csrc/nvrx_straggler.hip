@@ -3953,5 +3953,6 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_tail.inl"
 #include "nvrx_onset.inl"
 #include "nvrx_robust.inl"
+#include "nvrx_history.inl"
 #include "nvrx_period.inl"
 #include "nvrx_episode.inl"

@@ -46,6 +46,7 @@ class StragglerDetectionCallback(Callback):
         enable_ptl_logging: bool,
         profiling_interval: int = 1,
         logger_name: Optional[str] = "nemo_logger.StragglerDetectionCallback",
+        min_consecutive_reports: int = 1,
     ):
         """
         Args:
@@ -58,9 +59,14 @@ class StragglerDetectionCallback(Callback):
             enable_ptl_logging: log min/median/max GPU scores through ``pl_module.log_dict``.
             profiling_interval: forwarded to ``Detector.initialize``.
             logger_name: name of the ``logging`` logger to use.
+            min_consecutive_reports: 1 (the default, the reference's behaviour): a GPU is reported, and with
+                ``stop_if_detected`` the job is stopped, the first time a report flags it.  M > 1: only once its score has
+                been below the threshold in M reports in a row (``Report.identify_persistent_stragglers``; the detector
+                then keeps a score history of ``max(8, M)`` reports): one slow window -- a neighbour's checkpoint, a
+                page-cache flush -- no longer ends a healthy job.  Every report's scores are printed and logged as before.
 
         Raises:
-            ValueError: neither score family requested.
+            ValueError: neither score family requested, or ``min_consecutive_reports`` outside [1, 64].
         """
         self.initialized = False
         self.logger = logging.getLogger(logger_name)
@@ -83,17 +89,28 @@ class StragglerDetectionCallback(Callback):
                 "No straggler performance scores specified. "
                 "Check if calc_relative_gpu_perf=True or calc_individual_gpu_perf=True"
             )
+        if (isinstance(min_consecutive_reports, bool) or not isinstance(min_consecutive_reports, int)
+                or not 1 <= min_consecutive_reports <= 64):
+            raise ValueError(f"min_consecutive_reports must be an integer within [1, 64], got {min_consecutive_reports!r}")
+        self.min_consecutive_reports = min_consecutive_reports
         self.interval_est_was_reset = False
 
     # ---- Lightning hooks -----------------------------------------------------------------------
     def setup(self, trainer, pl_module, stage):
         if self.initialized:
             return
+        persistence = {}
+        if self.min_consecutive_reports > 1:
+            m = self.min_consecutive_reports
+            persistence = dict(score_history=max(8, m), persistence_min_reports=m,
+                               persistence_thresholds=(self.gpu_relative_perf_threshold, 0.75,
+                                                       self.gpu_individual_perf_threshold, 0.75))
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
             profiling_interval=self.profiling_interval,
             report_time_interval=self.report_time_interval,
+            **persistence,
         )
         step_owner = trainer.strategy
         assert getattr(step_owner, "training_step", None), f"{type(step_owner)} does not have 'training_step' method."
@@ -128,13 +145,20 @@ class StragglerDetectionCallback(Callback):
     )
 
     def _digest(self, pl_module, report) -> bool:
-        """Warn about flagged GPUs, print the best / worst ranks, feed the PTL loggers; True if anything was flagged."""
-        flagged = report.identify_stragglers(
-            gpu_rel_threshold=self.gpu_relative_perf_threshold,
-            gpu_indiv_threshold=self.gpu_individual_perf_threshold,
-        )
+        """Warn about flagged GPUs, print the best / worst ranks, feed the PTL loggers; True if anything was flagged -- with
+        ``min_consecutive_reports`` above 1: flagged in that many reports in a row."""
+        m = self.min_consecutive_reports
+        if m > 1:
+            flagged = report.identify_persistent_stragglers()
+        else:
+            flagged = report.identify_stragglers(
+                gpu_rel_threshold=self.gpu_relative_perf_threshold,
+                gpu_indiv_threshold=self.gpu_individual_perf_threshold,
+            )
         hits = [(text, flagged[key]) for _, _, key, _, _, text in self._FAMILIES if flagged[key]]
         for text, ranks in hits:
+            if m > 1:
+                text = f"{text.rstrip('.')} for {m} consecutive reports."
             self.logger.warning(f"STRAGGLER DETECTION WARNING: {text} Affected ranks: {ranks}")
         if hits:
             self._name_the_kernels(report, flagged)

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_uint32, c_uint64, c_void_p
 
 _LIB_NAME = "libnvrx_straggler_hip.so"
 # NVRX_DEBUG_LIB_DIR: load the native libraries from another directory (the sanitizer build of `make -C csrc asan` lives in
@@ -26,6 +26,7 @@ META_WORDS = 8
 ERR_TIMEOUT = -62
 ERR_RANGE = -34
 ERR_INVALID = -22
+ERR_STATE = -1
 ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
 TAIL_Q_PPM_MIN, TAIL_Q_PPM_MAX = 500000, 999999  # the accepted range of a tail quantile, in parts per million
 ROUTE_SINGLE, ROUTE_ROWS, ROUTE_ROWS_PRE, ROUTE_TILE16, ROUTE_TILE8 = 1, 2, 3, 4, 5  # NVRX_SCORE_ROUTE_*: what nvrx_score_route returns
@@ -39,6 +40,8 @@ PERIOD_PLANES = 7  # NVRX_PERIOD_PLANES: {e, peak, rest, strength, period, ago, 
 EPISODE_LEN_PPM_MIN, EPISODE_LEN_PPM_MAX = 1, 333333  # the accepted range of an episode's minimum length, in parts per million
 EPISODE_MIN_SAMPLES = 8  # ... and the length's floor in samples
 EPISODE_PLANES = 7  # NVRX_EPISODE_PLANES: {e, inside, outside, strength, length, ago, n} per kernel id and section id
+HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
+HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
 
 
 
@@ -88,6 +91,8 @@ SYMBOLS = [
     ("nvrx_row_episode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_episode_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
+                                   c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -127,6 +132,8 @@ SYMBOLS = [
     ("nvrx_period_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
+    ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
+                                    POINTER(c_double), c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
     ("nvrx_peer_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -221,6 +228,21 @@ def attr_words(n_ranks: int, top_n: int) -> int:
 def robust_words(n_ranks: int, K: int, S: int) -> int:
     """NVRX_ROBUST_WORDS: 32-bit words of a robust-score block: ``[K+S][4]`` column records, then ``[n_ranks][2][1 + S]``."""
     return 4 * (K + S) + n_ranks * 2 * (1 + S)
+
+
+def history_stride(H: int) -> int:
+    """NVRX_HISTORY_STRIDE: ring positions a history cell of depth ``H`` occupies: 16, 32 or 64, the smallest that is >= H."""
+    return 16 if H <= 16 else 32 if H <= 32 else 64
+
+
+def history_floats(n_ranks: int, S_cap: int, H: int) -> int:
+    """NVRX_HISTORY_FLOATS: floats of a history ring ``[n_ranks][2][1 + S_cap][stride]``."""
+    return n_ranks * 2 * (1 + S_cap) * history_stride(H)
+
+
+def history_words(n_ranks: int, S: int) -> int:
+    """NVRX_HISTORY_WORDS: 32-bit words of a history step's records ``[n_ranks][2][1 + S][8]``."""
+    return n_ranks * 2 * (1 + S) * HISTORY_RECORD_WORDS
 
 
 def tail_q_ppm(q) -> int:

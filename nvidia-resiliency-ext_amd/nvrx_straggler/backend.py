@@ -307,6 +307,61 @@ class Robust:
         return self._host
 
 
+class ScoreHistory:
+    """The score history of one ``ReportGenerator`` (``nvrx_score_history`` / ``nvrx_report_history``): the ring of the last
+    ``depth`` reports' scores -- ``hist``, f32 ``[n_ranks][2][1 + S_cap][stride]`` where the backend keeps it, NaN where
+    nothing was appended --, the number of reports appended so far and the section ids the ring has room for.  The backend
+    that runs the step allocates and grows ``hist`` (``HipBackend.score_history``); the state itself only says when the
+    history starts again: a change of the reported ranks, or ``reset()``."""
+
+    __slots__ = ("depth", "stride", "hist", "S_cap", "n_before", "ranks")
+
+    def __init__(self, depth: int):
+        self.depth, self.stride = int(depth), _native.history_stride(int(depth))
+        self.reset()
+
+    def reset(self) -> None:
+        self.hist, self.S_cap, self.n_before, self.ranks = None, 0, 0, None
+
+    def begin(self, first_rank: int, n_ranks: int) -> None:
+        """A step for ranks ``[first_rank, first_rank + n_ranks)`` is about to run: another range than last time starts the
+        history again."""
+        if self.ranks != (first_rank, n_ranks):
+            self.reset()
+            self.ranks = (first_rank, n_ranks)
+
+    @staticmethod
+    def capacity(S: int) -> int:
+        """Section ids a ring that has to hold ``S`` is given room for: the next multiple of 64."""
+        return max(64, -(-S // 64) * 64)
+
+
+class History:
+    """The score history after one report (``nvrx_score_history`` / ``nvrx_report_history``), enqueued and not waited for: once
+    the kernel has run, the workspace's device buffer holds ``[n_ranks][2][1 + S][8]`` 32-bit words ``{latest, median, worst,
+    best, streak, below, present, depth}`` (include/nvrx_straggler.h).  ``records()`` waits for it and takes the private host
+    copy (one ordered D2H on the backend's stream): when a ``Report`` first asks, or -- ``Workspace.history_settle`` --
+    before the next report on the same workspace rewrites the block the kernel read and the buffer it wrote."""
+
+    __slots__ = ("backend", "d_ptr", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, S: int, first_rank: int, n_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.S, self.first_rank, self.n_ranks = S, first_rank, n_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self) -> np.ndarray:
+        """``[n_ranks, 2, 1 + S, 8]`` uint32 (private copy); the first call waits for the kernel."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.history_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -473,7 +528,8 @@ class Workspace:
 
     def settle_readers(self) -> None:
         """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
-        reading it -- attribution, tails, robust scores, onsets, periods, episodes -- has run and delivered."""
+        reading it -- attribution, tails, robust scores, onsets, periods, episodes -- has run and delivered; and so has the
+        score history's step, which read the result block and wrote the records buffer."""
         if self._attr_last is not None:
             self.attr_settle()
         if self._family_state:
@@ -483,6 +539,8 @@ class Workspace:
         if self._family_state:
             for fam in FAMILIES[1:]:
                 self.family_settle(fam)
+        if self._history_last is not None:
+            self.history_settle()
 
     # ---- robust scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
     _robust_buf = None   # device: column records, then the scores of the last robust step of this workspace's table
@@ -500,6 +558,26 @@ class Workspace:
         """Before anything rewrites this workspace's table: the last robust step's kernels have run and their results are
         on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
         last, self._robust_last = self._robust_last, None
+        if last is not None:
+            last.records()
+
+    # ---- score history (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------
+    _history_buf = None   # device: the records of the last history step on this workspace's result blocks
+    _history_last = None  # the History whose kernel may still be reading a result block / writing _history_buf
+
+    def history_buffers(self, n_ranks: int):
+        """The records buffer for a history step over ``n_ranks`` ranks (cold: allocated once per shape)."""
+        words = _native.history_words(n_ranks, self.S)
+        if self._history_buf is None or self._history_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._history_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return self._history_buf
+
+    def history_settle(self) -> None:
+        """Before anything rewrites this workspace's result blocks or the records buffer: the last history step's kernel has
+        run and its records are on the host (a ``Report`` still alive keeps them; an unread one costs this one small
+        copy)."""
+        last, self._history_last = self._history_last, None
         if last is not None:
             last.records()
 
@@ -742,6 +820,46 @@ class HipBackend:
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, rb.d_ptr, n * 4, self._stream_handle))
         cols = host[: 4 * KS].reshape(KS, 4).copy()
         return cols, host[4 * KS :].view(np.float32).reshape(rb.n_ranks, 2, 1 + rb.S).copy()
+
+    def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
+        """What both routes of a history step share: the ring of ``state`` with room for this workspace's section ids (cold:
+        allocated -- every word a NaN -- or grown on the backend's stream, the old entries copied by slicing: ids are never
+        reassigned, so old columns keep their history), the records buffer, and the thresholds as the library takes them."""
+        state.begin(first_rank, n_ranks)
+        if state.hist is None or ws.S > state.S_cap:
+            cap = ScoreHistory.capacity(ws.S)
+            with torch.cuda.stream(self.stream):  # (allocated, written and read under the backend's stream)
+                ring = torch.full((n_ranks, 2, 1 + cap, 4 * state.stride), 0xFF, dtype=torch.uint8,
+                                  device=self.device).view(torch.float32)
+                if state.hist is not None:
+                    ring[:, :, : 1 + state.S_cap] = state.hist
+            state.hist, state.S_cap = ring, cap
+        ws.history_settle()
+        thr = tuple(float(t) for t in thresholds)
+        if len(thr) != 4:
+            raise ValueError(f"a score history takes four thresholds, got {thresholds!r}")
+        return ws.history_buffers(n_ranks), (ctypes.c_double * 4)(*thr)
+
+    def score_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,
+                      thresholds: Sequence[float] = DEFAULT_THRESHOLDS) -> History:
+        """Append the scores ``score`` just left in ``ws``'s current result block to ``state``'s ring, for ranks
+        ``[first_rank, first_rank + n_ranks)``: ``nvrx_score_history`` enqueued on the backend's stream behind the score
+        kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        buf, c_thr = self.history_prepare(ws, state, first_rank, n_ranks, thresholds)
+        rc = self.lib.nvrx_score_history(ws.d_scores, ws.R, ws.S, first_rank, n_ranks, state.hist.data_ptr(), state.S_cap,
+                                         state.depth, state.n_before, c_thr, buf.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        state.n_before += 1
+        out = ws._history_last = History(self, buf, ws.S, first_rank, n_ranks)
+        return out
+
+    def history_copy_out(self, h: History) -> np.ndarray:
+        """The one wait of a report's score history: a D2H of the records on the backend's stream, behind the kernel."""
+        host = np.empty((h.n_ranks, 2, 1 + h.S, _native.HISTORY_RECORD_WORDS), dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, h.d_ptr, host.nbytes, self._stream_handle))
+        return host
 
     def row_quantile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm: int) -> torch.Tensor:
         """Stateless nearest-rank quantile on caller tensors ([rows, stride] f32, [rows] u32/i32) -> [rows] f32, -1.0 where
@@ -1056,6 +1174,21 @@ class HipRings:
         if rc < 0:
             _native.check(rc)
         out = ws._robust_last = Robust(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
+        return out
+
+    def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,
+                       thresholds: Sequence[float] = DEFAULT_THRESHOLDS) -> History:
+        """Append the scores of the report ``report_fused`` just issued on ``ws`` to ``state``'s ring
+        (``nvrx_report_history``): enqueued behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        be = self.backend
+        buf, c_thr = be.history_prepare(ws, state, first_rank, n_ranks, thresholds)
+        rc = self.lib.nvrx_report_history(self.ctx, ws.block.desc_ref, first_rank, n_ranks, state.hist.data_ptr(),
+                                          state.S_cap, state.depth, state.n_before, c_thr, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        state.n_before += 1
+        out = ws._history_last = History(be, buf, ws.S, first_rank, n_ranks)
         return out
 
     def _family_local(self, fam: RowFamily, ws: Workspace, params: tuple, rows_active: int, fused: bool):

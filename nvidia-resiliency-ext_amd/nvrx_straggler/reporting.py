@@ -715,6 +715,49 @@ class _RobustSource:
         return self._built
 
 
+_HISTORY_FAMILIES = ((1, "relative"), (0, "individual"))  # (family word of the record, name) in the order the mappings are listed
+
+
+class _HistorySource:
+    """What a report keeps of the score history as it stood after that report: the backend's handle (``records()`` waits for
+    the kernel and copies the records out on first use), the ranks its rows stand for, the sections it shows with their ids,
+    which families were computed, and the generator's depth, streak length and thresholds."""
+
+    __slots__ = ("handle", "ranks", "sections", "has_rel", "has_indiv", "capacity", "min_reports", "thresholds", "_built")
+
+    def __init__(self, handle, ranks, sections, has_rel: bool, has_indiv: bool, capacity: int, min_reports: int, thresholds):
+        self.handle, self.ranks = handle, tuple(ranks)
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self.has_rel, self.has_indiv = has_rel, has_indiv
+        self.capacity, self.min_reports, self.thresholds = capacity, min_reports, tuple(thresholds)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            rec = np.ascontiguousarray(self.handle.records(), dtype=np.uint32)
+            f32 = rec.view(np.float32)[..., :4].tolist()
+            u32 = rec[..., 4:].tolist()
+            ranks = self.ranks
+
+            def record(i, fam, j):
+                f, u = f32[i][fam][j], u32[i][fam][j]
+                return {"latest": f[0], "median": f[1], "worst": f[2], "best": f[3], "streak": u[0], "below": u[1],
+                        "present": u[2]}
+
+            built: Dict[str, Any] = {"depth": int(rec[0, 0, 0, 7]) if rec.size else 0, "capacity": self.capacity,
+                                     "min_reports": self.min_reports, "thresholds": self.thresholds}
+            for fam, name in _HISTORY_FAMILIES:
+                if self.has_rel if fam else self.has_indiv:
+                    built["gpu_" + name] = {r: record(i, fam, 0) for i, r in enumerate(ranks)}
+            for fam, name in _HISTORY_FAMILIES:
+                if self.has_rel if fam else self.has_indiv:
+                    built["section_" + name] = {n: {r: record(i, fam, 1 + g) for i, r in enumerate(ranks)}
+                                                for n, g in self.sections.items()}
+            self._built = built
+            self.handle = None
+        return self._built
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -807,6 +850,9 @@ class Report:
         robust = self.__dict__.get("_robust")
         if robust is not None:
             state["_robust"] = robust.build() if isinstance(robust, _RobustSource) else robust
+        history = self.__dict__.get("_history")
+        if history is not None:
+            state["_history"] = history.build() if isinstance(history, _HistorySource) else history
         for fam in row_families.FAMILIES:
             scores = self.__dict__.get(fam.slot)
             if scores is not None:
@@ -954,6 +1000,47 @@ class Report:
         sr = {n: [r for r, z in v.items() if z > section_z_threshold] for n, v in t.get("section_z", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
                 "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def score_history(self) -> Dict[str, Any]:
+        """The score history as it stood after this report (``ReportGenerator(score_history=H)``; ``{}`` when the report
+        carries none).  Every other score looks inside one report window; this looks ACROSS reports: per rank and score, what
+        the last ``H`` reports of the generator said.
+
+        ``{"depth": reports the history holds (at most H), "capacity": H, "min_reports": M, "thresholds": (gpu_rel,
+        section_rel, gpu_indiv, section_indiv), "gpu_relative": {rank: rec}, "gpu_individual": {rank: rec},
+        "section_relative": {section: {rank: rec}}, "section_individual": {...}}`` with ``rec = {"latest": this report's
+        score, "median": the lower median of the scores present, "worst", "best", "streak": how many of the newest reports in
+        a row were below the threshold (0 when this one was not; a report without the score ends it), "below": reports below
+        the threshold, "present": reports that had the score at all}`` -- all actual scores, NaN where no report had one.
+        Families that were not computed are left out; ranks and sections as in the score mappings.  Plain dicts, floats and
+        ints.  The first call waits for the history kernel and copies its records; ``generate_report`` does not."""
+        history = self.__dict__.get("_history")
+        if history is None:
+            return {}
+        if isinstance(history, _HistorySource):
+            history = self.__dict__["_history"] = history.build()
+        return _copy_scores(history)
+
+    def identify_persistent_stragglers(self, min_reports: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks whose score has been below its threshold for the last ``min_reports`` reports IN A ROW, this one included
+        (default: the generator's ``persistence_min_reports``): the four keys of ``identify_stragglers``, ``StragglerId``
+        sets; a section appears only if somebody is flagged for it.  One slow window flags nobody here.  Empty sets when
+        the report carries no score history."""
+        t = self.score_history()
+        m = t.get("min_reports", 1) if min_reports is None else min_reports
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
+            raise ValueError(f"min_reports must be an integer >= 1, got {min_reports!r}")
+
+        def gpus(key):
+            return self._ids([r for r, rec in t.get(key, {}).items() if rec["streak"] >= m])
+
+        def sections(key):
+            flagged = {n: [r for r, rec in v.items() if rec["streak"] >= m] for n, v in t.get(key, {}).items()}
+            return {n: self._ids(r) for n, r in flagged.items() if r}
+
+        return {"straggler_gpus_relative": gpus("gpu_relative"), "straggler_gpus_individual": gpus("gpu_individual"),
+                "straggler_sections_relative": sections("section_relative"),
+                "straggler_sections_individual": sections("section_individual")}
 
     def _family_scores(self, name: str) -> Dict[str, Any]:
         """A private copy of one row family's scores (built from the device's planes on first use); ``{}`` without them."""
@@ -1129,7 +1216,8 @@ class ReportGenerator:
                  robust_min_ranks: int = 4, robust_floor: float = 0.02, onset_detection: bool = False,
                  onset_min_segment: float = 0.05, onset_min_strength: float = 0.5, period_detection: bool = False,
                  period_max: int = 1024, period_min_strength: float = 0.5, episode_detection: bool = False,
-                 episode_min_length: float = 0.005, episode_min_strength: float = 0.5) -> None:
+                 episode_min_length: float = 0.005, episode_min_strength: float = 0.5, score_history: int = 0,
+                 persistence_min_reports: int = 3, persistence_thresholds: Optional[Sequence[float]] = None) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1274,6 +1362,37 @@ class ReportGenerator:
                 raise RuntimeError(f"episode_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no episode scores (backend.episode_score)")
             self.episode_len_ppm, self.episode_min_strength = len_ppm, strength
+        # score history: every report also appends its scores to a device ring of the last H reports and says, per rank and
+        # score, for how many reports in a row the score has been below its threshold (Report.score_history,
+        # Report.identify_persistent_stragglers); 0 = off: no buffer, no launch, no backend call.  It reads what the score
+        # kernel wrote: no collective, so a mismatch between ranks cannot hang anything.  The history belongs to this generator
+        # and dies with it.
+        self._history = None  # (backend.ScoreHistory while the option is on)
+        depth = score_history
+        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not (
+                depth == 0 or 2 <= depth <= _backend_mod._native.HISTORY_MAX_DEPTH):
+            raise ValueError(f"score_history must be 0 (off) or an integer within [2, {_backend_mod._native.HISTORY_MAX_DEPTH}] "
+                             f"reports, got {score_history!r}")
+        self.score_history = int(depth)
+        if self.score_history:
+            m = persistence_min_reports
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= self.score_history:
+                raise ValueError(f"persistence_min_reports must be an integer within [1, score_history={self.score_history}], "
+                                 f"got {persistence_min_reports!r}")
+            try:
+                thr = self.thresholds if persistence_thresholds is None else tuple(float(t) for t in persistence_thresholds)
+            except (TypeError, ValueError):
+                raise ValueError(f"persistence_thresholds must be four finite numbers (gpu_rel, section_rel, gpu_indiv, "
+                                 f"section_indiv), got {persistence_thresholds!r}") from None
+            if len(thr) != 4 or not all(np.isfinite(thr)):
+                raise ValueError(f"persistence_thresholds must be four finite numbers (gpu_rel, section_rel, gpu_indiv, "
+                                 f"section_indiv), got {persistence_thresholds!r}")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "score_history"):
+                raise RuntimeError(f"score_history: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no score history (backend.score_history)")
+            self.persistence_min_reports, self.persistence_thresholds = int(m), thr
+            self._history = _backend_mod.ScoreHistory(self.score_history)
         # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
         # any, that needs the ring-start snapshot
         self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
@@ -1519,6 +1638,10 @@ class ReportGenerator:
             # likewise: enqueued behind the score kernel, waited for when the report is first asked
             self._attach_robust(report, _backend_mod.get_backend().robust_score(
                 ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor), ws, mapper, view)
+        if self._history is not None:
+            # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
+            self._attach_history(report, _backend_mod.get_backend().score_history(
+                ws, self._history, lo, hi - lo, self.persistence_thresholds), view)
         if stats is None:
             # the caller's own summaries travel with the report, untouched
             report.__dict__["local_section_summaries"] = section_summaries
@@ -1664,6 +1787,8 @@ class ReportGenerator:
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
         if fused and self.robust_scores and not hasattr(rings, "report_robust"):
             raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
+        if fused and self._history is not None and not hasattr(rings, "report_history"):
+            raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
         if fused:
             # ONE C call: flush -> statistics kernel -> [ncclAllGather] -> score kernel -> completion word
             wait = not self.asynchronous
@@ -1687,6 +1812,8 @@ class ReportGenerator:
                     self._attach_plan_attribution(report, plan, rings, True)
                 if self.robust_scores:
                     self._attach_plan_robust(report, plan, rings, True)
+                if self._history is not None:
+                    self._attach_plan_history(report, plan, rings, True)
                 return report
         else:
             rings.report_local(ws, True, rows_active=plan.rows_used)
@@ -1721,6 +1848,8 @@ class ReportGenerator:
             self._attach_plan_attribution(report, plan, rings, fused)
         if self.robust_scores:
             self._attach_plan_robust(report, plan, rings, fused)
+        if self._history is not None:
+            self._attach_plan_history(report, plan, rings, fused)
         return report
 
     def _attach_plan_attribution(self, report, plan, rings, fused: bool) -> None:
@@ -1756,6 +1885,29 @@ class ReportGenerator:
         else:
             handle = _backend_mod.get_backend().robust_score(ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor)
         self._attach_robust(report, handle, ws, plan.mapper, plan.view)
+
+    # ---- score history ------------------------------------------------------------------------------
+    def _attach_history(self, report, handle, view) -> None:
+        report.__dict__["_history"] = _HistorySource(handle, view.ranks, view.cols, self.is_computing_rel_scores,
+                                                     self.is_computing_indiv_scores, self.score_history,
+                                                     self.persistence_min_reports, self.persistence_thresholds)
+
+    def _attach_plan_history(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the history step of the planned report that was just issued, as ``_attach_plan_robust`` does, for the ranks
+        the report covers, and hang it on ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        lo, hi = plan.view.layout[5], plan.view.layout[6]
+        if fused:
+            handle = rings.report_history(ws, self._history, lo, hi - lo, self.persistence_thresholds)
+        else:
+            handle = _backend_mod.get_backend().score_history(ws, self._history, lo, hi - lo, self.persistence_thresholds)
+        self._attach_history(report, handle, plan.view)
+
+    def reset_score_history(self) -> None:
+        """Forget the score history: the next report starts a new one (after a restart from a checkpoint, a change of the
+        job's layout, a node swap).  Reports already handed out keep theirs."""
+        if self._history is not None:
+            self._history.reset()
 
     # ---- row families: tail, onset, period, episode scores ------------------------------------------
     def _family_step(self, fam, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:

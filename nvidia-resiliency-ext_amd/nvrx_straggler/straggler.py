@@ -162,6 +162,8 @@ class _Lane:
             return None  # (a row family's step follows the report in the generator's paths: DESIGN.md, "Row families")
         if getattr(reporter, "robust_scores", False):
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
+        if getattr(reporter, "score_history", 0):
+            return None  # (the history step follows the report in the generator's planned path: DESIGN.md, "Score history")
         ext = manager.cupti_ext
         ws = plan.ws
         if ws.block.desc_key is None or not ws.send_initialised:
@@ -395,6 +397,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
         episode_detection: Optional[bool] = None,
         episode_min_length: float = 0.005,
         episode_min_strength: float = 0.5,
+        score_history: Optional[int] = None,
+        persistence_min_reports: Optional[int] = None,
+        persistence_thresholds: Optional[Sequence[float]] = None,
     ):
         """
         Args:
@@ -464,6 +469,15 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 row's samples, within [0.000001, 0.333333]; never fewer than 8 samples.
             episode_min_strength: an episode counts when its two levels explain at least this share of the row's variance,
                 within [0, 1].  0.5 is a default, not a measurement.
+            score_history: 0 = off; H in 2..64: every report also appends its scores to a history of the last H reports and
+                says, per rank and score, for how many reports in a row the score has been below its threshold
+                (``Report.score_history()``, ``Report.identify_persistent_stragglers()``): a rank that was slow in one window
+                only -- a neighbour's checkpoint, a page-cache flush -- is not flagged, one that stays slow is.  Default:
+                ``NVRX_SCORE_HISTORY``, else 0.  Pass the same value on every rank (no collective depends on it).
+            persistence_min_reports: the streak that makes a rank persistently slow, within [1, score_history].  Default:
+                ``NVRX_PERSISTENCE_MIN_REPORTS``, else 3 (never more than ``score_history``).
+            persistence_thresholds: (gpu_rel, section_rel, gpu_indiv, section_indiv) a score has to be below; default: 0.75
+                each, the thresholds the reports' own flags are computed for.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -514,6 +528,22 @@ class Detector(metaclass=_DeviceSideOnDemand):
             period_detection = os.environ.get("NVRX_PERIOD_DETECTION", "0") not in ("", "0")
         if episode_detection is None:
             episode_detection = os.environ.get("NVRX_EPISODE_DETECTION", "0") not in ("", "0")
+        if score_history is None:
+            try:
+                score_history = int(os.environ.get("NVRX_SCORE_HISTORY", "0") or 0)
+            except ValueError:
+                raise ValueError("NVRX_SCORE_HISTORY must be an integer: 0 (off) or 2..64 reports") from None
+        if persistence_min_reports is None:
+            from_env = os.environ.get("NVRX_PERSISTENCE_MIN_REPORTS", "")
+            if from_env:
+                try:
+                    persistence_min_reports = int(from_env)
+                except ValueError:
+                    raise ValueError("NVRX_PERSISTENCE_MIN_REPORTS must be an integer within [1, NVRX_SCORE_HISTORY]") from None
+            else:
+                persistence_min_reports = 3
+                if score_history == 2:
+                    persistence_min_reports = 2  # (a history of two reports cannot hold a streak of three)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -521,7 +551,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        onset_min_segment=onset_min_segment, onset_min_strength=onset_min_strength,
                                        period_detection=period_detection, period_max=period_max,
                                        period_min_strength=period_min_strength, episode_detection=episode_detection,
-                                       episode_min_length=episode_min_length, episode_min_strength=episode_min_strength)
+                                       episode_min_length=episode_min_length, episode_min_strength=episode_min_strength,
+                                       score_history=score_history, persistence_min_reports=persistence_min_reports,
+                                       persistence_thresholds=persistence_thresholds)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
