@@ -56,6 +56,12 @@ rank 2 is 1.6x slower in report 6 only and rank 5 is 1.45x slower from report 10
 (``ReportGenerator(score_history=8, persistence_min_reports=3)``), and prints per report whom ``identify_stragglers`` flags and
 whom ``identify_persistent_stragglers`` does: rank 2 once and never persistently, rank 5 from report 10 and, persistently,
 from report 12 on.
+
+``--trend`` needs no training loop either: it plays 48 reports of a job of 8 ranks (folded onto one GPU, 1 % noise, seed 23) in
+which rank 5 gets 1.2 % slower with every report from report 8 on and rank 2 is 1.4x slower in report 14 only, with a score
+history of 16 reports and score trends (``ReportGenerator(score_history=16, persistence_min_reports=3, score_trends=True)``),
+and prints per report whom ``identify_declining_stragglers`` names next to the two rules above, with rank 5's slope, level and
+``reports_left``; at the end, the first report at which each rule named rank 5.
 """
 import argparse
 import os
@@ -250,6 +256,43 @@ def persist(reports: int = 20, ranks: int = 8, sections: int = 4, samples: int =
         job.close()
 
 
+def trend(reports: int = 48, ranks: int = 8, sections: int = 4, samples: int = 33) -> None:
+    """A rank that loses a percent per report against one bad window: what the score trends say, and when."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=64, scores_to_compute=("relative_perf_scores",),
+                    score_history=16, persistence_min_reports=3, score_trends=True)
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    first = {}
+    try:
+        for i in range(reports):
+            x = 1000.0 * (1.0 + 0.01 * np.random.default_rng([23, i]).standard_normal((ranks, sections, samples)))
+            x[5] *= 1.0 + 0.012 * max(0, i - 8)
+            if i == 14:
+                x[2] *= 1.4
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, x[r].astype(np.float32))
+            report = job.report()
+            rules = {"declining": named(report.identify_declining_stragglers()), "flagged": named(report.identify_stragglers()),
+                     "persistent": named(report.identify_persistent_stragglers())}
+            for rule, ranks_named in rules.items():
+                if 5 in ranks_named:
+                    first.setdefault(rule, i)
+            rec = report.score_trends()["section_relative"][job.section_names[0]][5]
+            print(f"report {i:2d}: declining {rules['declining']}, flagged {rules['flagged']}, for 3 reports in a row "
+                  f"{rules['persistent']}; rank 5 on {job.section_names[0]}: slope {rec['slope']:+.4f} per report, level "
+                  f"{rec['level']:.3f}, tau {rec['tau']:+.2f}, reports_left {rec['reports_left']}")
+        print("rank 5 first named: " + ", ".join(f"{rule} at report {first.get(rule)}" for rule in ("declining", "flagged", "persistent")))
+    finally:
+        job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -268,9 +311,15 @@ def main() -> None:
     ap.add_argument("--simulated-cycles", type=float, default=3e6, help="--slow-by simulated: spin cycles of the stand-in kernel")
     ap.add_argument("--persist", action="store_true",
                     help="no training: play the score-history scenario (one slow window against a rank that stays slow) and exit")
+    ap.add_argument("--trend", action="store_true",
+                    help="no training: play the score-trend scenario (a rank that loses a percent per report against one bad "
+                         "window) and exit")
     args = ap.parse_args()
     if args.persist:
         persist()
+        return
+    if args.trend:
+        trend()
         return
     if "RANK" in os.environ or args.num_processes == 1:
         train(args)

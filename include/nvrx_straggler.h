@@ -373,6 +373,36 @@ int nvrx_robust_score(const float *d_table, int R, int K, int S, int first_rank,
 int nvrx_score_history(const float *d_scores, int R, int S, int first_rank, int n_ranks, float *d_hist, int S_cap, int H,
                        uint64_t n_before, const double *thresholds, void *d_out, void *stream);
 
+/* Score trends: whether each score of the history ring is FALLING from report to report.  The history above says for how many
+ * reports a score has been below its threshold; a rank that loses a percent per report is invisible to it until it has
+ * crossed.  One step per report reads the ring nvrx_score_history keeps -- it writes nothing to it and needs no score rows --
+ * and leaves a robust, exact trend estimate per (rank r, family f, slot j) with j <= S (slots j > S are left alone).
+ *   d_hist, n_ranks, S, S_cap, H  the ring as nvrx_score_history left it (Hs = NVRX_HISTORY_STRIDE(H));
+ *   n_reports  reports appended so far, the latest included (the step's n_before + 1); at least 1.
+ * Per cell:
+ *   entries  depth = min(n_reports, H); x_a, a in [0, depth), is the entry of AGE a, at position (n_reports - 1 - a) mod H.
+ *            An entry is USABLE iff it is finite: NaN (absent) and +-inf are not.  p = number of usable entries;
+ *   pair slopes  for every pair of usable ages a < b (a the newer entry)
+ *            s_ab = (float)(((double)x_a - (double)x_b) / (double)(b - a)): the change per report, negative when the score
+ *            falls; N = p (p - 1) / 2 of them;
+ *   slope    the pair slope of rank (N - 1) >> 1 of the N pair slopes sorted by raw bit pattern (-inf < ... < -0.0 < +0.0 < ...
+ *            < +inf): the LOWER median of the Theil-Sen estimator, always an actual pair slope; NaN (0x7FC00000) when p < 2;
+ *   S        (i32) pairs with x_a > x_b minus pairs with x_a < x_b, as floats compare (-0.0 == +0.0): the Mann-Kendall
+ *            statistic, negative when the score falls; tau = S / N is the host's to derive;
+ *   level    the trend line's value at the newest report: the lower median, in the same order, of
+ *            v_a = (float)((double)x_a + (double)slope * (double)a) over the usable ages (the product is exact in f64, so a
+ *            fused multiply-add gives the same bits); the one usable entry when p == 1; NaN (0x7FC00000) when p == 0.  A v_a
+ *            that is a NaN -- possible only where the slope is infinite, entries more than FLT_MAX apart -- counts as
+ *            0x7FC00000 and orders behind +inf;
+ *   record, 16 bytes: {f32 slope, f32 level, i32 S, u32 usable = p}.  Every word is exact: one correctly rounded f64
+ *            operation and one conversion per value, no sum.
+ *   d_out  16-byte aligned, NVRX_TREND_WORDS(n_ranks, S) 32-bit words: [n_ranks][2][1 + S][4].
+ * One launch, behind the history step on its stream; it only reads the ring.  Errors as nvrx_score_history's (H, S_cap, the
+ * launch's size: NVRX_ERR_RANGE; pointers, S > S_cap, n_ranks < 1: NVRX_ERR_INVALID), and NVRX_ERR_INVALID for n_reports == 0
+ * -- reported before any device is touched. */
+#define NVRX_TREND_WORDS(n_ranks, S) ((size_t)(n_ranks) * 2 * (1 + (size_t)(S)) * 4)
+int nvrx_score_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -592,6 +622,11 @@ int nvrx_report_robust(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_ra
  * was issued through this descriptor. */
 int nvrx_report_history(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, float *d_hist, int S_cap,
                         int H, uint64_t n_before, const double *thresholds, void *d_out);
+/* nvrx_score_trend (above) on the context's stream -- the stream nvrx_report_history launched on.  The ring's only writers
+ * are history steps on that stream, so the launch is ordered behind the step it follows without an event.  The host does not
+ * wait; copy d_out with a D2H on the context's stream. */
+int nvrx_report_trend(nvrx_ctx *ctx, const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports,
+                      void *d_out);
 /* One report WINDOW in one call: what straggler.py:228-244 does around the report in the steady state -- wait for the
  * window's GPU measurements (torch.cuda.synchronize() + the profiler's get_stats there; here the kernel tracer's sync, or a
  * harvest of the region events), check that the set of rows holding samples is the one the caller's name tables were built

@@ -3954,5 +3954,6 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_onset.inl"
 #include "nvrx_robust.inl"
 #include "nvrx_history.inl"
+#include "nvrx_trend.inl"
 #include "nvrx_period.inl"
 #include "nvrx_episode.inl"

@@ -47,6 +47,7 @@ class StragglerDetectionCallback(Callback):
         profiling_interval: int = 1,
         logger_name: Optional[str] = "nemo_logger.StragglerDetectionCallback",
         min_consecutive_reports: int = 1,
+        warn_if_declining: bool = False,
     ):
         """
         Args:
@@ -64,6 +65,10 @@ class StragglerDetectionCallback(Callback):
                 been below the threshold in M reports in a row (``Report.identify_persistent_stragglers``; the detector
                 then keeps a score history of ``max(8, M)`` reports): one slow window -- a neighbour's checkpoint, a
                 page-cache flush -- no longer ends a healthy job.  Every report's scores are printed and logged as before.
+            warn_if_declining: False (the default): nothing changes.  True: the detector keeps a score history of at least 8
+                reports with score trends (``Detector.initialize(score_trends=True)``), and every report that finds a GPU
+                whose score is falling towards its threshold (``Report.identify_declining_stragglers``) logs one warning
+                that names the ranks and the reports left until they cross it.  A warning only: it never stops the job.
 
         Raises:
             ValueError: neither score family requested, or ``min_consecutive_reports`` outside [1, 64].
@@ -93,6 +98,7 @@ class StragglerDetectionCallback(Callback):
                 or not 1 <= min_consecutive_reports <= 64):
             raise ValueError(f"min_consecutive_reports must be an integer within [1, 64], got {min_consecutive_reports!r}")
         self.min_consecutive_reports = min_consecutive_reports
+        self.warn_if_declining = bool(warn_if_declining)
         self.interval_est_was_reset = False
 
     # ---- Lightning hooks -----------------------------------------------------------------------
@@ -105,6 +111,11 @@ class StragglerDetectionCallback(Callback):
             persistence = dict(score_history=max(8, m), persistence_min_reports=m,
                                persistence_thresholds=(self.gpu_relative_perf_threshold, 0.75,
                                                        self.gpu_individual_perf_threshold, 0.75))
+        if self.warn_if_declining:
+            persistence.setdefault("score_history", 8)
+            persistence.setdefault("persistence_thresholds", (self.gpu_relative_perf_threshold, 0.75,
+                                                              self.gpu_individual_perf_threshold, 0.75))
+            persistence["score_trends"] = True
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -129,6 +140,8 @@ class StragglerDetectionCallback(Callback):
         report = detector.generate_report_if_interval_elapsed()
         # gather_on_rank0: rank 0 alone holds the report and decides; the decision reaches the others below
         found = bool(report) and trainer.global_rank == 0 and self._digest(pl_module, report)
+        if self.warn_if_declining and bool(report) and trainer.global_rank == 0:
+            self._warn_declining(report)  # (a warning only: `found`, and with it the halt, does not depend on it)
         if not detector.is_interval_elapsed():
             return  # no report was due this iteration
         if self.stop_if_detected and self._decision_of_rank0(found):
@@ -172,6 +185,22 @@ class StragglerDetectionCallback(Callback):
             for _, field, _, _, prefix, _ in enabled:
                 self._log_extremes(pl_module, getattr(report, field), prefix)
         return bool(hits)
+
+    def _warn_declining(self, report) -> None:
+        """One warning per report that names the GPUs whose score is falling towards its threshold, with the reports left
+        until the trend line crosses it (``warn_if_declining``).  Never a reason to halt."""
+        declining = report.identify_declining_stragglers()
+        trends = report.score_trends()
+        parts = []
+        for family, key, table in (("relative", "straggler_gpus_relative", "gpu_relative"),
+                                   ("individual", "straggler_gpus_individual", "gpu_individual")):
+            per_rank = trends.get(table, {})
+            for rank in sorted(getattr(s, "rank", s) for s in declining[key]):
+                rec = per_rank[rank]
+                parts.append(f"rank {rank} {family} GPU score falls {-rec['slope']:.4f} per report "
+                             f"(level {rec['level']:.3f}, reports_left={rec['reports_left']})")
+        if parts:
+            self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs are getting slower: " + "; ".join(parts))
 
     def _name_the_kernels(self, report, flagged) -> None:
         """Kernel attribution (``NVRX_KERNEL_ATTRIBUTION=N``, off by default: nothing is logged then): for every flagged GPU the

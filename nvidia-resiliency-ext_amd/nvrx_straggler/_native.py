@@ -42,6 +42,7 @@ EPISODE_MIN_SAMPLES = 8  # ... and the length's floor in samples
 EPISODE_PLANES = 7  # NVRX_EPISODE_PLANES: {e, inside, outside, strength, length, ago, n} per kernel id and section id
 HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
 HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
+TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, family, slot)
 
 
 
@@ -93,6 +94,7 @@ SYMBOLS = [
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
+    ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -134,6 +136,7 @@ SYMBOLS = [
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
+    ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
     ("nvrx_peer_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -243,6 +246,11 @@ def history_floats(n_ranks: int, S_cap: int, H: int) -> int:
 def history_words(n_ranks: int, S: int) -> int:
     """NVRX_HISTORY_WORDS: 32-bit words of a history step's records ``[n_ranks][2][1 + S][8]``."""
     return n_ranks * 2 * (1 + S) * HISTORY_RECORD_WORDS
+
+
+def trend_words(n_ranks: int, S: int) -> int:
+    """NVRX_TREND_WORDS: 32-bit words of a trend step's records ``[n_ranks][2][1 + S][4]``."""
+    return n_ranks * 2 * (1 + S) * TREND_RECORD_WORDS
 
 
 def tail_q_ppm(q) -> int:

@@ -362,6 +362,32 @@ class History:
         return self._host
 
 
+class Trend:
+    """The score trends after one report (``nvrx_score_trend`` / ``nvrx_report_trend``), enqueued and not waited for: once the
+    kernel has run, the workspace's device buffer holds ``[n_ranks][2][1 + S][4]`` 32-bit words ``{slope, level, S, usable}``
+    (include/nvrx_straggler.h).  ``records()`` waits for it and takes the private host copy (one ordered D2H on the backend's
+    stream): when a ``Report`` first asks, or -- ``Workspace.trend_settle`` -- before the next trend step on the same
+    workspace rewrites the buffer."""
+
+    __slots__ = ("backend", "d_ptr", "S", "n_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, S: int, n_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.S, self.n_ranks = S, n_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self) -> np.ndarray:
+        """``[n_ranks, 2, 1 + S, 4]`` uint32 (private copy); the first call waits for the kernel."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.trend_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -541,6 +567,8 @@ class Workspace:
                 self.family_settle(fam)
         if self._history_last is not None:
             self.history_settle()
+        if self._trend_last is not None:
+            self.trend_settle()
 
     # ---- robust scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
     _robust_buf = None   # device: column records, then the scores of the last robust step of this workspace's table
@@ -578,6 +606,25 @@ class Workspace:
         run and its records are on the host (a ``Report`` still alive keeps them; an unread one costs this one small
         copy)."""
         last, self._history_last = self._history_last, None
+        if last is not None:
+            last.records()
+
+    # ---- score trends (off unless a ReportGenerator asks: nothing is allocated before) ----------------------------
+    _trend_buf = None   # device: the records of the last trend step issued through this workspace
+    _trend_last = None  # the Trend whose kernel may still be writing _trend_buf
+
+    def trend_buffers(self, n_ranks: int):
+        """The records buffer for a trend step over ``n_ranks`` ranks (cold: allocated once per shape)."""
+        words = _native.trend_words(n_ranks, self.S)
+        if self._trend_buf is None or self._trend_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._trend_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return self._trend_buf
+
+    def trend_settle(self) -> None:
+        """Before anything rewrites the trend records buffer: the last trend step's kernel has run and its records are on
+        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._trend_last = self._trend_last, None
         if last is not None:
             last.records()
 
@@ -859,6 +906,26 @@ class HipBackend:
         """The one wait of a report's score history: a D2H of the records on the backend's stream, behind the kernel."""
         host = np.empty((h.n_ranks, 2, 1 + h.S, _native.HISTORY_RECORD_WORDS), dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, h.d_ptr, host.nbytes, self._stream_handle))
+        return host
+
+    def score_trend(self, ws: Workspace, state: ScoreHistory) -> Trend:
+        """The trends of ``state``'s ring as the history step just issued on ``ws`` leaves it (``score_history``;
+        ``state.n_before`` counts that report): ``nvrx_score_trend`` enqueued on the backend's stream behind that step.
+        Nothing is waited for."""
+        ws.trend_settle()
+        n_ranks = state.ranks[1]
+        buf = ws.trend_buffers(n_ranks)
+        rc = self.lib.nvrx_score_trend(state.hist.data_ptr(), n_ranks, ws.S, state.S_cap, state.depth, state.n_before,
+                                       buf.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._trend_last = Trend(self, buf, ws.S, n_ranks)
+        return out
+
+    def trend_copy_out(self, t: Trend) -> np.ndarray:
+        """The one wait of a report's score trends: a D2H of the records on the backend's stream, behind the kernel."""
+        host = np.empty((t.n_ranks, 2, 1 + t.S, _native.TREND_RECORD_WORDS), dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, host.nbytes, self._stream_handle))
         return host
 
     def row_quantile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm: int) -> torch.Tensor:
@@ -1189,6 +1256,20 @@ class HipRings:
             _native.check(rc)
         state.n_before += 1
         out = ws._history_last = History(be, buf, ws.S, first_rank, n_ranks)
+        return out
+
+    def report_trend(self, ws: Workspace, state: ScoreHistory) -> Trend:
+        """The trends of ``state``'s ring as ``report_history`` just left it (``nvrx_report_trend``): enqueued on the
+        context's stream behind that step, nothing is waited for."""
+        be = self.backend
+        ws.trend_settle()
+        n_ranks = state.ranks[1]
+        buf = ws.trend_buffers(n_ranks)
+        rc = self.lib.nvrx_report_trend(self.ctx, state.hist.data_ptr(), n_ranks, ws.S, state.S_cap, state.depth,
+                                        state.n_before, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._trend_last = Trend(be, buf, ws.S, n_ranks)
         return out
 
     def _family_local(self, fam: RowFamily, ws: Workspace, params: tuple, rows_active: int, fused: bool):

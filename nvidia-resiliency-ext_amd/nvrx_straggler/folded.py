@@ -28,7 +28,8 @@ class FoldedJob:
                  onset_detection: bool = False, onset_min_segment: float = 0.05, onset_min_strength: float = 0.5,
                  period_detection: bool = False, period_max: int = 1024, period_min_strength: float = 0.5,
                  episode_detection: bool = False, episode_min_length: float = 0.005, episode_min_strength: float = 0.5,
-                 score_history: int = 0, persistence_min_reports: int = 3, persistence_thresholds=None):
+                 score_history: int = 0, persistence_min_reports: int = 3, persistence_thresholds=None,
+                 score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6, trend_horizon=None):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -48,7 +49,9 @@ class FoldedJob:
                                         episode_detection=episode_detection, episode_min_length=episode_min_length,
                                         episode_min_strength=episode_min_strength, score_history=score_history,
                                         persistence_min_reports=persistence_min_reports,
-                                        persistence_thresholds=persistence_thresholds)
+                                        persistence_thresholds=persistence_thresholds, score_trends=score_trends,
+                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
+                                        trend_horizon=trend_horizon)
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         self._no_kernel_rows = {}  # same object every report so the reporter's cached plan stays valid
 

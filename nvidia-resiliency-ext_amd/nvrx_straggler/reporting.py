@@ -24,6 +24,7 @@ import collections
 import dataclasses
 import itertools
 import logging
+import math
 import os
 import threading
 import time
@@ -758,6 +759,62 @@ class _HistorySource:
         return self._built
 
 
+class _TrendSource:
+    """What a report keeps of the score trends as they stood after that report: the backend's handle (``records()`` waits for
+    the kernel and copies the records out on first use), the ranks its rows stand for, the sections it shows with their ids,
+    which families were computed, and the generator's depth, thresholds and rules."""
+
+    __slots__ = ("handle", "ranks", "sections", "has_rel", "has_indiv", "depth", "min_reports", "min_tau", "horizon",
+                 "thresholds", "_built")
+
+    def __init__(self, handle, ranks, sections, has_rel: bool, has_indiv: bool, depth: int, min_reports: int, min_tau: float,
+                 horizon: int, thresholds):
+        self.handle, self.ranks = handle, tuple(ranks)
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self.has_rel, self.has_indiv = has_rel, has_indiv
+        self.depth, self.min_reports, self.min_tau, self.horizon = depth, min_reports, min_tau, horizon
+        self.thresholds = tuple(thresholds)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            rec = np.ascontiguousarray(self.handle.records(), dtype=np.uint32)
+            f32 = rec.view(np.float32)[..., :2].tolist()
+            mk = rec.view(np.int32)[..., 2].tolist()
+            usable = rec[..., 3].tolist()
+            ranks, min_reports, min_tau = self.ranks, self.min_reports, self.min_tau
+
+            def record(i, fam, j, thr):
+                (slope, level), s, p = f32[i][fam][j], mk[i][fam][j], usable[i][fam][j]
+                pairs = p * (p - 1) // 2
+                tau = s / pairs if pairs else 0.0
+                falling = p >= min_reports and slope < 0 and tau <= -min_tau
+                if level < thr:
+                    left = 0
+                elif falling:
+                    q = (level - thr) / -slope
+                    left = math.ceil(q) if math.isfinite(q) else None  # (a level beyond f32's range crosses nothing)
+                else:
+                    left = None
+                return {"slope": slope, "level": level, "tau": tau, "usable": p, "falling": falling, "reports_left": left}
+
+            built: Dict[str, Any] = {"depth": self.depth, "min_reports": min_reports, "min_tau": min_tau,
+                                     "horizon": self.horizon, "thresholds": self.thresholds}
+            g_rel, s_rel, g_ind, s_ind = self.thresholds
+            for fam, name in _HISTORY_FAMILIES:
+                if self.has_rel if fam else self.has_indiv:
+                    thr = g_rel if fam else g_ind
+                    built["gpu_" + name] = {r: record(i, fam, 0, thr) for i, r in enumerate(ranks)}
+            for fam, name in _HISTORY_FAMILIES:
+                if self.has_rel if fam else self.has_indiv:
+                    thr = s_rel if fam else s_ind
+                    built["section_" + name] = {n: {r: record(i, fam, 1 + g, thr) for i, r in enumerate(ranks)}
+                                                for n, g in self.sections.items()}
+            self._built = built
+            self.handle = None
+        return self._built
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -853,6 +910,9 @@ class Report:
         history = self.__dict__.get("_history")
         if history is not None:
             state["_history"] = history.build() if isinstance(history, _HistorySource) else history
+        trends = self.__dict__.get("_trends")
+        if trends is not None:
+            state["_trends"] = trends.build() if isinstance(trends, _TrendSource) else trends
         for fam in row_families.FAMILIES:
             scores = self.__dict__.get(fam.slot)
             if scores is not None:
@@ -1042,6 +1102,55 @@ class Report:
                 "straggler_sections_relative": sections("section_relative"),
                 "straggler_sections_individual": sections("section_individual")}
 
+    def score_trends(self) -> Dict[str, Any]:
+        """Whether each score is FALLING from report to report, as the score history stood after this report
+        (``ReportGenerator(score_history=H, score_trends=True)``; ``{}`` when the report carries none).  The history says for
+        how many reports a score has been below its threshold; this says that a score is on its way there, and when it
+        arrives.
+
+        ``{"depth": reports the history holds (at most H), "min_reports", "min_tau", "horizon", "thresholds": (gpu_rel,
+        section_rel, gpu_indiv, section_indiv), "gpu_relative": {rank: rec}, "gpu_individual": {rank: rec},
+        "section_relative": {section: {rank: rec}}, "section_individual": {...}}`` with ``rec = {"slope": the Theil-Sen slope
+        -- the lower median of the slopes of all pairs of usable (finite) scores, the change per report, negative when the
+        score falls; NaN with fewer than two --, "level": the trend line's value at this report, "tau": Kendall's tau, the
+        Mann-Kendall statistic over the number of pairs, in [-1, 1] (0.0 without a pair), "usable": scores the estimate rests
+        on, "falling": usable >= min_reports and slope < 0 and tau <= -min_tau, "reports_left": 0 where the level is already
+        below the threshold, else -- when falling -- the reports until the trend line crosses it,
+        ceil((level - threshold) / -slope), else None}``.  One bad window barely moves slope or level: both are medians.
+        Families that were not computed are left out; ranks and sections as in the score mappings.  Plain dicts, floats, ints
+        and bools.  The first call waits for the trend kernel and copies its records; ``generate_report`` does not."""
+        trends = self.__dict__.get("_trends")
+        if trends is None:
+            return {}
+        if isinstance(trends, _TrendSource):
+            trends = self.__dict__["_trends"] = trends.build()
+        return _copy_scores(trends)
+
+    def identify_declining_stragglers(self, horizon: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks whose score is falling and whose trend line crosses the threshold within ``horizon`` reports (default: the
+        generator's ``trend_horizon``) -- ``falling`` and ``reports_left <= horizon`` in ``score_trends()``: the four keys of
+        ``identify_stragglers``, ``StragglerId`` sets; a section appears only if somebody is flagged for it.  A warning, ahead
+        of ``identify_stragglers``: a rank named here may still be above its threshold.  Empty sets when the report carries
+        no score trends."""
+        t = self.score_trends()
+        h = t.get("horizon", 0) if horizon is None else horizon
+        if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < 0:
+            raise ValueError(f"horizon must be an integer >= 0, got {horizon!r}")
+
+        def hit(rec):
+            return rec["falling"] and rec["reports_left"] is not None and rec["reports_left"] <= h
+
+        def gpus(key):
+            return self._ids([r for r, rec in t.get(key, {}).items() if hit(rec)])
+
+        def sections(key):
+            flagged = {n: [r for r, rec in v.items() if hit(rec)] for n, v in t.get(key, {}).items()}
+            return {n: self._ids(r) for n, r in flagged.items() if r}
+
+        return {"straggler_gpus_relative": gpus("gpu_relative"), "straggler_gpus_individual": gpus("gpu_individual"),
+                "straggler_sections_relative": sections("section_relative"),
+                "straggler_sections_individual": sections("section_individual")}
+
     def _family_scores(self, name: str) -> Dict[str, Any]:
         """A private copy of one row family's scores (built from the device's planes on first use); ``{}`` without them."""
         fam = row_families.BY_NAME[name]
@@ -1217,7 +1326,9 @@ class ReportGenerator:
                  onset_min_segment: float = 0.05, onset_min_strength: float = 0.5, period_detection: bool = False,
                  period_max: int = 1024, period_min_strength: float = 0.5, episode_detection: bool = False,
                  episode_min_length: float = 0.005, episode_min_strength: float = 0.5, score_history: int = 0,
-                 persistence_min_reports: int = 3, persistence_thresholds: Optional[Sequence[float]] = None) -> None:
+                 persistence_min_reports: int = 3, persistence_thresholds: Optional[Sequence[float]] = None,
+                 score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6,
+                 trend_horizon: Optional[int] = None) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1393,6 +1504,34 @@ class ReportGenerator:
                                    "has no score history (backend.score_history)")
             self.persistence_min_reports, self.persistence_thresholds = int(m), thr
             self._history = _backend_mod.ScoreHistory(self.score_history)
+        # score trends: behind the history step, every report also estimates per rank and score whether the ring's scores are
+        # falling (Report.score_trends, Report.identify_declining_stragglers); off: no buffer, no launch, no backend call.  It
+        # reads the history ring only: no collective.  min_reports 6, min_tau 0.6 and the horizon H are defaults, not
+        # measurements.
+        self.score_trends = bool(score_trends)
+        if self.score_trends:
+            if self.score_history < 4:
+                raise ValueError(f"score_trends needs a score history of at least 4 reports (score_history within [4, "
+                                 f"{_backend_mod._native.HISTORY_MAX_DEPTH}]), got score_history={self.score_history!r}")
+            m = trend_min_reports
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 4 <= m <= self.score_history:
+                raise ValueError(f"trend_min_reports must be an integer within [4, score_history={self.score_history}], "
+                                 f"got {trend_min_reports!r}")
+            try:
+                tau = float(trend_min_tau)
+            except (TypeError, ValueError):
+                tau = float("nan")
+            if isinstance(trend_min_tau, bool) or not 0.0 < tau <= 1.0:
+                raise ValueError(f"trend_min_tau must be a number within (0, 1], got {trend_min_tau!r}")
+            hz = self.score_history if trend_horizon is None else trend_horizon
+            if isinstance(hz, bool) or not isinstance(hz, (int, np.integer)) or hz < 0:
+                raise ValueError(f"trend_horizon must be None (the history's depth) or an integer >= 0 reports, "
+                                 f"got {trend_horizon!r}")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "score_trend"):
+                raise RuntimeError(f"score_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no score trends (backend.score_trend)")
+            self.trend_min_reports, self.trend_min_tau, self.trend_horizon = int(m), tau, int(hz)
         # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
         # any, that needs the ring-start snapshot
         self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
@@ -1642,6 +1781,9 @@ class ReportGenerator:
             # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
             self._attach_history(report, _backend_mod.get_backend().score_history(
                 ws, self._history, lo, hi - lo, self.persistence_thresholds), view)
+            if self.score_trends:
+                # ... and the trends of the ring as that step leaves it, behind it
+                self._attach_trends(report, _backend_mod.get_backend().score_trend(ws, self._history), view)
         if stats is None:
             # the caller's own summaries travel with the report, untouched
             report.__dict__["local_section_summaries"] = section_summaries
@@ -1789,6 +1931,8 @@ class ReportGenerator:
             raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
         if fused and self._history is not None and not hasattr(rings, "report_history"):
             raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
+        if fused and self.score_trends and not hasattr(rings, "report_trend"):
+            raise RuntimeError("score_trends: these rings run the one-call report but have no report_trend")
         if fused:
             # ONE C call: flush -> statistics kernel -> [ncclAllGather] -> score kernel -> completion word
             wait = not self.asynchronous
@@ -1902,6 +2046,18 @@ class ReportGenerator:
         else:
             handle = _backend_mod.get_backend().score_history(ws, self._history, lo, hi - lo, self.persistence_thresholds)
         self._attach_history(report, handle, plan.view)
+        if self.score_trends:
+            if fused:
+                handle = rings.report_trend(ws, self._history)
+            else:
+                handle = _backend_mod.get_backend().score_trend(ws, self._history)
+            self._attach_trends(report, handle, plan.view)
+
+    def _attach_trends(self, report, handle, view) -> None:
+        report.__dict__["_trends"] = _TrendSource(handle, view.ranks, view.cols, self.is_computing_rel_scores,
+                                                  self.is_computing_indiv_scores, min(self._history.n_before, self.score_history),
+                                                  self.trend_min_reports, self.trend_min_tau, self.trend_horizon,
+                                                  self.persistence_thresholds)
 
     def reset_score_history(self) -> None:
         """Forget the score history: the next report starts a new one (after a restart from a checkpoint, a change of the

@@ -400,6 +400,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
         score_history: Optional[int] = None,
         persistence_min_reports: Optional[int] = None,
         persistence_thresholds: Optional[Sequence[float]] = None,
+        score_trends: Optional[bool] = None,
+        trend_min_reports: Optional[int] = None,
+        trend_min_tau: float = 0.6,
+        trend_horizon: Optional[int] = None,
     ):
         """
         Args:
@@ -478,6 +482,16 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 ``NVRX_PERSISTENCE_MIN_REPORTS``, else 3 (never more than ``score_history``).
             persistence_thresholds: (gpu_rel, section_rel, gpu_indiv, section_indiv) a score has to be below; default: 0.75
                 each, the thresholds the reports' own flags are computed for.
+            score_trends: behind the history step, every report also estimates per rank and score whether the history's scores
+                are FALLING from report to report -- the Theil-Sen slope, the trend line's level and Kendall's tau
+                (``Report.score_trends()``) -- and ``Report.identify_declining_stragglers()`` names the ranks that will cross
+                their threshold within ``trend_horizon`` reports, before any other rule flags them.  Needs ``score_history``
+                >= 4.  Default: ``NVRX_SCORE_TRENDS`` (set and not "0"), else off.
+            trend_min_reports: usable reports a trend needs, within [4, score_history].  Default: 6, or ``score_history`` where
+                that is less.
+            trend_min_tau: a score is falling when Kendall's tau is at most minus this, within (0, 1].
+            trend_horizon: reports ahead that ``identify_declining_stragglers`` looks; None = ``score_history``.  6, 0.6 and
+                that horizon are defaults, not measurements.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -544,6 +558,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 persistence_min_reports = 3
                 if score_history == 2:
                     persistence_min_reports = 2  # (a history of two reports cannot hold a streak of three)
+        if score_trends is None:
+            score_trends = os.environ.get("NVRX_SCORE_TRENDS", "0") not in ("", "0")
+        if trend_min_reports is None:
+            trend_min_reports = 6
+            if isinstance(score_history, int) and 4 <= score_history < 6:
+                trend_min_reports = score_history  # (a history of four reports cannot hold six)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -553,7 +573,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        period_min_strength=period_min_strength, episode_detection=episode_detection,
                                        episode_min_length=episode_min_length, episode_min_strength=episode_min_strength,
                                        score_history=score_history, persistence_min_reports=persistence_min_reports,
-                                       persistence_thresholds=persistence_thresholds)
+                                       persistence_thresholds=persistence_thresholds, score_trends=score_trends,
+                                       trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
+                                       trend_horizon=trend_horizon)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
