@@ -62,6 +62,12 @@ which rank 5 gets 1.2 % slower with every report from report 8 on and rank 2 is 
 history of 16 reports and score trends (``ReportGenerator(score_history=16, persistence_min_reports=3, score_trends=True)``),
 and prints per report whom ``identify_declining_stragglers`` names next to the two rules above, with rank 5's slope, level and
 ``reports_left``; at the end, the first report at which each rule named rank 5.
+
+``--slack`` needs no training loop either: it plays one report window of a job of 8 ranks (folded onto one GPU, seed 17) that
+runs 200 steps of one compute kernel (1000 us) and one all-reduce (200 us +- 2 % of transfer; the ranks arrive with an
+exponential skew of 20 us) in which rank 5's HOST is slow: it arrives 300 us late at every collective.  Its kernels take the
+usual time and the step lasts as long on every rank, so ``identify_stragglers`` names nobody; with slack scores
+(``ReportGenerator(collective_slack=True)``) ``identify_slack_stragglers`` names rank 5, and the report says what it costs.
 """
 import argparse
 import os
@@ -293,6 +299,44 @@ def trend(reports: int = 48, ranks: int = 8, sections: int = 4, samples: int = 3
         job.close()
 
 
+def slack(ranks: int = 8, calls: int = 200, late_rank: int = 5, late_us: float = 300.0) -> None:
+    """A rank whose host is slow: every score reads 1, the slack scores name it and say what the job loses."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    gemm, allreduce = "gemm_kernel<bf16>", "ncclDevKernel_AllReduce_Sum_bf16_RING_LL(ncclDevKernelArgsStorage<4096ul>)"
+    job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                    collective_slack=True, kernel_names=[gemm, allreduce])
+    rng = np.random.default_rng(17)
+    transfer = 200.0 * (1.0 + 0.02 * rng.standard_normal(calls))
+    arrival = rng.exponential(20.0, (ranks, calls))
+    arrival[late_rank] += late_us
+    last = arrival.max(0)
+    in_collective = transfer[None, :] + last[None, :] - arrival  # a rank waits for the last one, then the transfer runs
+    step = 1000.0 + transfer + last                              # the step ends with the collective: the same everywhere
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, step[None, :].astype(np.float32))
+            job.load_kernels(lr, np.stack([np.full(calls, 1000.0), in_collective[r]]).astype(np.float32))
+        report = job.report()
+        s = report.slack_scores()
+        print(f"identify_stragglers(): {named(report.identify_stragglers())}; lowest relative GPU score "
+              f"{min(report.gpu_relative_perf_scores.values()):.3f}")
+        print(f"identify_slack_stragglers(): {named(report.identify_slack_stragglers())}; the typical rank waits "
+              f"{s['typical_waited_us']:.0f} us per window, {100 * s['typical_share']:.1f} % of its traced GPU time")
+        for r, rec in sorted(s["ranks"].items()):
+            print(f"  rank {r}: {rec['calls']} calls, in collectives {rec['collective_us']:.0f} us, waited {rec['waited_us']:.0f} us "
+                  f"(share {rec['share']:.3f}), the others wait {rec['lead_us']:.0f} us for it")
+    finally:
+        job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -314,7 +358,13 @@ def main() -> None:
     ap.add_argument("--trend", action="store_true",
                     help="no training: play the score-trend scenario (a rank that loses a percent per report against one bad "
                          "window) and exit")
+    ap.add_argument("--slack", action="store_true",
+                    help="no training: play the slack-score scenario (a rank whose host is slow arrives late at every "
+                         "collective) and exit")
     args = ap.parse_args()
+    if args.slack:
+        slack()
+        return
     if args.persist:
         persist()
         return

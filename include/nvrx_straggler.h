@@ -403,6 +403,47 @@ int nvrx_score_history(const float *d_scores, int R, int S, int first_rank, int 
 #define NVRX_TREND_WORDS(n_ranks, S) ((size_t)(n_ranks) * 2 * (1 + (size_t)(S)) * 4)
 int nvrx_score_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, void *d_out, void *stream);
 
+/* Slack scores: the rank the others WAIT FOR in collectives.  Every score above compares how long a rank's own work takes; a
+ * rank whose host is slow (a busy CPU, a data loader, a GC pause) launches late, computes at the usual speed and ends its
+ * sections in a collective like everybody else, so all of them read 1.  The time the ranks spend inside collective kernels
+ * shows it: the rank that arrives last spends only the transfer time there, every other rank that plus the wait for it.  The
+ * rank with the LEAST time in collectives is the one the job waits for, and what the others spend above that floor is what it
+ * costs.  A lockstep job (data parallel, FSDP) is the model.
+ *   columns  NVRX_SLACK_COLS = 64.  A collective key (a kernel row whose name is a collective kernel's) has the column
+ *            digest(key) % 64, the digest being the name mapper's (64-bit BLAKE2b, little-endian): every rank computes the same column from
+ *            the same key, nothing is agreed or exchanged; keys that collide share a column and their times add on every rank
+ *            alike.
+ * Local step (nvrx_slack_local, below), per logical rank q and column c over the (row, column) list in its order, which is
+ * ascending in the row, rows r >= rows_active left out:
+ *   a row counts iff NUM >= 1 in its statistics row (the statistics kernel writes NUM = 0 for an empty row);
+ *   t = sum of (double)WEIGHT_r (WEIGHT = NUM * AVG, NVRX_STAT_WEIGHT), n = sum of (double)NUM_r: one sequence of f64 additions;
+ *   send rows [local_ranks][2][64] f32: plane 0 (float)t, plane 1 (float)n; {-1, 0} for a column without a counting row.
+ * Score step (nvrx_slack_score) on the gathered d_slack [R][2][64] and the report's exchanged d_table [R][L] (nvrx_score):
+ *   present  rank r in column c iff n > 0 and t >= 0 (a NaN is absent); avg = (float)((double)t / (double)n), the mean per
+ *            call -- windows that differ by a call between ranks do not read as slack;
+ *   column   referenced iff at least min(min_ranks, R) ranks are present; floor = the minimum of avg over the present ranks;
+ *            record, 16 bytes: {f32 floor (NaN 0x7FC00000 where not referenced), u32 present, 0, 0}.  Exact;
+ *   rank     over the referenced columns it is present in, sums in f64: collective_us = sum t, waited_us = sum (double)n *
+ *            ((double)avg - (double)floor), calls = sum n, columns = their number; compute_us = the sum of the weights
+ *            w[r][k] of the kernel ids whose med entry is >= 0 (0 at K = 0; d_table may then be NULL); share = (float)(waited /
+ *            (collective + compute)) on the f64 sums: the share of this rank's traced GPU time spent waiting;
+ *            record, 32 bytes: {f32 collective_us, f32 waited_us, f32 compute_us, f32 share, u32 calls, u32 columns, 0, 0};
+ *            NaN in the four floats and 0 in the counts for a rank without a referenced column.  The sums are taken across a
+ *            wave: their last bits depend on that order;
+ *   job      record, 32 bytes: {f32 typical_waited, f32 typical_share, u32 ranks_with_data, u32 columns_referenced, 0, 0, 0,
+ *            0}: the LOWER medians (rank (m - 1) >> 1 in value order, always an actual value) of waited_us and of share over
+ *            the ranks with data (columns > 0) -- a value that is a NaN (inf - inf, 0 / 0) does not enter its median, m
+ *            counting the values that do --, NaN 0x7FC00000 when none enters.
+ *   d_out    16-byte aligned, NVRX_SLACK_WORDS(R) 32-bit words: job record | 64 column records | R rank records.  All R ranks
+ *            are always computed: the medians need them.
+ * Three small launches on `stream` (columns, ranks, job); no atomics, no scratch.  NVRX_ERR_INVALID: R <= 0, K or S negative,
+ * a null pointer, d_slack or d_out not 16-byte aligned; NVRX_ERR_RANGE: R above NVRX_ROBUST_MAX_RANKS, K or S above
+ * NVRX_MAX_ROWS, min_ranks < 1 -- reported before any device is touched.  4 ranks, and the 0.05 / 0.25 of the Python rule
+ * built on these records, are defaults, not measurements. */
+#define NVRX_SLACK_COLS 64
+#define NVRX_SLACK_WORDS(R) (8 + 4 * (size_t)NVRX_SLACK_COLS + 8 * (size_t)(R))
+int nvrx_slack_score(const float *d_slack, const float *d_table, int R, int K, int S, int min_ranks, void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -627,6 +668,19 @@ int nvrx_report_history(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_r
  * wait; copy d_out with a D2H on the context's stream. */
 int nvrx_report_trend(nvrx_ctx *ctx, const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports,
                       void *d_out);
+/* The local step of the slack scores (nvrx_slack_score, above) on the STATISTICS of the report last issued -- it reads the
+ * statistics rows, not the rings.  rows[i], cols[i], i < n: host arrays, the collective rows of a logical rank (row within the
+ * rank, the same for every logical rank) in ascending order with their columns; the library keeps the list in device memory
+ * and uploads it, on the step's stream, only when it differs from the one it holds.  d_send [local_ranks][2][64], 16-byte
+ * aligned; every slot is written.  desc != NULL: the report went through nvrx_report; the rows are desc->d_stats (the
+ * statistics kernel writes them there also when the score kernel ran resident; d_stats is ignored), and the kernel is enqueued
+ * on the context's stream behind that report's last kernel and behind its statistics kernel.  desc == NULL: the stepwise path,
+ * on `stream` with the d_stats nvrx_report_local wrote there.  rows_active as for nvrx_report_local.  The host does not wait
+ * -- but the caller must before the next report, which rewrites the statistics.  NVRX_ERR_INVALID: a null pointer, n outside
+ * [0, rows_per_rank], rows not ascending, rows_active out of range, d_send misaligned; NVRX_ERR_RANGE: a row outside [0,
+ * rows_per_rank) or a column outside [0, 64); NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_slack_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, const float *d_stats, const int32_t *rows, const int32_t *cols,
+                     int n, float *d_send, int rows_active, void *stream);
 /* One report WINDOW in one call: what straggler.py:228-244 does around the report in the steady state -- wait for the
  * window's GPU measurements (torch.cuda.synchronize() + the profiler's get_stats there; here the kernel tracer's sync, or a
  * harvest of the region events), check that the set of rows holding samples is the one the caller's name tables were built

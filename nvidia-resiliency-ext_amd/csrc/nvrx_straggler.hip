@@ -2093,6 +2093,14 @@ struct nvrx_ctx {
     uint32_t *h_onset_starts = nullptr;   // pinned [rows]
     uint32_t *d_onset_starts = nullptr;   // device [rows]
 
+    // slack scores (nvrx_slack_local, nvrx_slack.inl): the stream the last statistics kernel was enqueued on -- what a reader
+    // of its rows has to be ordered behind where that is neither its own stream nor the report's last kernel's -- and the
+    // (row, column) list of the collective rows as it stands in device memory, with the host's copy of it
+    hipStream_t stats_stream = nullptr;
+    int32_t *d_slack_list = nullptr;  // device [rows_per_rank][2], allocated with the first nvrx_slack_local
+    std::vector<int32_t> slack_list;  // {row, column} pairs as uploaded last
+    bool slack_list_up = false;
+
     std::mutex mu;
 };
 
@@ -2626,6 +2634,7 @@ int nvrx_ctx_destroy(nvrx_ctx *ctx) {
     if (ctx->attr_scratch) (void)hipFree(ctx->attr_scratch);
     if (ctx->h_onset_starts) (void)hipHostFree(ctx->h_onset_starts);
     if (ctx->d_onset_starts) (void)hipFree(ctx->d_onset_starts);
+    if (ctx->d_slack_list) (void)hipFree(ctx->d_slack_list);
     {
         // score scratch of the streams this context's reports ran on (its own, the resident scorer's, every user stream
         // a report was re-homed onto): the device is idle, nothing reads it any more
@@ -3290,6 +3299,7 @@ static int report_local_impl(nvrx_ctx *ctx, float *d_stats, float *d_send, int K
     rc = flush_locked(ctx, st, &uniform_n, rows_active);
     if (rc) return rc;
     if (d_send) ctx->tail_uniform_n = uniform_n;  // (for nvrx_tail_local)
+    ctx->stats_stream = st;                       // (for nvrx_slack_local)
     if (ctx->onset_on && d_send) onset_snapshot_locked(ctx);  // (for nvrx_onset_local)
     report_clk(2);
     Epilogue ep{};
@@ -3955,5 +3965,6 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_robust.inl"
 #include "nvrx_history.inl"
 #include "nvrx_trend.inl"
+#include "nvrx_slack.inl"
 #include "nvrx_period.inl"
 #include "nvrx_episode.inl"

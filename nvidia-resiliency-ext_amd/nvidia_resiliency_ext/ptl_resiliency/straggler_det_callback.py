@@ -48,6 +48,7 @@ class StragglerDetectionCallback(Callback):
         logger_name: Optional[str] = "nemo_logger.StragglerDetectionCallback",
         min_consecutive_reports: int = 1,
         warn_if_declining: bool = False,
+        warn_if_waited_for: bool = False,
     ):
         """
         Args:
@@ -69,9 +70,15 @@ class StragglerDetectionCallback(Callback):
                 reports with score trends (``Detector.initialize(score_trends=True)``), and every report that finds a GPU
                 whose score is falling towards its threshold (``Report.identify_declining_stragglers``) logs one warning
                 that names the ranks and the reports left until they cross it.  A warning only: it never stops the job.
+            warn_if_waited_for: False (the default): nothing changes.  True: the detector also computes slack scores
+                (``Detector.initialize(collective_slack=True)``; per-kernel timing only), and every report in which the job
+                waits for some rank in its collectives (``Report.identify_slack_stragglers``: a slow HOST, which no other
+                score sees) logs one warning that names the ranks and the microseconds the others wait for each per report
+                window.  A warning only: it never stops the job.
 
         Raises:
-            ValueError: neither score family requested, or ``min_consecutive_reports`` outside [1, 64].
+            ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64], or
+                ``warn_if_waited_for`` without ``calc_relative_gpu_perf``.
         """
         self.initialized = False
         self.logger = logging.getLogger(logger_name)
@@ -99,6 +106,9 @@ class StragglerDetectionCallback(Callback):
             raise ValueError(f"min_consecutive_reports must be an integer within [1, 64], got {min_consecutive_reports!r}")
         self.min_consecutive_reports = min_consecutive_reports
         self.warn_if_declining = bool(warn_if_declining)
+        self.warn_if_waited_for = bool(warn_if_waited_for)
+        if self.warn_if_waited_for and not calc_relative_gpu_perf:
+            raise ValueError("warn_if_waited_for needs calc_relative_gpu_perf=True: slack scores compare ranks")
         self.interval_est_was_reset = False
 
     # ---- Lightning hooks -----------------------------------------------------------------------
@@ -116,6 +126,8 @@ class StragglerDetectionCallback(Callback):
             persistence.setdefault("persistence_thresholds", (self.gpu_relative_perf_threshold, 0.75,
                                                               self.gpu_individual_perf_threshold, 0.75))
             persistence["score_trends"] = True
+        if self.warn_if_waited_for:
+            persistence["collective_slack"] = True
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -142,6 +154,8 @@ class StragglerDetectionCallback(Callback):
         found = bool(report) and trainer.global_rank == 0 and self._digest(pl_module, report)
         if self.warn_if_declining and bool(report) and trainer.global_rank == 0:
             self._warn_declining(report)  # (a warning only: `found`, and with it the halt, does not depend on it)
+        if self.warn_if_waited_for and bool(report) and trainer.global_rank == 0:
+            self._warn_waited_for(report)  # (likewise)
         if not detector.is_interval_elapsed():
             return  # no report was due this iteration
         if self.stop_if_detected and self._decision_of_rank0(found):
@@ -201,6 +215,19 @@ class StragglerDetectionCallback(Callback):
                              f"(level {rec['level']:.3f}, reports_left={rec['reports_left']})")
         if parts:
             self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs are getting slower: " + "; ".join(parts))
+
+    def _warn_waited_for(self, report) -> None:
+        """One warning per report that names the GPUs the others wait for in collectives, with the time the typical rank
+        waits for each per report window (``warn_if_waited_for``).  Never a reason to halt."""
+        named = report.identify_slack_stragglers()["straggler_gpus_slack"]
+        if not named:
+            return
+        scores = report.slack_scores()
+        parts = [f"rank {rank} (the others wait {scores['ranks'][rank]['lead_us']:.0f} us per window for it)"
+                 for rank in sorted(getattr(s, "rank", s) for s in named)]
+        self.logger.warning("STRAGGLER DETECTION WARNING: The job waits for some GPUs in its collectives (slow host?): "
+                            + "; ".join(parts) + f"; the typical rank spends {100 * scores['typical_share']:.1f} % of its "
+                            "traced GPU time waiting")
 
     def _name_the_kernels(self, report, flagged) -> None:
         """Kernel attribution (``NVRX_KERNEL_ATTRIBUTION=N``, off by default: nothing is logged then): for every flagged GPU the

@@ -43,6 +43,9 @@ EPISODE_PLANES = 7  # NVRX_EPISODE_PLANES: {e, inside, outside, strength, length
 HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
 HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
 TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, family, slot)
+SLACK_COLS = 64  # NVRX_SLACK_COLS: columns the collective keys are folded into (digest % 64)
+SLACK_HEAD_WORDS = 8 + 4 * SLACK_COLS  # the job record and the column records in front of the rank records
+SLACK_RANK_WORDS = 8  # {f32 collective_us, waited_us, compute_us, share, u32 calls, columns, 0, 0} per rank
 
 
 
@@ -95,6 +98,7 @@ SYMBOLS = [
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
+    ("nvrx_slack_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -137,6 +141,7 @@ SYMBOLS = [
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
+    ("nvrx_slack_local", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
     ("nvrx_peer_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -251,6 +256,11 @@ def history_words(n_ranks: int, S: int) -> int:
 def trend_words(n_ranks: int, S: int) -> int:
     """NVRX_TREND_WORDS: 32-bit words of a trend step's records ``[n_ranks][2][1 + S][4]``."""
     return n_ranks * 2 * (1 + S) * TREND_RECORD_WORDS
+
+
+def slack_words(R: int) -> int:
+    """NVRX_SLACK_WORDS: 32-bit words of a slack score's output -- job record | 64 column records | ``R`` rank records."""
+    return SLACK_HEAD_WORDS + SLACK_RANK_WORDS * R
 
 
 def tail_q_ppm(q) -> int:

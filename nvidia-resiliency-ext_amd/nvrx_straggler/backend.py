@@ -388,6 +388,33 @@ class Trend:
         return self._host
 
 
+class Slack:
+    """The slack scores of one report (``nvrx_slack_score``), enqueued and not waited for: once the kernels have run, the
+    workspace's device buffer holds the job record, the 64 column records and every rank's record (include/
+    nvrx_straggler.h).  ``records()`` waits for them and takes the private host copy (one ordered D2H on the backend's stream):
+    when a ``Report`` first asks, or -- ``Workspace.slack_settle`` -- before the next slack step on the same workspace
+    rewrites the buffers."""
+
+    __slots__ = ("backend", "d_ptr", "first_rank", "n_ranks", "min_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, first_rank: int, n_ranks: int, min_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.first_rank, self.n_ranks, self.min_ranks = first_rank, n_ranks, min_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(job [8], columns [64, 4], ranks [n_ranks, 8])`` uint32 (private copies), the ranks being ``[first_rank,
+        first_rank + n_ranks)``; the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.slack_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -569,6 +596,31 @@ class Workspace:
             self.history_settle()
         if self._trend_last is not None:
             self.trend_settle()
+        if self._slack_last is not None:
+            self.slack_settle()
+
+    # ---- slack scores (off unless a ReportGenerator asks: nothing is allocated before) ----------------------------
+    _slack_state = None  # (send, table, out) once a slack step has run on this workspace
+    _slack_last = None   # the Slack whose kernels may still be reading the tables / writing the records
+
+    def slack_buffers(self):
+        """``(send [local_ranks, 2 * 64] f32, table [R, 2 * 64] f32, out)`` of the slack step (cold: allocated on first
+        use); ``send`` is the table itself when nothing is exchanged; ``out`` takes ``_native.slack_words(R)`` words."""
+        if self._slack_state is None:
+            dev, W = self._backend.device, 2 * _native.SLACK_COLS
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                table = torch.empty((self.R, W), dtype=torch.float32, device=dev)
+                send = table if self.R == self.local_ranks else torch.empty((self.local_ranks, W), dtype=torch.float32, device=dev)
+                out = torch.empty(_native.slack_words(self.R), dtype=torch.int32, device=dev)
+            self._slack_state = (send, table, out)
+        return self._slack_state
+
+    def slack_settle(self) -> None:
+        """Before anything rewrites the slack step's buffers or this workspace's table: the last step's kernels have run and
+        their records are on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._slack_last = self._slack_last, None
+        if last is not None:
+            last.records()
 
     # ---- robust scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
     _robust_buf = None   # device: column records, then the scores of the last robust step of this workspace's table
@@ -928,6 +980,34 @@ class HipBackend:
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, host.nbytes, self._stream_handle))
         return host
 
+    def slack_score(self, ws: Workspace, slack_table: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
+                    n_ranks: Optional[int] = None, min_ranks: int = 4) -> Slack:
+        """Slack scores from the gathered rows ``slack_table`` ([R, 2 * 64], ``HipRings.slack_local`` and the caller's
+        all-gather) and ``table`` ([R, L], the table ``score`` was given; its kernel weights are the compute time):
+        ``nvrx_slack_score`` enqueued on the backend's stream.  All R ranks are computed; the handle delivers ranks
+        ``[first_rank, first_rank + n_ranks)``.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if first_rank < 0 or n_ranks < 1 or first_rank + n_ranks > ws.R:
+            raise ValueError(f"ranks [{first_rank}, {first_rank}+{n_ranks}) outside the table's {ws.R}")
+        _, _, out = ws.slack_buffers()
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_slack_score(slack_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, min(int(min_ranks), ws.R),
+                                       out.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        handle = ws._slack_last = Slack(self, out, first_rank, n_ranks, min(int(min_ranks), ws.R))
+        return handle
+
+    def slack_copy_out(self, s: Slack):
+        """The one wait of a report's slack scores: a D2H of the head and of the rank records up to the last rank the report
+        covers, on the backend's stream, behind the kernels."""
+        head, rw = _native.SLACK_HEAD_WORDS, _native.SLACK_RANK_WORDS
+        n = head + rw * (s.first_rank + s.n_ranks)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, s.d_ptr, n * 4, self._stream_handle))
+        return (host[:8].copy(), host[8:head].reshape(_native.SLACK_COLS, 4).copy(),
+                host[head + rw * s.first_rank:].reshape(s.n_ranks, rw).copy())
+
     def row_quantile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm: int) -> torch.Tensor:
         """Stateless nearest-rank quantile on caller tensors ([rows, stride] f32, [rows] u32/i32) -> [rows] f32, -1.0 where
         a row holds no sample (``nvrx_row_quantile``)."""
@@ -1271,6 +1351,35 @@ class HipRings:
             _native.check(rc)
         out = ws._trend_last = Trend(be, buf, ws.S, n_ranks)
         return out
+
+    _slack_list = None  # (len(kernel_row_names), rows int32, columns int32, {column: keys}): names are only ever added
+
+    def slack_list(self):
+        """``(rows, columns, {column: (keys, ...)})`` of the collective kernels' rows, in ascending row order (cached until
+        ``kernel_row_names`` grows: rows are never recycled)."""
+        cached = self._slack_list
+        if cached is None or cached[0] != len(self.kernel_row_names):
+            from .reporting import slack_row_list  # (reporting imports this module)
+
+            rows, cols, keys = slack_row_list(self.kernel_row_names)
+            cached = self._slack_list = (len(self.kernel_row_names), np.asarray(rows, dtype=np.int32),
+                                         np.asarray(cols, dtype=np.int32), keys)
+        return cached[1:]
+
+    def slack_local(self, ws: Workspace, rows_active: int = 0, fused: bool = False):
+        """The local step of the slack scores on the statistics of the report just issued on ``ws`` (``nvrx_slack_local``;
+        ``fused``: that report was ``report_fused``'s, else ``report_local``'s): per logical rank and column the time and the
+        calls of the collective rows.  Returns ``(send [local_ranks, 2 * 64], table [R, 2 * 64])`` -- the same rows when
+        nothing is exchanged.  Waits for the kernel, as ``tail_local`` does: the next report rewrites the statistics."""
+        ws.slack_settle()
+        send, table, _ = ws.slack_buffers()
+        rows, cols, _ = self.slack_list()
+        rc = self.lib.nvrx_slack_local(self.ctx, ws.block.desc_ref if fused else None, ws.d_stats, rows.ctypes.data,
+                                       cols.ctypes.data, rows.size, send.data_ptr(), rows_active, self.backend._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        self.backend.stream.synchronize()
+        return send, table
 
     def _family_local(self, fam: RowFamily, ws: Workspace, params: tuple, rows_active: int, fused: bool):
         """A row family's ring kernel over every ring row as the report just issued on ``ws`` saw it, packed by gid into the

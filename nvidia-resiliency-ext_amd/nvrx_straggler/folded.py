@@ -29,7 +29,9 @@ class FoldedJob:
                  period_detection: bool = False, period_max: int = 1024, period_min_strength: float = 0.5,
                  episode_detection: bool = False, episode_min_length: float = 0.005, episode_min_strength: float = 0.5,
                  score_history: int = 0, persistence_min_reports: int = 3, persistence_thresholds=None,
-                 score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6, trend_horizon=None):
+                 score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6, trend_horizon=None,
+                 collective_slack: bool = False, slack_min_ranks: int = 4, slack_min_share: float = 0.05,
+                 slack_max_ratio: float = 0.25, kernel_names: Sequence[str] = ()):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -38,7 +40,8 @@ class FoldedJob:
         self.world_rank = dist_utils.get_rank(pg)
         self.section_names = list(section_names) if section_names is not None else [f"section_{s:03d}" for s in range(sections)]
         self.backend = get_backend()
-        self.rings = self.backend.make_rings(self.local_ranks, len(self.section_names), ring_cap)
+        self.kernel_names = list(kernel_names)  # per-kernel rows next to the sections (``load_kernels``); none by default
+        self.rings = self.backend.make_rings(self.local_ranks, len(self.section_names) + len(self.kernel_names), ring_cap)
         self.ring_cap = ring_cap
         self.reporter = ReportGenerator(list(scores_to_compute), gather_on_rank0=gather_on_rank0, pg=pg, node_name=node_name,
                                         kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -51,9 +54,12 @@ class FoldedJob:
                                         persistence_min_reports=persistence_min_reports,
                                         persistence_thresholds=persistence_thresholds, score_trends=score_trends,
                                         trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
-                                        trend_horizon=trend_horizon)
+                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
+                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
+                                        slack_max_ratio=slack_max_ratio)
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
-        self._no_kernel_rows = {}  # same object every report so the reporter's cached plan stays valid
+        # (the same object every report so the reporter's cached plan stays valid)
+        self._no_kernel_rows = {name: self.rings.row_for(_native.KIND_KERNEL, name) for name in self.kernel_names}
 
     def logical_ranks(self):
         """Global logical ranks held by this process."""
@@ -72,6 +78,12 @@ class FoldedJob:
             for s, row in enumerate(rows):
                 self.rings.push_device(row, samples[s].contiguous(), lr=lr)
         self.backend.synchronize()
+
+    def load_kernels(self, lr: int, samples) -> None:
+        """Append ``samples`` ([len(kernel_names), n] f32 host array: microseconds per call) to logical rank ``lr``'s kernel
+        rows, as the per-kernel tracer would."""
+        for name, values in zip(self.kernel_names, samples):
+            self.rings.push_many(self._no_kernel_rows[name], values, lr=lr)
 
     def rearm(self, n: int) -> None:
         """Declare every row holds ``n`` resident samples again (after a report emptied the rings)."""

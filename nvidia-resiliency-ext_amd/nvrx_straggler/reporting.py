@@ -34,7 +34,7 @@ import numpy as np
 
 from . import backend as _backend_mod
 from . import dist_utils, row_families
-from .name_mapper import NameMapper
+from .name_mapper import NameMapper, name_digest
 from .statistics import NUM_COLUMN, STAT_KEYS, Statistic
 
 _SummaryType = Mapping[Statistic, float]
@@ -103,6 +103,25 @@ _COLLECTIVE_MARKERS = (_NCCL_MARKER, "rcclGenericKernel", "mscclKernel")
 
 def is_collective_kernel(name: str) -> bool:
     return _NCCL_MARKER in name or "rcclGenericKernel" in name or "mscclKernel" in name
+
+
+SLACK_COLS = 64  # NVRX_SLACK_COLS (include/nvrx_straggler.h)
+
+
+def slack_column(key: str) -> int:
+    """The column of the slack scores that a collective kernel's key falls into: the same on every rank, from the key alone
+    -- nothing is agreed between ranks, so no name sync can hang on it.  Keys that collide share a column."""
+    return name_digest(key) % SLACK_COLS
+
+
+def slack_row_list(kernel_row_names: Mapping[str, int]):
+    """``(rows, columns, {column: (keys, ...)})`` of the collective kernels among ``kernel_row_names`` (key -> ring row), in
+    ascending row order: what the local step of the slack scores walks."""
+    pairs = sorted((row, slack_column(key), key) for key, row in kernel_row_names.items() if is_collective_kernel(key))
+    keys: Dict[int, tuple] = {}
+    for _, col, key in pairs:
+        keys[col] = keys.get(col, ()) + (key,)
+    return [p[0] for p in pairs], [p[1] for p in pairs], keys
 
 
 @dataclasses.dataclass(frozen=True)
@@ -815,6 +834,41 @@ class _TrendSource:
         return self._built
 
 
+class _SlackSource:
+    """What a report keeps of its slack scores: the backend's handle (``records()`` waits for the kernels and copies the
+    records out on first use), the ranks its rows stand for, this process' collective keys by column, and the generator's
+    rule."""
+
+    __slots__ = ("handle", "ranks", "keys", "min_ranks", "min_share", "max_ratio", "_built")
+
+    def __init__(self, handle, ranks, keys, min_ranks: int, min_share: float, max_ratio: float):
+        self.handle, self.ranks, self.keys = handle, tuple(ranks), keys
+        self.min_ranks, self.min_share, self.max_ratio = min_ranks, min_share, max_ratio
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            job, cols, ranks = (np.ascontiguousarray(a, dtype=np.uint32) for a in self.handle.records())
+            typical_waited, typical_share = job[:2].view(np.float32).tolist()
+            floors, present = cols[:, 0].copy().view(np.float32).tolist(), cols[:, 1].tolist()
+            f = ranks[:, :4].copy().view(np.float32).tolist()
+            counts = ranks[:, 4:6].tolist()
+            per_rank = {}
+            for i, r in enumerate(self.ranks):
+                if counts[i][1] == 0:
+                    continue  # (no referenced column: this rank has no slack scores)
+                coll, waited, comp, share = f[i]
+                per_rank[r] = {"collective_us": coll, "waited_us": waited, "compute_us": comp, "share": share,
+                               "calls": counts[i][0], "lead_us": typical_waited - waited}
+            columns = {c: {"floor_us": floors[c], "ranks": present[c], "kernels": list(self.keys.get(c, ()))}
+                       for c in range(SLACK_COLS) if present[c] and not math.isnan(floors[c])}
+            self._built = {"ranks": per_rank, "typical_waited_us": typical_waited, "typical_share": typical_share,
+                           "ranks_with_data": int(job[2]), "columns": columns, "min_ranks": self.min_ranks,
+                           "min_share": self.min_share, "max_ratio": self.max_ratio}
+            self.handle = None
+        return self._built
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -913,6 +967,9 @@ class Report:
         trends = self.__dict__.get("_trends")
         if trends is not None:
             state["_trends"] = trends.build() if isinstance(trends, _TrendSource) else trends
+        slack = self.__dict__.get("_slack")
+        if slack is not None:
+            state["_slack"] = slack.build() if isinstance(slack, _SlackSource) else slack
         for fam in row_families.FAMILIES:
             scores = self.__dict__.get(fam.slot)
             if scores is not None:
@@ -1151,6 +1208,46 @@ class Report:
                 "straggler_sections_relative": sections("section_relative"),
                 "straggler_sections_individual": sections("section_individual")}
 
+    def slack_scores(self) -> Dict[str, Any]:
+        """Whom the job WAITS FOR in collectives (``ReportGenerator(collective_slack=True)``; ``{}`` when the report carries
+        none).  A rank whose host is slow launches late, computes at the usual speed and ends its sections in a collective like
+        everybody else: every other score reads 1.  Inside the collective kernels the late rank spends only the transfer time,
+        every other rank that plus the wait for it.
+
+        ``{"ranks": {rank: {"collective_us": time in collective kernels this window, "waited_us": the part of it above the
+        job's floor -- per column (collective kernel) calls x (this rank's mean per call - the smallest mean of any rank) --,
+        "compute_us": time in the other kernels, "share": waited_us / (collective_us + compute_us), "calls", "lead_us":
+        typical_waited_us - waited_us, what the others wait for this rank}}, "typical_waited_us", "typical_share": the lower
+        medians over the ranks with data, "ranks_with_data", "columns": {column: {"floor_us", "ranks": ranks present,
+        "kernels": this process' collective kernels in it}}, "min_ranks", "min_share", "max_ratio"}``.  Only columns that at
+        least ``min_ranks`` ranks have are used; a rank without one is left out.  Per-kernel timing only: without collective
+        rows (region timing) the result is empty.  Plain dicts, floats and ints.  The first call waits for the kernels and
+        copies their records; ``generate_report`` does not."""
+        slack = self.__dict__.get("_slack")
+        if slack is None:
+            return {}
+        if isinstance(slack, _SlackSource):
+            slack = self.__dict__["_slack"] = slack.build()
+        return _copy_scores(slack)
+
+    def identify_slack_stragglers(self, min_share: Optional[float] = None, max_ratio: Optional[float] = None) -> Dict[str, Any]:
+        """Ranks the others wait for: ``{"straggler_gpus_slack": set[StragglerId]}``.  A rank with data is named iff the job
+        as a whole waits (``typical_share >= min_share``, default the generator's 0.05, and ``typical_waited_us > 0``) and
+        this rank hardly does (``waited_us <= max_ratio * typical_waited_us``, default 0.25).  If half the ranks or more are
+        late the typical wait is about 0 and nobody is named.  0.05 and 0.25 are defaults, not measurements.  An empty set
+        when the report carries no slack scores."""
+        s = self.slack_scores()
+        share = s.get("min_share", 0.05) if min_share is None else min_share
+        ratio = s.get("max_ratio", 0.25) if max_ratio is None else max_ratio
+        for name, v in (("min_share", share), ("max_ratio", ratio)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not v >= 0:
+                raise ValueError(f"{name} must be a number >= 0, got {v!r}")
+        named = []
+        if s and s["typical_share"] >= share and s["typical_waited_us"] > 0:
+            limit = ratio * s["typical_waited_us"]
+            named = [r for r, rec in s["ranks"].items() if rec["waited_us"] <= limit]
+        return {"straggler_gpus_slack": self._ids(named)}
+
     def _family_scores(self, name: str) -> Dict[str, Any]:
         """A private copy of one row family's scores (built from the device's planes on first use); ``{}`` without them."""
         fam = row_families.BY_NAME[name]
@@ -1328,7 +1425,8 @@ class ReportGenerator:
                  episode_min_length: float = 0.005, episode_min_strength: float = 0.5, score_history: int = 0,
                  persistence_min_reports: int = 3, persistence_thresholds: Optional[Sequence[float]] = None,
                  score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6,
-                 trend_horizon: Optional[int] = None) -> None:
+                 trend_horizon: Optional[int] = None, collective_slack: bool = False, slack_min_ranks: int = 4,
+                 slack_min_share: float = 0.05, slack_max_ratio: float = 0.25) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1532,6 +1630,31 @@ class ReportGenerator:
                 raise RuntimeError(f"score_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no score trends (backend.score_trend)")
             self.trend_min_reports, self.trend_min_tau, self.trend_horizon = int(m), tau, int(hz)
+        # slack scores: every ring report also says whom the job waits for in collectives (Report.slack_scores,
+        # Report.identify_slack_stragglers) from the statistics of the collective kernels' rows, which every other score drops;
+        # off: no buffer, no launch, no collective, no backend call.  The step adds one collective per report, so EVERY rank
+        # must pass the same value.  4 ranks, 0.05 and 0.25 are defaults, not measurements.
+        self.collective_slack = bool(collective_slack)
+        if self.collective_slack:
+            if isinstance(slack_min_ranks, bool) or not isinstance(slack_min_ranks, (int, np.integer)) or slack_min_ranks < 1:
+                raise ValueError(f"slack_min_ranks must be an integer >= 1, got {slack_min_ranks!r}")
+            rule = []
+            for name, v in (("slack_min_share", slack_min_share), ("slack_max_ratio", slack_max_ratio)):
+                try:
+                    x = float(v)
+                except (TypeError, ValueError):
+                    x = float("nan")
+                if isinstance(v, bool) or not (x >= 0.0 and math.isfinite(x)):
+                    raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+                rule.append(x)
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"collective_slack needs relative_perf_scores among scores_to_compute (got "
+                                 f"{scores_to_compute!r}): slack scores compare ranks")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "slack_score"):
+                raise RuntimeError(f"collective_slack: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no slack scores (backend.slack_score)")
+            self.slack_min_ranks, (self.slack_min_share, self.slack_max_ratio) = int(slack_min_ranks), rule
         # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
         # any, that needs the ring-start snapshot
         self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
@@ -1601,16 +1724,18 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
-        if self._row_families:
-            fam = self._row_families[0]
-            # a row family's collective is a torch.distributed call between two kernels: reports with one stay on that route
-            # as a whole (the option has the same value on every rank, so every rank decides alike -- no collective here)
+        if self._row_families or self.collective_slack:
+            # a row family's collective -- and the slack step's -- is a torch.distributed call between two kernels: reports
+            # with one stay on that route as a whole (the option has the same value on every rank, so every rank decides alike
+            # -- no collective here).  A row family that is on is the one named.
+            option, what = ((self._row_families[0].option, self._row_families[0].name) if self._row_families
+                            else ("collective_slack", "slack"))
             self._direct = None
-            self.exchange_info = {"route": f"torch.distributed all-gather on the job's own process group ({fam.option} is "
-                                           f"set: reports with {fam.name} scores do not use the in-stream routes)", "mode": "c10d"}
+            self.exchange_info = {"route": f"torch.distributed all-gather on the job's own process group ({option} is "
+                                           f"set: reports with {what} scores do not use the in-stream routes)", "mode": "c10d"}
             if mode != "c10d":
                 _LOG.warning("nvrx straggler: NVRX_EXCHANGE=%s is ignored while %s is set: reports with %s scores "
-                             "run on torch.distributed's route (c10d)", mode, fam.option, fam.name)
+                             "run on torch.distributed's route (c10d)", mode, option, what)
             return
         # c10d (the default) on ANY rank keeps every rank on torch.distributed (the decision has to be the same everywhere:
         # building a communicator is collective)
@@ -2098,6 +2223,35 @@ class ReportGenerator:
         for fam in self._row_families:
             self._family_step(fam, report, rings, ws, mapper, rows_active, fused, local_ranks)
 
+    # ---- slack scores -------------------------------------------------------------------------------
+    def _slack_step(self, report, rings, ws, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The slack step of a ring report, once per ``generate_report_from_rings`` call right behind the row families'
+        steps, on the same workspace: the local kernel on the statistics the report wrote (the collective kernels' rows, which
+        the report itself does not exchange) -> [one all-gather of its rows] -> the score kernels, hung on ``report`` unread.
+        Like a family's step, every rank issues it at every report, whatever the report found and whether or not it holds a
+        report: same collectives everywhere."""
+        be = _backend_mod.get_backend()
+        local, score = getattr(rings, "slack_local", None), getattr(be, "slack_score", None)
+        if local is None or score is None or not hasattr(rings, "slack_list"):
+            raise RuntimeError("collective_slack: the active backend has no slack scores (rings.slack_local, rings.slack_list / "
+                               "backend.slack_score)")
+        send, table = local(ws, rows_active, fused)
+        if self.world_size > 1:
+            with be.stream_context():  # (behind the local kernel)
+                table = dist_utils.all_gather_rows(send, table, self.group)
+        if report is None or report is False:
+            return
+        if self.gather_on_rank0:
+            lo, hi = 0, ws.R
+        else:
+            lo = self.rank * local_ranks
+            hi = lo + local_ranks
+        view = report.__dict__["_src"].view
+        min_ranks = min(self.slack_min_ranks, ws.R)
+        handle = score(ws, table, ws.table, lo, hi - lo, min_ranks)
+        report.__dict__["_slack"] = _SlackSource(handle, view.ranks, rings.slack_list()[2], min_ranks, self.slack_min_share,
+                                                 self.slack_max_ratio)
+
     # ---- public: summaries given as dicts (reference signature) -------------------------------------
     def generate_report(self, section_summaries: Mapping[str, _SummaryType],
                         kernel_summaries: Mapping[str, _SummaryType]):
@@ -2184,6 +2338,8 @@ class ReportGenerator:
                 raise
             if out is not False:
                 self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+                if self.collective_slack:
+                    self._slack_step(out, rings, plan.ws, plan.rows_used, self._last_plan_fused, local_ranks)
                 return out
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
@@ -2198,6 +2354,8 @@ class ReportGenerator:
                                      + [r for n, r in section_rows.items() if n not in known_s])
             out = self._report_from_plan(plan, rings, t0, order_after, names_ok=False)
             self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
+            if self.collective_slack:
+                self._slack_step(out, rings, plan.ws, plan.rows_used, self._last_plan_fused, local_ranks)
             return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
@@ -2225,6 +2383,9 @@ class ReportGenerator:
         report = self._assemble(ws, mapper, snames, dict(section_rows), dict(kernel_rows), t0, local_ranks=local_ranks,
                                 stats=ws.stats[:stats_needed].copy())
         self._family_steps(report, rings, ws, mapper, rows_used, False, local_ranks)  # (before the plan below re-points the ring rows)
+        if self.collective_slack:
+            # (its list is built from the rings' own table of kernel rows: the collective ones were filtered out of kernel_rows above)
+            self._slack_step(report, rings, ws, rows_used, False, local_ranks)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

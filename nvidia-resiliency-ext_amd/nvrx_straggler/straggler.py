@@ -164,6 +164,8 @@ class _Lane:
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         if getattr(reporter, "score_history", 0):
             return None  # (the history step follows the report in the generator's planned path: DESIGN.md, "Score history")
+        if getattr(reporter, "collective_slack", False):
+            return None  # (the slack step follows the report in the generator's paths: DESIGN.md, "Slack scores")
         ext = manager.cupti_ext
         ws = plan.ws
         if ws.block.desc_key is None or not ws.send_initialised:
@@ -404,6 +406,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
         trend_min_reports: Optional[int] = None,
         trend_min_tau: float = 0.6,
         trend_horizon: Optional[int] = None,
+        collective_slack: Optional[bool] = None,
+        slack_min_ranks: int = 4,
+        slack_min_share: float = 0.05,
+        slack_max_ratio: float = 0.25,
     ):
         """
         Args:
@@ -492,6 +498,16 @@ class Detector(metaclass=_DeviceSideOnDemand):
             trend_min_tau: a score is falling when Kendall's tau is at most minus this, within (0, 1].
             trend_horizon: reports ahead that ``identify_declining_stragglers`` looks; None = ``score_history``.  6, 0.6 and
                 that horizon are defaults, not measurements.
+            collective_slack: every report also says whom the job WAITS FOR in collectives (``Report.slack_scores()``,
+                ``Report.identify_slack_stragglers()``): a rank whose host is slow launches late and computes at the usual
+                speed, so every other score reads 1; inside the collective kernels it spends the least time of all ranks and
+                the others the wait for it on top.  Per-kernel timing only (region timing has no collective rows: the result
+                is empty); needs ``relative_perf_scores``; the same value on EVERY rank (one more collective per report).
+                Default: ``NVRX_COLLECTIVE_SLACK`` (set and not "0"), else off.
+            slack_min_ranks: ranks a collective kernel must have been seen on to be used (never more than the job has).
+            slack_min_share, slack_max_ratio: the rule of ``identify_slack_stragglers``: the typical rank waits at least
+                this share of its traced GPU time, and the named rank at most this fraction of the typical wait.  4, 0.05 and
+                0.25 are defaults, not measurements.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -560,6 +576,8 @@ class Detector(metaclass=_DeviceSideOnDemand):
                     persistence_min_reports = 2  # (a history of two reports cannot hold a streak of three)
         if score_trends is None:
             score_trends = os.environ.get("NVRX_SCORE_TRENDS", "0") not in ("", "0")
+        if collective_slack is None:
+            collective_slack = os.environ.get("NVRX_COLLECTIVE_SLACK", "0") not in ("", "0")
         if trend_min_reports is None:
             trend_min_reports = 6
             if isinstance(score_history, int) and 4 <= score_history < 6:
@@ -575,7 +593,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        score_history=score_history, persistence_min_reports=persistence_min_reports,
                                        persistence_thresholds=persistence_thresholds, score_trends=score_trends,
                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
-                                       trend_horizon=trend_horizon)
+                                       trend_horizon=trend_horizon, collective_slack=collective_slack,
+                                       slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
+                                       slack_max_ratio=slack_max_ratio)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
