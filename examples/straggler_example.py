@@ -68,6 +68,11 @@ runs 200 steps of one compute kernel (1000 us) and one all-reduce (200 us +- 2 %
 exponential skew of 20 us) in which rank 5's HOST is slow: it arrives 300 us late at every collective.  Its kernels take the
 usual time and the step lasts as long on every rank, so ``identify_stragglers`` names nobody; with slack scores
 (``ReportGenerator(collective_slack=True)``) ``identify_slack_stragglers`` names rank 5, and the report says what it costs.
+
+``--peer`` needs no training loop either: it plays one report of a job of 8 ranks in two pipeline stages (folded onto one GPU,
+1 % noise, seed 29): ranks 0-3 run a stage of 1000 us, ranks 4-7 one of 1500 us, and rank 6 is 1.4x slower than its stage's
+peers.  ``identify_stragglers`` names ranks 4-7, three of them healthy; with peer groups (``ReportGenerator(peer_groups=
+"block:4")``) ``identify_peer_stragglers`` names rank 6 alone, and both scores are printed side by side.
 """
 import argparse
 import os
@@ -337,6 +342,37 @@ def slack(ranks: int = 8, calls: int = 200, late_rank: int = 5, late_us: float =
         job.close()
 
 
+def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 6) -> None:
+    """Two pipeline stages of different length: whom the job-wide rule names, and whom the peer-group scores do."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=64, scores_to_compute=("relative_perf_scores",),
+                    peer_groups=f"block:{ranks // 2}")
+    x = np.repeat(np.array([1000.0] * (ranks // 2) + [1500.0] * (ranks - ranks // 2)), sections * samples).reshape(ranks, sections, samples)
+    x *= 1.0 + 0.01 * np.random.default_rng(29).standard_normal(x.shape)
+    x[slow_rank] *= 1.4
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, x[r].astype(np.float32))
+        report = job.report()
+        t = report.peer_scores()
+        name = job.section_names[0]
+        print(f"identify_stragglers(): {named(report.identify_stragglers())}")
+        print(f"identify_peer_stragglers(): {named(report.identify_peer_stragglers())}; groups {t['groups']}")
+        for r in sorted(t["group_of"]):
+            print(f"  rank {r} (group {t['group_of'][r]}): {name} against the job "
+                  f"{report.section_relative_perf_scores[name][r]:.3f}, against its peers {t['section_relative'][name][r]:.3f}")
+    finally:
+        job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -361,9 +397,15 @@ def main() -> None:
     ap.add_argument("--slack", action="store_true",
                     help="no training: play the slack-score scenario (a rank whose host is slow arrives late at every "
                          "collective) and exit")
+    ap.add_argument("--peer", action="store_true",
+                    help="no training: play the peer-group scenario (two pipeline stages of different length, one rank slow "
+                         "within its stage) and exit")
     args = ap.parse_args()
     if args.slack:
         slack()
+        return
+    if args.peer:
+        peer()
         return
     if args.persist:
         persist()

@@ -335,6 +335,41 @@ int nvrx_episode_score(const float *d_episode, const float *d_table, int R, int 
 int nvrx_robust_score(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks,
                       float floor_rel, void *d_out, void *stream);
 
+/* Peer-group scores: every rank against the fastest rank of ITS OWN group.  The relative scores of reporting.py:196-253 take
+ * the fastest rank of the whole job as the reference: a lockstep data-parallel model.  In a job of pipeline stages, expert
+ * groups or actor / critic roles, ranks legitimately differ, and the caller says which ranks are peers.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_ROBUST_MAX_RANKS.
+ *   d_groups  ONE device array of 2R + G + 1 int32 words, group[R] | members[R] | start[G+1], 1 <= G <= R and G <=
+ *      NVRX_PEER_MAX_GROUPS: group[r] is rank r's group id, every rank in exactly one group; members holds the ranks sorted
+ *      by (group id, rank); start[g] .. start[g+1] is group g's stretch of members.
+ *   Per (group g, column c < K+S of the table's med part), over the members of g: a member is PRESENT iff its value v >= 0
+ *   (the -1 sentinel and NaN are absent, as in the robust scores);
+ *      floor       the present value whose key (raw bit pattern order: -0.0 < +0.0 < ... < +inf) is smallest;
+ *      floor_rank  the lowest rank that holds that key;
+ *      the pair is REFERENCED iff present >= min_ranks; one that is not has floor = the canonical NaN 0x7FC00000 and
+ *      floor_rank = -1 (present and members are still written; pairs with no present member are written too);
+ *      record, 16 bytes: {f32 floor, u32 present, i32 floor_rank, u32 members}, at d_out[g * (K+S) + c] in 16-byte units.
+ *   Per reported rank r in [first_rank, first_rank + n_ranks), behind the G * (K+S) records, 1 + S floats:
+ *      slot 1 + s: (float)((double)floor / (double)v) of column K + s of r's group; NaN where r is absent or the pair is not
+ *      referenced;
+ *      slot 0 (GPU): (float)(sum_k w_k * ((double)floor_k / (double)v_k) / sum_k w_k) in f64 over the kernel columns k < K
+ *      where r is present and the pair is referenced, w_k = table[r][2(K+S) + k]; NaN when there is no such column (also at
+ *      K = 0).  The sum is taken across a wave: its last bits depend on that order.
+ *   min_ranks >= 1 and NOT clamped to the group's size: at 2 a rank alone in its group has no peer and is unrated (NaN), not
+ *   rated 1.0.  With one group and min_ranks = 1 the section slots are nvrx_score's relative section scores in every section
+ *   that every rank has (one that some rank lacks has no job-wide reference, and here rates the ranks that have it).
+ *   d_out  16-byte aligned, NVRX_PEER_WORDS(G, n_ranks, K, S) 32-bit words.
+ *   The CONTENTS of d_groups are guarded on the device: a group[r] outside [0, G) rates rank r NaN, a members entry outside
+ *   [0, R) is skipped, start values are clamped to [0, R] (`members` of a record is the clamped stretch's length); no content
+ *   makes a kernel read or write outside the table, the array or d_out.
+ * Two launches on `stream` (columns, ranks); no atomics, no scratch.  Argument errors, reported before any device is touched:
+ * those of nvrx_robust_score in its order, then NVRX_ERR_INVALID for G < 1, NVRX_ERR_RANGE for G > R or G >
+ * NVRX_PEER_MAX_GROUPS, NVRX_ERR_INVALID for a null pointer or a d_out that is not 16-byte aligned. */
+#define NVRX_PEER_MAX_GROUPS 4096
+#define NVRX_PEER_WORDS(G, n_ranks, K, S) (4 * (size_t)(G) * ((size_t)(K) + (S)) + (size_t)(n_ranks) * (1 + (size_t)(S)))
+int nvrx_peer_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int first_rank, int n_ranks,
+                    int min_ranks, void *d_out, void *stream);
+
 /* Score history: how each score behaved over the last H reports.  Every score above looks inside one report window; the one
  * thing a report carries over from its predecessors is the running minimum of MED.  Here a device ring keeps the last H
  * reports' scores per reported rank, family f (0 individual, 1 relative: the parity of the score row's first two columns)
@@ -656,6 +691,13 @@ int nvrx_episode_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min
  * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_robust(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int min_ranks,
                        float floor_rel, void *d_out);
+/* nvrx_peer_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor; d_groups sized for the descriptor's R).  Ordered behind that report's kernels exactly
+ * as nvrx_report_robust orders itself: the context's stream, with an event when the report was re-homed or scored resident.
+ * The host does not wait; copy d_out with a D2H on the context's stream, and do not let a later report rewrite the table
+ * before the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_peer(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int first_rank, int n_ranks,
+                     int min_ranks, void *d_out);
 /* nvrx_score_history (above) on the result block of the report LAST issued through `desc` on `ctx` (desc->d_scores; R and S
  * from the descriptor).  Ordered behind that report's last kernel exactly as nvrx_report_robust orders itself: the context's
  * stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a D2H on the

@@ -3968,3 +3968,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_slack.inl"
 #include "nvrx_period.inl"
 #include "nvrx_episode.inl"
+#include "nvrx_peer.inl"

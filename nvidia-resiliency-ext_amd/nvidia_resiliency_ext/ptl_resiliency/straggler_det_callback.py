@@ -49,6 +49,7 @@ class StragglerDetectionCallback(Callback):
         min_consecutive_reports: int = 1,
         warn_if_declining: bool = False,
         warn_if_waited_for: bool = False,
+        peer_groups=None,
     ):
         """
         Args:
@@ -75,10 +76,17 @@ class StragglerDetectionCallback(Callback):
                 waits for some rank in its collectives (``Report.identify_slack_stragglers``: a slow HOST, which no other
                 score sees) logs one warning that names the ranks and the microseconds the others wait for each per report
                 window.  A warning only: it never stops the job.
+            peer_groups: None (the default): nothing changes.  Otherwise which ranks do the same work, as
+                ``Detector.initialize(peer_groups=...)`` takes it: labels, one per rank, or ``"block:N"`` / ``"mod:N"``.  The
+                RELATIVE family's warning, and with ``stop_if_detected`` the halt, then come from
+                ``Report.identify_peer_stragglers`` -- each rank against the fastest rank of its own group -- so that the
+                healthy ranks of a slower pipeline stage do not stop the job.  Ranks without a peer are unrated; they are
+                logged once.  The individual family is untouched.
 
         Raises:
-            ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64], or
-                ``warn_if_waited_for`` without ``calc_relative_gpu_perf``.
+            ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64],
+                ``warn_if_waited_for`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
+                ``min_consecutive_reports`` > 1 (the score history does not hold peer scores).
         """
         self.initialized = False
         self.logger = logging.getLogger(logger_name)
@@ -109,6 +117,14 @@ class StragglerDetectionCallback(Callback):
         self.warn_if_waited_for = bool(warn_if_waited_for)
         if self.warn_if_waited_for and not calc_relative_gpu_perf:
             raise ValueError("warn_if_waited_for needs calc_relative_gpu_perf=True: slack scores compare ranks")
+        self.peer_groups = peer_groups
+        if peer_groups is not None:
+            if not calc_relative_gpu_perf:
+                raise ValueError("peer_groups needs calc_relative_gpu_perf=True: peer-group scores are relative scores")
+            if min_consecutive_reports > 1:
+                raise ValueError("peer_groups cannot be combined with min_consecutive_reports > 1: the score history does "
+                                 "not hold peer-group scores")
+        self._unrated_said = False
         self.interval_est_was_reset = False
 
     # ---- Lightning hooks -----------------------------------------------------------------------
@@ -128,6 +144,8 @@ class StragglerDetectionCallback(Callback):
             persistence["score_trends"] = True
         if self.warn_if_waited_for:
             persistence["collective_slack"] = True
+        if self.peer_groups is not None:
+            persistence["peer_groups"] = self.peer_groups
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -182,7 +200,19 @@ class StragglerDetectionCallback(Callback):
                 gpu_rel_threshold=self.gpu_relative_perf_threshold,
                 gpu_indiv_threshold=self.gpu_individual_perf_threshold,
             )
-        hits = [(text, flagged[key]) for _, _, key, _, _, text in self._FAMILIES if flagged[key]]
+        texts = {}
+        if self.peer_groups is not None:
+            # the relative family's verdict: each rank against its own group
+            flagged = dict(flagged)
+            flagged["straggler_gpus_relative"] = report.identify_peer_stragglers(
+                gpu_rel_threshold=self.gpu_relative_perf_threshold)["straggler_gpus_relative"]
+            texts["straggler_gpus_relative"] = "Some GPUs have worse performance than their peer group."
+            if not self._unrated_said:
+                self._unrated_said = True
+                unrated = report.peer_scores().get("unrated_ranks", [])
+                if unrated:
+                    self.logger.info(f"Straggler detection: ranks without a peer in their group are not rated: {unrated}")
+        hits = [(texts.get(key, text), flagged[key]) for _, _, key, _, _, text in self._FAMILIES if flagged[key]]
         for text, ranks in hits:
             if m > 1:
                 text = f"{text.rstrip('.')} for {m} consecutive reports."

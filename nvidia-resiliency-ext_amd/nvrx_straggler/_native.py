@@ -31,6 +31,7 @@ ATTR_MAX_TOP = 16  # NVRX_ATTR_MAX_TOP
 TAIL_Q_PPM_MIN, TAIL_Q_PPM_MAX = 500000, 999999  # the accepted range of a tail quantile, in parts per million
 ROUTE_SINGLE, ROUTE_ROWS, ROUTE_ROWS_PRE, ROUTE_TILE16, ROUTE_TILE8 = 1, 2, 3, 4, 5  # NVRX_SCORE_ROUTE_*: what nvrx_score_route returns
 ROBUST_MAX_RANKS = 65536  # NVRX_ROBUST_MAX_RANKS
+PEER_MAX_GROUPS = 4096  # NVRX_PEER_MAX_GROUPS
 ONSET_SEG_PPM_MIN, ONSET_SEG_PPM_MAX = 1, 500000  # the accepted range of an onset's minimum segment, in parts per million
 ONSET_MIN_SEG_SAMPLES = 8  # ... and the segment's floor in samples
 ONSET_PLANES = 6  # NVRX_ONSET_PLANES: {e, before, after, strength, ago, n} per kernel id and section id
@@ -95,6 +96,7 @@ SYMBOLS = [
     ("nvrx_row_episode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_episode_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
@@ -138,6 +140,7 @@ SYMBOLS = [
     ("nvrx_period_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
+    ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
@@ -236,6 +239,11 @@ def attr_words(n_ranks: int, top_n: int) -> int:
 def robust_words(n_ranks: int, K: int, S: int) -> int:
     """NVRX_ROBUST_WORDS: 32-bit words of a robust-score block: ``[K+S][4]`` column records, then ``[n_ranks][2][1 + S]``."""
     return 4 * (K + S) + n_ranks * 2 * (1 + S)
+
+
+def peer_words(G: int, n_ranks: int, K: int, S: int) -> int:
+    """NVRX_PEER_WORDS: 32-bit words of a peer-score block: ``[G][K+S][4]`` column records, then ``[n_ranks][1 + S]``."""
+    return 4 * G * (K + S) + n_ranks * (1 + S)
 
 
 def history_stride(H: int) -> int:

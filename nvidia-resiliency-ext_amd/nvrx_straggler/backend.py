@@ -23,7 +23,7 @@ import ctypes
 import os
 import threading
 import weakref
-from typing import Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -303,6 +303,89 @@ class Robust:
             with self._lock:
                 if self._host is None:
                     self._host = self.backend.robust_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
+class PeerGroups:
+    """The peer groups of one ``ReportGenerator``, resolved for a table of ``R`` logical ranks: ``labels`` in order of first
+    appearance by ascending rank (their positions are the dense group ids), and the array ``nvrx_peer_score`` takes --
+    ``group[R] | members[R] | start[G+1]`` int32 (include/nvrx_straggler.h) -- on the host and, uploaded once under the
+    backend's stream by the backend that first asks, on the device."""
+
+    __slots__ = ("R", "G", "labels", "host", "_dev")
+
+    def __init__(self, rank_labels: Sequence[Any]):
+        self.R = len(rank_labels)
+        ids: Dict[Any, int] = {}
+        group = np.fromiter((ids.setdefault(lab, len(ids)) for lab in rank_labels), dtype=np.int32, count=self.R)
+        self.labels = tuple(ids)
+        self.G = len(ids)
+        if self.G > _native.PEER_MAX_GROUPS:
+            raise ValueError(f"peer_groups: {self.G} groups, at most {_native.PEER_MAX_GROUPS}")
+        members = np.argsort(group, kind="stable").astype(np.int32)  # by (group id, rank)
+        start = np.zeros(self.G + 1, dtype=np.int32)
+        np.cumsum(np.bincount(group, minlength=self.G), out=start[1:])
+        self.host = np.concatenate((group, members, start))
+        self._dev = None
+
+    @classmethod
+    def resolve(cls, spec, R: int) -> "PeerGroups":
+        """``spec`` as ``ReportGenerator`` keeps it -- ``("block", N)``, ``("mod", N)`` or a tuple of labels, one per
+        logical rank -- for a table of ``R`` ranks."""
+        if isinstance(spec, _PeerRule):
+            kind, n = spec
+            return cls([r // n if kind == "block" else r % n for r in range(R)])
+        if len(spec) != R:
+            raise ValueError(f"peer_groups has {len(spec)} labels, the job has {R} logical ranks")
+        return cls(spec)
+
+    @property
+    def group(self) -> np.ndarray:
+        return self.host[: self.R]
+
+    def members(self, g: int) -> List[int]:
+        start = self.host[2 * self.R :]
+        return self.host[self.R + start[g] : self.R + start[g + 1]].tolist()
+
+    def device(self, backend: "HipBackend") -> torch.Tensor:
+        if self._dev is None:
+            with torch.cuda.stream(backend.stream):  # (allocated, written and read under the backend's stream)
+                self._dev = torch.from_numpy(self.host).to(backend.device)
+        return self._dev
+
+
+class _PeerRule(tuple):
+    """``("block", N)`` / ``("mod", N)``: a rule that yields the labels once the number of ranks is known (a plain tuple is a
+    list of labels)."""
+
+
+class Peer:
+    """Peer-group scores of one report (``nvrx_peer_score`` / ``nvrx_report_peer``), enqueued and not waited for: once the
+    kernels have run, the workspace's device buffer holds the ``G * (K+S)`` column records ``{floor, present, floor_rank,
+    members}`` and, behind them, ``[n_ranks][1 + S]`` f32 scores of the reported ranks (include/nvrx_straggler.h).
+    ``records()`` waits for them and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report``
+    first asks, or -- ``Workspace.peer_settle`` -- before the next report on the same workspace rewrites the table the
+    kernels read and the buffer they write."""
+
+    __slots__ = ("backend", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "min_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, K: int, S: int, first_rank: int, n_ranks: int,
+                 min_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.G, self.K, self.S = G, K, S
+        self.first_rank, self.n_ranks, self.min_ranks = first_rank, n_ranks, min_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(cols [G, K+S, 4] uint32, scores [n_ranks, 1 + S] f32)`` (private copies); the first call waits for the
+        kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.peer_copy_out(self)
                     self.backend = self._keep = None
         return self._host
 
@@ -589,6 +672,8 @@ class Workspace:
             self.family_settle(TAIL)
         if self._robust_last is not None:
             self.robust_settle()
+        if self._peer_last is not None:
+            self.peer_settle()
         if self._family_state:
             for fam in FAMILIES[1:]:
                 self.family_settle(fam)
@@ -641,8 +726,27 @@ class Workspace:
         if last is not None:
             last.records()
 
+    # ---- peer-group scores (off unless a ReportGenerator asks: nothing is allocated before) -----------------------
+    _peer_buf = None   # device: column records, then the scores of the last peer step of this workspace's table
+    _peer_last = None  # the Peer whose kernels may still be reading the table / writing _peer_buf
+
+    def peer_buffers(self, G: int, n_ranks: int):
+        """The records buffer for peer scores of ``n_ranks`` ranks in ``G`` groups (cold: allocated once per shape)."""
+        words = _native.peer_words(G, n_ranks, self.K, self.S)
+        if self._peer_buf is None or self._peer_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._peer_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return self._peer_buf
+
+    def peer_settle(self) -> None:
+        """Before anything rewrites this workspace's table: the last peer step's kernels have run and their results are on
+        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._peer_last = self._peer_last, None
+        if last is not None:
+            last.records()
+
     # ---- score history (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------
-    _history_buf = None   # device: the records of the last history step on this workspace's result blocks
+    _history_buf = None  # device: the records of the last history step on this workspace's result blocks
     _history_last = None  # the History whose kernel may still be reading a result block / writing _history_buf
 
     def history_buffers(self, n_ranks: int):
@@ -919,6 +1023,32 @@ class HipBackend:
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, rb.d_ptr, n * 4, self._stream_handle))
         cols = host[: 4 * KS].reshape(KS, 4).copy()
         return cols, host[4 * KS :].view(np.float32).reshape(rb.n_ranks, 2, 1 + rb.S).copy()
+
+    def peer_score(self, ws: Workspace, table: torch.Tensor, groups: PeerGroups, first_rank: int = 0,
+                   n_ranks: Optional[int] = None, min_ranks: int = 2) -> Peer:
+        """Peer-group scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank +
+        n_ranks)``: ``nvrx_peer_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if groups.R != ws.R:
+            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
+        ws.peer_settle()
+        buf = ws.peer_buffers(groups.G, n_ranks)
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_peer_score(table_ptr, ws.R, ws.K, ws.S, groups.device(self).data_ptr(), groups.G, first_rank,
+                                      n_ranks, min_ranks, buf.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._peer_last = Peer(self, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks)
+        return out
+
+    def peer_copy_out(self, pr: Peer):
+        """The one wait of a report's peer scores: a D2H of the records on the backend's stream, behind the kernels."""
+        KS = pr.K + pr.S
+        n = _native.peer_words(pr.G, pr.n_ranks, pr.K, pr.S)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pr.d_ptr, n * 4, self._stream_handle))
+        cols = host[: 4 * pr.G * KS].reshape(pr.G, KS, 4).copy()
+        return cols, host[4 * pr.G * KS :].view(np.float32).reshape(pr.n_ranks, 1 + pr.S).copy()
 
     def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
         """What both routes of a history step share: the ring of ``state`` with room for this workspace's section ids (cold:
@@ -1321,6 +1451,22 @@ class HipRings:
         if rc < 0:
             _native.check(rc)
         out = ws._robust_last = Robust(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
+        return out
+
+    def report_peer(self, ws: Workspace, groups: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                    min_ranks: int = 2) -> Peer:
+        """Peer-group scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_peer``):
+        enqueued behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if groups.R != ws.R:
+            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
+        ws.peer_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
+        buf = ws.peer_buffers(groups.G, n_ranks)
+        rc = self.lib.nvrx_report_peer(self.ctx, ws.block.desc_ref, groups.device(self.backend).data_ptr(), groups.G,
+                                       first_rank, n_ranks, min_ranks, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._peer_last = Peer(self.backend, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks)
         return out
 
     def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,

@@ -31,7 +31,7 @@ class FoldedJob:
                  score_history: int = 0, persistence_min_reports: int = 3, persistence_thresholds=None,
                  score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6, trend_horizon=None,
                  collective_slack: bool = False, slack_min_ranks: int = 4, slack_min_share: float = 0.05,
-                 slack_max_ratio: float = 0.25, kernel_names: Sequence[str] = ()):
+                 slack_max_ratio: float = 0.25, kernel_names: Sequence[str] = (), peer_groups=None, peer_min_ranks: int = 2):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -56,7 +56,8 @@ class FoldedJob:
                                         trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
                                         trend_horizon=trend_horizon, collective_slack=collective_slack,
                                         slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                        slack_max_ratio=slack_max_ratio)
+                                        slack_max_ratio=slack_max_ratio, peer_groups=peer_groups,
+                                        peer_min_ranks=peer_min_ranks)
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         # (the same object every report so the reporter's cached plan stays valid)
         self._no_kernel_rows = {name: self.rings.row_for(_native.KIND_KERNEL, name) for name in self.kernel_names}

@@ -735,6 +735,90 @@ class _RobustSource:
         return self._built
 
 
+def _peer_spec(peer_groups):
+    """``ReportGenerator``'s ``peer_groups`` as the generator keeps it: None (off), a rule (``"block:N"``: label ``rank //
+    N``, contiguous stages; ``"mod:N"``: label ``rank % N``) or a tuple of ``int`` / ``str`` labels, one per logical rank.
+    Nothing else is accepted."""
+    if peer_groups is None:
+        return None
+    if isinstance(peer_groups, str):
+        kind, sep, num = peer_groups.partition(":")
+        if kind not in ("block", "mod") or not sep or not num.strip().isdigit():
+            raise ValueError(f"peer_groups must be 'block:N', 'mod:N' or a sequence of labels, got {peer_groups!r}")
+        n = int(num)
+        if n < 1:
+            raise ValueError(f"peer_groups={peer_groups!r}: N must be at least 1")
+        return _backend_mod._PeerRule((kind, n))
+    if not isinstance(peer_groups, (list, tuple, np.ndarray)):
+        raise TypeError("peer_groups must be 'block:N', 'mod:N' or a list, tuple or ndarray of int or str labels, "
+                        f"got {type(peer_groups).__name__}")
+    if isinstance(peer_groups, np.ndarray):
+        if peer_groups.ndim != 1:
+            raise ValueError(f"peer_groups must have one label per logical rank, got an array of shape {peer_groups.shape}")
+        peer_groups = peer_groups.tolist()
+    labels = []
+    for lab in peer_groups:
+        if isinstance(lab, bool) or not isinstance(lab, (int, np.integer, str)):
+            raise TypeError(f"peer_groups labels must be int or str, got {lab!r}")
+        labels.append(lab if isinstance(lab, str) else int(lab))
+    if not labels:
+        raise ValueError("peer_groups must have one label per logical rank, got none")
+    return tuple(labels)
+
+
+def _copy_peer(d):
+    """A private copy of a report's peer scores (plain dicts and lists all the way down)."""
+    if isinstance(d, dict):
+        return {k: _copy_peer(x) for k, x in d.items()}
+    return list(d) if isinstance(d, list) else d
+
+
+class _PeerSource:
+    """What a report keeps of its peer-group scores: the backend's handle (``records()`` waits for the kernels and copies the
+    column records and the scores out on first use), the ranks its rows stand for, the sections it shows with their ids,
+    the kernel names by id as the report's mapper had them at report time, the resolved groups and ``min_ranks``."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "groups", "min_ranks", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, groups, min_ranks: int):
+        self.handle, self.ranks, self.kernels = handle, tuple(ranks), kernels
+        self.groups, self.min_ranks = groups, min_ranks
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            cols, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks, labels, min_ranks = self.ranks, self.groups.labels, self.min_ranks
+            group = self.groups.group.tolist()
+            G = len(labels)
+            floor = np.ascontiguousarray(cols).view(np.float32)[:, :, 0].tolist()
+            present = cols[:, :, 1].tolist()
+            fastest = cols[:, :, 2].view(np.int32).tolist() if cols.size else []
+            sc = scores.tolist()
+
+            def referenced(values, c):
+                return {labels[g]: values[g][c] for g in range(G) if present[g][c] >= min_ranks}
+
+            with_data = {name: {labels[g]: present[g][k] for g in range(G)} for k, name in enumerate(self.kernels)}
+            with_data.update((name, {labels[g]: present[g][K + c] for g in range(G)}) for name, c in self.sections.items())
+            self._built = {
+                "groups": {labels[g]: self.groups.members(g) for g in range(G)},
+                "group_of": {r: labels[group[r]] for r in ranks},
+                "min_ranks": min_ranks,
+                "gpu_relative": {r: sc[i][0] for i, r in enumerate(ranks)},
+                "section_relative": {name: {r: sc[i][1 + c] for i, r in enumerate(ranks)} for name, c in self.sections.items()},
+                "section_floor": {name: referenced(floor, K + c) for name, c in self.sections.items()},
+                "section_fastest": {name: referenced(fastest, K + c) for name, c in self.sections.items()},
+                "kernel_floor": {name: referenced(floor, k) for k, name in enumerate(self.kernels)},
+                "ranks_with_data": with_data,
+                "unrated_ranks": [r for i, r in enumerate(ranks) if all(x != x for x in sc[i])],
+            }
+            self.handle = None
+        return self._built
+
+
 _HISTORY_FAMILIES = ((1, "relative"), (0, "individual"))  # (family word of the record, name) in the order the mappings are listed
 
 
@@ -961,6 +1045,9 @@ class Report:
         robust = self.__dict__.get("_robust")
         if robust is not None:
             state["_robust"] = robust.build() if isinstance(robust, _RobustSource) else robust
+        peer = self.__dict__.get("_peer")
+        if peer is not None:
+            state["_peer"] = peer.build() if isinstance(peer, _PeerSource) else peer
         history = self.__dict__.get("_history")
         if history is not None:
             state["_history"] = history.build() if isinstance(history, _HistorySource) else history
@@ -1117,6 +1204,33 @@ class Report:
         sr = {n: [r for r, z in v.items() if z > section_z_threshold] for n, v in t.get("section_z", {}).items()}
         return {"straggler_gpus_relative": self._ids(gr),
                 "straggler_sections_relative": {n: self._ids(r) for n, r in sr.items() if r}}
+
+    def peer_scores(self) -> Dict[str, Any]:
+        """Peer-group scores (``ReportGenerator(peer_groups=...)``; ``{}`` when the report carries none).  Every relative score
+        of a report divides the median of the fastest rank OF THE WHOLE JOB by this rank's; these take the fastest rank of the
+        rank's own group -- the ranks doing the same work: a pipeline stage, an expert group, a role -- as the reference.
+
+        ``{"groups": {label: [ranks]}`` (every logical rank of the job), ``"group_of": {rank: label}`` (this report's ranks),
+        ``"min_ranks": n, "gpu_relative": {rank: x}, "section_relative": {section: {rank: floor / median}}, "section_floor":
+        {section: {label: microseconds}}, "section_fastest": {section: {label: rank}}, "kernel_floor": {kernel: {label:
+        microseconds}}, "ranks_with_data": {section or kernel: {label: ranks of the group that have the row}},
+        "unrated_ranks": [ranks whose every score is NaN]}`` -- the GPU entries are the means of the per-kernel quotients
+        weighted by the microseconds spent in each kernel; NaN where a rank lacks the row or fewer than ``min_ranks`` ranks of
+        its group have it (a group appears under a floor only where it has one); a rank alone in its group has no peer and is
+        unrated at the default ``min_ranks`` of 2.  Plain dicts, lists, floats and ints.  The first call waits for the peer
+        kernels and copies their results; ``generate_report`` does not."""
+        peer = self.__dict__.get("_peer")
+        if peer is None:
+            return {}
+        if isinstance(peer, _PeerSource):
+            peer = self.__dict__["_peer"] = peer.build()
+        return _copy_peer(peer)
+
+    def identify_peer_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose PEER-GROUP scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no peer scores."""
+        return self._identify_relative(self.peer_scores(), gpu_rel_threshold, section_rel_threshold)
 
     def score_history(self) -> Dict[str, Any]:
         """The score history as it stood after this report (``ReportGenerator(score_history=H)``; ``{}`` when the report
@@ -1426,7 +1540,8 @@ class ReportGenerator:
                  persistence_min_reports: int = 3, persistence_thresholds: Optional[Sequence[float]] = None,
                  score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6,
                  trend_horizon: Optional[int] = None, collective_slack: bool = False, slack_min_ranks: int = 4,
-                 slack_min_share: float = 0.05, slack_max_ratio: float = 0.25) -> None:
+                 slack_min_share: float = 0.05, slack_max_ratio: float = 0.25, peer_groups=None,
+                 peer_min_ranks: int = 2) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1510,6 +1625,22 @@ class ReportGenerator:
                 raise RuntimeError(f"robust_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no robust scores (backend.robust_score)")
             self.robust_min_ranks, self.robust_floor = int(robust_min_ranks), floor
+        # peer-group scores: every report also rates each rank against the fastest rank of its own group -- the ranks doing the
+        # same work (Report.peer_scores); None = off: no buffer, no launch, no backend call.  They read the exchanged table
+        # only: no collective, so a mismatch between ranks cannot hang anything -- but every rank should pass the same value.
+        self.peer_groups = _peer_spec(peer_groups)  # None, a backend._PeerRule or a tuple of labels, one per logical rank
+        self._peer_resolved = None  # backend.PeerGroups for the R of the tables seen so far
+        if self.peer_groups is not None:
+            if isinstance(peer_min_ranks, bool) or not isinstance(peer_min_ranks, (int, np.integer)) or peer_min_ranks < 1:
+                raise ValueError(f"peer_min_ranks must be an integer >= 1, got {peer_min_ranks!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"peer_groups needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "peer-group scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "peer_score"):
+                raise RuntimeError(f"peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no peer-group scores (backend.peer_score)")
+            self.peer_min_ranks = int(peer_min_ranks)
         # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
         # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
         # call.  The step adds one collective per report, so EVERY rank must pass the same value.
@@ -1902,6 +2033,11 @@ class ReportGenerator:
             # likewise: enqueued behind the score kernel, waited for when the report is first asked
             self._attach_robust(report, _backend_mod.get_backend().robust_score(
                 ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor), ws, mapper, view)
+        if self.peer_groups is not None:
+            # likewise, behind the robust step
+            groups = self._peer_for(ws)
+            self._attach_peer(report, _backend_mod.get_backend().peer_score(
+                ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks), groups, ws, mapper, view)
         if self._history is not None:
             # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
             self._attach_history(report, _backend_mod.get_backend().score_history(
@@ -2054,6 +2190,8 @@ class ReportGenerator:
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
         if fused and self.robust_scores and not hasattr(rings, "report_robust"):
             raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
+        if fused and self.peer_groups is not None and not hasattr(rings, "report_peer"):
+            raise RuntimeError("peer_groups: these rings run the one-call report but have no report_peer")
         if fused and self._history is not None and not hasattr(rings, "report_history"):
             raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
         if fused and self.score_trends and not hasattr(rings, "report_trend"):
@@ -2081,6 +2219,8 @@ class ReportGenerator:
                     self._attach_plan_attribution(report, plan, rings, True)
                 if self.robust_scores:
                     self._attach_plan_robust(report, plan, rings, True)
+                if self.peer_groups is not None:
+                    self._attach_plan_peer(report, plan, rings, True)
                 if self._history is not None:
                     self._attach_plan_history(report, plan, rings, True)
                 return report
@@ -2117,6 +2257,8 @@ class ReportGenerator:
             self._attach_plan_attribution(report, plan, rings, fused)
         if self.robust_scores:
             self._attach_plan_robust(report, plan, rings, fused)
+        if self.peer_groups is not None:
+            self._attach_plan_peer(report, plan, rings, fused)
         if self._history is not None:
             self._attach_plan_history(report, plan, rings, fused)
         return report
@@ -2154,6 +2296,31 @@ class ReportGenerator:
         else:
             handle = _backend_mod.get_backend().robust_score(ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor)
         self._attach_robust(report, handle, ws, plan.mapper, plan.view)
+
+    # ---- peer-group scores --------------------------------------------------------------------------
+    def _peer_for(self, ws):
+        """The groups resolved for the logical ranks of ``ws``' table (cold: once per R; a label list of another length
+        is refused here, where R is first known)."""
+        groups = self._peer_resolved
+        if groups is None or groups.R != ws.R:
+            groups = self._peer_resolved = _backend_mod.PeerGroups.resolve(self.peer_groups, ws.R)
+        return groups
+
+    def _attach_peer(self, report, handle, groups, ws, mapper, view) -> None:
+        report.__dict__["_peer"] = _PeerSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), groups,
+                                               self.peer_min_ranks)
+
+    def _attach_plan_peer(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the peer-group scores of the planned report that was just issued, as ``_attach_plan_robust`` does, for the
+        ranks the report covers, and hang them on ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        lo, hi = plan.view.layout[5], plan.view.layout[6]
+        groups = self._peer_for(ws)
+        if fused:
+            handle = rings.report_peer(ws, groups, lo, hi - lo, self.peer_min_ranks)
+        else:
+            handle = _backend_mod.get_backend().peer_score(ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks)
+        self._attach_peer(report, handle, groups, ws, plan.mapper, plan.view)
 
     # ---- score history ------------------------------------------------------------------------------
     def _attach_history(self, report, handle, view) -> None:

@@ -162,6 +162,8 @@ class _Lane:
             return None  # (a row family's step follows the report in the generator's paths: DESIGN.md, "Row families")
         if getattr(reporter, "robust_scores", False):
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
+        if getattr(reporter, "peer_groups", None) is not None:
+            return None  # (the peer launch follows the report in the generator's planned path: DESIGN.md, "Peer-group scores")
         if getattr(reporter, "score_history", 0):
             return None  # (the history step follows the report in the generator's planned path: DESIGN.md, "Score history")
         if getattr(reporter, "collective_slack", False):
@@ -296,6 +298,21 @@ class _Lane:
         return rep
 
 
+def _peer_groups_from_env(value: str):
+    """``NVRX_PEER_GROUPS``: ``block:N``, ``mod:N`` or a comma-separated list of integer labels, one per logical rank; unset
+    or empty: None (off)."""
+    value = value.strip()
+    if not value:
+        return None
+    if ":" in value:
+        return value  # (ReportGenerator checks the rule)
+    try:
+        return [int(x) for x in value.split(",")]
+    except ValueError:
+        raise ValueError("NVRX_PEER_GROUPS must be 'block:N', 'mod:N' or a comma-separated list of integers, "
+                         f"got {value!r}") from None
+
+
 class _DeviceSideOnDemand(type):
     """``Detector.rings`` and ``Detector.cupti_manager`` -- everything that lives on a GPU -- come into being the first
     time they are touched, on the device that is current THEN.  The reference's own example initialises the detector
@@ -410,6 +427,8 @@ class Detector(metaclass=_DeviceSideOnDemand):
         slack_min_ranks: int = 4,
         slack_min_share: float = 0.05,
         slack_max_ratio: float = 0.25,
+        peer_groups=None,
+        peer_min_ranks: Optional[int] = None,
     ):
         """
         Args:
@@ -508,6 +527,15 @@ class Detector(metaclass=_DeviceSideOnDemand):
             slack_min_share, slack_max_ratio: the rule of ``identify_slack_stragglers``: the typical rank waits at least
                 this share of its traced GPU time, and the named rank at most this fraction of the typical wait.  4, 0.05 and
                 0.25 are defaults, not measurements.
+            peer_groups: which ranks do the SAME WORK -- a pipeline stage, an expert group, a role: every report also rates
+                each rank against the fastest rank of its own group instead of the fastest of the whole job
+                (``Report.peer_scores()``, ``Report.identify_peer_stragglers()``), so that the healthy ranks of a slower
+                stage are not named.  A list, tuple or ndarray of ``int`` or ``str`` labels, one per LOGICAL rank of the job,
+                or ``"block:N"`` (label ``rank // N``: contiguous stages) or ``"mod:N"`` (label ``rank % N``).  Needs
+                ``relative_perf_scores``.  Default: ``NVRX_PEER_GROUPS`` (``block:N``, ``mod:N`` or a comma-separated list
+                of integers), else off.  Same value on every rank (no collective depends on it).
+            peer_min_ranks: ranks of a group that must have a section or kernel for the group to have a reference; at the
+                default of 2 (``NVRX_PEER_MIN_RANKS``) a rank alone in its group has no peer and is unrated, not rated 1.0.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -582,6 +610,16 @@ class Detector(metaclass=_DeviceSideOnDemand):
             trend_min_reports = 6
             if isinstance(score_history, int) and 4 <= score_history < 6:
                 trend_min_reports = score_history  # (a history of four reports cannot hold six)
+        peer_options = {}  # (off: the generator is built exactly as before)
+        if peer_groups is None:
+            peer_groups = _peer_groups_from_env(os.environ.get("NVRX_PEER_GROUPS", ""))
+        if peer_groups is not None:
+            if peer_min_ranks is None:
+                try:
+                    peer_min_ranks = int(os.environ.get("NVRX_PEER_MIN_RANKS", "") or 2)
+                except ValueError:
+                    raise ValueError("NVRX_PEER_MIN_RANKS must be an integer >= 1") from None
+            peer_options = {"peer_groups": peer_groups, "peer_min_ranks": peer_min_ranks}
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -595,7 +633,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                       slack_max_ratio=slack_max_ratio)
+                                       slack_max_ratio=slack_max_ratio, **peer_options)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
