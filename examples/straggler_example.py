@@ -73,6 +73,12 @@ usual time and the step lasts as long on every rank, so ``identify_stragglers`` 
 1 % noise, seed 29): ranks 0-3 run a stage of 1000 us, ranks 4-7 one of 1500 us, and rank 6 is 1.4x slower than its stage's
 peers.  ``identify_stragglers`` names ranks 4-7, three of them healthy; with peer groups (``ReportGenerator(peer_groups=
 "block:4")``) ``identify_peer_stragglers`` names rank 6 alone, and both scores are printed side by side.
+
+``--pace`` needs no training loop either: it plays one report of a job of 8 ranks x 120 kernels (folded onto one GPU, lognormal
+kernel times, 1 % noise per entry, seed 2026, 200 calls of every kernel) in which rank 5 is 4 % slower in EVERY kernel -- a card
+held a clock step down.  Its relative GPU score reads about 0.95 and its robust z about 2: ``identify_stragglers`` and
+``identify_robust_stragglers`` name nobody; with pace scores (``ReportGenerator(pace_scores=True)``) the report says that rank
+5 is slower than the job's median in 120 of 120 kernels, and ``identify_pace_stragglers`` names it alone.
 """
 import argparse
 import os
@@ -373,6 +379,43 @@ def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 
         job.close()
 
 
+def pace(ranks: int = 8, kernels: int = 120, calls: int = 200, slow_rank: int = 5, slowdown: float = 1.04) -> None:
+    """A rank that is a little slower in everything: whom the threshold rules name, and whom the pace scores do."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    names = [f"kernel_{k:03d}" for k in range(kernels)]
+    job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                    kernel_names=names, robust_scores=True, pace_scores=True)
+    rng = np.random.default_rng(2026)
+    med = rng.lognormal(np.log(100.0), 0.5, kernels)[None, :] * (1.0 + 0.01 * rng.standard_normal((ranks, kernels)))
+    med[slow_rank] *= slowdown
+    med = med.astype(np.float32)
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, np.full((1, calls), med[r].sum(), dtype=np.float32))
+            job.load_kernels(lr, np.repeat(med[r][:, None], calls, axis=1))
+        report = job.report()
+        t = report.pace_scores()
+        robust = report.robust_scores()
+        print(f"identify_stragglers(): {named(report.identify_stragglers())}")
+        print(f"identify_robust_stragglers(): {named(report.identify_robust_stragglers())}")
+        print(f"identify_pace_stragglers(): {named(report.identify_pace_stragglers())}; rule {t['params']}")
+        for r in sorted(t["ranks"]):
+            gpu = t["ranks"][r]["gpu"]
+            print(f"  rank {r}: relative GPU score {report.gpu_relative_perf_scores[r]:.3f}, robust z {robust['gpu_z'][r]:+.2f}, "
+                  f"pace {gpu['pace']:.3f} (spread {gpu['spread']:.3f}), slower / faster than the job's median in "
+                  f"{gpu['slower']} / {gpu['faster']} of {gpu['columns']} kernels, {gpu['excess_us']:+.0f} us above its pace")
+    finally:
+        job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -400,7 +443,13 @@ def main() -> None:
     ap.add_argument("--peer", action="store_true",
                     help="no training: play the peer-group scenario (two pipeline stages of different length, one rank slow "
                          "within its stage) and exit")
+    ap.add_argument("--pace", action="store_true",
+                    help="no training: play the pace-score scenario (a rank 4 %% slower in every one of its 120 kernels) and "
+                         "exit")
     args = ap.parse_args()
+    if args.pace:
+        pace()
+        return
     if args.slack:
         slack()
         return

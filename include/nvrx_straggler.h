@@ -370,6 +370,46 @@ int nvrx_robust_score(const float *d_table, int R, int K, int S, int first_rank,
 int nvrx_peer_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int first_rank, int n_ranks,
                     int min_ranks, void *d_out, void *stream);
 
+/* Pace scores: the rank that is a LITTLE slower in nearly all of its kernels.  Every score above asks whether some row of a
+ * rank is much slower than a reference; a card held a clock step down, a throttling HBM stack or a marginal power rail loses
+ * 3-5 % on every kernel, which no threshold on one row and no weighted mean of per-kernel z sees.  Being slower than the job's
+ * median in 120 of 120 kernels does not happen by chance: here an order statistic ACROSS a rank's columns says so.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_ROBUST_MAX_RANKS.  A column c < K is a kernel id, K <= c < K+S a section id;
+ *   v = table[r][c] is PRESENT iff v >= 0 (the -1 sentinel and NaN are absent, as in the robust scores).
+ *   Per column:
+ *      n      present values;
+ *      ctr    their LOWER median: the element of rank (n-1) >> 1 sorted by raw bit pattern (-0.0 < +0.0 < ... < +inf): exactly
+ *             the robust scores' ctr;
+ *      the column is REFERENCED iff n >= min_ranks;
+ *      above  present values whose key is greater than ctr's, below those whose key is less (both 0 at n = 0);
+ *      record, 16 bytes: {f32 ctr (the canonical NaN 0x7FC00000 where not referenced), u32 n, u32 above, u32 below}; the three
+ *      counts are always written.
+ *   Per reported rank r in [first_rank, first_rank + n_ranks) and part p (0: the kernel columns, 1: the section columns); a
+ *   column of the part is ELIGIBLE iff r is present in it and it is referenced:
+ *      q_c      (float)((double)ctr_c / (double)v_c): above 1 = faster than the job's median.  The IEEE result is kept: v = 0
+ *               gives +inf, or NaN where ctr is 0 too;
+ *      columns  eligible columns;
+ *      slower   those whose key of v is greater than the key of ctr, faster those where it is less;
+ *      pace     the lower median of the q_c that are not NaN: rank (m-1) >> 1 by key over those m values, an actual quotient;
+ *               NaN at m = 0;
+ *      spread   the lower median of fabsf(q_c - pace) over the same m values (f32; a NaN deviation orders above +inf);
+ *      part 0 only, in f64 with w_c = table[r][2(K+S) + c]:
+ *      total_us   sum of w_c over the eligible columns;
+ *      slower_us  sum of w_c over the slower columns;
+ *      excess_us  sum of w_c * (1 - (double)ctr_c / (double)v_c) over the eligible columns with a non-NaN q_c: the
+ *                 microseconds this rank spent above the job's median pace in the window (signed);
+ *      part 1 writes +0.0 in these three slots;
+ *      record, 32 bytes: {f32 pace, f32 spread, u32 columns, u32 slower, u32 faster, f32 total_us, f32 slower_us,
+ *      f32 excess_us}.
+ *   pace, spread and every count are exact: no sum, and no rounding beyond one f64 quotient and one f32 subtraction.  The three
+ *   sums are taken across a workgroup: their last bits depend on that order.
+ *   d_out  16-byte aligned, NVRX_PACE_WORDS(n_ranks, K, S) 32-bit words: K+S column records, then [n_ranks][2] rank records.
+ * Two launches on `stream` (columns, ranks); no atomics on global memory, no scratch.  Argument errors, reported before any
+ * device is touched: those of nvrx_robust_score in its order, without floor_rel. */
+#define NVRX_PACE_WORDS(n_ranks, K, S) (4 * ((size_t)(K) + (S)) + 16 * (size_t)(n_ranks))
+int nvrx_pace_score(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks, void *d_out,
+                    void *stream);
+
 /* Score history: how each score behaved over the last H reports.  Every score above looks inside one report window; the one
  * thing a report carries over from its predecessors is the running minimum of MED.  Here a device ring keeps the last H
  * reports' scores per reported rank, family f (0 individual, 1 relative: the parity of the score row's first two columns)
@@ -698,6 +738,12 @@ int nvrx_report_robust(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_ra
  * before the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_peer(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int first_rank, int n_ranks,
                      int min_ranks, void *d_out);
+/* nvrx_pace_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as nvrx_report_robust orders itself: the
+ * context's stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a
+ * D2H on the context's stream, and do not let a later report rewrite the table before the kernels have run.  NVRX_ERR_STATE:
+ * no report was issued through this descriptor. */
+int nvrx_report_pace(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int min_ranks, void *d_out);
 /* nvrx_score_history (above) on the result block of the report LAST issued through `desc` on `ctx` (desc->d_scores; R and S
  * from the descriptor).  Ordered behind that report's last kernel exactly as nvrx_report_robust orders itself: the context's
  * stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a D2H on the

@@ -60,15 +60,56 @@ __device__ __forceinline__ int robust_wave_select(uint32_t key, bool present, un
     return __ffsll((long long)hit) - 1;
 }
 
+// What every pass of a radix select does once its histogram is complete (the caller's barrier is behind it): thread sums, a
+// scan over the workgroup, and the one thread whose stretch holds rank k names the bin.  Returns that bin; k becomes the rank
+// inside it.  Every thread of the workgroup calls it (two barriers inside; s_sel and s_wave are rewritten only behind the next
+// pass' two barriers).
+template <int THREADS>
+__device__ __forceinline__ uint32_t radix_pick(const uint32_t *s_hist, uint32_t *s_wave, uint32_t *s_sel, uint32_t &k) {
+    constexpr int WAVES = THREADS / 64;
+    constexpr int PER = TAIL_BINS / THREADS;
+    static_assert(PER % 4 == 0, "a thread's bins are read as 16-byte words");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t h[PER];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < PER; j += 4) {
+        const uint4 q = reinterpret_cast<const uint4 *>(s_hist)[(tid * PER + j) >> 2];
+        h[j] = q.x, h[j + 1] = q.y, h[j + 2] = q.z, h[j + 3] = q.w;
+        mine += q.x + q.y + q.z + q.w;
+    }
+    const uint32_t incl = wave_scan_u32(mine);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t below = incl - mine;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) below += w < wave ? s_wave[w] : 0u;
+    if (k >= below && k < below + mine) {  // exactly one thread
+        uint32_t b = 0, acc = below;
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            const bool adv = !found && k >= acc + h[j];
+            acc += adv ? h[j] : 0u;
+            b += adv ? 1u : 0u;
+            found = found || !adv;
+        }
+        s_sel[0] = (uint32_t)(tid * PER) + b;
+        s_sel[1] = acc;
+    }
+    __syncthreads();
+    const uint32_t bin = uni(s_sel[0]);
+    k -= uni(s_sel[1]);
+    return bin;
+}
+
 // three-pass radix select over the column's present entries: the key of rank k.  `dev`: keys are robust_dev_bits(v, ctr),
 // else f2key(v).  Every thread of the workgroup calls it with the same arguments (barriers inside).
 template <int THREADS, bool DEV>
 __device__ __forceinline__ uint32_t robust_radix_select(const float *__restrict__ col, int R, int L, float v0, float ctr,
                                                         uint32_t k, uint32_t *s_hist, uint32_t *s_wave, uint32_t *s_sel) {
-    constexpr int WAVES = THREADS / 64;
     constexpr int PER = TAIL_BINS / THREADS;
-    static_assert(PER % 4 == 0, "a thread's bins are read as 16-byte words");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     uint32_t prefix = 0;
 #pragma unroll 1
     for (int pass = 0; pass < 3; pass++) {
@@ -85,36 +126,7 @@ __device__ __forceinline__ uint32_t robust_radix_select(const float *__restrict_
             tail_hist_add(s_hist, (key >> shift) & bmask, on);
         }
         __syncthreads();
-        uint32_t h[PER];
-        uint32_t mine = 0;
-#pragma unroll
-        for (int j = 0; j < PER; j += 4) {
-            const uint4 q = reinterpret_cast<const uint4 *>(s_hist)[(tid * PER + j) >> 2];
-            h[j] = q.x, h[j + 1] = q.y, h[j + 2] = q.z, h[j + 3] = q.w;
-            mine += q.x + q.y + q.z + q.w;
-        }
-        const uint32_t incl = wave_scan_u32(mine);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t below = incl - mine;
-#pragma unroll
-        for (int w = 0; w < WAVES; w++) below += w < wave ? s_wave[w] : 0u;
-        if (k >= below && k < below + mine) {  // exactly one thread
-            uint32_t b = 0, acc = below;
-            bool found = false;
-#pragma unroll
-            for (int j = 0; j < PER; j++) {
-                const bool adv = !found && k >= acc + h[j];
-                acc += adv ? h[j] : 0u;
-                b += adv ? 1u : 0u;
-                found = found || !adv;
-            }
-            s_sel[0] = (uint32_t)(tid * PER) + b;
-            s_sel[1] = acc;
-        }
-        __syncthreads();
-        const uint32_t bin = uni(s_sel[0]);
-        k -= uni(s_sel[1]);
+        const uint32_t bin = radix_pick<THREADS>(s_hist, s_wave, s_sel, k);
         prefix = pass == 2 ? ((prefix << 8) | bin) : ((prefix << 12) | bin);
         // (s_sel and s_wave are rewritten only behind the next pass' two barriers)
     }

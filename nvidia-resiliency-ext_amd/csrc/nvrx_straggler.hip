@@ -3969,3 +3969,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_period.inl"
 #include "nvrx_episode.inl"
 #include "nvrx_peer.inl"
+#include "nvrx_pace.inl"

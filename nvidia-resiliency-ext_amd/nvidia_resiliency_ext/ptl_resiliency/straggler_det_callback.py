@@ -50,6 +50,7 @@ class StragglerDetectionCallback(Callback):
         warn_if_declining: bool = False,
         warn_if_waited_for: bool = False,
         peer_groups=None,
+        warn_if_off_pace: bool = False,
     ):
         """
         Args:
@@ -82,10 +83,15 @@ class StragglerDetectionCallback(Callback):
                 ``Report.identify_peer_stragglers`` -- each rank against the fastest rank of its own group -- so that the
                 healthy ranks of a slower pipeline stage do not stop the job.  Ranks without a peer are unrated; they are
                 logged once.  The individual family is untouched.
+            warn_if_off_pace: False (the default): nothing changes.  True: the detector also computes pace scores
+                (``Detector.initialize(pace_scores=True)``), and every report that finds a GPU a little slower than the job's
+                median in nearly all of its kernels (``Report.identify_pace_stragglers``: a degraded card, which no threshold
+                on one score sees) logs one warning that names the ranks with their pace and the microseconds they spent
+                above the job's median pace.  A warning only: it never stops the job.
 
         Raises:
             ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64],
-                ``warn_if_waited_for`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
+                ``warn_if_waited_for``, ``warn_if_off_pace`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
                 ``min_consecutive_reports`` > 1 (the score history does not hold peer scores).
         """
         self.initialized = False
@@ -117,6 +123,9 @@ class StragglerDetectionCallback(Callback):
         self.warn_if_waited_for = bool(warn_if_waited_for)
         if self.warn_if_waited_for and not calc_relative_gpu_perf:
             raise ValueError("warn_if_waited_for needs calc_relative_gpu_perf=True: slack scores compare ranks")
+        self.warn_if_off_pace = bool(warn_if_off_pace)
+        if self.warn_if_off_pace and not calc_relative_gpu_perf:
+            raise ValueError("warn_if_off_pace needs calc_relative_gpu_perf=True: pace scores compare ranks")
         self.peer_groups = peer_groups
         if peer_groups is not None:
             if not calc_relative_gpu_perf:
@@ -146,6 +155,8 @@ class StragglerDetectionCallback(Callback):
             persistence["collective_slack"] = True
         if self.peer_groups is not None:
             persistence["peer_groups"] = self.peer_groups
+        if self.warn_if_off_pace:
+            persistence["pace_scores"] = True
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -174,6 +185,8 @@ class StragglerDetectionCallback(Callback):
             self._warn_declining(report)  # (a warning only: `found`, and with it the halt, does not depend on it)
         if self.warn_if_waited_for and bool(report) and trainer.global_rank == 0:
             self._warn_waited_for(report)  # (likewise)
+        if self.warn_if_off_pace and bool(report) and trainer.global_rank == 0:
+            self._warn_off_pace(report)  # (likewise)
         if not detector.is_interval_elapsed():
             return  # no report was due this iteration
         if self.stop_if_detected and self._decision_of_rank0(found):
@@ -258,6 +271,22 @@ class StragglerDetectionCallback(Callback):
         self.logger.warning("STRAGGLER DETECTION WARNING: The job waits for some GPUs in its collectives (slow host?): "
                             + "; ".join(parts) + f"; the typical rank spends {100 * scores['typical_share']:.1f} % of its "
                             "traced GPU time waiting")
+
+    def _warn_off_pace(self, report) -> None:
+        """One warning per report that names the GPUs that are a little slower than the job's median in nearly all of their
+        kernels, with their pace and the microseconds spent above the median pace (``warn_if_off_pace``).  Never a reason to
+        halt."""
+        named = report.identify_pace_stragglers()["straggler_gpus_relative"]
+        if not named:
+            return
+        ranks = report.pace_scores()["ranks"]
+        parts = []
+        for rank in sorted(getattr(s, "rank", s) for s in named):
+            gpu = ranks[rank]["gpu"]
+            parts.append(f"rank {rank} (pace {gpu['pace']:.3f}, slower in {gpu['slower']} of {gpu['columns']} kernels, "
+                         f"excess_us={gpu['excess_us']:.0f})")
+        self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs are a little slower in nearly all of their kernels "
+                            "(degraded card?): " + "; ".join(parts))
 
     def _name_the_kernels(self, report, flagged) -> None:
         """Kernel attribution (``NVRX_KERNEL_ATTRIBUTION=N``, off by default: nothing is logged then): for every flagged GPU the

@@ -97,6 +97,7 @@ SYMBOLS = [
     ("nvrx_episode_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
@@ -141,6 +142,7 @@ SYMBOLS = [
     ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
@@ -244,6 +246,11 @@ def robust_words(n_ranks: int, K: int, S: int) -> int:
 def peer_words(G: int, n_ranks: int, K: int, S: int) -> int:
     """NVRX_PEER_WORDS: 32-bit words of a peer-score block: ``[G][K+S][4]`` column records, then ``[n_ranks][1 + S]``."""
     return 4 * G * (K + S) + n_ranks * (1 + S)
+
+
+def pace_words(n_ranks: int, K: int, S: int) -> int:
+    """NVRX_PACE_WORDS: 32-bit words of a pace-score block: ``[K+S][4]`` column records, then ``[n_ranks][2][8]``."""
+    return 4 * (K + S) + 16 * n_ranks
 
 
 def history_stride(H: int) -> int:

@@ -390,6 +390,35 @@ class Peer:
         return self._host
 
 
+class Pace:
+    """Pace scores of one report (``nvrx_pace_score`` / ``nvrx_report_pace``), enqueued and not waited for: once the kernels
+    have run, the workspace's device buffer holds the ``K + S`` column records ``{ctr, n, above, below}`` and, behind them,
+    ``[n_ranks][2]`` rank records ``{pace, spread, columns, slower, faster, total_us, slower_us, excess_us}`` of the reported
+    ranks (include/nvrx_straggler.h).  ``records()`` waits for them and takes the private host copy (one ordered D2H on the
+    backend's stream): when a ``Report`` first asks, or -- ``Workspace.pace_settle`` -- before the next report on the same
+    workspace rewrites the table the kernels read and the buffer they write."""
+
+    __slots__ = ("backend", "d_ptr", "K", "S", "first_rank", "n_ranks", "min_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, K: int, S: int, first_rank: int, n_ranks: int, min_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.K, self.S = K, S
+        self.first_rank, self.n_ranks, self.min_ranks = first_rank, n_ranks, min_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(cols [K+S, 4] uint32, ranks [n_ranks, 2, 8] uint32)`` (private copies; the float fields are bit patterns); the
+        first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.pace_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class ScoreHistory:
     """The score history of one ``ReportGenerator`` (``nvrx_score_history`` / ``nvrx_report_history``): the ring of the last
     ``depth`` reports' scores -- ``hist``, f32 ``[n_ranks][2][1 + S_cap][stride]`` where the backend keeps it, NaN where
@@ -674,6 +703,8 @@ class Workspace:
             self.robust_settle()
         if self._peer_last is not None:
             self.peer_settle()
+        if self._pace_last is not None:
+            self.pace_settle()
         if self._family_state:
             for fam in FAMILIES[1:]:
                 self.family_settle(fam)
@@ -742,6 +773,25 @@ class Workspace:
         """Before anything rewrites this workspace's table: the last peer step's kernels have run and their results are on
         the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
         last, self._peer_last = self._peer_last, None
+        if last is not None:
+            last.records()
+
+    # ---- pace scores (off unless a ReportGenerator asks: nothing is allocated before) ------------------------------
+    _pace_buf = None   # device: column records, then the rank records of the last pace step of this workspace's table
+    _pace_last = None  # the Pace whose kernels may still be reading the table / writing _pace_buf
+
+    def pace_buffers(self, n_ranks: int):
+        """The records buffer for pace scores of ``n_ranks`` ranks (cold: allocated once per shape)."""
+        words = _native.pace_words(n_ranks, self.K, self.S)
+        if self._pace_buf is None or self._pace_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._pace_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return self._pace_buf
+
+    def pace_settle(self) -> None:
+        """Before anything rewrites this workspace's table: the last pace step's kernels have run and their results are on
+        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._pace_last = self._pace_last, None
         if last is not None:
             last.records()
 
@@ -1049,6 +1099,29 @@ class HipBackend:
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pr.d_ptr, n * 4, self._stream_handle))
         cols = host[: 4 * pr.G * KS].reshape(pr.G, KS, 4).copy()
         return cols, host[4 * pr.G * KS :].view(np.float32).reshape(pr.n_ranks, 1 + pr.S).copy()
+
+    def pace_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
+                   min_ranks: int = 4) -> Pace:
+        """Pace scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank + n_ranks)``:
+        ``nvrx_pace_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        ws.pace_settle()
+        buf = ws.pace_buffers(n_ranks)
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_pace_score(table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks, min_ranks, buf.data_ptr(),
+                                      self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._pace_last = Pace(self, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks)
+        return out
+
+    def pace_copy_out(self, pc: Pace):
+        """The one wait of a report's pace scores: a D2H of the records on the backend's stream, behind the kernels."""
+        KS = pc.K + pc.S
+        n = _native.pace_words(pc.n_ranks, pc.K, pc.S)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pc.d_ptr, n * 4, self._stream_handle))
+        return host[: 4 * KS].reshape(KS, 4).copy(), host[4 * KS :].reshape(pc.n_ranks, 2, 8).copy()
 
     def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
         """What both routes of a history step share: the ring of ``state`` with room for this workspace's section ids (cold:
@@ -1467,6 +1540,18 @@ class HipRings:
         if rc < 0:
             _native.check(rc)
         out = ws._peer_last = Peer(self.backend, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks)
+        return out
+
+    def report_pace(self, ws: Workspace, first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 4) -> Pace:
+        """Pace scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_pace``): enqueued
+        behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        ws.pace_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
+        buf = ws.pace_buffers(n_ranks)
+        rc = self.lib.nvrx_report_pace(self.ctx, ws.block.desc_ref, first_rank, n_ranks, min_ranks, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._pace_last = Pace(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks)
         return out
 
     def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,

@@ -735,6 +735,48 @@ class _RobustSource:
         return self._built
 
 
+class _PaceSource:
+    """What a report keeps of its pace scores: the backend's handle (``records()`` waits for the kernels and copies the column
+    and rank records out on first use), the ranks its rows stand for, the sections it shows with their ids, the kernel names
+    by id as the report's mapper had them at report time, and the parameters in force."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "params", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, params: dict):
+        self.handle, self.ranks, self.kernels, self.params = handle, tuple(ranks), kernels, params
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            cols, recs = self.handle.records()
+            K = len(self.kernels)
+            center = np.ascontiguousarray(cols).view(np.float32)[:, 0].tolist()
+            counts = cols[:, 1:].tolist()
+            recs = np.ascontiguousarray(recs)
+            f, u = recs.view(np.float32).tolist(), recs.tolist()
+
+            def part(i, p):
+                columns, slower = u[i][p][2], u[i][p][3]
+                d = {"pace": f[i][p][0], "spread": f[i][p][1], "columns": columns, "slower": slower, "faster": u[i][p][4],
+                     "breadth": slower / columns if columns else None}
+                if p == 0:
+                    d.update(total_us=f[i][p][5], slower_us=f[i][p][6], excess_us=f[i][p][7])
+                return d
+
+            def column(c):
+                return {"center": center[c], "ranks": counts[c][0], "above": counts[c][1], "below": counts[c][2]}
+
+            self._built = {
+                "ranks": {r: {"gpu": part(i, 0), "sections": part(i, 1)} for i, r in enumerate(self.ranks)},
+                "kernels": {name: column(k) for k, name in enumerate(self.kernels)},
+                "section_columns": {name: column(K + g) for name, g in self.sections.items()},
+                "params": dict(self.params),
+            }
+            self.handle = None
+        return self._built
+
+
 def _peer_spec(peer_groups):
     """``ReportGenerator``'s ``peer_groups`` as the generator keeps it: None (off), a rule (``"block:N"``: label ``rank //
     N``, contiguous stages; ``"mod:N"``: label ``rank % N``) or a tuple of ``int`` / ``str`` labels, one per logical rank.
@@ -1048,6 +1090,9 @@ class Report:
         peer = self.__dict__.get("_peer")
         if peer is not None:
             state["_peer"] = peer.build() if isinstance(peer, _PeerSource) else peer
+        pace = self.__dict__.get("_pace")
+        if pace is not None:
+            state["_pace"] = pace.build() if isinstance(pace, _PaceSource) else pace
         history = self.__dict__.get("_history")
         if history is not None:
             state["_history"] = history.build() if isinstance(history, _HistorySource) else history
@@ -1231,6 +1276,53 @@ class Report:
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no peer scores."""
         return self._identify_relative(self.peer_scores(), gpu_rel_threshold, section_rel_threshold)
+
+    def pace_scores(self) -> Dict[str, Any]:
+        """Pace scores (``ReportGenerator(pace_scores=True)``; ``{}`` when the report carries none).  Every other score asks
+        whether some row of a rank is MUCH slower than a reference; these ask whether a rank is a LITTLE slower in nearly all of
+        its kernels -- a card held a clock step down, a throttling HBM stack, a marginal power rail.  Per kernel and section
+        the reference is the job's lower median; a rank's ``pace`` is the lower median, across its columns, of median / own
+        (above 1: faster than the job's median), ``spread`` the median absolute deviation of those quotients around it.
+
+        ``{"ranks": {rank: {"gpu": {...}, "sections": {...}}}, "kernels": {kernel: {...}}, "section_columns": {section: {...}},
+        "params": {"min_ranks", "min_columns", "min_effect", "min_breadth"}}`` -- a rank's ``gpu`` (its kernel columns) and
+        ``sections`` parts hold ``pace``, ``spread``, ``columns`` (those where the rank has data and at least ``min_ranks``
+        ranks do), ``slower`` / ``faster`` (columns where it is above / below the job's median), ``breadth`` (``slower /
+        columns``, None at 0) and, for ``gpu``, ``total_us``, ``slower_us`` (microseconds in all / in the slower columns) and
+        ``excess_us`` (microseconds spent above the job's median pace in the window, signed).  A kernel or section holds the
+        column's ``center`` (NaN where fewer than ``min_ranks`` ranks have it), ``ranks`` with data and how many of them are
+        ``above`` / ``below`` the center.  NaN where a part has no column.  Plain dicts, floats and ints.  The first call waits
+        for the pace kernels and copies their results; ``generate_report`` does not."""
+        pace = self.__dict__.get("_pace")
+        if pace is None:
+            return {}
+        if isinstance(pace, _PaceSource):
+            pace = self.__dict__["_pace"] = pace.build()
+        return _copy_scores(pace)
+
+    def identify_pace_stragglers(self, min_effect: Optional[float] = None, min_breadth: Optional[float] = None,
+                                 min_columns: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks that are a little slower in nearly everything: a part of a rank (its kernels, its sections) is named iff it
+        has at least ``min_columns`` columns, its ``pace`` is at most ``1 - min_effect`` and it is slower than the job's median
+        in at least ``min_breadth`` of them (NaN never names).  Both an effect size and breadth: a healthy rank whose silicon
+        is 1 % slow is also slower in nearly every kernel.  ``{'straggler_gpus_relative': set[StragglerId],
+        'straggler_section_ranks_relative': set[StragglerId]}``; the defaults are the generator's (8, 0.03 and 0.9 unless
+        told otherwise: defaults, not measurements).  Empty sets when the report carries no pace scores."""
+        t = self.pace_scores()
+        if not t:
+            return {"straggler_gpus_relative": set(), "straggler_section_ranks_relative": set()}
+        params = t["params"]
+        effect = params["min_effect"] if min_effect is None else min_effect
+        breadth = params["min_breadth"] if min_breadth is None else min_breadth
+        columns = params["min_columns"] if min_columns is None else min_columns
+
+        def named(part):
+            return [r for r, d in t["ranks"].items()
+                    if d[part]["columns"] >= columns and d[part]["columns"] > 0 and d[part]["pace"] <= 1.0 - effect
+                    and d[part]["slower"] / d[part]["columns"] >= breadth]
+
+        return {"straggler_gpus_relative": self._ids(named("gpu")),
+                "straggler_section_ranks_relative": self._ids(named("sections"))}
 
     def score_history(self) -> Dict[str, Any]:
         """The score history as it stood after this report (``ReportGenerator(score_history=H)``; ``{}`` when the report
@@ -1541,7 +1633,8 @@ class ReportGenerator:
                  score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6,
                  trend_horizon: Optional[int] = None, collective_slack: bool = False, slack_min_ranks: int = 4,
                  slack_min_share: float = 0.05, slack_max_ratio: float = 0.25, peer_groups=None,
-                 peer_min_ranks: int = 2) -> None:
+                 peer_min_ranks: int = 2, pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8,
+                 pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1641,6 +1734,33 @@ class ReportGenerator:
                 raise RuntimeError(f"peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no peer-group scores (backend.peer_score)")
             self.peer_min_ranks = int(peer_min_ranks)
+        # pace scores: every report also says whether a rank is a little slower in nearly all of its kernels
+        # (Report.pace_scores); off: no buffer, no launch, no backend call.  They read the exchanged table only: no collective,
+        # so a mismatch between ranks cannot hang anything -- but every rank should pass the same value.
+        self.pace_scores = bool(pace_scores)
+        if self.pace_scores:
+            if isinstance(pace_min_ranks, bool) or not isinstance(pace_min_ranks, (int, np.integer)) or pace_min_ranks < 1:
+                raise ValueError(f"pace_min_ranks must be an integer >= 1, got {pace_min_ranks!r}")
+            if isinstance(pace_min_columns, bool) or not isinstance(pace_min_columns, (int, np.integer)) or pace_min_columns < 1:
+                raise ValueError(f"pace_min_columns must be an integer >= 1, got {pace_min_columns!r}")
+            try:
+                effect, breadth = float(pace_min_effect), float(pace_min_breadth)
+            except (TypeError, ValueError):
+                raise ValueError(f"pace_min_effect and pace_min_breadth must be numbers, got {pace_min_effect!r} and "
+                                 f"{pace_min_breadth!r}") from None
+            if not 0.0 <= effect < 1.0:
+                raise ValueError(f"pace_min_effect must be within [0, 1), got {pace_min_effect!r}")
+            if not 0.0 < breadth <= 1.0:
+                raise ValueError(f"pace_min_breadth must be within (0, 1], got {pace_min_breadth!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"pace_scores needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "pace scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "pace_score"):
+                raise RuntimeError(f"pace_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no pace scores (backend.pace_score)")
+            self.pace_min_ranks, self.pace_min_columns = int(pace_min_ranks), int(pace_min_columns)
+            self.pace_min_effect, self.pace_min_breadth = effect, breadth
         # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
         # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
         # call.  The step adds one collective per report, so EVERY rank must pass the same value.
@@ -2038,6 +2158,10 @@ class ReportGenerator:
             groups = self._peer_for(ws)
             self._attach_peer(report, _backend_mod.get_backend().peer_score(
                 ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks), groups, ws, mapper, view)
+        if self.pace_scores:
+            # likewise, behind the robust and peer steps
+            self._attach_pace(report, _backend_mod.get_backend().pace_score(
+                ws, ws.table, lo, hi - lo, self._pace_min(ws)), ws, mapper, view)
         if self._history is not None:
             # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
             self._attach_history(report, _backend_mod.get_backend().score_history(
@@ -2192,6 +2316,8 @@ class ReportGenerator:
             raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
         if fused and self.peer_groups is not None and not hasattr(rings, "report_peer"):
             raise RuntimeError("peer_groups: these rings run the one-call report but have no report_peer")
+        if fused and self.pace_scores and not hasattr(rings, "report_pace"):
+            raise RuntimeError("pace_scores: these rings run the one-call report but have no report_pace")
         if fused and self._history is not None and not hasattr(rings, "report_history"):
             raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
         if fused and self.score_trends and not hasattr(rings, "report_trend"):
@@ -2221,6 +2347,8 @@ class ReportGenerator:
                     self._attach_plan_robust(report, plan, rings, True)
                 if self.peer_groups is not None:
                     self._attach_plan_peer(report, plan, rings, True)
+                if self.pace_scores:
+                    self._attach_plan_pace(report, plan, rings, True)
                 if self._history is not None:
                     self._attach_plan_history(report, plan, rings, True)
                 return report
@@ -2259,6 +2387,8 @@ class ReportGenerator:
             self._attach_plan_robust(report, plan, rings, fused)
         if self.peer_groups is not None:
             self._attach_plan_peer(report, plan, rings, fused)
+        if self.pace_scores:
+            self._attach_plan_pace(report, plan, rings, fused)
         if self._history is not None:
             self._attach_plan_history(report, plan, rings, fused)
         return report
@@ -2321,6 +2451,27 @@ class ReportGenerator:
         else:
             handle = _backend_mod.get_backend().peer_score(ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks)
         self._attach_peer(report, handle, groups, ws, plan.mapper, plan.view)
+
+    # ---- pace scores --------------------------------------------------------------------------------
+    def _pace_min(self, ws) -> int:
+        """``pace_min_ranks``, but never more than the ranks the table has, as ``_robust_min``."""
+        return min(self.pace_min_ranks, ws.R)
+
+    def _attach_pace(self, report, handle, ws, mapper, view) -> None:
+        params = {"min_ranks": self._pace_min(ws), "min_columns": self.pace_min_columns, "min_effect": self.pace_min_effect,
+                  "min_breadth": self.pace_min_breadth}
+        report.__dict__["_pace"] = _PaceSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
+
+    def _attach_plan_pace(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the pace scores of the planned report that was just issued, as ``_attach_plan_robust`` does, for the ranks
+        the report covers, and hang them on ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        lo, hi = plan.view.layout[5], plan.view.layout[6]
+        if fused:
+            handle = rings.report_pace(ws, lo, hi - lo, self._pace_min(ws))
+        else:
+            handle = _backend_mod.get_backend().pace_score(ws, ws.table, lo, hi - lo, self._pace_min(ws))
+        self._attach_pace(report, handle, ws, plan.mapper, plan.view)
 
     # ---- score history ------------------------------------------------------------------------------
     def _attach_history(self, report, handle, view) -> None:

@@ -164,6 +164,8 @@ class _Lane:
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         if getattr(reporter, "peer_groups", None) is not None:
             return None  # (the peer launch follows the report in the generator's planned path: DESIGN.md, "Peer-group scores")
+        if getattr(reporter, "pace_scores", False):
+            return None  # (the pace launches follow the report in the generator's planned path: DESIGN.md, "Pace scores")
         if getattr(reporter, "score_history", 0):
             return None  # (the history step follows the report in the generator's planned path: DESIGN.md, "Score history")
         if getattr(reporter, "collective_slack", False):
@@ -429,6 +431,11 @@ class Detector(metaclass=_DeviceSideOnDemand):
         slack_max_ratio: float = 0.25,
         peer_groups=None,
         peer_min_ranks: Optional[int] = None,
+        pace_scores: Optional[bool] = None,
+        pace_min_ranks: int = 4,
+        pace_min_columns: int = 8,
+        pace_min_effect: float = 0.03,
+        pace_min_breadth: float = 0.9,
     ):
         """
         Args:
@@ -536,6 +543,16 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 of integers), else off.  Same value on every rank (no collective depends on it).
             peer_min_ranks: ranks of a group that must have a section or kernel for the group to have a reference; at the
                 default of 2 (``NVRX_PEER_MIN_RANKS``) a rank alone in its group has no peer and is unrated, not rated 1.0.
+            pace_scores: every report also says whether a rank is a LITTLE slower in nearly ALL of its kernels -- a card held a
+                clock step down, a throttling HBM stack, a marginal power rail: 3-5 % on every kernel, which no threshold on
+                one row sees (``Report.pace_scores()``, ``Report.identify_pace_stragglers()``).  Needs
+                ``relative_perf_scores``.  Default: ``NVRX_PACE_SCORES`` (set and not "0"), else off.  Same value on every
+                rank (no collective depends on it).
+            pace_min_ranks: ranks that must have a kernel or section for its median to be a reference (clamped to the job's
+                ranks).
+            pace_min_columns, pace_min_effect, pace_min_breadth: the rule of ``identify_pace_stragglers``: at least this many
+                columns, a pace of at most ``1 - pace_min_effect`` and slower than the job's median in at least this share of
+                the columns.  8, 0.03 and 0.9 are defaults, not measurements.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -620,6 +637,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 except ValueError:
                     raise ValueError("NVRX_PEER_MIN_RANKS must be an integer >= 1") from None
             peer_options = {"peer_groups": peer_groups, "peer_min_ranks": peer_min_ranks}
+        pace_options = {}  # (off: the generator is built exactly as before)
+        if pace_scores is None:
+            pace_scores = os.environ.get("NVRX_PACE_SCORES", "0") not in ("", "0")
+        if pace_scores:
+            pace_options = {"pace_scores": True, "pace_min_ranks": pace_min_ranks, "pace_min_columns": pace_min_columns,
+                            "pace_min_effect": pace_min_effect, "pace_min_breadth": pace_min_breadth}
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -633,7 +656,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                       slack_max_ratio=slack_max_ratio, **peer_options)
+                                       slack_max_ratio=slack_max_ratio, **peer_options, **pace_options)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
