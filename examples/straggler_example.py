@@ -79,6 +79,12 @@ kernel times, 1 % noise per entry, seed 2026, 200 calls of every kernel) in whic
 held a clock step down.  Its relative GPU score reads about 0.95 and its robust z about 2: ``identify_stragglers`` and
 ``identify_robust_stragglers`` name nobody; with pace scores (``ReportGenerator(pace_scores=True)``) the report says that rank
 5 is slower than the job's median in 120 of 120 kernels, and ``identify_pace_stragglers`` names it alone.
+
+``--pace-peer`` plays the same kind of report for a PIPELINE job: 8 ranks x 120 kernels in two stages (``block:4``), the second
+stage 1.5 x slower in every kernel, and rank 6 4 % slower than its stage in every kernel.  Against the median of the whole job
+every rank of the slower stage is slower in 120 of 120 kernels and ``identify_pace_stragglers`` names ranks 4-7, three of them
+healthy; with ``ReportGenerator(pace_peer_groups=True)`` each rank is rated against the median of its own stage and rank 6 is
+named alone.  Both are printed.
 """
 import argparse
 import os
@@ -416,6 +422,43 @@ def pace(ranks: int = 8, kernels: int = 120, calls: int = 200, slow_rank: int = 
         job.close()
 
 
+def pace_peer(ranks: int = 8, kernels: int = 120, calls: int = 200, stage: int = 4, slow_rank: int = 6,
+              slowdown: float = 1.04, seed: int = 2026) -> None:
+    """A degraded GPU in a pipeline job: whom the job-wide pace rule names, and whom the rule per peer group does."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    names = [f"kernel_{k:03d}" for k in range(kernels)]
+    rng = np.random.default_rng(seed)
+    med = rng.lognormal(np.log(100.0), 0.5, kernels)[None, :] * (1.0 + 0.01 * rng.standard_normal((ranks, kernels)))
+    med[(np.arange(ranks) // stage) % 2 == 1] *= 1.5  # the odd stages are 1.5 x slower
+    med[slow_rank] *= slowdown
+    med = med.astype(np.float32)
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    for title, grouped in (("job-wide", False), ("per-peer-group", True)):
+        job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                        kernel_names=names, pace_scores=True, peer_groups=f"block:{stage}", pace_peer_groups=grouped)
+        try:
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, np.full((1, calls), med[r].sum(), dtype=np.float32))
+                job.load_kernels(lr, np.repeat(med[r][:, None], calls, axis=1))
+            report = job.report()
+            t = report.pace_scores()
+            print(f"identify_pace_stragglers() {title}: {named(report.identify_pace_stragglers())}; rule {t['params']}")
+            for r in sorted(t["ranks"]):
+                gpu = t["ranks"][r]["gpu"]
+                against = f"group {t['group_of'][r]}'s" if grouped else "the job's"
+                print(f"  rank {r}: pace {gpu['pace']:.3f} (spread {gpu['spread']:.3f}), slower / faster than {against} median in "
+                      f"{gpu['slower']} / {gpu['faster']} of {gpu['columns']} kernels, {gpu['excess_us']:+.0f} us above its pace")
+        finally:
+            job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -446,7 +489,13 @@ def main() -> None:
     ap.add_argument("--pace", action="store_true",
                     help="no training: play the pace-score scenario (a rank 4 %% slower in every one of its 120 kernels) and "
                          "exit")
+    ap.add_argument("--pace-peer", action="store_true",
+                    help="no training: play the pace-score scenario of a pipeline job (two stages, the second 1.5 x slower, rank 6 "
+                         "4 %% slower than its stage in every kernel) with the job-wide rule and the rule per peer group, and exit")
     args = ap.parse_args()
+    if args.pace_peer:
+        pace_peer()
+        return
     if args.pace:
         pace()
         return

@@ -410,6 +410,41 @@ int nvrx_peer_score(const float *d_table, int R, int K, int S, const int32_t *d_
 int nvrx_pace_score(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks, void *d_out,
                     void *stream);
 
+/* Pace scores per peer group: nvrx_pace_score with the lower median of the rank's OWN group as the reference point.  The
+ * median of the whole job is the wrong centre in a job of pipeline stages or expert groups: every healthy rank of the slower
+ * stage is slower than it in all of its kernels.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_ROBUST_MAX_RANKS.
+ *   d_groups  nvrx_peer_score's array, unchanged: group[R] | members[R] | start[G+1], 1 <= G <= R and G <=
+ *      NVRX_PEER_MAX_GROUPS.
+ *   max_group  in 1..R: the size of the largest group as the host knows it.  It selects the kernel variant (at most 64: one
+ *      wave per column; at most 1024: 256 threads per pair; beyond: 1024).
+ *   The MEMBERS of group g are members[s .. e), s and e being start[g] and start[g+1] clamped to [0, R], e at least s, and
+ *   e - s clamped to max_group; an entry outside [0, R) is skipped.  size_g is that stretch's length (skipped entries count).
+ *   Per pair (group g, column c < K+S of the table's med part), over the members of g; a member is PRESENT iff its value
+ *   v >= 0:
+ *      n      present values;
+ *      ctr    their LOWER median: the element of rank (n-1) >> 1 sorted by raw bit pattern, always an actual value;
+ *      above  present values whose key is greater than ctr's, below those whose key is less (both 0 at n = 0);
+ *      the pair is REFERENCED iff n >= max(min_peers, min(min_ranks, size_g)): min_ranks is clamped to the group's size (the
+ *      job-wide rule's caller clamps it to R in the same way) but never goes below min_peers.  At min_peers = 2 a rank alone
+ *      in its group has no peer and is unrated, not rated 1.0, and a group of two is rated against its faster member;
+ *      record, 16 bytes: {f32 ctr (the canonical NaN 0x7FC00000 where not referenced), u32 n, u32 above, u32 below}, at
+ *      d_out[g * (K+S) + c] in 16-byte units; the three counts are always written.
+ *   Per reported rank r in [first_rank, first_rank + n_ranks) and part p: exactly nvrx_pace_score's record -- q_c, columns,
+ *   slower, faster, pace, spread and for part 0 the three f64 sums -- over the columns where r is present and the pair
+ *   (group[r], c) is referenced, ctr being the group's.  A rank whose group[r] is outside [0, G) has no eligible column: NaN,
+ *   NaN and zeros.
+ *   d_out  16-byte aligned, NVRX_PACE_GROUP_WORDS(G, n_ranks, K, S) 32-bit words: [G][K+S] column records, then [n_ranks][2]
+ *   32-byte rank records.
+ *   The CONTENTS of d_groups are guarded on the device as stated above; no content makes a kernel read or write outside the
+ *   table, the array or d_out.  With one group of all ranks and min_peers = 1 every record is nvrx_pace_score's.
+ * Two launches on `stream` (columns, ranks); no atomics on global memory, no scratch.  Argument errors, reported before any
+ * device is touched: those of nvrx_pace_score in its order, then nvrx_peer_score's checks of G, then NVRX_ERR_RANGE for a
+ * max_group outside 1..R or min_peers < 1, then NVRX_ERR_INVALID for a null pointer or a d_out that is not 16-byte aligned. */
+#define NVRX_PACE_GROUP_WORDS(G, n_ranks, K, S) (4 * (size_t)(G) * ((size_t)(K) + (S)) + 16 * (size_t)(n_ranks))
+int nvrx_pace_group_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group,
+                          int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out, void *stream);
+
 /* Score history: how each score behaved over the last H reports.  Every score above looks inside one report window; the one
  * thing a report carries over from its predecessors is the running minimum of MED.  Here a device ring keeps the last H
  * reports' scores per reported rank, family f (0 individual, 1 relative: the parity of the score row's first two columns)
@@ -744,6 +779,13 @@ int nvrx_report_peer(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t 
  * D2H on the context's stream, and do not let a later report rewrite the table before the kernels have run.  NVRX_ERR_STATE:
  * no report was issued through this descriptor. */
 int nvrx_report_pace(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int min_ranks, void *d_out);
+/* nvrx_pace_group_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor; d_groups sized for the descriptor's R).  Ordered behind that report's kernels exactly as
+ * nvrx_report_pace orders itself: the context's stream, with an event when the report was re-homed or scored resident.  The
+ * host does not wait; copy d_out with a D2H on the context's stream, and do not let a later report rewrite the table before
+ * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_pace_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group,
+                           int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out);
 /* nvrx_score_history (above) on the result block of the report LAST issued through `desc` on `ctx` (desc->d_scores; R and S
  * from the descriptor).  Ordered behind that report's last kernel exactly as nvrx_report_robust orders itself: the context's
  * stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a D2H on the

@@ -27,6 +27,8 @@
 //   nearly every key to one or two bins, the same-address LDS-atomic case tail_hist_add aggregates per wave.
 //   Always exact, ties included; no data-dependent trip count, no sort, no scratch, no global atomics, no float atomics.
 
+#include <type_traits>
+
 namespace {
 
 constexpr uint32_t PACE_MARK = 0xFFFFFFFFu;  // "no quotient here": f2key of no non-NaN float, and above every |x| bit pattern
@@ -130,6 +132,16 @@ struct PaceRankArgs {
     uint4 *out;  // [n_ranks][2] records of two 16-byte words
 };
 
+// k_pace_rank's GROUPED form (nvrx_pace_group.inl): the records of the rank's own group
+struct PaceGroupRankArgs {
+    const float *table;     // [R][L]
+    const uint4 *cols;      // [G][KS]
+    const int32_t *groups;  // group[R] | ...
+    int K, S, G;
+    int first_rank;
+    uint4 *out;  // [n_ranks][2] records of two 16-byte words
+};
+
 // One column of a rank's part: what the counts and sums take from it, and the key of its quotient.
 struct PaceCol {
     uint32_t qkey;  // f2key of (float)((double)ctr / (double)v); PACE_MARK where not eligible or the quotient is NaN
@@ -137,7 +149,9 @@ struct PaceCol {
     double quot;  // the f64 quotient (read only where qkey is not the marker)
 };
 
-// row and recs point at the part's first column; i >= ncols reads nothing
+// row and recs point at the part's first column; i >= ncols reads nothing.  GROUPED: the records are those of the rank's group,
+// whose centre is a number exactly where the pair is referenced, and min_ranks says whether the rank has a group at all (0 / 1).
+template <bool GROUPED = false>
 __device__ __forceinline__ PaceCol pace_column(const float *__restrict__ row, const uint4 *__restrict__ recs, int i, int ncols,
                                                int min_ranks) {
     PaceCol o;
@@ -146,7 +160,10 @@ __device__ __forceinline__ PaceCol pace_column(const float *__restrict__ row, co
         const float v = row[i];
         const uint4 rec = recs[i];
         const float ctr = __uint_as_float(rec.x);
-        o.eligible = v >= 0.0f && rec.y != 0u && (int)rec.y >= min_ranks;
+        if constexpr (GROUPED)
+            o.eligible = v >= 0.0f && min_ranks != 0 && ctr == ctr;
+        else
+            o.eligible = v >= 0.0f && rec.y != 0u && (int)rec.y >= min_ranks;
         const uint32_t kv = f2key(v), kc = f2key(ctr);
         o.slower = o.eligible && kv > kc;
         o.faster = o.eligible && kv < kc;
@@ -207,9 +224,11 @@ __device__ __forceinline__ void pace_store(uint4 *dst, float pace, float spread,
     dst[1] = make_uint4(faster, __float_as_uint((float)total), __float_as_uint((float)slow), __float_as_uint((float)excess));
 }
 
-// THREADS 64 (NREG 1): one wave, one column per lane; 256 with NREG 16: keys in registers; 1024 with NREG 0: re-reading
-template <int THREADS, int NREG>
-__global__ __launch_bounds__(THREADS) void k_pace_rank(PaceRankArgs a) {
+// THREADS 64 (NREG 1): one wave, one column per lane; 256 with NREG 16: keys in registers; 1024 with NREG 0: re-reading.
+// GROUPED (a compile-time flag: the job-wide instantiations are what they were): the records at cols + group[r] * (K+S), a
+// column eligible iff the rank is present and its group's pair is referenced.
+template <int THREADS, int NREG, bool GROUPED = false>
+__global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPED, PaceGroupRankArgs, PaceRankArgs> a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int K = a.K, S = a.S, KS = K + S;
     const int L = NVRX_TABLE_LEN(K, S);
@@ -219,12 +238,20 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(PaceRankArgs a) {
     const float *__restrict__ row = a.table + (size_t)(a.first_rank + (int)blockIdx.x) * (size_t)L;
     const float *__restrict__ wrow = row + 2 * (size_t)KS;  // the weights NUM*AVG of the kernel columns (part 0 only)
     const uint4 *__restrict__ recs = a.cols + base;
+    int min_ranks;  // GROUPED: 1 where the rank has a group, else 0 (no eligible column)
+    if constexpr (GROUPED) {
+        const int g = a.groups[a.first_rank + (int)blockIdx.x];
+        min_ranks = (uint32_t)g < (uint32_t)a.G ? 1 : 0;  // block-uniform
+        recs += (size_t)(min_ranks ? g : 0) * (size_t)KS;
+    } else {
+        min_ranks = a.min_ranks;
+    }
     uint4 *__restrict__ dst = a.out + ((size_t)blockIdx.x * 2 + (size_t)part) * 2;
     const float NaN = __builtin_nanf("");
     row += base;
 
     if constexpr (THREADS == 64) {
-        const PaceCol col = pace_column(row, recs, lane, ncols, a.min_ranks);
+        const PaceCol col = pace_column<GROUPED>(row, recs, lane, ncols, min_ranks);
         const bool has_q = col.qkey != PACE_MARK;
         const double w = (part == 0 && col.eligible) ? (double)wrow[lane] : 0.0;
         const double total = wave_sum_f64(w);
@@ -271,13 +298,13 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(PaceRankArgs a) {
 #pragma unroll
             for (int j = 0; j < NREG; j++) {
                 const int i = tid + j * THREADS;
-                const PaceCol col = pace_column(row, recs, i, ncols, a.min_ranks);
+                const PaceCol col = pace_column<GROUPED>(row, recs, i, ncols, min_ranks);
                 keys[j] = col.qkey;
                 take(col, i);
             }
         } else {
             keys[0] = PACE_MARK;
-            for (int i = tid; i < ncols; i += THREADS) take(pace_column(row, recs, i, ncols, a.min_ranks), i);
+            for (int i = tid; i < ncols; i += THREADS) take(pace_column<GROUPED>(row, recs, i, ncols, min_ranks), i);
         }
         total = wave_sum_f64(total);
         slow = wave_sum_f64(slow);
@@ -298,16 +325,16 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(PaceRankArgs a) {
         float pace = NaN, spread = NaN;
         if (m != 0) {  // block-uniform
             const uint32_t target = (m - 1u) >> 1;
-            const int mr = a.min_ranks;
+            const int mr = min_ranks;
             if constexpr (NREG > 0) {
                 pace = key2f(pace_radix_select<THREADS, NREG>([&](int j) { return keys[j]; }, ncols, target, s_hist, s_wave, s_sel));
                 spread = __uint_as_float(pace_radix_select<THREADS, NREG>([&](int j) { return pace_dev_key(keys[j], pace); }, ncols,
                                                                           target, s_hist, s_wave, s_sel));
             } else {
-                pace = key2f(pace_radix_select<THREADS, 0>([&](int i) { return pace_column(row, recs, i, ncols, mr).qkey; }, ncols,
+                pace = key2f(pace_radix_select<THREADS, 0>([&](int i) { return pace_column<GROUPED>(row, recs, i, ncols, mr).qkey; }, ncols,
                                                            target, s_hist, s_wave, s_sel));
                 spread = __uint_as_float(pace_radix_select<THREADS, 0>(
-                    [&](int i) { return pace_dev_key(pace_column(row, recs, i, ncols, mr).qkey, pace); }, ncols, target, s_hist,
+                    [&](int i) { return pace_dev_key(pace_column<GROUPED>(row, recs, i, ncols, mr).qkey, pace); }, ncols, target, s_hist,
                     s_wave, s_sel));
             }
         }

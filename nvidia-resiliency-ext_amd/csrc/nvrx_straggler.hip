@@ -3970,3 +3970,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_episode.inl"
 #include "nvrx_peer.inl"
 #include "nvrx_pace.inl"
+#include "nvrx_pace_group.inl"

@@ -51,6 +51,7 @@ class StragglerDetectionCallback(Callback):
         warn_if_waited_for: bool = False,
         peer_groups=None,
         warn_if_off_pace: bool = False,
+        pace_peer_groups: bool = False,
     ):
         """
         Args:
@@ -88,11 +89,17 @@ class StragglerDetectionCallback(Callback):
                 median in nearly all of its kernels (``Report.identify_pace_stragglers``: a degraded card, which no threshold
                 on one score sees) logs one warning that names the ranks with their pace and the microseconds they spent
                 above the job's median pace.  A warning only: it never stops the job.
+            pace_peer_groups: False (the default): nothing changes.  True (needs ``warn_if_off_pace`` and ``peer_groups``):
+                the pace scores rate each rank against the median of its own peer group
+                (``Detector.initialize(pace_peer_groups=True)``), so that the healthy ranks of a slower pipeline stage are not
+                warned about at every report, and the warning says the ranks are off their peer group's pace.  Still a
+                warning only.
 
         Raises:
             ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64],
                 ``warn_if_waited_for``, ``warn_if_off_pace`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
-                ``min_consecutive_reports`` > 1 (the score history does not hold peer scores).
+                ``min_consecutive_reports`` > 1 (the score history does not hold peer scores), or ``pace_peer_groups`` without
+                ``warn_if_off_pace`` or without ``peer_groups``.
         """
         self.initialized = False
         self.logger = logging.getLogger(logger_name)
@@ -133,6 +140,12 @@ class StragglerDetectionCallback(Callback):
             if min_consecutive_reports > 1:
                 raise ValueError("peer_groups cannot be combined with min_consecutive_reports > 1: the score history does "
                                  "not hold peer-group scores")
+        self.pace_peer_groups = bool(pace_peer_groups)
+        if self.pace_peer_groups:
+            if not self.warn_if_off_pace:
+                raise ValueError("pace_peer_groups needs warn_if_off_pace=True: it changes what the pace scores compare with")
+            if peer_groups is None:
+                raise ValueError("pace_peer_groups needs peer_groups: which ranks do the same work")
         self._unrated_said = False
         self.interval_est_was_reset = False
 
@@ -157,6 +170,8 @@ class StragglerDetectionCallback(Callback):
             persistence["peer_groups"] = self.peer_groups
         if self.warn_if_off_pace:
             persistence["pace_scores"] = True
+        if self.pace_peer_groups:
+            persistence["pace_peer_groups"] = True
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -285,6 +300,10 @@ class StragglerDetectionCallback(Callback):
             gpu = ranks[rank]["gpu"]
             parts.append(f"rank {rank} (pace {gpu['pace']:.3f}, slower in {gpu['slower']} of {gpu['columns']} kernels, "
                          f"excess_us={gpu['excess_us']:.0f})")
+        if self.pace_peer_groups:
+            self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs are off their peer group's pace, a little slower than "
+                                "their group's median in nearly all of their kernels (degraded card?): " + "; ".join(parts))
+            return
         self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs are a little slower in nearly all of their kernels "
                             "(degraded card?): " + "; ".join(parts))
 

@@ -98,6 +98,8 @@ SYMBOLS = [
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("nvrx_pace_group_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
@@ -143,6 +145,8 @@ SYMBOLS = [
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
+    ("nvrx_report_pace_group", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
@@ -251,6 +255,12 @@ def peer_words(G: int, n_ranks: int, K: int, S: int) -> int:
 def pace_words(n_ranks: int, K: int, S: int) -> int:
     """NVRX_PACE_WORDS: 32-bit words of a pace-score block: ``[K+S][4]`` column records, then ``[n_ranks][2][8]``."""
     return 4 * (K + S) + 16 * n_ranks
+
+
+def pace_group_words(G: int, n_ranks: int, K: int, S: int) -> int:
+    """NVRX_PACE_GROUP_WORDS: 32-bit words of a block of pace scores per peer group: ``[G][K+S][4]`` column records, then
+    ``[n_ranks][2][8]``."""
+    return 4 * G * (K + S) + 16 * n_ranks
 
 
 def history_stride(H: int) -> int:

@@ -313,7 +313,7 @@ class PeerGroups:
     ``group[R] | members[R] | start[G+1]`` int32 (include/nvrx_straggler.h) -- on the host and, uploaded once under the
     backend's stream by the backend that first asks, on the device."""
 
-    __slots__ = ("R", "G", "labels", "host", "_dev")
+    __slots__ = ("R", "G", "labels", "host", "_dev", "_max_size")
 
     def __init__(self, rank_labels: Sequence[Any]):
         self.R = len(rank_labels)
@@ -328,6 +328,7 @@ class PeerGroups:
         np.cumsum(np.bincount(group, minlength=self.G), out=start[1:])
         self.host = np.concatenate((group, members, start))
         self._dev = None
+        self._max_size = None
 
     @classmethod
     def resolve(cls, spec, R: int) -> "PeerGroups":
@@ -343,6 +344,13 @@ class PeerGroups:
     @property
     def group(self) -> np.ndarray:
         return self.host[: self.R]
+
+    @property
+    def max_size(self) -> int:
+        """The largest group's size (``nvrx_pace_group_score``'s ``max_group``; worked out when first asked for)."""
+        if self._max_size is None:
+            self._max_size = int(np.diff(self.host[2 * self.R :]).max())
+        return self._max_size
 
     def members(self, g: int) -> List[int]:
         start = self.host[2 * self.R :]
@@ -415,6 +423,33 @@ class Pace:
             with self._lock:
                 if self._host is None:
                     self._host = self.backend.pace_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
+class PaceGroup:
+    """Pace scores per peer group of one report (``nvrx_pace_group_score`` / ``nvrx_report_pace_group``), enqueued and not
+    waited for: ``Pace`` with ``[G][K + S]`` column records, one set per group, in front of the rank records.  It lives in
+    the workspace's pace buffer and is settled as a ``Pace`` is (``Workspace.pace_settle``)."""
+
+    __slots__ = ("backend", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "min_ranks", "min_peers", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, K: int, S: int, first_rank: int, n_ranks: int,
+                 min_ranks: int, min_peers: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.G, self.K, self.S = G, K, S
+        self.first_rank, self.n_ranks, self.min_ranks, self.min_peers = first_rank, n_ranks, min_ranks, min_peers
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(cols [G, K+S, 4] uint32, ranks [n_ranks, 2, 8] uint32)`` (private copies; the float fields are bit patterns);
+        the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.pace_group_copy_out(self)
                     self.backend = self._keep = None
         return self._host
 
@@ -780,9 +815,10 @@ class Workspace:
     _pace_buf = None   # device: column records, then the rank records of the last pace step of this workspace's table
     _pace_last = None  # the Pace whose kernels may still be reading the table / writing _pace_buf
 
-    def pace_buffers(self, n_ranks: int):
-        """The records buffer for pace scores of ``n_ranks`` ranks (cold: allocated once per shape)."""
-        words = _native.pace_words(n_ranks, self.K, self.S)
+    def pace_buffers(self, n_ranks: int, G: int = 0):
+        """The records buffer for pace scores of ``n_ranks`` ranks, per peer group with ``G`` groups (cold: allocated once
+        per shape)."""
+        words = _native.pace_group_words(G, n_ranks, self.K, self.S) if G else _native.pace_words(n_ranks, self.K, self.S)
         if self._pace_buf is None or self._pace_buf.numel() < words:
             with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
                 self._pace_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
@@ -1122,6 +1158,33 @@ class HipBackend:
         host = np.empty(n, dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pc.d_ptr, n * 4, self._stream_handle))
         return host[: 4 * KS].reshape(KS, 4).copy(), host[4 * KS :].reshape(pc.n_ranks, 2, 8).copy()
+
+    def pace_group_score(self, ws: Workspace, table: torch.Tensor, groups: PeerGroups, first_rank: int = 0,
+                         n_ranks: Optional[int] = None, min_ranks: int = 4, min_peers: int = 2) -> PaceGroup:
+        """Pace scores of ``table`` against each rank's own peer group for ranks ``[first_rank, first_rank + n_ranks)``:
+        ``nvrx_pace_group_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if groups.R != ws.R:
+            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
+        ws.pace_settle()
+        buf = ws.pace_buffers(n_ranks, groups.G)
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_pace_group_score(table_ptr, ws.R, ws.K, ws.S, groups.device(self).data_ptr(), groups.G,
+                                            groups.max_size, first_rank, n_ranks, min_ranks, min_peers, buf.data_ptr(),
+                                            self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._pace_last = PaceGroup(self, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks, min_peers)
+        return out
+
+    def pace_group_copy_out(self, pc: PaceGroup):
+        """The one wait of a report's pace scores per peer group: a D2H of the records on the backend's stream, behind the
+        kernels."""
+        KS = pc.K + pc.S
+        n = _native.pace_group_words(pc.G, pc.n_ranks, pc.K, pc.S)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pc.d_ptr, n * 4, self._stream_handle))
+        return host[: 4 * pc.G * KS].reshape(pc.G, KS, 4).copy(), host[4 * pc.G * KS :].reshape(pc.n_ranks, 2, 8).copy()
 
     def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
         """What both routes of a history step share: the ring of ``state`` with room for this workspace's section ids (cold:
@@ -1552,6 +1615,22 @@ class HipRings:
         if rc < 0:
             _native.check(rc)
         out = ws._pace_last = Pace(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks)
+        return out
+
+    def report_pace_group(self, ws: Workspace, groups: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                          min_ranks: int = 4, min_peers: int = 2) -> PaceGroup:
+        """Pace scores per peer group of the table of the report ``report_fused`` just issued on ``ws``
+        (``nvrx_report_pace_group``): enqueued behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if groups.R != ws.R:
+            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
+        ws.pace_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
+        buf = ws.pace_buffers(n_ranks, groups.G)
+        rc = self.lib.nvrx_report_pace_group(self.ctx, ws.block.desc_ref, groups.device(self.backend).data_ptr(), groups.G,
+                                             groups.max_size, first_rank, n_ranks, min_ranks, min_peers, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._pace_last = PaceGroup(self.backend, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks, min_peers)
         return out
 
     def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,

@@ -33,7 +33,7 @@ class FoldedJob:
                  collective_slack: bool = False, slack_min_ranks: int = 4, slack_min_share: float = 0.05,
                  slack_max_ratio: float = 0.25, kernel_names: Sequence[str] = (), peer_groups=None, peer_min_ranks: int = 2,
                  pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8, pace_min_effect: float = 0.03,
-                 pace_min_breadth: float = 0.9):
+                 pace_min_breadth: float = 0.9, pace_peer_groups: bool = False):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -61,7 +61,8 @@ class FoldedJob:
                                         slack_max_ratio=slack_max_ratio, peer_groups=peer_groups,
                                         peer_min_ranks=peer_min_ranks, pace_scores=pace_scores,
                                         pace_min_ranks=pace_min_ranks, pace_min_columns=pace_min_columns,
-                                        pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth)
+                                        pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth,
+                                        **({"pace_peer_groups": True} if pace_peer_groups else {}))
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         # (the same object every report so the reporter's cached plan stays valid)
         self._no_kernel_rows = {name: self.rings.row_for(_native.KIND_KERNEL, name) for name in self.kernel_names}

@@ -735,6 +735,22 @@ class _RobustSource:
         return self._built
 
 
+def _pace_rank_parts(recs, ranks) -> dict:
+    """``{rank: {"gpu": {...}, "sections": {...}}}`` of ``[n_ranks][2][8]`` pace rank records (uint32 bit patterns)."""
+    recs = np.ascontiguousarray(recs)
+    f, u = recs.view(np.float32).tolist(), recs.tolist()
+
+    def part(i, p):
+        columns, slower = u[i][p][2], u[i][p][3]
+        d = {"pace": f[i][p][0], "spread": f[i][p][1], "columns": columns, "slower": slower, "faster": u[i][p][4],
+             "breadth": slower / columns if columns else None}
+        if p == 0:
+            d.update(total_us=f[i][p][5], slower_us=f[i][p][6], excess_us=f[i][p][7])
+        return d
+
+    return {r: {"gpu": part(i, 0), "sections": part(i, 1)} for i, r in enumerate(ranks)}
+
+
 class _PaceSource:
     """What a report keeps of its pace scores: the backend's handle (``records()`` waits for the kernels and copies the column
     and rank records out on first use), the ranks its rows stand for, the sections it shows with their ids, the kernel names
@@ -753,25 +769,53 @@ class _PaceSource:
             K = len(self.kernels)
             center = np.ascontiguousarray(cols).view(np.float32)[:, 0].tolist()
             counts = cols[:, 1:].tolist()
-            recs = np.ascontiguousarray(recs)
-            f, u = recs.view(np.float32).tolist(), recs.tolist()
-
-            def part(i, p):
-                columns, slower = u[i][p][2], u[i][p][3]
-                d = {"pace": f[i][p][0], "spread": f[i][p][1], "columns": columns, "slower": slower, "faster": u[i][p][4],
-                     "breadth": slower / columns if columns else None}
-                if p == 0:
-                    d.update(total_us=f[i][p][5], slower_us=f[i][p][6], excess_us=f[i][p][7])
-                return d
 
             def column(c):
                 return {"center": center[c], "ranks": counts[c][0], "above": counts[c][1], "below": counts[c][2]}
 
             self._built = {
-                "ranks": {r: {"gpu": part(i, 0), "sections": part(i, 1)} for i, r in enumerate(self.ranks)},
+                "ranks": _pace_rank_parts(recs, self.ranks),
                 "kernels": {name: column(k) for k, name in enumerate(self.kernels)},
                 "section_columns": {name: column(K + g) for name, g in self.sections.items()},
                 "params": dict(self.params),
+            }
+            self.handle = None
+        return self._built
+
+
+class _PaceGroupSource(_PaceSource):
+    """``_PaceSource`` for pace scores per peer group: the handle's column records come per group, and the report also says
+    which ranks form which group."""
+
+    __slots__ = ("groups",)
+
+    def __init__(self, handle, ranks, sections, kernels, params: dict, groups):
+        super().__init__(handle, ranks, sections, kernels, params)
+        self.groups = groups
+
+    def build(self) -> dict:
+        if self._built is None:
+            cols, recs = self.handle.records()
+            rated = _pace_rank_parts(recs, self.ranks)
+            K = len(self.kernels)
+            labels = self.groups.labels
+            group = self.groups.group.tolist()
+            G = len(labels)
+            center = np.ascontiguousarray(cols).view(np.float32)[:, :, 0].tolist()
+            counts = cols[:, :, 1:].tolist()
+
+            def column(c):
+                return {labels[g]: {"center": center[g][c], "ranks": counts[g][c][0], "above": counts[g][c][1],
+                                    "below": counts[g][c][2]} for g in range(G)}
+
+            self._built = {
+                "ranks": rated,
+                "kernels": {name: column(k) for k, name in enumerate(self.kernels)},
+                "section_columns": {name: column(K + g) for name, g in self.sections.items()},
+                "params": dict(self.params),
+                "groups": {labels[g]: self.groups.members(g) for g in range(G)},
+                "group_of": {r: labels[group[r]] for r in self.ranks},
+                "unrated_ranks": [r for r, d in rated.items() if d["gpu"]["columns"] == 0 and d["sections"]["columns"] == 0],
             }
             self.handle = None
         return self._built
@@ -1292,12 +1336,21 @@ class Report:
         ``excess_us`` (microseconds spent above the job's median pace in the window, signed).  A kernel or section holds the
         column's ``center`` (NaN where fewer than ``min_ranks`` ranks have it), ``ranks`` with data and how many of them are
         ``above`` / ``below`` the center.  NaN where a part has no column.  Plain dicts, floats and ints.  The first call waits
-        for the pace kernels and copies their results; ``generate_report`` does not."""
+        for the pace kernels and copies their results; ``generate_report`` does not.
+
+        With ``ReportGenerator(pace_peer_groups=True)`` the reference of a column is the lower median of the rank's OWN peer
+        group, and "the job's median" above reads "its group's median".  ``"ranks"`` keeps its shape; ``"params"`` gains
+        ``"min_peers"`` and ``"peer_groups": True``; a kernel or section maps each group's label to its ``{"center", "ranks",
+        "above", "below"}``; and ``"groups"``, ``"group_of"`` and ``"unrated_ranks"`` (ranks without a column in either
+        part: alone in their group, say) are spelled as in ``peer_scores()``.  A pair of group and column is a reference
+        when at least ``max(min_peers, min(min_ranks, the group's size))`` of the group's ranks have it."""
         pace = self.__dict__.get("_pace")
         if pace is None:
             return {}
         if isinstance(pace, _PaceSource):
             pace = self.__dict__["_pace"] = pace.build()
+        if pace["params"].get("peer_groups"):
+            return _copy_peer(pace)  # (the groups' member lists are copied too)
         return _copy_scores(pace)
 
     def identify_pace_stragglers(self, min_effect: Optional[float] = None, min_breadth: Optional[float] = None,
@@ -1634,7 +1687,7 @@ class ReportGenerator:
                  trend_horizon: Optional[int] = None, collective_slack: bool = False, slack_min_ranks: int = 4,
                  slack_min_share: float = 0.05, slack_max_ratio: float = 0.25, peer_groups=None,
                  peer_min_ranks: int = 2, pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8,
-                 pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9) -> None:
+                 pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9, pace_peer_groups: bool = False) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1761,6 +1814,19 @@ class ReportGenerator:
                                    "has no pace scores (backend.pace_score)")
             self.pace_min_ranks, self.pace_min_columns = int(pace_min_ranks), int(pace_min_columns)
             self.pace_min_effect, self.pace_min_breadth = effect, breadth
+        # pace scores per peer group: the pace step rates each rank against the lower median of its OWN group
+        # (nvrx_pace_group_score); off: the pace step is the job-wide one, whatever peer_groups says
+        self.pace_peer_groups = bool(pace_peer_groups)
+        if self.pace_peer_groups:
+            if not self.pace_scores or self.peer_groups is None:
+                missing = [name for name, on in (("pace_scores", self.pace_scores), ("peer_groups", self.peer_groups is not None))
+                           if not on]
+                raise ValueError(f"pace_peer_groups needs pace_scores and peer_groups; {' and '.join(missing)} "
+                                 f"{'is' if len(missing) == 1 else 'are'} not set")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "pace_group_score"):
+                raise RuntimeError(f"pace_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no pace scores per peer group (backend.pace_group_score)")
         # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
         # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
         # call.  The step adds one collective per report, so EVERY rank must pass the same value.
@@ -2160,8 +2226,13 @@ class ReportGenerator:
                 ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks), groups, ws, mapper, view)
         if self.pace_scores:
             # likewise, behind the robust and peer steps
-            self._attach_pace(report, _backend_mod.get_backend().pace_score(
-                ws, ws.table, lo, hi - lo, self._pace_min(ws)), ws, mapper, view)
+            if self.pace_peer_groups:
+                groups = self._peer_for(ws)
+                self._attach_pace(report, _backend_mod.get_backend().pace_group_score(
+                    ws, ws.table, groups, lo, hi - lo, self._pace_min(ws), self.peer_min_ranks), ws, mapper, view, groups)
+            else:
+                self._attach_pace(report, _backend_mod.get_backend().pace_score(
+                    ws, ws.table, lo, hi - lo, self._pace_min(ws)), ws, mapper, view)
         if self._history is not None:
             # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
             self._attach_history(report, _backend_mod.get_backend().score_history(
@@ -2316,7 +2387,9 @@ class ReportGenerator:
             raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
         if fused and self.peer_groups is not None and not hasattr(rings, "report_peer"):
             raise RuntimeError("peer_groups: these rings run the one-call report but have no report_peer")
-        if fused and self.pace_scores and not hasattr(rings, "report_pace"):
+        if fused and self.pace_scores and not hasattr(rings, "report_pace_group" if self.pace_peer_groups else "report_pace"):
+            if self.pace_peer_groups:
+                raise RuntimeError("pace_peer_groups: these rings run the one-call report but have no report_pace_group")
             raise RuntimeError("pace_scores: these rings run the one-call report but have no report_pace")
         if fused and self._history is not None and not hasattr(rings, "report_history"):
             raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
@@ -2457,9 +2530,14 @@ class ReportGenerator:
         """``pace_min_ranks``, but never more than the ranks the table has, as ``_robust_min``."""
         return min(self.pace_min_ranks, ws.R)
 
-    def _attach_pace(self, report, handle, ws, mapper, view) -> None:
+    def _attach_pace(self, report, handle, ws, mapper, view, groups=None) -> None:
         params = {"min_ranks": self._pace_min(ws), "min_columns": self.pace_min_columns, "min_effect": self.pace_min_effect,
                   "min_breadth": self.pace_min_breadth}
+        if groups is not None:  # per peer group
+            params.update(min_peers=self.peer_min_ranks, peer_groups=True)
+            report.__dict__["_pace"] = _PaceGroupSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params,
+                                                        groups)
+            return
         report.__dict__["_pace"] = _PaceSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
 
     def _attach_plan_pace(self, report, plan, rings, fused: bool) -> None:
@@ -2467,6 +2545,15 @@ class ReportGenerator:
         the report covers, and hang them on ``report``.  Nothing is waited for."""
         ws = plan.ws
         lo, hi = plan.view.layout[5], plan.view.layout[6]
+        if self.pace_peer_groups:
+            groups = self._peer_for(ws)
+            if fused:
+                handle = rings.report_pace_group(ws, groups, lo, hi - lo, self._pace_min(ws), self.peer_min_ranks)
+            else:
+                handle = _backend_mod.get_backend().pace_group_score(ws, ws.table, groups, lo, hi - lo, self._pace_min(ws),
+                                                                     self.peer_min_ranks)
+            self._attach_pace(report, handle, ws, plan.mapper, plan.view, groups)
+            return
         if fused:
             handle = rings.report_pace(ws, lo, hi - lo, self._pace_min(ws))
         else:

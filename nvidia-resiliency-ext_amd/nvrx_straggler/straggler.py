@@ -436,6 +436,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         pace_min_columns: int = 8,
         pace_min_effect: float = 0.03,
         pace_min_breadth: float = 0.9,
+        pace_peer_groups: Optional[bool] = None,
     ):
         """
         Args:
@@ -553,6 +554,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
             pace_min_columns, pace_min_effect, pace_min_breadth: the rule of ``identify_pace_stragglers``: at least this many
                 columns, a pace of at most ``1 - pace_min_effect`` and slower than the job's median in at least this share of
                 the columns.  8, 0.03 and 0.9 are defaults, not measurements.
+            pace_peer_groups: the pace scores rate each rank against the lower median of its OWN peer group instead of the
+                whole job's -- the right centre in a job of pipeline stages or expert groups, where the job's median names
+                every healthy rank of the slower stage.  Needs ``pace_scores`` and ``peer_groups``; a group needs
+                ``max(peer_min_ranks, min(pace_min_ranks, its size))`` ranks with a kernel for its median to be a reference.
+                Default: ``NVRX_PACE_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank (no collective depends
+                on it).
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -643,6 +650,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
         if pace_scores:
             pace_options = {"pace_scores": True, "pace_min_ranks": pace_min_ranks, "pace_min_columns": pace_min_columns,
                             "pace_min_effect": pace_min_effect, "pace_min_breadth": pace_min_breadth}
+        if pace_peer_groups is None:
+            from_env = os.environ.get("NVRX_PACE_PEER_GROUPS", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_PACE_PEER_GROUPS must be 0 or 1, got {from_env!r}")
+            pace_peer_groups = from_env == "1"
+        if pace_peer_groups:
+            pace_options["pace_peer_groups"] = True  # (the generator says which of pace_scores and peer_groups it misses)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,

@@ -12,6 +12,11 @@
 ``report``: ``generate_report_from_rings`` + ``identify_stragglers()`` of the headline shape (8 folded ranks x 64 sections x
     10 000 samples) with ``pace_scores`` off and on, alternating in one process, median and p95 of ``--reports`` each; with
     the option on also the time until ``pace_scores()`` has returned.
+``--grouped``: pace scores per peer group (docs/MEASUREMENTS.md, "Pace scores per peer group").  ``kernels``:
+    ``nvrx_pace_group_score`` (``k_pace_group_cols`` + the grouped ``k_pace_rank``) next to ``nvrx_pace_score`` on the same
+    tables in the same run: 8 ranks x 64 sections in 2 groups, 8 ranks x 4096 kernels in 2 groups, 1024 ranks x 128 ids in 8
+    and in 128 groups (``mod:G``: interleaved memberships); under the profiler a run per ``--shape``.  ``report``: both
+    generators have ``pace_scores`` and ``peer_groups="mod:2"``, ``pace_peer_groups`` is what alternates.
 Prints one JSON line per measurement.
 """
 import argparse
@@ -27,6 +32,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 SHAPES = [(8, 0, 64), (8, 4096, 0), (1024, 64, 64)]  # (ranks, kernel ids, section ids)
+GROUPED_SHAPES = [(8, 0, 64, 2), (8, 4096, 0, 2), (1024, 64, 64, 8), (1024, 64, 64, 128)]  # (..., groups)
 
 
 def _timed(fn, launches, warmup, stream):
@@ -84,6 +90,39 @@ def kernels(args):
         print(json.dumps(out), flush=True)
 
 
+def kernels_grouped(args):
+    from nvrx_straggler import _native
+    from nvrx_straggler.backend import PeerGroups, get_backend
+
+    torch.cuda.set_device(0)
+    be = get_backend()
+    lib, st = be.lib, be.stream_handle
+    rng = np.random.default_rng(0)
+    for i, (R, K, S, G) in enumerate(GROUPED_SHAPES):
+        if args.shape >= 0 and i != args.shape:
+            continue
+        ws = be.workspace(R, K, S, R, 0)
+        with torch.cuda.stream(be.stream):
+            ws.send.copy_(torch.from_numpy(_table(rng, R, K, S)))
+        groups = PeerGroups([r % G for r in range(R)])
+        pbuf = ws.pace_buffers(R, G)
+        gptr, largest = groups.device(be).data_ptr(), groups.max_size
+        be.synchronize()
+
+        def pace():
+            _native.check(lib.nvrx_pace_score(ws.send_ptr, R, K, S, 0, R, 4, pbuf.data_ptr(), st))
+
+        def grouped():
+            _native.check(lib.nvrx_pace_group_score(ws.send_ptr, R, K, S, gptr, G, largest, 0, R, 4, 2, pbuf.data_ptr(), st))
+
+        out = {"what": "kernels, grouped", "ranks": R, "kernel_ids": K, "section_ids": S, "groups": G, "largest": largest,
+               "launches": args.launches}
+        out["pace_us"] = round(_timed(pace, args.launches, args.warmup, be.stream), 2)
+        be.synchronize()
+        out["pace_group_us"] = round(_timed(grouped, args.launches, args.warmup, be.stream), 2)
+        print(json.dumps(out), flush=True)
+
+
 def report(args):
     torch.cuda.set_device(0)
     from nvrx_straggler import _native
@@ -103,6 +142,10 @@ def report(args):
     torch.cuda.synchronize()
     gens = {0: ReportGenerator(["relative_perf_scores"], node_name="n"),
             1: ReportGenerator(["relative_perf_scores"], node_name="n", pace_scores=True)}
+    if args.grouped:
+        gens = {0: ReportGenerator(["relative_perf_scores"], node_name="n", pace_scores=True, peer_groups="mod:2"),
+                1: ReportGenerator(["relative_perf_scores"], node_name="n", pace_scores=True, peer_groups="mod:2",
+                                   pace_peer_groups=True)}
     lat, readable = {0: [], 1: []}, []
     try:
         for i in range(2 * (args.reports + args.warmup)):
@@ -120,7 +163,7 @@ def report(args):
                 if on:
                     readable.append((t2 - t0) * 1e-3)
             be.synchronize()
-        out = {"what": "ring report, call -> flagged set", "processes": 1, "reports_each": args.reports, "shape": "8 x 64 x 10000"}
+        out = {"what": "ring report, call -> flagged set" + (", pace_peer_groups off / on" if args.grouped else ""), "processes": 1, "reports_each": args.reports, "shape": "8 x 64 x 10000"}
         for on, key in ((0, "off"), (1, "on")):
             out[f"{key}_median_us"] = round(float(np.median(lat[on])), 1)
             out[f"{key}_p95_us"] = round(float(np.percentile(lat[on], 95)), 1)
@@ -140,9 +183,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--reports", type=int, default=200)
     ap.add_argument("--shape", type=int, default=-1, help="kernels: only that entry of SHAPES (a profiler run per shape)")
+    ap.add_argument("--grouped", action="store_true", help="pace scores per peer group (see the module's text)")
     args = ap.parse_args()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    {"kernels": kernels, "report": report}[args.what](args)
+    {"kernels": kernels_grouped if args.grouped else kernels, "report": report}[args.what](args)
 
 
 if __name__ == "__main__":
