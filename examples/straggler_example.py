@@ -85,6 +85,12 @@ stage 1.5 x slower in every kernel, and rank 6 4 % slower than its stage in ever
 every rank of the slower stage is slower in 120 of 120 kernels and ``identify_pace_stragglers`` names ranks 4-7, three of them
 healthy; with ``ReportGenerator(pace_peer_groups=True)`` each rank is rated against the median of its own stage and rank 6 is
 named alone.  Both are printed.
+
+``--node`` plays a report of 32 ranks x 120 kernels on 4 nodes of 8 (``node_groups="block:8"``; 1 % noise, seed 2026) in which
+every rank of node 2 is 4 % slower in every kernel -- failed fans, a capped PSU -- and rank 5 on node 0 is 4 % slower on its
+own.  ``identify_pace_stragglers`` names nine ranks and cannot say which of them are one incident; with node scores
+(``ReportGenerator(node_scores=True)``) ``identify_node_stragglers`` names node 2 alone, 8 of its 8 ranks agreeing, and hands
+rank 5 back as a rank that is off pace without its node.
 """
 import argparse
 import os
@@ -459,6 +465,46 @@ def pace_peer(ranks: int = 8, kernels: int = 120, calls: int = 200, stage: int =
             job.close()
 
 
+def node(ranks: int = 32, per_node: int = 8, kernels: int = 120, calls: int = 200, slow_node: int = 2, slow_rank: int = 5,
+         slowdown: float = 1.04, seed: int = 2026) -> None:
+    """A slow host and a slow GPU in one job: whom the pace rule names, and what the node rule makes of them."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    names = [f"kernel_{k:03d}" for k in range(kernels)]
+    rng = np.random.default_rng(seed)
+    med = rng.lognormal(np.log(100.0), 0.5, kernels)[None, :] * (1.0 + 0.01 * rng.standard_normal((ranks, kernels)))
+    med[slow_node * per_node : (slow_node + 1) * per_node] *= slowdown  # the whole node
+    med[slow_rank] *= slowdown                                          # one card elsewhere
+    med = med.astype(np.float32)
+    job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                    kernel_names=names, pace_scores=True, node_scores=True, node_groups=f"block:{per_node}")
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, np.full((1, calls), med[r].sum(), dtype=np.float32))
+            job.load_kernels(lr, np.repeat(med[r][:, None], calls, axis=1))
+        report = job.report()
+        t = report.node_scores()
+        found = report.identify_node_stragglers()
+        print(f"identify_pace_stragglers(): {sorted(s.rank for s in report.identify_pace_stragglers()['straggler_gpus_relative'])}")
+        print(f"identify_node_stragglers() nodes: {sorted(found['straggler_nodes'])}; rule {t['params']}")
+        print(f"identify_node_stragglers() ranks off pace alone: {sorted(s.rank for s in found['ranks_off_pace_alone'])}")
+        for label in sorted(t["node_scores"]):
+            d = t["node_scores"][label]
+            gpu = d["gpu"]
+            print(f"  node {label} (ranks {t['nodes'][label][0]}-{t['nodes'][label][-1]}): pace {gpu['pace']:.4f} (spread "
+                  f"{gpu['spread']:.4f}), slower / faster than the nodes' median in {gpu['slower']} / {gpu['faster']} of "
+                  f"{gpu['columns']} kernels, {d['members_off_pace']} of {d['members_rated']} ranks off pace")
+        for r in sorted(s.rank for s in found["ranks_off_pace_alone"]):
+            gpu = t["ranks"][r]["gpu"]
+            print(f"  rank {r} (node {t['node_of'][r]}): pace {gpu['pace']:.3f}, slower in {gpu['slower']} of {gpu['columns']} "
+                  f"kernels, {gpu['excess_us']:+.0f} us above the nodes' pace")
+    finally:
+        job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -492,7 +538,13 @@ def main() -> None:
     ap.add_argument("--pace-peer", action="store_true",
                     help="no training: play the pace-score scenario of a pipeline job (two stages, the second 1.5 x slower, rank 6 "
                          "4 %% slower than its stage in every kernel) with the job-wide rule and the rule per peer group, and exit")
+    ap.add_argument("--node", action="store_true",
+                    help="no training: play the node-score scenario (32 ranks on 4 nodes, every rank of node 2 and rank 5 of node "
+                         "0 4 %% slower in every kernel) with the pace rule and the node rule, and exit")
     args = ap.parse_args()
+    if args.node:
+        node()
+        return
     if args.pace_peer:
         pace_peer()
         return

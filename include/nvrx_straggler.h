@@ -445,6 +445,45 @@ int nvrx_pace_score(const float *d_table, int R, int K, int S, int first_rank, i
 int nvrx_pace_group_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group,
                           int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out, void *stream);
 
+/* Node scores: tell a slow HOST from a slow GPU.  Every score above rates a rank; an operator cordons a node.  A chassis whose
+ * fans failed, a capped PSU or a throttling host CPU makes every GPU of one node a few per cent slower in everything: the pace
+ * scores name all of its ranks and cannot say that they are one incident.  Here a node votes once per column, with the lower
+ * median of its members, and a node's pace is taken against the lower median of the nodes.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_ROBUST_MAX_RANKS.
+ *   d_groups  the NODE array, nvrx_peer_score's format unchanged, a node being a group: group[R] | members[R] | start[G+1],
+ *      1 <= G <= R and G <= NVRX_PEER_MAX_GROUPS.
+ *   max_group  as nvrx_pace_group_score takes it: in 1..R, the size of the largest node as the host knows it.
+ *   min_members >= 1: present members a (node, column) pair needs; min_nodes >= 1: referenced nodes a column needs.
+ *   Presence (v >= 0), keys (raw bit pattern order), the lower median (rank (n-1) >> 1 by key) and the canonical NaN 0x7FC00000
+ *   are the pace scores' own.
+ *   Block A, [G][K+S] pair records {f32 med, u32 n, u32 above, u32 below}: exactly nvrx_pace_group_score's column block with
+ *      min_ranks = min_members and min_peers = 1 -- med is the lower median of node g's present members, NaN where
+ *      n < max(1, min(min_members, size_g)) (the pair is then not REFERENCED); the same guards on the array's contents: start
+ *      values clamped to [0, R], a stretch cut to max_group, a member outside [0, R) skipped.
+ *   Block B, [K+S] column records {f32 N_c, u32 nodes, u32 above, u32 below} across the nodes: nodes counts the referenced pairs
+ *      of the column; N_c is the lower median of their med values -- one node, one vote, whatever the nodes' sizes --, NaN where
+ *      nodes < min_nodes (the column is then not referenced); above / below count the referenced nodes whose key of med is
+ *      greater / less than the key of that lower median (both 0 at nodes = 0).  The three counts are always written.
+ *   Block C, [G][2] node records, 32 bytes each, nvrx_pace_score's rank record with v = the node's med and ctr = N_c; a column
+ *      of the part is eligible iff the pair is referenced and the column is referenced: q = (float)((double)N_c / (double)med),
+ *      pace, spread, columns, slower, faster as defined there; the three sum slots are +0.0 in both parts.
+ *   So every word of A, B and C is exact, ties included.
+ *   Block D, [n_ranks][2] rank records: exactly nvrx_pace_score's rank record of each reported rank in [first_rank, first_rank +
+ *      n_ranks) with ctr = N_c, a column eligible iff the rank is present and the column is referenced; part 0 keeps the three
+ *      f64 sums (taken across a workgroup: their last bits depend on that order).  D says whether a node's members agree with
+ *      it, and gives each rank's microseconds above the pace of the job's nodes.
+ *   d_out  16-byte aligned, NVRX_NODE_WORDS(G, n_ranks, K, S) 32-bit words: A, B, C, D in this order.
+ *   The CONTENTS of d_groups are guarded on the device as stated above; no content makes a kernel read or write outside the
+ *   table, the array or d_out.  (group[R] is not read: D's centre is the job's.)
+ * R <= 64: three launches on `stream` (A and B in one, C, D); beyond: four (A, B, C, D).  No atomics on global memory, no
+ * scratch.  Argument errors, reported before any device is touched: those of nvrx_pace_group_score in its order (without its
+ * two thresholds), then NVRX_ERR_RANGE for min_members < 1 or min_nodes < 1, then NVRX_ERR_INVALID for a null pointer or a d_out
+ * that is not 16-byte aligned. */
+#define NVRX_NODE_WORDS(G, n_ranks, K, S) \
+    (4 * (size_t)(G) * ((size_t)(K) + (S)) + 4 * ((size_t)(K) + (S)) + 16 * (size_t)(G) + 16 * (size_t)(n_ranks))
+int nvrx_node_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group, int min_members,
+                    int min_nodes, int first_rank, int n_ranks, void *d_out, void *stream);
+
 /* Score history: how each score behaved over the last H reports.  Every score above looks inside one report window; the one
  * thing a report carries over from its predecessors is the running minimum of MED.  Here a device ring keeps the last H
  * reports' scores per reported rank, family f (0 individual, 1 relative: the parity of the score row's first two columns)
@@ -786,6 +825,13 @@ int nvrx_report_pace(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank
  * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_pace_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group,
                            int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out);
+/* nvrx_node_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor; d_groups sized for the descriptor's R).  Ordered behind that report's kernels exactly as
+ * nvrx_report_pace_group orders itself: the context's stream, with an event when the report was re-homed or scored resident.
+ * The host does not wait; copy d_out with a D2H on the context's stream, and do not let a later report rewrite the table before
+ * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_node(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group, int min_members,
+                     int min_nodes, int first_rank, int n_ranks, void *d_out);
 /* nvrx_score_history (above) on the result block of the report LAST issued through `desc` on `ctx` (desc->d_scores; R and S
  * from the descriptor).  Ordered behind that report's last kernel exactly as nvrx_report_robust orders itself: the context's
  * stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a D2H on the

@@ -1,0 +1,84 @@
+// node_args_check.cpp -- a stand-alone host program for `make node-args-check`: it drives the argument checks of
+// nvrx_node_score and nvrx_report_node with INVALID arguments only, so no call reaches a device, and is meant to be built
+// together with nvrx_straggler.hip with AddressSanitizer and UndefinedBehaviorSanitizer on the host code.  Exit status 0 when
+// every call returned the error the header promises.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "nvrx_straggler.h"
+
+static int failures = 0;
+
+static void expect(const char *what, int got, int want, const char *needle) {
+    const char *msg = nvrx_last_error();
+    if (got != want || (needle && (!msg || !strstr(msg, needle)))) {
+        fprintf(stderr, "FAIL %s: returned %d (want %d), message \"%s\" (want \"%s\")\n", what, got, want, msg ? msg : "", needle ? needle : "");
+        failures++;
+    }
+}
+
+int main() {
+    float *table = reinterpret_cast<float *>(uintptr_t{8192});  // never dereferenced: every call below fails its checks
+    int32_t *groups = reinterpret_cast<int32_t *>(uintptr_t{12288});
+    void *out = reinterpret_cast<void *>(uintptr_t{16384});
+    void *odd = reinterpret_cast<void *>(uintptr_t{16392});
+    // (table, R, K, S, groups, G, max_group, min_members, min_nodes, first_rank, n_ranks, out, stream)
+    expect("R 0", nvrx_node_score(table, 0, 5, 2, groups, 1, 1, 2, 3, 0, 1, out, nullptr), NVRX_ERR_INVALID, "shape");
+    expect("R < 0", nvrx_node_score(table, -3, 5, 2, groups, 1, 1, 2, 3, 0, 1, out, nullptr), NVRX_ERR_INVALID, "shape");
+    expect("K < 0", nvrx_node_score(table, 8, -1, 2, groups, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_INVALID, "shape");
+    expect("S < 0", nvrx_node_score(table, 8, 5, -1, groups, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_INVALID, "shape");
+    expect("R too large", nvrx_node_score(table, NVRX_ROBUST_MAX_RANKS + 1, 5, 2, groups, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE,
+           "ranks");
+    expect("K too large", nvrx_node_score(table, 8, NVRX_MAX_ROWS + 1, 2, groups, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "ids");
+    expect("S too large", nvrx_node_score(table, 8, 5, NVRX_MAX_ROWS + 1, groups, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "ids");
+    expect("first_rank < 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, 3, -1, 4, out, nullptr), NVRX_ERR_RANGE, "outside");
+    expect("n_ranks 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, 3, 0, 0, out, nullptr), NVRX_ERR_RANGE, "outside");
+    expect("ranks past R", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, 3, 5, 4, out, nullptr), NVRX_ERR_RANGE, "outside");
+    expect("G 0", nvrx_node_score(table, 8, 5, 2, groups, 0, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_INVALID, "groups");
+    expect("G < 0", nvrx_node_score(table, 8, 5, 2, groups, -1, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_INVALID, "groups");
+    expect("G > R", nvrx_node_score(table, 8, 5, 2, groups, 9, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "groups");
+    expect("G too large", nvrx_node_score(table, NVRX_PEER_MAX_GROUPS + 2, 5, 2, groups, NVRX_PEER_MAX_GROUPS + 1, 4, 2, 3, 0, 8, out,
+                                          nullptr), NVRX_ERR_RANGE, "at most");
+    expect("max_group 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 0, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "max_group");
+    expect("max_group < 0", nvrx_node_score(table, 8, 5, 2, groups, 2, -4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "max_group");
+    expect("max_group > R", nvrx_node_score(table, 8, 5, 2, groups, 2, 9, 2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "max_group");
+    expect("min_members 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 0, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "min_members");
+    expect("min_members < 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, -2, 3, 0, 8, out, nullptr), NVRX_ERR_RANGE, "min_members");
+    expect("min_nodes 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, 0, 0, 8, out, nullptr), NVRX_ERR_RANGE, "min_nodes");
+    expect("min_nodes < 0", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, -1, 0, 8, out, nullptr), NVRX_ERR_RANGE, "min_nodes");
+    expect("null table", nvrx_node_score(nullptr, 8, 5, 2, groups, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_INVALID, "null");
+    expect("null groups", nvrx_node_score(table, 8, 5, 2, nullptr, 2, 4, 2, 3, 0, 8, out, nullptr), NVRX_ERR_INVALID, "null");
+    expect("null records", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, 3, 0, 8, nullptr, nullptr), NVRX_ERR_INVALID, "null");
+    expect("misaligned records", nvrx_node_score(table, 8, 5, 2, groups, 2, 4, 2, 3, 0, 8, odd, nullptr), NVRX_ERR_INVALID, "aligned");
+    // the order: a bad shape wins over a bad rank range, that over G, that over max_group, that over min_members, that over
+    // min_nodes, that over the pointers
+    expect("shape before ranks", nvrx_node_score(nullptr, 0, 5, 2, nullptr, 0, 0, 0, 0, 5, 4, odd, nullptr), NVRX_ERR_INVALID, "shape");
+    expect("ranks before G", nvrx_node_score(nullptr, 8, 5, 2, nullptr, 0, 0, 0, 0, 5, 4, odd, nullptr), NVRX_ERR_RANGE, "outside");
+    expect("G before max_group", nvrx_node_score(nullptr, 8, 5, 2, nullptr, 9, 0, 0, 0, 0, 8, odd, nullptr), NVRX_ERR_RANGE, "groups");
+    expect("max_group before min_members", nvrx_node_score(nullptr, 8, 5, 2, nullptr, 2, 0, 0, 0, 0, 8, odd, nullptr), NVRX_ERR_RANGE, "max_group");
+    expect("min_members before min_nodes", nvrx_node_score(nullptr, 8, 5, 2, nullptr, 2, 4, 0, 0, 0, 8, odd, nullptr), NVRX_ERR_RANGE, "min_members");
+    expect("min_nodes before pointers", nvrx_node_score(nullptr, 8, 5, 2, nullptr, 2, 4, 2, 0, 0, 8, odd, nullptr), NVRX_ERR_RANGE, "min_nodes");
+
+    // nvrx_report_node: every check that precedes the look at the context reads the descriptor's shape only, so a context that
+    // was never created will do (the state check -- a report issued through this descriptor -- is the GPU tests' to cover)
+    nvrx_ctx *ctx = reinterpret_cast<nvrx_ctx *>(uintptr_t{4096});
+    nvrx_report_desc d;
+    memset(&d, 0, sizeof d);
+    d.R = 8, d.K = 5, d.S = 2;
+    expect("null context", nvrx_report_node(nullptr, &d, groups, 2, 4, 2, 3, 0, 8, out), NVRX_ERR_INVALID, "null");
+    expect("null descriptor", nvrx_report_node(ctx, nullptr, groups, 2, 4, 2, 3, 0, 8, out), NVRX_ERR_INVALID, "null");
+    expect("report: ranks past R", nvrx_report_node(ctx, &d, groups, 2, 4, 2, 3, 5, 4, out), NVRX_ERR_RANGE, "outside");
+    expect("report: G 0", nvrx_report_node(ctx, &d, groups, 0, 4, 2, 3, 0, 8, out), NVRX_ERR_INVALID, "groups");
+    expect("report: G > R", nvrx_report_node(ctx, &d, groups, 9, 4, 2, 3, 0, 8, out), NVRX_ERR_RANGE, "groups");
+    expect("report: max_group > R", nvrx_report_node(ctx, &d, groups, 2, 9, 2, 3, 0, 8, out), NVRX_ERR_RANGE, "max_group");
+    expect("report: min_members 0", nvrx_report_node(ctx, &d, groups, 2, 4, 0, 3, 0, 8, out), NVRX_ERR_RANGE, "min_members");
+    expect("report: min_nodes 0", nvrx_report_node(ctx, &d, groups, 2, 4, 2, 0, 0, 8, out), NVRX_ERR_RANGE, "min_nodes");
+    expect("report: null groups", nvrx_report_node(ctx, &d, nullptr, 2, 4, 2, 3, 0, 8, out), NVRX_ERR_INVALID, "null");
+    expect("report: null records", nvrx_report_node(ctx, &d, groups, 2, 4, 2, 3, 0, 8, nullptr), NVRX_ERR_INVALID, "aligned");
+    expect("report: misaligned records", nvrx_report_node(ctx, &d, groups, 2, 4, 2, 3, 0, 8, odd), NVRX_ERR_INVALID, "aligned");
+    d.R = 0;
+    expect("report: R 0", nvrx_report_node(ctx, &d, groups, 1, 1, 2, 3, 0, 1, out), NVRX_ERR_INVALID, "shape");
+    printf("node_args_check: %d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}

@@ -151,16 +151,18 @@ struct PaceCol {
 
 // row and recs point at the part's first column; i >= ncols reads nothing.  GROUPED: the records are those of the rank's group,
 // whose centre is a number exactly where the pair is referenced, and min_ranks says whether the rank has a group at all (0 / 1).
-template <bool GROUPED = false>
+// NODE (nvrx_node.inl): the "row" is a node's stretch of pair records, its value the first of a record's four words -- NaN, so
+// not present, where the pair is not referenced --, and the centre is a number exactly where the column is referenced.
+template <bool GROUPED = false, bool NODE = false>
 __device__ __forceinline__ PaceCol pace_column(const float *__restrict__ row, const uint4 *__restrict__ recs, int i, int ncols,
                                                int min_ranks) {
     PaceCol o;
     o.qkey = PACE_MARK, o.eligible = o.slower = o.faster = false, o.quot = 0.0;
     if (i < ncols) {
-        const float v = row[i];
+        const float v = row[NODE ? 4 * i : i];
         const uint4 rec = recs[i];
         const float ctr = __uint_as_float(rec.x);
-        if constexpr (GROUPED)
+        if constexpr (GROUPED || NODE)
             o.eligible = v >= 0.0f && min_ranks != 0 && ctr == ctr;
         else
             o.eligible = v >= 0.0f && rec.y != 0u && (int)rec.y >= min_ranks;
@@ -227,11 +229,13 @@ __device__ __forceinline__ void pace_store(uint4 *dst, float pace, float spread,
 // THREADS 64 (NREG 1): one wave, one column per lane; 256 with NREG 16: keys in registers; 1024 with NREG 0: re-reading.
 // GROUPED (a compile-time flag: the job-wide instantiations are what they were): the records at cols + group[r] * (K+S), a
 // column eligible iff the rank is present and its group's pair is referenced.
-template <int THREADS, int NREG, bool GROUPED = false>
+// NODE (likewise; nvrx_node.inl): `table` is the [G][K+S] pair records, a row of 4 (K+S) words per node; no weights, so the
+// three sums stay +0.0 in both parts.
+template <int THREADS, int NREG, bool GROUPED = false, bool NODE = false>
 __global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPED, PaceGroupRankArgs, PaceRankArgs> a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int K = a.K, S = a.S, KS = K + S;
-    const int L = NVRX_TABLE_LEN(K, S);
+    const int L = NODE ? 4 * KS : NVRX_TABLE_LEN(K, S);
     const int part = (int)blockIdx.y;
     const int ncols = part ? S : K;
     const int base = part ? K : 0;
@@ -248,15 +252,15 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPE
     }
     uint4 *__restrict__ dst = a.out + ((size_t)blockIdx.x * 2 + (size_t)part) * 2;
     const float NaN = __builtin_nanf("");
-    row += base;
+    row += NODE ? 4 * base : base;
 
     if constexpr (THREADS == 64) {
-        const PaceCol col = pace_column<GROUPED>(row, recs, lane, ncols, min_ranks);
+        const PaceCol col = pace_column<GROUPED, NODE>(row, recs, lane, ncols, min_ranks);
         const bool has_q = col.qkey != PACE_MARK;
-        const double w = (part == 0 && col.eligible) ? (double)wrow[lane] : 0.0;
+        const double w = (!NODE && part == 0 && col.eligible) ? (double)wrow[lane] : 0.0;
         const double total = wave_sum_f64(w);
         const double slow = wave_sum_f64(col.slower ? w : 0.0);
-        const double excess = wave_sum_f64((part == 0 && has_q) ? w * (1.0 - col.quot) : 0.0);
+        const double excess = wave_sum_f64((!NODE && part == 0 && has_q) ? w * (1.0 - col.quot) : 0.0);
         const uint32_t columns = (uint32_t)__popcll(__ballot(col.eligible));
         const uint32_t slower = (uint32_t)__popcll(__ballot(col.slower));
         const uint32_t faster = (uint32_t)__popcll(__ballot(col.faster));
@@ -285,10 +289,10 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPE
         uint32_t columns = 0, slower = 0, faster = 0, m = 0;
         auto take = [&](const PaceCol &col, int i) {
             const bool has_q = col.qkey != PACE_MARK;
-            const double w = (part == 0 && col.eligible) ? (double)wrow[i] : 0.0;
+            const double w = (!NODE && part == 0 && col.eligible) ? (double)wrow[i] : 0.0;
             total += w;
             slow += col.slower ? w : 0.0;
-            excess += (part == 0 && has_q) ? w * (1.0 - col.quot) : 0.0;  // (part 1 keeps +0.0: no 0 * inf)
+            excess += (!NODE && part == 0 && has_q) ? w * (1.0 - col.quot) : 0.0;  // (part 1 keeps +0.0: no 0 * inf)
             columns += col.eligible ? 1u : 0u;
             slower += col.slower ? 1u : 0u;
             faster += col.faster ? 1u : 0u;
@@ -298,13 +302,13 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPE
 #pragma unroll
             for (int j = 0; j < NREG; j++) {
                 const int i = tid + j * THREADS;
-                const PaceCol col = pace_column<GROUPED>(row, recs, i, ncols, min_ranks);
+                const PaceCol col = pace_column<GROUPED, NODE>(row, recs, i, ncols, min_ranks);
                 keys[j] = col.qkey;
                 take(col, i);
             }
         } else {
             keys[0] = PACE_MARK;
-            for (int i = tid; i < ncols; i += THREADS) take(pace_column<GROUPED>(row, recs, i, ncols, min_ranks), i);
+            for (int i = tid; i < ncols; i += THREADS) take(pace_column<GROUPED, NODE>(row, recs, i, ncols, min_ranks), i);
         }
         total = wave_sum_f64(total);
         slow = wave_sum_f64(slow);
@@ -331,10 +335,10 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPE
                 spread = __uint_as_float(pace_radix_select<THREADS, NREG>([&](int j) { return pace_dev_key(keys[j], pace); }, ncols,
                                                                           target, s_hist, s_wave, s_sel));
             } else {
-                pace = key2f(pace_radix_select<THREADS, 0>([&](int i) { return pace_column<GROUPED>(row, recs, i, ncols, mr).qkey; }, ncols,
+                pace = key2f(pace_radix_select<THREADS, 0>([&](int i) { return pace_column<GROUPED, NODE>(row, recs, i, ncols, mr).qkey; }, ncols,
                                                            target, s_hist, s_wave, s_sel));
                 spread = __uint_as_float(pace_radix_select<THREADS, 0>(
-                    [&](int i) { return pace_dev_key(pace_column<GROUPED>(row, recs, i, ncols, mr).qkey, pace); }, ncols, target, s_hist,
+                    [&](int i) { return pace_dev_key(pace_column<GROUPED, NODE>(row, recs, i, ncols, mr).qkey, pace); }, ncols, target, s_hist,
                     s_wave, s_sel));
             }
         }

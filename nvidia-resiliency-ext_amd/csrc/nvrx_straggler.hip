@@ -3971,3 +3971,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_peer.inl"
 #include "nvrx_pace.inl"
 #include "nvrx_pace_group.inl"
+#include "nvrx_node.inl"

@@ -52,6 +52,8 @@ class StragglerDetectionCallback(Callback):
         peer_groups=None,
         warn_if_off_pace: bool = False,
         pace_peer_groups: bool = False,
+        warn_if_node_off_pace: bool = False,
+        node_groups=None,
     ):
         """
         Args:
@@ -94,12 +96,19 @@ class StragglerDetectionCallback(Callback):
                 (``Detector.initialize(pace_peer_groups=True)``), so that the healthy ranks of a slower pipeline stage are not
                 warned about at every report, and the warning says the ranks are off their peer group's pace.  Still a
                 warning only.
+            warn_if_node_off_pace: False (the default): nothing changes.  True: the detector also computes node scores
+                (``Detector.initialize(node_scores=True)``), and every report that finds a NODE a little slower than the job's
+                nodes in nearly all of its kernels, most of its GPUs agreeing (``Report.identify_node_stragglers``: a host
+                fault -- fans, PSU, host CPU, power profile), logs one warning that names the nodes with their pace and how
+                many of their GPUs are off pace.  A warning only: it never stops the job.
+            node_groups: which ranks share a node, for ``warn_if_node_off_pace`` (None: the node names the detector gathers;
+                else ``"block:N"``, ``"mod:N"`` or one label per rank, as ``Detector.initialize(node_groups=...)``).
 
         Raises:
             ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64],
                 ``warn_if_waited_for``, ``warn_if_off_pace`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
                 ``min_consecutive_reports`` > 1 (the score history does not hold peer scores), or ``pace_peer_groups`` without
-                ``warn_if_off_pace`` or without ``peer_groups``.
+                ``warn_if_off_pace`` or without ``peer_groups``, or ``warn_if_node_off_pace`` without ``calc_relative_gpu_perf``.
         """
         self.initialized = False
         self.logger = logging.getLogger(logger_name)
@@ -146,6 +155,10 @@ class StragglerDetectionCallback(Callback):
                 raise ValueError("pace_peer_groups needs warn_if_off_pace=True: it changes what the pace scores compare with")
             if peer_groups is None:
                 raise ValueError("pace_peer_groups needs peer_groups: which ranks do the same work")
+        self.warn_if_node_off_pace = bool(warn_if_node_off_pace)
+        if self.warn_if_node_off_pace and not calc_relative_gpu_perf:
+            raise ValueError("warn_if_node_off_pace needs calc_relative_gpu_perf=True: node scores compare nodes")
+        self.node_groups = node_groups
         self._unrated_said = False
         self.interval_est_was_reset = False
 
@@ -172,6 +185,10 @@ class StragglerDetectionCallback(Callback):
             persistence["pace_scores"] = True
         if self.pace_peer_groups:
             persistence["pace_peer_groups"] = True
+        if self.warn_if_node_off_pace:
+            persistence["node_scores"] = True
+            if self.node_groups is not None:
+                persistence["node_groups"] = self.node_groups
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -202,6 +219,8 @@ class StragglerDetectionCallback(Callback):
             self._warn_waited_for(report)  # (likewise)
         if self.warn_if_off_pace and bool(report) and trainer.global_rank == 0:
             self._warn_off_pace(report)  # (likewise)
+        if self.warn_if_node_off_pace and bool(report) and trainer.global_rank == 0:
+            self._warn_node_off_pace(report)  # (likewise)
         if not detector.is_interval_elapsed():
             return  # no report was due this iteration
         if self.stop_if_detected and self._decision_of_rank0(found):
@@ -306,6 +325,22 @@ class StragglerDetectionCallback(Callback):
             return
         self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs are a little slower in nearly all of their kernels "
                             "(degraded card?): " + "; ".join(parts))
+
+    def _warn_node_off_pace(self, report) -> None:
+        """One warning per report that names the nodes that are a little slower than the job's nodes in nearly all of their
+        kernels, most of their GPUs agreeing, with their pace and how many of their GPUs are off pace
+        (``warn_if_node_off_pace``).  Never a reason to halt."""
+        named = report.identify_node_stragglers()["straggler_nodes"]
+        if not named:
+            return
+        nodes = report.node_scores()["node_scores"]
+        parts = []
+        for label in sorted(named, key=str):
+            d = nodes[label]
+            parts.append(f"node {label} (pace {d['gpu']['pace']:.3f}, slower in {d['gpu']['slower']} of {d['gpu']['columns']} "
+                         f"kernels, {d['members_off_pace']} of {d['members_rated']} GPUs off pace)")
+        self.logger.warning("STRAGGLER DETECTION WARNING: Some nodes are a little slower in nearly all of their kernels on most "
+                            "of their GPUs (host fault: cooling, power, host CPU?): " + "; ".join(parts))
 
     def _name_the_kernels(self, report, flagged) -> None:
         """Kernel attribution (``NVRX_KERNEL_ATTRIBUTION=N``, off by default: nothing is logged then): for every flagged GPU the

@@ -100,6 +100,8 @@ SYMBOLS = [
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_group_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p]),
+    ("nvrx_node_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
@@ -147,6 +149,7 @@ SYMBOLS = [
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace_group", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p]),
+    ("nvrx_report_node", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
@@ -261,6 +264,12 @@ def pace_group_words(G: int, n_ranks: int, K: int, S: int) -> int:
     """NVRX_PACE_GROUP_WORDS: 32-bit words of a block of pace scores per peer group: ``[G][K+S][4]`` column records, then
     ``[n_ranks][2][8]``."""
     return 4 * G * (K + S) + 16 * n_ranks
+
+
+def node_words(G: int, n_ranks: int, K: int, S: int) -> int:
+    """NVRX_NODE_WORDS: 32-bit words of a node-score block: ``[G][K+S][4]`` pair records, ``[K+S][4]`` column records across
+    the nodes, ``[G][2][8]`` node records, then ``[n_ranks][2][8]`` rank records."""
+    return 4 * G * (K + S) + 4 * (K + S) + 16 * G + 16 * n_ranks
 
 
 def history_stride(H: int) -> int:

@@ -331,14 +331,14 @@ class PeerGroups:
         self._max_size = None
 
     @classmethod
-    def resolve(cls, spec, R: int) -> "PeerGroups":
+    def resolve(cls, spec, R: int, what: str = "peer_groups") -> "PeerGroups":
         """``spec`` as ``ReportGenerator`` keeps it -- ``("block", N)``, ``("mod", N)`` or a tuple of labels, one per
-        logical rank -- for a table of ``R`` ranks."""
+        logical rank -- for a table of ``R`` ranks (``what``: the option's name in the message)."""
         if isinstance(spec, _PeerRule):
             kind, n = spec
             return cls([r // n if kind == "block" else r % n for r in range(R)])
         if len(spec) != R:
-            raise ValueError(f"peer_groups has {len(spec)} labels, the job has {R} logical ranks")
+            raise ValueError(f"{what} has {len(spec)} labels, the job has {R} logical ranks")
         return cls(spec)
 
     @property
@@ -450,6 +450,37 @@ class PaceGroup:
             with self._lock:
                 if self._host is None:
                     self._host = self.backend.pace_group_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
+class Node:
+    """Node scores of one report (``nvrx_node_score`` / ``nvrx_report_node``), enqueued and not waited for: once the kernels
+    have run, the workspace's device buffer holds the ``[G][K + S]`` pair records ``{med, n, above, below}``, the ``K + S``
+    column records across the nodes ``{center, nodes, above, below}``, ``[G][2]`` node records and ``[n_ranks][2]`` rank
+    records, both spelled as a ``Pace`` rank record (include/nvrx_straggler.h).  ``records()`` waits for them and takes the
+    private host copy (one ordered D2H on the backend's stream): when a ``Report`` first asks, or --
+    ``Workspace.node_settle`` -- before the next report on the same workspace rewrites the table the kernels read and the
+    buffer they write."""
+
+    __slots__ = ("backend", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "min_members", "min_nodes", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, K: int, S: int, first_rank: int, n_ranks: int,
+                 min_members: int, min_nodes: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.G, self.K, self.S = G, K, S
+        self.first_rank, self.n_ranks, self.min_members, self.min_nodes = first_rank, n_ranks, min_members, min_nodes
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(pairs [G, K+S, 4], cols [K+S, 4], nodes [G, 2, 8], ranks [n_ranks, 2, 8])`` uint32 (private copies; the float
+        fields are bit patterns); the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.node_copy_out(self)
                     self.backend = self._keep = None
         return self._host
 
@@ -740,6 +771,8 @@ class Workspace:
             self.peer_settle()
         if self._pace_last is not None:
             self.pace_settle()
+        if self._node_last is not None:
+            self.node_settle()
         if self._family_state:
             for fam in FAMILIES[1:]:
                 self.family_settle(fam)
@@ -828,6 +861,25 @@ class Workspace:
         """Before anything rewrites this workspace's table: the last pace step's kernels have run and their results are on
         the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
         last, self._pace_last = self._pace_last, None
+        if last is not None:
+            last.records()
+
+    # ---- node scores (off unless a ReportGenerator asks: nothing is allocated before) ------------------------------
+    _node_buf = None   # device: the four record blocks of the last node step of this workspace's table
+    _node_last = None  # the Node whose kernels may still be reading the table / writing _node_buf
+
+    def node_buffers(self, G: int, n_ranks: int):
+        """The records buffer for node scores of ``n_ranks`` ranks on ``G`` nodes (cold: allocated once per shape)."""
+        words = _native.node_words(G, n_ranks, self.K, self.S)
+        if self._node_buf is None or self._node_buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._node_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return self._node_buf
+
+    def node_settle(self) -> None:
+        """Before anything rewrites this workspace's table: the last node step's kernels have run and their results are on
+        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._node_last = self._node_last, None
         if last is not None:
             last.records()
 
@@ -1185,6 +1237,34 @@ class HipBackend:
         host = np.empty(n, dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pc.d_ptr, n * 4, self._stream_handle))
         return host[: 4 * pc.G * KS].reshape(pc.G, KS, 4).copy(), host[4 * pc.G * KS :].reshape(pc.n_ranks, 2, 8).copy()
+
+    def node_score(self, ws: Workspace, table: torch.Tensor, nodes: PeerGroups, first_rank: int = 0,
+                   n_ranks: Optional[int] = None, min_members: int = 2, min_nodes: int = 3) -> Node:
+        """Node scores of ``table`` ([R, L], the table ``score`` was given) with the ranks of ``nodes`` (a ``PeerGroups`` whose
+        groups are the nodes) for ranks ``[first_rank, first_rank + n_ranks)``: ``nvrx_node_score`` enqueued on the backend's
+        stream behind the score kernel.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if nodes.R != ws.R:
+            raise ValueError(f"node groups resolved for {nodes.R} ranks, the table has {ws.R}")
+        ws.node_settle()
+        buf = ws.node_buffers(nodes.G, n_ranks)
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_node_score(table_ptr, ws.R, ws.K, ws.S, nodes.device(self).data_ptr(), nodes.G, nodes.max_size,
+                                      min_members, min_nodes, first_rank, n_ranks, buf.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._node_last = Node(self, buf, nodes.G, ws.K, ws.S, first_rank, n_ranks, min_members, min_nodes)
+        return out
+
+    def node_copy_out(self, nd: Node):
+        """The one wait of a report's node scores: a D2H of the records on the backend's stream, behind the kernels."""
+        KS, G = nd.K + nd.S, nd.G
+        n = _native.node_words(G, nd.n_ranks, nd.K, nd.S)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, nd.d_ptr, n * 4, self._stream_handle))
+        a, b, c = 4 * G * KS, 4 * G * KS + 4 * KS, 4 * G * KS + 4 * KS + 16 * G
+        return (host[:a].reshape(G, KS, 4).copy(), host[a:b].reshape(KS, 4).copy(), host[b:c].reshape(G, 2, 8).copy(),
+                host[c:].reshape(nd.n_ranks, 2, 8).copy())
 
     def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
         """What both routes of a history step share: the ring of ``state`` with room for this workspace's section ids (cold:
@@ -1631,6 +1711,22 @@ class HipRings:
         if rc < 0:
             _native.check(rc)
         out = ws._pace_last = PaceGroup(self.backend, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks, min_peers)
+        return out
+
+    def report_node(self, ws: Workspace, nodes: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                    min_members: int = 2, min_nodes: int = 3) -> Node:
+        """Node scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_node``): enqueued
+        behind that report's kernels by the library, nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if nodes.R != ws.R:
+            raise ValueError(f"node groups resolved for {nodes.R} ranks, the table has {ws.R}")
+        ws.node_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
+        buf = ws.node_buffers(nodes.G, n_ranks)
+        rc = self.lib.nvrx_report_node(self.ctx, ws.block.desc_ref, nodes.device(self.backend).data_ptr(), nodes.G,
+                                       nodes.max_size, min_members, min_nodes, first_rank, n_ranks, buf.data_ptr())
+        if rc < 0:
+            _native.check(rc)
+        out = ws._node_last = Node(self.backend, buf, nodes.G, ws.K, ws.S, first_rank, n_ranks, min_members, min_nodes)
         return out
 
     def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,

@@ -33,7 +33,9 @@ class FoldedJob:
                  collective_slack: bool = False, slack_min_ranks: int = 4, slack_min_share: float = 0.05,
                  slack_max_ratio: float = 0.25, kernel_names: Sequence[str] = (), peer_groups=None, peer_min_ranks: int = 2,
                  pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8, pace_min_effect: float = 0.03,
-                 pace_min_breadth: float = 0.9, pace_peer_groups: bool = False):
+                 pace_min_breadth: float = 0.9, pace_peer_groups: bool = False, node_scores: bool = False, node_groups=None,
+                 node_min_members: int = 2, node_min_nodes: int = 3, node_min_columns: int = 8, node_min_effect: float = 0.03,
+                 node_min_breadth: float = 0.9, node_min_agree: float = 0.75):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -62,7 +64,12 @@ class FoldedJob:
                                         peer_min_ranks=peer_min_ranks, pace_scores=pace_scores,
                                         pace_min_ranks=pace_min_ranks, pace_min_columns=pace_min_columns,
                                         pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth,
-                                        **({"pace_peer_groups": True} if pace_peer_groups else {}))
+                                        **({"pace_peer_groups": True} if pace_peer_groups else {}),
+                                        **({"node_scores": True, "node_groups": node_groups,
+                                            "node_min_members": node_min_members, "node_min_nodes": node_min_nodes,
+                                            "node_min_columns": node_min_columns, "node_min_effect": node_min_effect,
+                                            "node_min_breadth": node_min_breadth, "node_min_agree": node_min_agree}
+                                           if node_scores else {}))
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         # (the same object every report so the reporter's cached plan stays valid)
         self._no_kernel_rows = {name: self.rings.row_for(_native.KIND_KERNEL, name) for name in self.kernel_names}

@@ -821,34 +821,103 @@ class _PaceGroupSource(_PaceSource):
         return self._built
 
 
-def _peer_spec(peer_groups):
+def _node_member_rule(d: dict, columns: int, effect: float, breadth: float):
+    """``(rated, off_pace)`` of one part of a pace rank record: the pace rule of ``identify_pace_stragglers``."""
+    rated = d["columns"] >= columns and d["columns"] > 0
+    return rated, bool(rated and d["pace"] <= 1.0 - effect and d["slower"] / d["columns"] >= breadth)
+
+
+def _node_agreement(t: dict, part: str, label, columns: int, effect: float, breadth: float):
+    """``(members_rated, members_off_pace, agree)`` of one node: over its members the report covers, how many have enough
+    columns to be rated by the pace rule against the nodes' centre, how many of those are off pace, and the quotient (None
+    when the report covers no rated member)."""
+    ranks = t["ranks"]
+    rule = [_node_member_rule(ranks[r][part], columns, effect, breadth) for r in t["nodes"][label] if r in ranks]
+    rated, off = sum(1 for x, _ in rule if x), sum(1 for _, y in rule if y)
+    return rated, off, (off / rated if rated else None)
+
+
+class _NodeSource:
+    """What a report keeps of its node scores: the backend's handle (``records()`` waits for the kernels and copies the four
+    record blocks out on first use), the ranks its rank rows stand for, the sections it shows with their ids, the kernel names
+    by id as the report's mapper had them at report time, the parameters in force and the nodes (a ``backend.PeerGroups``)."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "params", "nodes", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, params: dict, nodes):
+        self.handle, self.ranks, self.kernels, self.params, self.nodes = handle, tuple(ranks), kernels, params, nodes
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            pairs, cols, nrecs, rrecs = self.handle.records()
+            K = len(self.kernels)
+            labels = self.nodes.labels
+            node = self.nodes.group.tolist()
+            G = len(labels)
+            center = np.ascontiguousarray(cols).view(np.float32)[:, 0].tolist()
+            counts = cols[:, 1:].tolist()
+            median = np.ascontiguousarray(pairs).view(np.float32)[:, :, 0].tolist()
+            present = pairs[:, :, 1].tolist()
+
+            def column(c):
+                return {"center": center[c], "nodes": counts[c][0], "above": counts[c][1], "below": counts[c][2],
+                        "per_node": {labels[g]: {"median": median[g][c], "ranks": present[g][c]} for g in range(G)}}
+
+            rated = _pace_rank_parts(nrecs, labels)
+            for d in rated.values():  # (a node record has no weights: its three sums are empty)
+                for key in ("total_us", "slower_us", "excess_us"):
+                    del d["gpu"][key]
+            t = self._built = {
+                "nodes": {labels[g]: self.nodes.members(g) for g in range(G)},
+                "node_of": {r: labels[g] for r, g in enumerate(node)},
+                "kernels": {name: column(k) for k, name in enumerate(self.kernels)},
+                "section_columns": {name: column(K + g) for name, g in self.sections.items()},
+                "node_scores": rated,
+                "ranks": _pace_rank_parts(rrecs, self.ranks),
+                "unrated_nodes": [lab for lab, d in rated.items() if d["gpu"]["columns"] == 0 and d["sections"]["columns"] == 0],
+                "params": dict(self.params),
+            }
+            p = self.params
+            for lab, d in rated.items():
+                for part in ("gpu", "sections"):
+                    d[part]["members_rated"], d[part]["members_off_pace"], d[part]["agree"] = _node_agreement(
+                        t, part, lab, p["min_columns"], p["min_effect"], p["min_breadth"])
+                for key in ("members_rated", "members_off_pace", "agree"):
+                    d[key] = d["gpu"][key]
+            self.handle = None
+        return self._built
+
+
+def _peer_spec(peer_groups, what: str = "peer_groups"):
     """``ReportGenerator``'s ``peer_groups`` as the generator keeps it: None (off), a rule (``"block:N"``: label ``rank //
     N``, contiguous stages; ``"mod:N"``: label ``rank % N``) or a tuple of ``int`` / ``str`` labels, one per logical rank.
-    Nothing else is accepted."""
+    Nothing else is accepted.  ``node_groups`` is parsed here too: ``what`` is the option's name in the messages."""
     if peer_groups is None:
         return None
     if isinstance(peer_groups, str):
         kind, sep, num = peer_groups.partition(":")
         if kind not in ("block", "mod") or not sep or not num.strip().isdigit():
-            raise ValueError(f"peer_groups must be 'block:N', 'mod:N' or a sequence of labels, got {peer_groups!r}")
+            raise ValueError(f"{what} must be 'block:N', 'mod:N' or a sequence of labels, got {peer_groups!r}")
         n = int(num)
         if n < 1:
-            raise ValueError(f"peer_groups={peer_groups!r}: N must be at least 1")
+            raise ValueError(f"{what}={peer_groups!r}: N must be at least 1")
         return _backend_mod._PeerRule((kind, n))
     if not isinstance(peer_groups, (list, tuple, np.ndarray)):
-        raise TypeError("peer_groups must be 'block:N', 'mod:N' or a list, tuple or ndarray of int or str labels, "
+        raise TypeError(f"{what} must be 'block:N', 'mod:N' or a list, tuple or ndarray of int or str labels, "
                         f"got {type(peer_groups).__name__}")
     if isinstance(peer_groups, np.ndarray):
         if peer_groups.ndim != 1:
-            raise ValueError(f"peer_groups must have one label per logical rank, got an array of shape {peer_groups.shape}")
+            raise ValueError(f"{what} must have one label per logical rank, got an array of shape {peer_groups.shape}")
         peer_groups = peer_groups.tolist()
     labels = []
     for lab in peer_groups:
         if isinstance(lab, bool) or not isinstance(lab, (int, np.integer, str)):
-            raise TypeError(f"peer_groups labels must be int or str, got {lab!r}")
+            raise TypeError(f"{what} labels must be int or str, got {lab!r}")
         labels.append(lab if isinstance(lab, str) else int(lab))
     if not labels:
-        raise ValueError("peer_groups must have one label per logical rank, got none")
+        raise ValueError(f"{what} must have one label per logical rank, got none")
     return tuple(labels)
 
 
@@ -1137,6 +1206,9 @@ class Report:
         pace = self.__dict__.get("_pace")
         if pace is not None:
             state["_pace"] = pace.build() if isinstance(pace, _PaceSource) else pace
+        node = self.__dict__.get("_node")
+        if node is not None:
+            state["_node"] = node.build() if isinstance(node, _NodeSource) else node
         history = self.__dict__.get("_history")
         if history is not None:
             state["_history"] = history.build() if isinstance(history, _HistorySource) else history
@@ -1376,6 +1448,70 @@ class Report:
 
         return {"straggler_gpus_relative": self._ids(named("gpu")),
                 "straggler_section_ranks_relative": self._ids(named("sections"))}
+
+    def node_scores(self) -> Dict[str, Any]:
+        """Node scores (``ReportGenerator(node_scores=True)``; ``{}`` when the report carries none): the pace scores one level
+        up.  A fault of the HOST -- failed fans, a capped PSU, a throttling CPU, the wrong power profile -- makes every GPU of
+        one node a few per cent slower in everything; the pace scores then name all of its ranks and cannot say that they are
+        one incident.  Here a node's value of a kernel or section is the lower median of its ranks, the reference of a column
+        is the lower median of the NODES' values (one node, one vote), and a node's ``pace`` is the lower median across its
+        columns of reference / own.  The centre is the job's: a lockstep model, as for the job-wide pace scores.
+
+        ``{"nodes": {label: [ranks]}, "node_of": {rank: label}, "kernels": {kernel: {...}}, "section_columns": {section:
+        {...}}, "node_scores": {label: {...}}, "ranks": {rank: {...}}, "unrated_nodes": [labels], "params": {...}}``.  A kernel
+        or section holds ``center`` (NaN where fewer than ``min_nodes`` nodes have a value), ``nodes`` with a value, how many
+        of them are ``above`` / ``below`` it, and ``per_node``: label -> ``{"median", "ranks"}`` (NaN where fewer than
+        ``max(1, min(min_members, the node's size))`` of its ranks have data).  A node holds ``gpu`` and ``sections`` parts with
+        ``pace``, ``spread``, ``columns``, ``slower``, ``faster`` and ``breadth`` as ``pace_scores()`` spells a rank's, plus
+        ``members_rated`` (its ranks THIS REPORT COVERS that have at least ``min_columns`` columns), ``members_off_pace``
+        (those of them the pace rule names against the nodes' centre) and ``agree`` (their quotient; None where no member is
+        rated); the three of the ``gpu`` part are repeated at the node's top level.  A report that covers one rank only
+        (``gather_on_rank0=False``) still holds every node's record, with ``agree`` over what it sees.  ``ranks`` holds every
+        reported rank's record against the nodes' centre, spelled as in ``pace_scores()``: ``excess_us`` is the microseconds
+        above the pace of the job's nodes.  ``unrated_nodes``: nodes without a column in either part.  Plain dicts, lists,
+        floats and ints.  The first call waits for the node kernels and copies their results; ``generate_report`` does not."""
+        node = self.__dict__.get("_node")
+        if node is None:
+            return {}
+        if isinstance(node, _NodeSource):
+            node = self.__dict__["_node"] = node.build()
+        return _copy_peer(node)  # (the nodes' member lists are copied too)
+
+    def identify_node_stragglers(self, min_effect: Optional[float] = None, min_breadth: Optional[float] = None,
+                                 min_columns: Optional[int] = None, min_agree: Optional[float] = None) -> Dict[str, Any]:
+        """Nodes that are a little slower in nearly everything: a part of a node (its kernels, its sections) is named iff it has
+        at least ``min_columns`` columns, its ``pace`` is at most ``1 - min_effect``, it is slower than the nodes' centre in at
+        least ``min_breadth`` of them, and at least ``min_agree`` of its rated members that the report covers are themselves
+        off pace by the pace rule against the same centre (a node none of whose rated members the report covers is not
+        named).  ``{'straggler_nodes': set of labels, 'straggler_section_nodes': set of labels, 'ranks_off_pace_alone':
+        set[StragglerId], 'section_ranks_off_pace_alone': set[StragglerId]}`` -- the last two are the ranks off pace whose
+        node is not named: a slow GPU, not a slow host.  The defaults are the generator's (8, 0.03, 0.9 and 0.75 unless
+        told otherwise: defaults, not measurements).  Empty sets when the report carries no node scores."""
+        t = self.node_scores()
+        if not t:
+            return {"straggler_nodes": set(), "straggler_section_nodes": set(), "ranks_off_pace_alone": set(),
+                    "section_ranks_off_pace_alone": set()}
+        params = t["params"]
+        effect = params["min_effect"] if min_effect is None else min_effect
+        breadth = params["min_breadth"] if min_breadth is None else min_breadth
+        columns = params["min_columns"] if min_columns is None else min_columns
+        agree = params["min_agree"] if min_agree is None else min_agree
+
+        def named(part):
+            nodes = set()
+            for lab, d in t["node_scores"].items():
+                if not _node_member_rule(d[part], columns, effect, breadth)[1]:
+                    continue
+                share = _node_agreement(t, part, lab, columns, effect, breadth)[2]
+                if share is not None and share >= agree:
+                    nodes.add(lab)
+            alone = [r for r, d in t["ranks"].items()
+                     if _node_member_rule(d[part], columns, effect, breadth)[1] and t["node_of"][r] not in nodes]
+            return nodes, self._ids(alone)
+
+        gpu, sections = named("gpu"), named("sections")
+        return {"straggler_nodes": gpu[0], "straggler_section_nodes": sections[0], "ranks_off_pace_alone": gpu[1],
+                "section_ranks_off_pace_alone": sections[1]}
 
     def score_history(self) -> Dict[str, Any]:
         """The score history as it stood after this report (``ReportGenerator(score_history=H)``; ``{}`` when the report
@@ -1687,7 +1823,10 @@ class ReportGenerator:
                  trend_horizon: Optional[int] = None, collective_slack: bool = False, slack_min_ranks: int = 4,
                  slack_min_share: float = 0.05, slack_max_ratio: float = 0.25, peer_groups=None,
                  peer_min_ranks: int = 2, pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8,
-                 pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9, pace_peer_groups: bool = False) -> None:
+                 pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9, pace_peer_groups: bool = False,
+                 node_scores: bool = False, node_groups=None, node_min_members: int = 2, node_min_nodes: int = 3,
+                 node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
+                 node_min_agree: float = 0.75) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1827,6 +1966,40 @@ class ReportGenerator:
             if be is not None and not hasattr(be, "pace_group_score"):
                 raise RuntimeError(f"pace_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no pace scores per peer group (backend.pace_group_score)")
+        # node scores: every report also says whether a NODE is a little slower in nearly all of its kernels (Report.node_scores);
+        # off: nothing is allocated, resolved, launched or called.  They read the exchanged table and rank_to_node only: no
+        # collective, so ranks need not agree on the option.
+        self.node_scores = bool(node_scores)
+        self.node_groups = None
+        self._node_resolved = None  # backend.PeerGroups of the nodes for the R (and rank_to_node) of the tables seen so far
+        self._node_source = None    # the rank_to_node object _node_resolved was built from (node_groups=None)
+        if self.node_scores:
+            for name, val in (("node_min_members", node_min_members), ("node_min_nodes", node_min_nodes),
+                              ("node_min_columns", node_min_columns)):
+                if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < 1:
+                    raise ValueError(f"{name} must be an integer >= 1, got {val!r}")
+            try:
+                effect, breadth, agree = float(node_min_effect), float(node_min_breadth), float(node_min_agree)
+            except (TypeError, ValueError):
+                raise ValueError(f"node_min_effect, node_min_breadth and node_min_agree must be numbers, got {node_min_effect!r}, "
+                                 f"{node_min_breadth!r} and {node_min_agree!r}") from None
+            if not 0.0 <= effect < 1.0:
+                raise ValueError(f"node_min_effect must be within [0, 1), got {node_min_effect!r}")
+            if not 0.0 < breadth <= 1.0:
+                raise ValueError(f"node_min_breadth must be within (0, 1], got {node_min_breadth!r}")
+            if not 0.0 < agree <= 1.0:
+                raise ValueError(f"node_min_agree must be within (0, 1], got {node_min_agree!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"node_scores needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "node scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "node_score"):
+                raise RuntimeError(f"node_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no node scores (backend.node_score)")
+            self.node_groups = _peer_spec(node_groups, "node_groups")  # None: the nodes are rank_to_node's
+            self.node_min_members, self.node_min_nodes = int(node_min_members), int(node_min_nodes)
+            self.node_min_columns = int(node_min_columns)
+            self.node_min_effect, self.node_min_breadth, self.node_min_agree = effect, breadth, agree
         # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
         # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
         # call.  The step adds one collective per report, so EVERY rank must pass the same value.
@@ -2233,6 +2406,11 @@ class ReportGenerator:
             else:
                 self._attach_pace(report, _backend_mod.get_backend().pace_score(
                     ws, ws.table, lo, hi - lo, self._pace_min(ws)), ws, mapper, view)
+        if self.node_scores:
+            # likewise, behind the pace step
+            nodes = self._node_for(ws)
+            self._attach_node(report, _backend_mod.get_backend().node_score(
+                ws, ws.table, nodes, lo, hi - lo, self.node_min_members, self._node_min(nodes)), nodes, ws, mapper, view)
         if self._history is not None:
             # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
             self._attach_history(report, _backend_mod.get_backend().score_history(
@@ -2391,6 +2569,8 @@ class ReportGenerator:
             if self.pace_peer_groups:
                 raise RuntimeError("pace_peer_groups: these rings run the one-call report but have no report_pace_group")
             raise RuntimeError("pace_scores: these rings run the one-call report but have no report_pace")
+        if fused and self.node_scores and not hasattr(rings, "report_node"):
+            raise RuntimeError("node_scores: these rings run the one-call report but have no report_node")
         if fused and self._history is not None and not hasattr(rings, "report_history"):
             raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
         if fused and self.score_trends and not hasattr(rings, "report_trend"):
@@ -2422,6 +2602,8 @@ class ReportGenerator:
                     self._attach_plan_peer(report, plan, rings, True)
                 if self.pace_scores:
                     self._attach_plan_pace(report, plan, rings, True)
+                if self.node_scores:
+                    self._attach_plan_node(report, plan, rings, True)
                 if self._history is not None:
                     self._attach_plan_history(report, plan, rings, True)
                 return report
@@ -2462,6 +2644,8 @@ class ReportGenerator:
             self._attach_plan_peer(report, plan, rings, fused)
         if self.pace_scores:
             self._attach_plan_pace(report, plan, rings, fused)
+        if self.node_scores:
+            self._attach_plan_node(report, plan, rings, fused)
         if self._history is not None:
             self._attach_plan_history(report, plan, rings, fused)
         return report
@@ -2559,6 +2743,49 @@ class ReportGenerator:
         else:
             handle = _backend_mod.get_backend().pace_score(ws, ws.table, lo, hi - lo, self._pace_min(ws))
         self._attach_pace(report, handle, ws, plan.mapper, plan.view)
+
+    # ---- node scores --------------------------------------------------------------------------------
+    def _node_for(self, ws):
+        """The nodes resolved for the logical ranks of ``ws``' table (cold: once per R and, with ``node_groups=None``, per
+        ``rank_to_node`` -- a plain dict that is replaced, never edited, when it changes; a label list of another length is
+        refused here, where R is first known).  No collective: ``rank_to_node`` is what the name sync gathered."""
+        nodes = self._node_resolved
+        if self.node_groups is not None:
+            if nodes is None or nodes.R != ws.R:
+                nodes = self._node_resolved = _backend_mod.PeerGroups.resolve(self.node_groups, ws.R, "node_groups")
+            return nodes
+        r2n = self.rank_to_node
+        if nodes is None or nodes.R != ws.R or self._node_source is not r2n:
+            missing = [r for r in range(ws.R) if r not in r2n]
+            if missing:
+                raise ValueError(f"node_scores: rank_to_node names {len(r2n)} of the job's {ws.R} logical ranks (it is gathered "
+                                 f"with gather_on_rank0=True; rank {missing[0]} is missing); pass node_groups "
+                                 "('block:N', 'mod:N' or one label per logical rank)")
+            nodes = self._node_resolved = _backend_mod.PeerGroups([r2n[r] for r in range(ws.R)])
+            self._node_source = r2n
+        return nodes
+
+    def _node_min(self, nodes) -> int:
+        """``node_min_nodes``, but never more than the nodes the job has, as ``_pace_min``."""
+        return min(self.node_min_nodes, nodes.G)
+
+    def _attach_node(self, report, handle, nodes, ws, mapper, view) -> None:
+        params = {"min_members": self.node_min_members, "min_nodes": self._node_min(nodes), "min_columns": self.node_min_columns,
+                  "min_effect": self.node_min_effect, "min_breadth": self.node_min_breadth, "min_agree": self.node_min_agree}
+        report.__dict__["_node"] = _NodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, nodes)
+
+    def _attach_plan_node(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the node scores of the planned report that was just issued, as ``_attach_plan_pace`` does, for the ranks
+        the report covers, and hang them on ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        lo, hi = plan.view.layout[5], plan.view.layout[6]
+        nodes = self._node_for(ws)
+        if fused:
+            handle = rings.report_node(ws, nodes, lo, hi - lo, self.node_min_members, self._node_min(nodes))
+        else:
+            handle = _backend_mod.get_backend().node_score(ws, ws.table, nodes, lo, hi - lo, self.node_min_members,
+                                                           self._node_min(nodes))
+        self._attach_node(report, handle, nodes, ws, plan.mapper, plan.view)
 
     # ---- score history ------------------------------------------------------------------------------
     def _attach_history(self, report, handle, view) -> None:

@@ -166,6 +166,8 @@ class _Lane:
             return None  # (the peer launch follows the report in the generator's planned path: DESIGN.md, "Peer-group scores")
         if getattr(reporter, "pace_scores", False):
             return None  # (the pace launches follow the report in the generator's planned path: DESIGN.md, "Pace scores")
+        if getattr(reporter, "node_scores", False):
+            return None  # (the node launches follow the report in the generator's planned path: DESIGN.md, "Node scores")
         if getattr(reporter, "score_history", 0):
             return None  # (the history step follows the report in the generator's planned path: DESIGN.md, "Score history")
         if getattr(reporter, "collective_slack", False):
@@ -300,9 +302,9 @@ class _Lane:
         return rep
 
 
-def _peer_groups_from_env(value: str):
-    """``NVRX_PEER_GROUPS``: ``block:N``, ``mod:N`` or a comma-separated list of integer labels, one per logical rank; unset
-    or empty: None (off)."""
+def _peer_groups_from_env(value: str, name: str = "NVRX_PEER_GROUPS"):
+    """``NVRX_PEER_GROUPS`` (and ``NVRX_NODE_GROUPS``, by ``name``): ``block:N``, ``mod:N`` or a comma-separated list of
+    integer labels, one per logical rank; unset or empty: None (off; for the nodes: ``rank_to_node``)."""
     value = value.strip()
     if not value:
         return None
@@ -311,7 +313,7 @@ def _peer_groups_from_env(value: str):
     try:
         return [int(x) for x in value.split(",")]
     except ValueError:
-        raise ValueError("NVRX_PEER_GROUPS must be 'block:N', 'mod:N' or a comma-separated list of integers, "
+        raise ValueError(f"{name} must be 'block:N', 'mod:N' or a comma-separated list of integers, "
                          f"got {value!r}") from None
 
 
@@ -437,6 +439,14 @@ class Detector(metaclass=_DeviceSideOnDemand):
         pace_min_effect: float = 0.03,
         pace_min_breadth: float = 0.9,
         pace_peer_groups: Optional[bool] = None,
+        node_scores: Optional[bool] = None,
+        node_groups=None,
+        node_min_members: int = 2,
+        node_min_nodes: int = 3,
+        node_min_columns: int = 8,
+        node_min_effect: float = 0.03,
+        node_min_breadth: float = 0.9,
+        node_min_agree: float = 0.75,
     ):
         """
         Args:
@@ -560,6 +570,23 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 ``max(peer_min_ranks, min(pace_min_ranks, its size))`` ranks with a kernel for its median to be a reference.
                 Default: ``NVRX_PACE_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank (no collective depends
                 on it).
+            node_scores: every report also says whether a NODE is a little slower in nearly all of its kernels -- failed fans,
+                a capped PSU, a throttling host CPU, the wrong power profile: all GPUs of one host lose a few per cent, the
+                pace scores name every one of them, and only a score per node says that they are one incident
+                (``Report.node_scores()``, ``Report.identify_node_stragglers()``).  Needs ``relative_perf_scores``.  The
+                centre is the job's (a lockstep model); node scores inside pipeline stages are out of scope.  Default:
+                ``NVRX_NODE_SCORES`` ("1"; "0" or unset: off).  No collective depends on it.
+            node_groups: which logical ranks share a node: None -- ``rank_to_node`` as the name sync gathered it (needs
+                ``gather_on_rank0=True``, which gathers it for every rank) --, or ``"block:N"``, ``"mod:N"`` or one label
+                per logical rank, parsed as ``peer_groups`` is: the only way a folded run or a one-box test gets more than
+                one node.  Default: ``NVRX_NODE_GROUPS`` (a rule, or comma-separated integer labels, as
+                ``NVRX_PEER_GROUPS``).
+            node_min_members: ranks of a node that must have a kernel for the node's median to count (clamped to its size).
+            node_min_nodes: nodes that must have a median for a kernel to have a reference (clamped to the job's nodes).
+            node_min_columns, node_min_effect, node_min_breadth, node_min_agree: the rule of ``identify_node_stragglers``:
+                at least this many columns, a pace of at most ``1 - node_min_effect``, slower than the nodes' centre in at
+                least this share of the columns, and at least this share of the node's rated ranks off pace themselves.
+                8, 0.03, 0.9 and 0.75 are defaults, not measurements.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -657,6 +684,19 @@ class Detector(metaclass=_DeviceSideOnDemand):
             pace_peer_groups = from_env == "1"
         if pace_peer_groups:
             pace_options["pace_peer_groups"] = True  # (the generator says which of pace_scores and peer_groups it misses)
+        node_options = {}  # (off: the generator is built exactly as before)
+        if node_scores is None:
+            from_env = os.environ.get("NVRX_NODE_SCORES", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_NODE_SCORES must be 0 or 1, got {from_env!r}")
+            node_scores = from_env == "1"
+        if node_scores:
+            if node_groups is None:
+                node_groups = _peer_groups_from_env(os.environ.get("NVRX_NODE_GROUPS", ""), "NVRX_NODE_GROUPS")
+            node_options = {"node_scores": True, "node_groups": node_groups, "node_min_members": node_min_members,
+                            "node_min_nodes": node_min_nodes, "node_min_columns": node_min_columns,
+                            "node_min_effect": node_min_effect, "node_min_breadth": node_min_breadth,
+                            "node_min_agree": node_min_agree}
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -670,7 +710,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                       slack_max_ratio=slack_max_ratio, **peer_options, **pace_options)
+                                       slack_max_ratio=slack_max_ratio, **peer_options, **pace_options, **node_options)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)

@@ -17,6 +17,11 @@
     tables in the same run: 8 ranks x 64 sections in 2 groups, 8 ranks x 4096 kernels in 2 groups, 1024 ranks x 128 ids in 8
     and in 128 groups (``mod:G``: interleaved memberships); under the profiler a run per ``--shape``.  ``report``: both
     generators have ``pace_scores`` and ``peer_groups="mod:2"``, ``pace_peer_groups`` is what alternates.
+``--node``: node scores (docs/MEASUREMENTS.md, "Node scores").  ``kernels``: ``nvrx_node_score`` (``k_node_cols``, or
+    ``k_pace_group_cols`` + ``k_node_across``, then the rank kernel twice) next to ``nvrx_pace_score`` and
+    ``nvrx_pace_group_score`` on the same tables in the same run: 8 ranks x 64 sections on 2 nodes, 64 ranks x 4096 kernels
+    on 8 nodes, 1024 ranks x 128 ids on 128 nodes (``block:N``); under the profiler a run per ``--shape``.  ``report``:
+    ``node_scores`` (``node_groups="block:4"``) is what alternates.
 Prints one JSON line per measurement.
 """
 import argparse
@@ -32,6 +37,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 SHAPES = [(8, 0, 64), (8, 4096, 0), (1024, 64, 64)]  # (ranks, kernel ids, section ids)
+NODE_SHAPES = [(8, 0, 64, 2), (64, 4096, 0, 8), (1024, 64, 64, 128)]  # (..., nodes)
 GROUPED_SHAPES = [(8, 0, 64, 2), (8, 4096, 0, 2), (1024, 64, 64, 8), (1024, 64, 64, 128)]  # (..., groups)
 
 
@@ -123,6 +129,42 @@ def kernels_grouped(args):
         print(json.dumps(out), flush=True)
 
 
+def kernels_node(args):
+    from nvrx_straggler import _native
+    from nvrx_straggler.backend import PeerGroups, get_backend
+
+    torch.cuda.set_device(0)
+    be = get_backend()
+    lib, st = be.lib, be.stream_handle
+    rng = np.random.default_rng(0)
+    for i, (R, K, S, G) in enumerate(NODE_SHAPES):
+        if args.shape >= 0 and i != args.shape:
+            continue
+        ws = be.workspace(R, K, S, R, 0)
+        with torch.cuda.stream(be.stream):
+            ws.send.copy_(torch.from_numpy(_table(rng, R, K, S)))
+        nodes = PeerGroups([r // (R // G) for r in range(R)])
+        pbuf, nbuf = ws.pace_buffers(R, G), ws.node_buffers(G, R)
+        gptr, largest = nodes.device(be).data_ptr(), nodes.max_size
+        be.synchronize()
+
+        def pace():
+            _native.check(lib.nvrx_pace_score(ws.send_ptr, R, K, S, 0, R, 4, pbuf.data_ptr(), st))
+
+        def grouped():
+            _native.check(lib.nvrx_pace_group_score(ws.send_ptr, R, K, S, gptr, G, largest, 0, R, 2, 1, pbuf.data_ptr(), st))
+
+        def node():
+            _native.check(lib.nvrx_node_score(ws.send_ptr, R, K, S, gptr, G, largest, 2, min(3, G), 0, R, nbuf.data_ptr(), st))
+
+        out = {"what": "kernels, node", "ranks": R, "kernel_ids": K, "section_ids": S, "nodes": G, "largest": largest,
+               "launches": args.launches}
+        for name, fn in (("pace_us", pace), ("pace_group_us", grouped), ("node_us", node)):
+            out[name] = round(_timed(fn, args.launches, args.warmup, be.stream), 2)
+            be.synchronize()
+        print(json.dumps(out), flush=True)
+
+
 def report(args):
     torch.cuda.set_device(0)
     from nvrx_straggler import _native
@@ -146,6 +188,9 @@ def report(args):
         gens = {0: ReportGenerator(["relative_perf_scores"], node_name="n", pace_scores=True, peer_groups="mod:2"),
                 1: ReportGenerator(["relative_perf_scores"], node_name="n", pace_scores=True, peer_groups="mod:2",
                                    pace_peer_groups=True)}
+    if args.node:
+        gens = {0: ReportGenerator(["relative_perf_scores"], node_name="n"),
+                1: ReportGenerator(["relative_perf_scores"], node_name="n", node_scores=True, node_groups="block:4")}
     lat, readable = {0: [], 1: []}, []
     try:
         for i in range(2 * (args.reports + args.warmup)):
@@ -156,19 +201,20 @@ def report(args):
             rep.identify_stragglers()
             t1 = time.perf_counter_ns()
             if on:
-                assert len(rep.pace_scores()["section_columns"]) == sections
+                scores = rep.node_scores() if args.node else rep.pace_scores()
+                assert len(scores["section_columns"]) == sections
             t2 = time.perf_counter_ns()
             if i >= 2 * args.warmup:
                 lat[on].append((t1 - t0) * 1e-3)
                 if on:
                     readable.append((t2 - t0) * 1e-3)
             be.synchronize()
-        out = {"what": "ring report, call -> flagged set" + (", pace_peer_groups off / on" if args.grouped else ""), "processes": 1, "reports_each": args.reports, "shape": "8 x 64 x 10000"}
+        out = {"what": "ring report, call -> flagged set" + (", pace_peer_groups off / on" if args.grouped else ", node_scores off / on" if args.node else ""), "processes": 1, "reports_each": args.reports, "shape": "8 x 64 x 10000"}
         for on, key in ((0, "off"), (1, "on")):
             out[f"{key}_median_us"] = round(float(np.median(lat[on])), 1)
             out[f"{key}_p95_us"] = round(float(np.percentile(lat[on], 95)), 1)
         out["delta_median_us"] = round(out["on_median_us"] - out["off_median_us"], 1)
-        out["pace_readable_median_us"] = round(float(np.median(readable)), 1)
+        out["node_readable_median_us" if args.node else "pace_readable_median_us"] = round(float(np.median(readable)), 1)
         print(json.dumps(out), flush=True)
     finally:
         for g in gens.values():
@@ -184,9 +230,10 @@ def main():
     ap.add_argument("--reports", type=int, default=200)
     ap.add_argument("--shape", type=int, default=-1, help="kernels: only that entry of SHAPES (a profiler run per shape)")
     ap.add_argument("--grouped", action="store_true", help="pace scores per peer group (see the module's text)")
+    ap.add_argument("--node", action="store_true", help="node scores (see the module's text)")
     args = ap.parse_args()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    {"kernels": kernels_grouped if args.grouped else kernels, "report": report}[args.what](args)
+    {"kernels": kernels_node if args.node else kernels_grouped if args.grouped else kernels, "report": report}[args.what](args)
 
 
 if __name__ == "__main__":
