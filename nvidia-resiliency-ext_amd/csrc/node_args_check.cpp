@@ -2,21 +2,7 @@
 // nvrx_node_score and nvrx_report_node with INVALID arguments only, so no call reaches a device, and is meant to be built
 // together with nvrx_straggler.hip with AddressSanitizer and UndefinedBehaviorSanitizer on the host code.  Exit status 0 when
 // every call returned the error the header promises.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-
-#include "nvrx_straggler.h"
-
-static int failures = 0;
-
-static void expect(const char *what, int got, int want, const char *needle) {
-    const char *msg = nvrx_last_error();
-    if (got != want || (needle && (!msg || !strstr(msg, needle)))) {
-        fprintf(stderr, "FAIL %s: returned %d (want %d), message \"%s\" (want \"%s\")\n", what, got, want, msg ? msg : "", needle ? needle : "");
-        failures++;
-    }
-}
+#include "args_check.h"
 
 int main() {
     float *table = reinterpret_cast<float *>(uintptr_t{8192});  // never dereferenced: every call below fails its checks

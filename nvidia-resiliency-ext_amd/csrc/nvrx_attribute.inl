@@ -209,8 +209,7 @@ int nvrx_attribute(const float *d_table, int R, int K, int S, int first_rank, in
                    int do_rel, float *d_minmed_scratch, void *d_out, void *stream) {
     const int rc = attr_check(R, K, S, first_rank, n_ranks, top_n);
     if (rc) return rc;
-    if (!d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_table != nullptr, false)) return rc;
     if (do_rel && K > 0 && !d_minmed_scratch) return fail(NVRX_ERR_INVALID, "the relative family needs d_minmed_scratch");
     return attr_launch(d_table, R, K, S, first_rank, n_ranks, top_n, do_indiv, do_rel, d_minmed_scratch, d_out, as_stream(stream));
 }
@@ -219,21 +218,11 @@ int nvrx_report_attribute(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first
     if (!ctx || !desc) return fail(NVRX_ERR_INVALID, "null argument");
     const int rc = attr_check(desc->R, desc->K, desc->S, first_rank, n_ranks, top_n);
     if (rc) return rc;
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is null or not 16-byte aligned");
-    hipStream_t last = nullptr, home = nullptr;
+    if (const int rc = out_check(d_out, true, true)) return rc;
+    hipStream_t home = nullptr;
     {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // the report's last kernel ran elsewhere (re-homed onto the caller's stream, or the resident scorer's own):
-            // kernel-boundary ordering through an event, never the completion word (its stores are not fenced)
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
+        std::lock_guard<std::mutex> lk(ctx->mu);  // (held on: the scratch below is the context's)
+        if (const int rc = behind_report(ctx, desc, &home)) return rc;
         if (desc->do_rel && desc->K > 0 && ctx->attr_scratch_elems < (size_t)NVRX_ATTR_SCRATCH_FLOATS(desc->K)) {
             // (hipFree waits for the device: nothing still reads the old buffer; every user is on `home`)
             if (ctx->attr_scratch) HIP_TRY(hipFree(ctx->attr_scratch));

@@ -181,19 +181,7 @@ int nvrx_report_history(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_r
     const int rc = history_check(desc->R, desc->S, first_rank, n_ranks, d_hist, S_cap, H, thresholds, d_out);
     if (rc) return rc;
     hipStream_t home = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        const hipStream_t last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // behind the report's last kernel, as nvrx_report_robust orders itself
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
-    }
+    if (const int rc = report_table(ctx, desc, &home, nullptr)) return rc;  // (this step reads the report's scores, not its table)
     return history_launch(desc->d_scores, desc->S, first_rank, n_ranks, d_hist, S_cap, H, n_before, thresholds, d_out, home);
 }
 

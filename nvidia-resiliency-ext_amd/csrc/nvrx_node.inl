@@ -262,17 +262,6 @@ int node_check(int R, int K, int S, int G, int max_group, int first_rank, int n_
     return NVRX_OK;
 }
 
-template <bool NODE>
-void node_rank_launch(const PaceRankArgs &a, int rows, hipStream_t st) {
-    const int widest = a.K > a.S ? a.K : a.S;
-    if (widest <= PACE_WAVE_COLS)
-        hipLaunchKernelGGL((k_pace_rank<64, 1, false, NODE>), dim3(rows, 2), dim3(64), 0, st, a);
-    else if (widest <= PACE_REG_COLS)
-        hipLaunchKernelGGL((k_pace_rank<256, 16, false, NODE>), dim3(rows, 2), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_pace_rank<1024, 0, false, NODE>), dim3(rows, 2), dim3(1024), 0, st, a);
-}
-
 int node_launch(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group, int min_members,
                 int min_nodes, int first_rank, int n_ranks, void *d_out, hipStream_t st) {
     const int KS = K + S;
@@ -292,12 +281,7 @@ int node_launch(const float *d_table, int R, int K, int S, const int32_t *d_grou
         c.table = d_table, c.groups = d_groups, c.R = R, c.KS = KS, c.L = NVRX_TABLE_LEN(K, S);
         c.max_group = max_group, c.min_ranks = min_members, c.min_peers = 1;
         c.cols = pairs;
-        if (max_group <= PACE_GROUP_WAVE)
-            hipLaunchKernelGGL(k_pace_group_cols<0>, dim3((KS + ROBUST_TILE - 1) / ROBUST_TILE, G), dim3(ROBUST_THREADS), 0, st, c);
-        else if (max_group <= PACE_GROUP_SMALL)
-            hipLaunchKernelGGL(k_pace_group_cols<256>, dim3(KS, G), dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(k_pace_group_cols<1024>, dim3(KS, G), dim3(1024), 0, st, c);
+        pace_group_cols_launch(c, G, st);
         HIP_TRY(hipGetLastError());
         NodeAcrossArgs x{};
         x.pairs = pairs, x.G = G, x.KS = KS, x.min_nodes = min_nodes, x.cols = cols;
@@ -312,14 +296,14 @@ int node_launch(const float *d_table, int R, int K, int S, const int32_t *d_grou
     n.table = reinterpret_cast<const float *>(pairs), n.cols = cols;
     n.K = K, n.S = S, n.first_rank = 0, n.min_ranks = 1;
     n.out = nodes;
-    node_rank_launch<true>(n, G, st);
+    pace_rank_launch<false, true>(n, G, st);
     HIP_TRY(hipGetLastError());
     // block D: the job-wide rank kernel with block B as its column records
     PaceRankArgs r{};
     r.table = d_table, r.cols = cols;
     r.K = K, r.S = S, r.first_rank = first_rank, r.min_ranks = min_nodes;
     r.out = ranks;
-    node_rank_launch<false>(r, n_ranks, st);
+    pace_rank_launch(r, n_ranks, st);
     HIP_TRY(hipGetLastError());
     return NVRX_OK;
 }
@@ -332,8 +316,7 @@ int nvrx_node_score(const float *d_table, int R, int K, int S, const int32_t *d_
                     int min_nodes, int first_rank, int n_ranks, void *d_out, void *stream) {
     const int rc = node_check(R, K, S, G, max_group, first_rank, n_ranks, min_members, min_nodes);
     if (rc) return rc;
-    if (!d_table || !d_groups || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_table && d_groups, false)) return rc;
     return node_launch(d_table, R, K, S, d_groups, G, max_group, min_members, min_nodes, first_rank, n_ranks, d_out,
                        as_stream(stream));
 }
@@ -343,23 +326,10 @@ int nvrx_report_node(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t 
     if (!ctx || !desc) return fail(NVRX_ERR_INVALID, "null argument");
     const int rc = node_check(desc->R, desc->K, desc->S, G, max_group, first_rank, n_ranks, min_members, min_nodes);
     if (rc) return rc;
-    if (!d_groups) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is null or not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_groups != nullptr, true)) return rc;
     hipStream_t home = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        const hipStream_t last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // behind the report's last kernel, as nvrx_report_pace_group orders itself
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
-    }
-    const float *table = desc->allgather_fn ? desc->d_table : desc->d_send;
+    const float *table = nullptr;
+    if (const int rc = report_table(ctx, desc, &home, &table)) return rc;
     return node_launch(table, desc->R, desc->K, desc->S, d_groups, G, max_group, min_members, min_nodes, first_rank, n_ranks,
                        d_out, home);
 }

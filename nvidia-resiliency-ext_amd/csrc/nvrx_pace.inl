@@ -357,15 +357,17 @@ __global__ __launch_bounds__(THREADS) void k_pace_rank(std::conditional_t<GROUPE
 constexpr int PACE_WAVE_COLS = 64;        // columns of a part one wave takes
 constexpr int PACE_REG_COLS = 256 * 16;  // ... and 256 threads keep in registers
 
-// argument checks shared by both entry points, in robust_check's sequence; nothing here touches a device
-int pace_check(int R, int K, int S, int first_rank, int n_ranks, int min_ranks) {
-    if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
-    if (R > NVRX_ROBUST_MAX_RANKS) return fail(NVRX_ERR_RANGE, "R=%d ranks, at most %d", R, NVRX_ROBUST_MAX_RANKS);
-    if (K > NVRX_MAX_ROWS || S > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d S=%d ids, at most %d each", K, S, NVRX_MAX_ROWS);
-    if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
-        return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
-    if (min_ranks < 1) return fail(NVRX_ERR_RANGE, "min_ranks=%d, at least 1", min_ranks);
-    return NVRX_OK;
+// The variant of k_pace_rank by the wider of a rank's two parts, one workgroup per (row, part).  GROUPED and NODE as the kernel
+// has them; Args is the kernel's argument struct.
+template <bool GROUPED = false, bool NODE = false, class Args>
+void pace_rank_launch(const Args &a, int rows, hipStream_t st) {
+    const int widest = a.K > a.S ? a.K : a.S;
+    if (widest <= PACE_WAVE_COLS)
+        hipLaunchKernelGGL((k_pace_rank<64, 1, GROUPED, NODE>), dim3(rows, 2), dim3(64), 0, st, a);
+    else if (widest <= PACE_REG_COLS)
+        hipLaunchKernelGGL((k_pace_rank<256, 16, GROUPED, NODE>), dim3(rows, 2), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_pace_rank<1024, 0, GROUPED, NODE>), dim3(rows, 2), dim3(1024), 0, st, a);
 }
 
 int pace_launch(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks, void *d_out,
@@ -376,25 +378,14 @@ int pace_launch(const float *d_table, int R, int K, int S, int first_rank, int n
         c.table = d_table, c.R = R, c.KS = KS, c.L = NVRX_TABLE_LEN(K, S);
         c.min_ranks = min_ranks;
         c.cols = static_cast<uint4 *>(d_out);
-        if (R <= 64)
-            hipLaunchKernelGGL(k_pace_cols<0>, dim3((KS + ROBUST_TILE - 1) / ROBUST_TILE), dim3(ROBUST_THREADS), 0, st, c);
-        else if (R <= 1024)
-            hipLaunchKernelGGL(k_pace_cols<256>, dim3(KS), dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(k_pace_cols<1024>, dim3(KS), dim3(1024), 0, st, c);
+        cols_launch(k_pace_cols<0>, k_pace_cols<256>, k_pace_cols<1024>, R, KS, 1, c, st);
         HIP_TRY(hipGetLastError());
     }
     PaceRankArgs a{};
     a.table = d_table, a.cols = static_cast<const uint4 *>(d_out);
     a.K = K, a.S = S, a.first_rank = first_rank, a.min_ranks = min_ranks;
     a.out = static_cast<uint4 *>(d_out) + (size_t)KS;
-    const int widest = K > S ? K : S;
-    if (widest <= PACE_WAVE_COLS)
-        hipLaunchKernelGGL((k_pace_rank<64, 1>), dim3(n_ranks, 2), dim3(64), 0, st, a);
-    else if (widest <= PACE_REG_COLS)
-        hipLaunchKernelGGL((k_pace_rank<256, 16>), dim3(n_ranks, 2), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_pace_rank<1024, 0>), dim3(n_ranks, 2), dim3(1024), 0, st, a);
+    pace_rank_launch(a, n_ranks, st);
     HIP_TRY(hipGetLastError());
     return NVRX_OK;
 }
@@ -405,33 +396,20 @@ extern "C" {
 
 int nvrx_pace_score(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks, void *d_out,
                     void *stream) {
-    const int rc = pace_check(R, K, S, first_rank, n_ranks, min_ranks);
+    const int rc = table_min_ranks_check(R, K, S, first_rank, n_ranks, min_ranks);
     if (rc) return rc;
-    if (!d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_table != nullptr, false)) return rc;
     return pace_launch(d_table, R, K, S, first_rank, n_ranks, min_ranks, d_out, as_stream(stream));
 }
 
 int nvrx_report_pace(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank, int n_ranks, int min_ranks, void *d_out) {
     if (!ctx || !desc) return fail(NVRX_ERR_INVALID, "null argument");
-    const int rc = pace_check(desc->R, desc->K, desc->S, first_rank, n_ranks, min_ranks);
+    const int rc = table_min_ranks_check(desc->R, desc->K, desc->S, first_rank, n_ranks, min_ranks);
     if (rc) return rc;
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is null or not 16-byte aligned");
+    if (const int rc = out_check(d_out, true, true)) return rc;
     hipStream_t home = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        const hipStream_t last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // behind the report's last kernel, as nvrx_report_robust orders itself
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
-    }
-    const float *table = desc->allgather_fn ? desc->d_table : desc->d_send;
+    const float *table = nullptr;
+    if (const int rc = report_table(ctx, desc, &home, &table)) return rc;
     return pace_launch(table, desc->R, desc->K, desc->S, first_rank, n_ranks, min_ranks, d_out, home);
 }
 

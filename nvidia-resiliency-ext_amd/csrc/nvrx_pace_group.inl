@@ -134,20 +134,20 @@ __global__ __launch_bounds__(THREADS ? THREADS : ROBUST_THREADS) void k_pace_gro
     }
 }
 
-constexpr int PACE_GROUP_WAVE = 64;      // members of the largest group the tiled kernel takes
-constexpr int PACE_GROUP_SMALL = 1024;  // ... and the 256-thread radix kernel
-
 // argument checks shared by both entry points: nvrx_pace_score's, then nvrx_peer_score's of G, then the two of this family;
 // nothing here touches a device
 int pace_group_check(int R, int K, int S, int G, int max_group, int first_rank, int n_ranks, int min_ranks, int min_peers) {
-    const int rc = pace_check(R, K, S, first_rank, n_ranks, min_ranks);
+    int rc = table_min_ranks_check(R, K, S, first_rank, n_ranks, min_ranks);
+    if (!rc) rc = groups_check(R, G);
     if (rc) return rc;
-    if (G < 1) return fail(NVRX_ERR_INVALID, "G=%d groups, at least 1", G);
-    if (G > R) return fail(NVRX_ERR_RANGE, "G=%d groups for R=%d ranks", G, R);
-    if (G > NVRX_PEER_MAX_GROUPS) return fail(NVRX_ERR_RANGE, "G=%d groups, at most %d", G, NVRX_PEER_MAX_GROUPS);
     if (max_group < 1 || max_group > R) return fail(NVRX_ERR_RANGE, "max_group=%d, within 1..%d", max_group, R);
     if (min_peers < 1) return fail(NVRX_ERR_RANGE, "min_peers=%d, at least 1", min_peers);
     return NVRX_OK;
+}
+
+// k_pace_group_cols by the largest group's size: cols_launch's thresholds (the tiled kernel takes groups of at most 64)
+void pace_group_cols_launch(const PaceGroupColsArgs &c, int G, hipStream_t st) {
+    cols_launch(k_pace_group_cols<0>, k_pace_group_cols<256>, k_pace_group_cols<1024>, c.max_group, c.KS, G, c, st);
 }
 
 int pace_group_launch(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group, int first_rank,
@@ -158,25 +158,14 @@ int pace_group_launch(const float *d_table, int R, int K, int S, const int32_t *
         c.table = d_table, c.groups = d_groups, c.R = R, c.KS = KS, c.L = NVRX_TABLE_LEN(K, S);
         c.max_group = max_group, c.min_ranks = min_ranks, c.min_peers = min_peers;
         c.cols = static_cast<uint4 *>(d_out);
-        if (max_group <= PACE_GROUP_WAVE)
-            hipLaunchKernelGGL(k_pace_group_cols<0>, dim3((KS + ROBUST_TILE - 1) / ROBUST_TILE, G), dim3(ROBUST_THREADS), 0, st, c);
-        else if (max_group <= PACE_GROUP_SMALL)
-            hipLaunchKernelGGL(k_pace_group_cols<256>, dim3(KS, G), dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(k_pace_group_cols<1024>, dim3(KS, G), dim3(1024), 0, st, c);
+        pace_group_cols_launch(c, G, st);
         HIP_TRY(hipGetLastError());
     }
     PaceGroupRankArgs a{};
     a.table = d_table, a.cols = static_cast<const uint4 *>(d_out), a.groups = d_groups;
     a.K = K, a.S = S, a.G = G, a.first_rank = first_rank;
     a.out = static_cast<uint4 *>(d_out) + (size_t)G * (size_t)KS;
-    const int widest = K > S ? K : S;
-    if (widest <= PACE_WAVE_COLS)
-        hipLaunchKernelGGL((k_pace_rank<64, 1, true>), dim3(n_ranks, 2), dim3(64), 0, st, a);
-    else if (widest <= PACE_REG_COLS)
-        hipLaunchKernelGGL((k_pace_rank<256, 16, true>), dim3(n_ranks, 2), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_pace_rank<1024, 0, true>), dim3(n_ranks, 2), dim3(1024), 0, st, a);
+    pace_rank_launch<true>(a, n_ranks, st);
     HIP_TRY(hipGetLastError());
     return NVRX_OK;
 }
@@ -189,8 +178,7 @@ int nvrx_pace_group_score(const float *d_table, int R, int K, int S, const int32
                           int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out, void *stream) {
     const int rc = pace_group_check(R, K, S, G, max_group, first_rank, n_ranks, min_ranks, min_peers);
     if (rc) return rc;
-    if (!d_table || !d_groups || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_table && d_groups, false)) return rc;
     return pace_group_launch(d_table, R, K, S, d_groups, G, max_group, first_rank, n_ranks, min_ranks, min_peers, d_out,
                              as_stream(stream));
 }
@@ -200,23 +188,10 @@ int nvrx_report_pace_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const in
     if (!ctx || !desc) return fail(NVRX_ERR_INVALID, "null argument");
     const int rc = pace_group_check(desc->R, desc->K, desc->S, G, max_group, first_rank, n_ranks, min_ranks, min_peers);
     if (rc) return rc;
-    if (!d_groups) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is null or not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_groups != nullptr, true)) return rc;
     hipStream_t home = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        const hipStream_t last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // behind the report's last kernel, as nvrx_report_pace orders itself
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
-    }
-    const float *table = desc->allgather_fn ? desc->d_table : desc->d_send;
+    const float *table = nullptr;
+    if (const int rc = report_table(ctx, desc, &home, &table)) return rc;
     return pace_group_launch(table, desc->R, desc->K, desc->S, d_groups, G, max_group, first_rank, n_ranks, min_ranks, min_peers,
                              d_out, home);
 }

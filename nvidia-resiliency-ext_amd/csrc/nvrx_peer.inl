@@ -157,16 +157,8 @@ __global__ __launch_bounds__(PGROUP_THREADS) void k_peer_rank(PeerRankArgs a) {
 
 // argument checks shared by both entry points, in robust_check's sequence; nothing here touches a device
 int peer_check(int R, int K, int S, int G, int first_rank, int n_ranks, int min_ranks) {
-    if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
-    if (R > NVRX_ROBUST_MAX_RANKS) return fail(NVRX_ERR_RANGE, "R=%d ranks, at most %d", R, NVRX_ROBUST_MAX_RANKS);
-    if (K > NVRX_MAX_ROWS || S > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d S=%d ids, at most %d each", K, S, NVRX_MAX_ROWS);
-    if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
-        return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
-    if (min_ranks < 1) return fail(NVRX_ERR_RANGE, "min_ranks=%d, at least 1", min_ranks);
-    if (G < 1) return fail(NVRX_ERR_INVALID, "G=%d groups, at least 1", G);
-    if (G > R) return fail(NVRX_ERR_RANGE, "G=%d groups for R=%d ranks", G, R);
-    if (G > NVRX_PEER_MAX_GROUPS) return fail(NVRX_ERR_RANGE, "G=%d groups, at most %d", G, NVRX_PEER_MAX_GROUPS);
-    return NVRX_OK;
+    const int rc = table_min_ranks_check(R, K, S, first_rank, n_ranks, min_ranks);
+    return rc ? rc : groups_check(R, G);
 }
 
 int peer_launch(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int first_rank, int n_ranks,
@@ -197,8 +189,7 @@ int nvrx_peer_score(const float *d_table, int R, int K, int S, const int32_t *d_
                     int min_ranks, void *d_out, void *stream) {
     const int rc = peer_check(R, K, S, G, first_rank, n_ranks, min_ranks);
     if (rc) return rc;
-    if (!d_table || !d_groups || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_table && d_groups, false)) return rc;
     return peer_launch(d_table, R, K, S, d_groups, G, first_rank, n_ranks, min_ranks, d_out, as_stream(stream));
 }
 
@@ -207,23 +198,10 @@ int nvrx_report_peer(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t 
     if (!ctx || !desc) return fail(NVRX_ERR_INVALID, "null argument");
     const int rc = peer_check(desc->R, desc->K, desc->S, G, first_rank, n_ranks, min_ranks);
     if (rc) return rc;
-    if (!d_groups) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is null or not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_groups != nullptr, true)) return rc;
     hipStream_t home = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        const hipStream_t last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // behind the report's last kernel, as nvrx_report_robust orders itself
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
-    }
-    const float *table = desc->allgather_fn ? desc->d_table : desc->d_send;
+    const float *table = nullptr;
+    if (const int rc = report_table(ctx, desc, &home, &table)) return rc;
     return peer_launch(table, desc->R, desc->K, desc->S, d_groups, G, first_rank, n_ranks, min_ranks, d_out, home);
 }
 

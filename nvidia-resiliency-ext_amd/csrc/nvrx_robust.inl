@@ -270,15 +270,24 @@ __global__ __launch_bounds__(ROBUST_THREADS) void k_robust_rank(RobustRankArgs a
 
 // argument checks shared by both entry points; nothing here touches a device
 int robust_check(int R, int K, int S, int first_rank, int n_ranks, int min_ranks, float floor_rel) {
-    if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
-    if (R > NVRX_ROBUST_MAX_RANKS) return fail(NVRX_ERR_RANGE, "R=%d ranks, at most %d", R, NVRX_ROBUST_MAX_RANKS);
-    if (K > NVRX_MAX_ROWS || S > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d S=%d ids, at most %d each", K, S, NVRX_MAX_ROWS);
-    if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
-        return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
-    if (min_ranks < 1) return fail(NVRX_ERR_RANGE, "min_ranks=%d, at least 1", min_ranks);
+    const int rc = table_min_ranks_check(R, K, S, first_rank, n_ranks, min_ranks);
+    if (rc) return rc;
     if (!(floor_rel == floor_rel) || floor_rel - floor_rel != 0.0f) return fail(NVRX_ERR_INVALID, "floor_rel is not finite");
     if (floor_rel < 0.0f || floor_rel > 1.0f) return fail(NVRX_ERR_RANGE, "floor_rel=%g outside [0,1]", (double)floor_rel);
     return NVRX_OK;
+}
+
+// The variant of a columns kernel by the rows a column has (a table's R ranks, or the largest group's members): the tiled kernel
+// up to 64 (a row per lane), one workgroup of 256 per column up to 1024, of 1024 beyond.  G > 1: the grid's y, a group each.
+template <class Args>
+void cols_launch(void (*tiled)(Args), void (*k256)(Args), void (*k1024)(Args), int rows, int KS, int G, const Args &c,
+                 hipStream_t st) {
+    if (rows <= 64)
+        hipLaunchKernelGGL(tiled, dim3((KS + ROBUST_TILE - 1) / ROBUST_TILE, G), dim3(ROBUST_THREADS), 0, st, c);
+    else if (rows <= 1024)
+        hipLaunchKernelGGL(k256, dim3(KS, G), dim3(256), 0, st, c);
+    else
+        hipLaunchKernelGGL(k1024, dim3(KS, G), dim3(1024), 0, st, c);
 }
 
 int robust_launch(const float *d_table, int R, int K, int S, int first_rank, int n_ranks, int min_ranks, float floor_rel,
@@ -289,12 +298,7 @@ int robust_launch(const float *d_table, int R, int K, int S, int first_rank, int
         c.table = d_table, c.R = R, c.KS = KS, c.L = NVRX_TABLE_LEN(K, S);
         c.min_ranks = min_ranks, c.floor_rel = floor_rel;
         c.cols = static_cast<uint4 *>(d_out);
-        if (R <= 64)
-            hipLaunchKernelGGL(k_robust_cols<0>, dim3((KS + ROBUST_TILE - 1) / ROBUST_TILE), dim3(ROBUST_THREADS), 0, st, c);
-        else if (R <= 1024)
-            hipLaunchKernelGGL(k_robust_cols<256>, dim3(KS), dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(k_robust_cols<1024>, dim3(KS), dim3(1024), 0, st, c);
+        cols_launch(k_robust_cols<0>, k_robust_cols<256>, k_robust_cols<1024>, R, KS, 1, c, st);
         HIP_TRY(hipGetLastError());
     }
     RobustRankArgs a{};
@@ -314,8 +318,7 @@ int nvrx_robust_score(const float *d_table, int R, int K, int S, int first_rank,
                       float floor_rel, void *d_out, void *stream) {
     const int rc = robust_check(R, K, S, first_rank, n_ranks, min_ranks, floor_rel);
     if (rc) return rc;
-    if (!d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (const int rc = out_check(d_out, d_table != nullptr, false)) return rc;
     return robust_launch(d_table, R, K, S, first_rank, n_ranks, min_ranks, floor_rel, d_out, as_stream(stream));
 }
 
@@ -324,22 +327,10 @@ int nvrx_report_robust(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_ra
     if (!ctx || !desc) return fail(NVRX_ERR_INVALID, "null argument");
     const int rc = robust_check(desc->R, desc->K, desc->S, first_rank, n_ranks, min_ranks, floor_rel);
     if (rc) return rc;
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(NVRX_ERR_INVALID, "d_out is null or not 16-byte aligned");
+    if (const int rc = out_check(d_out, true, true)) return rc;
     hipStream_t home = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-        const hipStream_t last = ctx->attr_stream;
-        home = ctx->default_stream;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (last != home) {
-            // behind the report's last kernel, as nvrx_report_attribute orders itself
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, last));
-            HIP_TRY(hipStreamWaitEvent(home, ctx->attr_ev, 0));
-        }
-    }
-    const float *table = desc->allgather_fn ? desc->d_table : desc->d_send;
+    const float *table = nullptr;
+    if (const int rc = report_table(ctx, desc, &home, &table)) return rc;
     return robust_launch(table, desc->R, desc->K, desc->S, first_rank, n_ranks, min_ranks, floor_rel, d_out, home);
 }
 

@@ -1,6 +1,6 @@
 // nvrx_rowfam.inl -- the host side that the row families (tail, onset, period, episode scores) share.  Part of the
 // translation unit nvrx_straggler.hip (included ahead of the four families' files: it uses that file's context, fill kernel
-// and error helpers, and nvrx_tail.inl's score launch).  Host code only: every kernel and every kernel-argument struct
+// and error helpers, nvrx_tablefam.inl's ordering behind a report, and nvrx_tail.inl's score launch).  Host code only: every kernel and every kernel-argument struct
 // stays with its family.
 //
 // A row family is one pipeline with its own ring kernel in front ("Row families"): ring kernel by gid into
@@ -66,7 +66,7 @@ void window_args(const LocalWindow &w, Args *a) {
 // The front of nvrx_{tail,onset,period,episode}_local, in its order: null and K/S checks, the family's parameters
 // (param_check() -> code), the rows_active range and default; then, under the context's lock: the ring-start snapshot must be
 // on where the family needs it (starts_off_msg: what to say if it is not; null: not needed), the descriptor is the last
-// report's, *stream is put behind that report's last kernel (as nvrx_report_attribute orders itself), and a wrapped ring's
+// report's, *stream is put behind that report's last kernel (behind_report, nvrx_tablefam.inl), and a wrapped ring's
 // starts are uploaded.  Nothing is flushed: counts and ring starts are those of the window the report's statistics kernel read.
 template <class ParamCheck>
 int local_window(nvrx_ctx *ctx, const nvrx_report_desc *desc, const float *d_send, int K, int S, int rows_active,
@@ -82,15 +82,10 @@ int local_window(nvrx_ctx *ctx, const nvrx_report_desc *desc, const float *d_sen
     hipStream_t st = *stream;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (starts_off_msg && !ctx->onset_on) return fail(NVRX_ERR_STATE, "%s", starts_off_msg);
-    if (desc && ctx->attr_desc != desc) return fail(NVRX_ERR_STATE, "no report was issued through this descriptor on this context");
-    HIP_TRY(hipSetDevice(ctx->device));
     if (desc) {
-        st = ctx->default_stream;
-        if (ctx->attr_stream != st) {
-            if (!ctx->attr_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->attr_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ctx->attr_ev, ctx->attr_stream));
-            HIP_TRY(hipStreamWaitEvent(st, ctx->attr_ev, 0));
-        }
+        if (const int rc = behind_report(ctx, desc, &st)) return rc;
+    } else {
+        HIP_TRY(hipSetDevice(ctx->device));
     }
     *win = LocalWindow{};
     win->uniform_n = ctx->tail_uniform_n;

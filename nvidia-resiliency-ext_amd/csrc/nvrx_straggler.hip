@@ -3958,6 +3958,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 
 }  // extern "C"
 
+#include "nvrx_tablefam.inl"
 #include "nvrx_attribute.inl"
 #include "nvrx_rowfam.inl"
 #include "nvrx_tail.inl"

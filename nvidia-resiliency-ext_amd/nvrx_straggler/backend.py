@@ -30,6 +30,7 @@ import torch
 
 from . import _native
 from .row_families import EPISODE, FAMILIES, ONSET, PERIOD, TAIL, RowFamily
+from .table_families import NODE, PACE, PACE_GROUP, PEER, ROBUST, SLOTS, TableFamily
 
 DEFAULT_THRESHOLDS = (0.75, 0.75, 0.75, 0.75)  # gpu_rel, section_rel, gpu_indiv, section_indiv
 
@@ -276,35 +277,45 @@ class _FamilyBuffers:
     __slots__ = ("buf", "send", "table", "scratch", "last")
 
 
-class Robust:
-    """Robust scores of one report (``nvrx_robust_score`` / ``nvrx_report_robust``), enqueued and not waited for: once the
-    kernels have run, the workspace's device buffer holds the ``K+S`` column records ``{ctr, mad, scale, n}`` and, behind
-    them, ``[n_ranks][2][1 + S]`` f32 ``{ratio, z}`` of the reported ranks (include/nvrx_straggler.h).  ``records()`` waits
-    for them and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report`` first asks, or
-    -- ``Workspace.robust_settle`` -- before the next report on the same workspace rewrites the table the kernels read and
-    the buffer they write."""
+class TableScores:
+    """One table family's scores of one report (``nvrx_<family>_score`` / ``nvrx_report_<family>``; table_families.py),
+    enqueued and not waited for: once the kernels have run, the family's slot of the workspace holds its block of 32-bit
+    words (include/nvrx_straggler.h).  ``records()`` waits for them and takes the private host copy (one ordered D2H on the
+    backend's stream): when a ``Report`` first asks, or -- ``Workspace.table_settle`` -- before the next report on the same
+    workspace rewrites the table the kernels read and the buffer they write.  ``G`` is 0 for a job-wide family; the family's
+    parameters (``min_ranks``, ``floor_rel``, ...) read as attributes."""
 
-    __slots__ = ("backend", "d_ptr", "K", "S", "first_rank", "n_ranks", "min_ranks", "floor_rel", "_host", "_lock", "_keep")
+    __slots__ = ("backend", "family", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "params", "_host", "_lock", "_keep")
 
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, K: int, S: int, first_rank: int, n_ranks: int,
-                 min_ranks: int, floor_rel: float):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.K, self.S = K, S
-        self.first_rank, self.n_ranks = first_rank, n_ranks
-        self.min_ranks, self.floor_rel = min_ranks, floor_rel
+    def __init__(self, backend: "HipBackend", family: TableFamily, buf: torch.Tensor, G: int, K: int, S: int, first_rank: int,
+                 n_ranks: int, params: tuple):
+        self.backend, self.family, self.d_ptr = backend, family, buf.data_ptr()
+        self.G, self.K, self.S = G, K, S
+        self.first_rank, self.n_ranks, self.params = first_rank, n_ranks, params
         self._host = None
         self._lock = threading.Lock()
         self._keep = buf  # the device buffer lives at least until the copy is taken
 
+    def __getattr__(self, name):  # (only what the slots do not have: the family's parameters by name)
+        names = object.__getattribute__(self, "family").params
+        if name in names:
+            return self.params[names.index(name)]
+        raise AttributeError(name)
+
     def records(self):
-        """``(cols [K+S, 4] uint32, scores [n_ranks, 2, 1 + S] f32)`` (private copies); the first call waits for the
-        kernels."""
+        """The family's arrays (``TableFamily.blocks``: private copies); the first call waits for the kernels."""
         if self._host is None:
             with self._lock:
                 if self._host is None:
-                    self._host = self.backend.robust_copy_out(self)
+                    self._host = getattr(self.backend, self.family.name + "_copy_out")(self)
                     self.backend = self._keep = None
         return self._host
+
+
+class _TableBuffers:
+    """A workspace's records buffer of one table-family slot, and the handle that may still be using it."""
+
+    __slots__ = ("buf", "last")
 
 
 class PeerGroups:
@@ -366,123 +377,6 @@ class PeerGroups:
 class _PeerRule(tuple):
     """``("block", N)`` / ``("mod", N)``: a rule that yields the labels once the number of ranks is known (a plain tuple is a
     list of labels)."""
-
-
-class Peer:
-    """Peer-group scores of one report (``nvrx_peer_score`` / ``nvrx_report_peer``), enqueued and not waited for: once the
-    kernels have run, the workspace's device buffer holds the ``G * (K+S)`` column records ``{floor, present, floor_rank,
-    members}`` and, behind them, ``[n_ranks][1 + S]`` f32 scores of the reported ranks (include/nvrx_straggler.h).
-    ``records()`` waits for them and takes the private host copy (one ordered D2H on the backend's stream): when a ``Report``
-    first asks, or -- ``Workspace.peer_settle`` -- before the next report on the same workspace rewrites the table the
-    kernels read and the buffer they write."""
-
-    __slots__ = ("backend", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "min_ranks", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, K: int, S: int, first_rank: int, n_ranks: int,
-                 min_ranks: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.G, self.K, self.S = G, K, S
-        self.first_rank, self.n_ranks, self.min_ranks = first_rank, n_ranks, min_ranks
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(cols [G, K+S, 4] uint32, scores [n_ranks, 1 + S] f32)`` (private copies); the first call waits for the
-        kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.peer_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
-
-
-class Pace:
-    """Pace scores of one report (``nvrx_pace_score`` / ``nvrx_report_pace``), enqueued and not waited for: once the kernels
-    have run, the workspace's device buffer holds the ``K + S`` column records ``{ctr, n, above, below}`` and, behind them,
-    ``[n_ranks][2]`` rank records ``{pace, spread, columns, slower, faster, total_us, slower_us, excess_us}`` of the reported
-    ranks (include/nvrx_straggler.h).  ``records()`` waits for them and takes the private host copy (one ordered D2H on the
-    backend's stream): when a ``Report`` first asks, or -- ``Workspace.pace_settle`` -- before the next report on the same
-    workspace rewrites the table the kernels read and the buffer they write."""
-
-    __slots__ = ("backend", "d_ptr", "K", "S", "first_rank", "n_ranks", "min_ranks", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, K: int, S: int, first_rank: int, n_ranks: int, min_ranks: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.K, self.S = K, S
-        self.first_rank, self.n_ranks, self.min_ranks = first_rank, n_ranks, min_ranks
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(cols [K+S, 4] uint32, ranks [n_ranks, 2, 8] uint32)`` (private copies; the float fields are bit patterns); the
-        first call waits for the kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.pace_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
-
-
-class PaceGroup:
-    """Pace scores per peer group of one report (``nvrx_pace_group_score`` / ``nvrx_report_pace_group``), enqueued and not
-    waited for: ``Pace`` with ``[G][K + S]`` column records, one set per group, in front of the rank records.  It lives in
-    the workspace's pace buffer and is settled as a ``Pace`` is (``Workspace.pace_settle``)."""
-
-    __slots__ = ("backend", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "min_ranks", "min_peers", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, K: int, S: int, first_rank: int, n_ranks: int,
-                 min_ranks: int, min_peers: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.G, self.K, self.S = G, K, S
-        self.first_rank, self.n_ranks, self.min_ranks, self.min_peers = first_rank, n_ranks, min_ranks, min_peers
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(cols [G, K+S, 4] uint32, ranks [n_ranks, 2, 8] uint32)`` (private copies; the float fields are bit patterns);
-        the first call waits for the kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.pace_group_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
-
-
-class Node:
-    """Node scores of one report (``nvrx_node_score`` / ``nvrx_report_node``), enqueued and not waited for: once the kernels
-    have run, the workspace's device buffer holds the ``[G][K + S]`` pair records ``{med, n, above, below}``, the ``K + S``
-    column records across the nodes ``{center, nodes, above, below}``, ``[G][2]`` node records and ``[n_ranks][2]`` rank
-    records, both spelled as a ``Pace`` rank record (include/nvrx_straggler.h).  ``records()`` waits for them and takes the
-    private host copy (one ordered D2H on the backend's stream): when a ``Report`` first asks, or --
-    ``Workspace.node_settle`` -- before the next report on the same workspace rewrites the table the kernels read and the
-    buffer they write."""
-
-    __slots__ = ("backend", "d_ptr", "G", "K", "S", "first_rank", "n_ranks", "min_members", "min_nodes", "_host", "_lock", "_keep")
-
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, K: int, S: int, first_rank: int, n_ranks: int,
-                 min_members: int, min_nodes: int):
-        self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.G, self.K, self.S = G, K, S
-        self.first_rank, self.n_ranks, self.min_members, self.min_nodes = first_rank, n_ranks, min_members, min_nodes
-        self._host = None
-        self._lock = threading.Lock()
-        self._keep = buf  # the device buffer lives at least until the copy is taken
-
-    def records(self):
-        """``(pairs [G, K+S, 4], cols [K+S, 4], nodes [G, 2, 8], ranks [n_ranks, 2, 8])`` uint32 (private copies; the float
-        fields are bit patterns); the first call waits for the kernels."""
-        if self._host is None:
-            with self._lock:
-                if self._host is None:
-                    self._host = self.backend.node_copy_out(self)
-                    self.backend = self._keep = None
-        return self._host
 
 
 class ScoreHistory:
@@ -765,14 +659,9 @@ class Workspace:
             self.attr_settle()
         if self._family_state:
             self.family_settle(TAIL)
-        if self._robust_last is not None:
-            self.robust_settle()
-        if self._peer_last is not None:
-            self.peer_settle()
-        if self._pace_last is not None:
-            self.pace_settle()
-        if self._node_last is not None:
-            self.node_settle()
+        if self._table_state:
+            for fam in SLOTS:
+                self.table_settle(fam)
         if self._family_state:
             for fam in FAMILIES[1:]:
                 self.family_settle(fam)
@@ -806,82 +695,55 @@ class Workspace:
         if last is not None:
             last.records()
 
-    # ---- robust scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------
-    _robust_buf = None   # device: column records, then the scores of the last robust step of this workspace's table
-    _robust_last = None  # the Robust whose kernels may still be reading the table / writing _robust_buf
+    # ---- table families: robust, peer, pace and node scores (off unless a ReportGenerator asks: nothing is allocated before) ----
+    _table_state = None  # slot name -> _TableBuffers, once a family of that slot has run on this workspace
 
-    def robust_buffers(self, n_ranks: int):
-        """The records buffer for robust scores of ``n_ranks`` ranks (cold: allocated once per shape)."""
-        words = _native.robust_words(n_ranks, self.K, self.S)
-        if self._robust_buf is None or self._robust_buf.numel() < words:
+    def table_buffers(self, fam: TableFamily, n_ranks: int, G: int = 0):
+        """The records buffer of ``fam``'s slot for ``n_ranks`` ranks in ``G`` groups (cold: allocated once per shape)."""
+        words = fam.n_words(G, n_ranks, self.K, self.S)
+        if self._table_state is None:
+            self._table_state = {}
+        st = self._table_state.get(fam.slot)
+        if st is None:
+            st = self._table_state[fam.slot] = _TableBuffers()
+            st.buf = st.last = None  # last: the TableScores whose kernels may still be reading the table / writing buf
+        if st.buf is None or st.buf.numel() < words:
             with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._robust_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
-        return self._robust_buf
+                st.buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+        return st.buf
+
+    def table_settle(self, fam: TableFamily) -> None:
+        """Before anything rewrites this workspace's table or that slot's buffer: the slot's last step's kernels have run and
+        their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        st = self._table_state.get(fam.slot) if self._table_state else None
+        if st is not None and st.last is not None:
+            last, st.last = st.last, None
+            last.records()
+
+    # (the slots by name, as the cost tools and the tests have them: one-line delegations)
+    def robust_buffers(self, n_ranks: int):
+        return self.table_buffers(ROBUST, n_ranks)
 
     def robust_settle(self) -> None:
-        """Before anything rewrites this workspace's table: the last robust step's kernels have run and their results are
-        on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
-        last, self._robust_last = self._robust_last, None
-        if last is not None:
-            last.records()
-
-    # ---- peer-group scores (off unless a ReportGenerator asks: nothing is allocated before) -----------------------
-    _peer_buf = None   # device: column records, then the scores of the last peer step of this workspace's table
-    _peer_last = None  # the Peer whose kernels may still be reading the table / writing _peer_buf
+        self.table_settle(ROBUST)
 
     def peer_buffers(self, G: int, n_ranks: int):
-        """The records buffer for peer scores of ``n_ranks`` ranks in ``G`` groups (cold: allocated once per shape)."""
-        words = _native.peer_words(G, n_ranks, self.K, self.S)
-        if self._peer_buf is None or self._peer_buf.numel() < words:
-            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._peer_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
-        return self._peer_buf
+        return self.table_buffers(PEER, n_ranks, G)
 
     def peer_settle(self) -> None:
-        """Before anything rewrites this workspace's table: the last peer step's kernels have run and their results are on
-        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
-        last, self._peer_last = self._peer_last, None
-        if last is not None:
-            last.records()
-
-    # ---- pace scores (off unless a ReportGenerator asks: nothing is allocated before) ------------------------------
-    _pace_buf = None   # device: column records, then the rank records of the last pace step of this workspace's table
-    _pace_last = None  # the Pace whose kernels may still be reading the table / writing _pace_buf
+        self.table_settle(PEER)
 
     def pace_buffers(self, n_ranks: int, G: int = 0):
-        """The records buffer for pace scores of ``n_ranks`` ranks, per peer group with ``G`` groups (cold: allocated once
-        per shape)."""
-        words = _native.pace_group_words(G, n_ranks, self.K, self.S) if G else _native.pace_words(n_ranks, self.K, self.S)
-        if self._pace_buf is None or self._pace_buf.numel() < words:
-            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._pace_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
-        return self._pace_buf
+        return self.table_buffers(PACE_GROUP if G else PACE, n_ranks, G)
 
     def pace_settle(self) -> None:
-        """Before anything rewrites this workspace's table: the last pace step's kernels have run and their results are on
-        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
-        last, self._pace_last = self._pace_last, None
-        if last is not None:
-            last.records()
-
-    # ---- node scores (off unless a ReportGenerator asks: nothing is allocated before) ------------------------------
-    _node_buf = None   # device: the four record blocks of the last node step of this workspace's table
-    _node_last = None  # the Node whose kernels may still be reading the table / writing _node_buf
+        self.table_settle(PACE)
 
     def node_buffers(self, G: int, n_ranks: int):
-        """The records buffer for node scores of ``n_ranks`` ranks on ``G`` nodes (cold: allocated once per shape)."""
-        words = _native.node_words(G, n_ranks, self.K, self.S)
-        if self._node_buf is None or self._node_buf.numel() < words:
-            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                self._node_buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
-        return self._node_buf
+        return self.table_buffers(NODE, n_ranks, G)
 
     def node_settle(self) -> None:
-        """Before anything rewrites this workspace's table: the last node step's kernels have run and their results are on
-        the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
-        last, self._node_last = self._node_last, None
-        if last is not None:
-            last.records()
+        self.table_settle(NODE)
 
     # ---- score history (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------
     _history_buf = None  # device: the records of the last history step on this workspace's result blocks
@@ -1138,133 +1000,76 @@ class HipBackend:
         """Records ``{ago | length << 16, inside, outside, strength}``."""
         return self._row_op(EPISODE, samples, counts, min_len_ppm, starts)
 
-    def robust_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
-                     min_ranks: int = 4, floor_rel: float = 0.02) -> Robust:
-        """Robust scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank +
-        n_ranks)``: ``nvrx_robust_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
+    def _table_step(self, fam: TableFamily, ws: Workspace, entry, head: tuple, tail: tuple, groups: Optional[PeerGroups],
+                    first_rank: int, n_ranks: Optional[int], params: tuple) -> TableScores:
+        """What both routes of a table family share: the slot settled, its buffer, ``entry(*head, [d_groups, G, [max_size]],
+        rank range and parameters in the family's order, d_out, *tail)``, and the handle noted in the slot."""
         n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        ws.robust_settle()
-        buf = ws.robust_buffers(n_ranks)
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_robust_score(table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel,
-                                        buf.data_ptr(), self._stream_handle)
+        G, lead = 0, ()
+        if fam.groups:
+            if groups.R != ws.R:
+                raise ValueError(f"{fam.groups} groups resolved for {groups.R} ranks, the table has {ws.R}")
+            G = groups.G
+            lead = (groups.device(self).data_ptr(), G, groups.max_size) if fam.max_size else (groups.device(self).data_ptr(), G)
+        ws.table_settle(fam)  # (the records buffer is about to be rewritten)
+        buf = ws.table_buffers(fam, n_ranks, G)
+        rc = entry(*head, *lead, *fam.rank_args(first_rank, n_ranks, params), buf.data_ptr(), *tail)
         if rc < 0:
             _native.check(rc)
-        out = ws._robust_last = Robust(self, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
+        out = ws._table_state[fam.slot].last = TableScores(self, fam, buf, G, ws.K, ws.S, first_rank, n_ranks, params)
         return out
 
-    def robust_copy_out(self, rb: Robust):
-        """The one wait of a report's robust scores: a D2H of the records on the backend's stream, behind the kernels."""
-        KS = rb.K + rb.S
-        n = _native.robust_words(rb.n_ranks, rb.K, rb.S)
+    def _table_score(self, fam: TableFamily, ws: Workspace, table: torch.Tensor, groups: Optional[PeerGroups], first_rank: int,
+                     n_ranks: Optional[int], params: tuple) -> TableScores:
+        """One table family's scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank
+        + n_ranks)``, with the ranks of ``groups`` where the family takes them: ``nvrx_<family>_score`` enqueued on the
+        backend's stream behind the score kernel.  Nothing is waited for."""
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        return self._table_step(fam, ws, getattr(self.lib, fam.c_score), (table_ptr, ws.R, ws.K, ws.S), (self._stream_handle,),
+                                groups, first_rank, n_ranks, params)
+
+    def table_copy_out(self, t: TableScores):
+        """The one wait of a report's table family: a D2H of its block on the backend's stream, behind the kernels."""
+        n = t.family.n_words(t.G, t.n_ranks, t.K, t.S)
         host = np.empty(n, dtype=np.uint32)
-        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, rb.d_ptr, n * 4, self._stream_handle))
-        cols = host[: 4 * KS].reshape(KS, 4).copy()
-        return cols, host[4 * KS :].view(np.float32).reshape(rb.n_ranks, 2, 1 + rb.S).copy()
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        return t.family.cut(host, t.G, t.n_ranks, t.K, t.S)
+
+    # (the families by name, as reporting.py, the oracle backends and the tests have them: one-line delegations)
+    def robust_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
+                     min_ranks: int = 4, floor_rel: float = 0.02) -> TableScores:
+        return self._table_score(ROBUST, ws, table, None, first_rank, n_ranks, (min_ranks, floor_rel))
 
     def peer_score(self, ws: Workspace, table: torch.Tensor, groups: PeerGroups, first_rank: int = 0,
-                   n_ranks: Optional[int] = None, min_ranks: int = 2) -> Peer:
-        """Peer-group scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank +
-        n_ranks)``: ``nvrx_peer_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        if groups.R != ws.R:
-            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
-        ws.peer_settle()
-        buf = ws.peer_buffers(groups.G, n_ranks)
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_peer_score(table_ptr, ws.R, ws.K, ws.S, groups.device(self).data_ptr(), groups.G, first_rank,
-                                      n_ranks, min_ranks, buf.data_ptr(), self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._peer_last = Peer(self, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks)
-        return out
-
-    def peer_copy_out(self, pr: Peer):
-        """The one wait of a report's peer scores: a D2H of the records on the backend's stream, behind the kernels."""
-        KS = pr.K + pr.S
-        n = _native.peer_words(pr.G, pr.n_ranks, pr.K, pr.S)
-        host = np.empty(n, dtype=np.uint32)
-        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pr.d_ptr, n * 4, self._stream_handle))
-        cols = host[: 4 * pr.G * KS].reshape(pr.G, KS, 4).copy()
-        return cols, host[4 * pr.G * KS :].view(np.float32).reshape(pr.n_ranks, 1 + pr.S).copy()
+                   n_ranks: Optional[int] = None, min_ranks: int = 2) -> TableScores:
+        return self._table_score(PEER, ws, table, groups, first_rank, n_ranks, (min_ranks,))
 
     def pace_score(self, ws: Workspace, table: torch.Tensor, first_rank: int = 0, n_ranks: Optional[int] = None,
-                   min_ranks: int = 4) -> Pace:
-        """Pace scores of ``table`` ([R, L], the table ``score`` was given) for ranks ``[first_rank, first_rank + n_ranks)``:
-        ``nvrx_pace_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        ws.pace_settle()
-        buf = ws.pace_buffers(n_ranks)
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_pace_score(table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks, min_ranks, buf.data_ptr(),
-                                      self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._pace_last = Pace(self, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks)
-        return out
-
-    def pace_copy_out(self, pc: Pace):
-        """The one wait of a report's pace scores: a D2H of the records on the backend's stream, behind the kernels."""
-        KS = pc.K + pc.S
-        n = _native.pace_words(pc.n_ranks, pc.K, pc.S)
-        host = np.empty(n, dtype=np.uint32)
-        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pc.d_ptr, n * 4, self._stream_handle))
-        return host[: 4 * KS].reshape(KS, 4).copy(), host[4 * KS :].reshape(pc.n_ranks, 2, 8).copy()
+                   min_ranks: int = 4) -> TableScores:
+        return self._table_score(PACE, ws, table, None, first_rank, n_ranks, (min_ranks,))
 
     def pace_group_score(self, ws: Workspace, table: torch.Tensor, groups: PeerGroups, first_rank: int = 0,
-                         n_ranks: Optional[int] = None, min_ranks: int = 4, min_peers: int = 2) -> PaceGroup:
-        """Pace scores of ``table`` against each rank's own peer group for ranks ``[first_rank, first_rank + n_ranks)``:
-        ``nvrx_pace_group_score`` enqueued on the backend's stream behind the score kernel.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        if groups.R != ws.R:
-            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
-        ws.pace_settle()
-        buf = ws.pace_buffers(n_ranks, groups.G)
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_pace_group_score(table_ptr, ws.R, ws.K, ws.S, groups.device(self).data_ptr(), groups.G,
-                                            groups.max_size, first_rank, n_ranks, min_ranks, min_peers, buf.data_ptr(),
-                                            self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._pace_last = PaceGroup(self, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks, min_peers)
-        return out
-
-    def pace_group_copy_out(self, pc: PaceGroup):
-        """The one wait of a report's pace scores per peer group: a D2H of the records on the backend's stream, behind the
-        kernels."""
-        KS = pc.K + pc.S
-        n = _native.pace_group_words(pc.G, pc.n_ranks, pc.K, pc.S)
-        host = np.empty(n, dtype=np.uint32)
-        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, pc.d_ptr, n * 4, self._stream_handle))
-        return host[: 4 * pc.G * KS].reshape(pc.G, KS, 4).copy(), host[4 * pc.G * KS :].reshape(pc.n_ranks, 2, 8).copy()
+                         n_ranks: Optional[int] = None, min_ranks: int = 4, min_peers: int = 2) -> TableScores:
+        return self._table_score(PACE_GROUP, ws, table, groups, first_rank, n_ranks, (min_ranks, min_peers))
 
     def node_score(self, ws: Workspace, table: torch.Tensor, nodes: PeerGroups, first_rank: int = 0,
-                   n_ranks: Optional[int] = None, min_members: int = 2, min_nodes: int = 3) -> Node:
-        """Node scores of ``table`` ([R, L], the table ``score`` was given) with the ranks of ``nodes`` (a ``PeerGroups`` whose
-        groups are the nodes) for ranks ``[first_rank, first_rank + n_ranks)``: ``nvrx_node_score`` enqueued on the backend's
-        stream behind the score kernel.  Nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        if nodes.R != ws.R:
-            raise ValueError(f"node groups resolved for {nodes.R} ranks, the table has {ws.R}")
-        ws.node_settle()
-        buf = ws.node_buffers(nodes.G, n_ranks)
-        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
-        rc = self.lib.nvrx_node_score(table_ptr, ws.R, ws.K, ws.S, nodes.device(self).data_ptr(), nodes.G, nodes.max_size,
-                                      min_members, min_nodes, first_rank, n_ranks, buf.data_ptr(), self._stream_handle)
-        if rc < 0:
-            _native.check(rc)
-        out = ws._node_last = Node(self, buf, nodes.G, ws.K, ws.S, first_rank, n_ranks, min_members, min_nodes)
-        return out
+                   n_ranks: Optional[int] = None, min_members: int = 2, min_nodes: int = 3) -> TableScores:
+        return self._table_score(NODE, ws, table, nodes, first_rank, n_ranks, (min_members, min_nodes))
 
-    def node_copy_out(self, nd: Node):
-        """The one wait of a report's node scores: a D2H of the records on the backend's stream, behind the kernels."""
-        KS, G = nd.K + nd.S, nd.G
-        n = _native.node_words(G, nd.n_ranks, nd.K, nd.S)
-        host = np.empty(n, dtype=np.uint32)
-        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, nd.d_ptr, n * 4, self._stream_handle))
-        a, b, c = 4 * G * KS, 4 * G * KS + 4 * KS, 4 * G * KS + 4 * KS + 16 * G
-        return (host[:a].reshape(G, KS, 4).copy(), host[a:b].reshape(KS, 4).copy(), host[b:c].reshape(G, 2, 8).copy(),
-                host[c:].reshape(nd.n_ranks, 2, 8).copy())
+    def robust_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
+
+    def peer_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
+
+    def pace_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
+
+    def pace_group_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
+
+    def node_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
 
     def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
         """What both routes of a history step share: the ring of ``state`` with room for this workspace's section ids (cold:
@@ -1656,78 +1461,33 @@ class HipRings:
         out = ws._attr_last = Attribution(self.backend, buf, first_rank, n_ranks, top_n)
         return out
 
+    def _table_report(self, fam: TableFamily, ws: Workspace, groups: Optional[PeerGroups], first_rank: int,
+                      n_ranks: Optional[int], params: tuple) -> TableScores:
+        """One table family's scores of the table of the report ``report_fused`` just issued on ``ws``
+        (``nvrx_report_<family>``): enqueued behind that report's kernels by the library, nothing is waited for.  (The caller
+        settled the workspace before the report already.)"""
+        return self.backend._table_step(fam, ws, getattr(self.lib, fam.c_report), (self.ctx, ws.block.desc_ref), (), groups,
+                                        first_rank, n_ranks, params)
+
+    # (the families by name: one-line delegations)
     def report_robust(self, ws: Workspace, first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 4,
-                      floor_rel: float = 0.02) -> Robust:
-        """Robust scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_robust``): enqueued
-        behind that report's kernels by the library, nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        ws.robust_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
-        buf = ws.robust_buffers(n_ranks)
-        rc = self.lib.nvrx_report_robust(self.ctx, ws.block.desc_ref, first_rank, n_ranks, min_ranks, floor_rel, buf.data_ptr())
-        if rc < 0:
-            _native.check(rc)
-        out = ws._robust_last = Robust(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks, floor_rel)
-        return out
+                      floor_rel: float = 0.02) -> TableScores:
+        return self._table_report(ROBUST, ws, None, first_rank, n_ranks, (min_ranks, floor_rel))
 
     def report_peer(self, ws: Workspace, groups: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
-                    min_ranks: int = 2) -> Peer:
-        """Peer-group scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_peer``):
-        enqueued behind that report's kernels by the library, nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        if groups.R != ws.R:
-            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
-        ws.peer_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
-        buf = ws.peer_buffers(groups.G, n_ranks)
-        rc = self.lib.nvrx_report_peer(self.ctx, ws.block.desc_ref, groups.device(self.backend).data_ptr(), groups.G,
-                                       first_rank, n_ranks, min_ranks, buf.data_ptr())
-        if rc < 0:
-            _native.check(rc)
-        out = ws._peer_last = Peer(self.backend, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks)
-        return out
+                    min_ranks: int = 2) -> TableScores:
+        return self._table_report(PEER, ws, groups, first_rank, n_ranks, (min_ranks,))
 
-    def report_pace(self, ws: Workspace, first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 4) -> Pace:
-        """Pace scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_pace``): enqueued
-        behind that report's kernels by the library, nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        ws.pace_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
-        buf = ws.pace_buffers(n_ranks)
-        rc = self.lib.nvrx_report_pace(self.ctx, ws.block.desc_ref, first_rank, n_ranks, min_ranks, buf.data_ptr())
-        if rc < 0:
-            _native.check(rc)
-        out = ws._pace_last = Pace(self.backend, buf, ws.K, ws.S, first_rank, n_ranks, min_ranks)
-        return out
+    def report_pace(self, ws: Workspace, first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 4) -> TableScores:
+        return self._table_report(PACE, ws, None, first_rank, n_ranks, (min_ranks,))
 
     def report_pace_group(self, ws: Workspace, groups: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
-                          min_ranks: int = 4, min_peers: int = 2) -> PaceGroup:
-        """Pace scores per peer group of the table of the report ``report_fused`` just issued on ``ws``
-        (``nvrx_report_pace_group``): enqueued behind that report's kernels by the library, nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        if groups.R != ws.R:
-            raise ValueError(f"peer groups resolved for {groups.R} ranks, the table has {ws.R}")
-        ws.pace_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
-        buf = ws.pace_buffers(n_ranks, groups.G)
-        rc = self.lib.nvrx_report_pace_group(self.ctx, ws.block.desc_ref, groups.device(self.backend).data_ptr(), groups.G,
-                                             groups.max_size, first_rank, n_ranks, min_ranks, min_peers, buf.data_ptr())
-        if rc < 0:
-            _native.check(rc)
-        out = ws._pace_last = PaceGroup(self.backend, buf, groups.G, ws.K, ws.S, first_rank, n_ranks, min_ranks, min_peers)
-        return out
+                          min_ranks: int = 4, min_peers: int = 2) -> TableScores:
+        return self._table_report(PACE_GROUP, ws, groups, first_rank, n_ranks, (min_ranks, min_peers))
 
     def report_node(self, ws: Workspace, nodes: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
-                    min_members: int = 2, min_nodes: int = 3) -> Node:
-        """Node scores of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_node``): enqueued
-        behind that report's kernels by the library, nothing is waited for."""
-        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
-        if nodes.R != ws.R:
-            raise ValueError(f"node groups resolved for {nodes.R} ranks, the table has {ws.R}")
-        ws.node_settle()  # (the records buffer is about to be rewritten; the caller settled before the report already)
-        buf = ws.node_buffers(nodes.G, n_ranks)
-        rc = self.lib.nvrx_report_node(self.ctx, ws.block.desc_ref, nodes.device(self.backend).data_ptr(), nodes.G,
-                                       nodes.max_size, min_members, min_nodes, first_rank, n_ranks, buf.data_ptr())
-        if rc < 0:
-            _native.check(rc)
-        out = ws._node_last = Node(self.backend, buf, nodes.G, ws.K, ws.S, first_rank, n_ranks, min_members, min_nodes)
-        return out
+                    min_members: int = 2, min_nodes: int = 3) -> TableScores:
+        return self._table_report(NODE, ws, nodes, first_rank, n_ranks, (min_members, min_nodes))
 
     def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,
                        thresholds: Sequence[float] = DEFAULT_THRESHOLDS) -> History:

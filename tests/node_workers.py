@@ -158,7 +158,7 @@ def folded_option_off(rank, world, reports=4, asynchronous=False):
     be = get_backend()
 
     def with_node_state():
-        return [ws for ws in be._workspaces.values() if ws._node_buf is not None or ws._node_last is not None]
+        return [ws for ws in be._workspaces.values() if ws._table_state and "node" in ws._table_state]
 
     before = with_node_state()  # (other jobs of this process may have left theirs; the objects are kept alive, so ids hold)
     job = FoldedJob(total_ranks=6, section_names=["step"], ring_cap=64, scores_to_compute=("relative_perf_scores",),
@@ -176,8 +176,11 @@ def folded_option_off(rank, world, reports=4, asynchronous=False):
         be.synchronize()
         torch.cuda.synchronize()
         ws = job.reporter._ring_plan.ws
+        slots = ws._table_state or {}  # slot -> its buffer and the step in flight, for the slots that ever ran
+        node = slots.get("node")
+        assert set(slots) == {"pace"}, sorted(slots)  # (robust and peer scores are off as well; pace scores ran)
         return {"said": said, "fused": fused, "new": [w for w in with_node_state() if not any(w is b for b in before)],
-                "planned_ws": (ws._node_buf, ws._node_last, "_node_buf" in ws.__dict__, (ws.R, ws.K, ws.S)),
+                "planned_ws": (node and node.buf, node and node.last, "node" in slots, (ws.R, ws.K, ws.S)),
                 "resolved": job.reporter._node_resolved, "option": job.reporter.node_scores}
     finally:
         job.close()

@@ -422,13 +422,17 @@ def test_option_off_calls_nothing(emulate_fused, asynchronous):
 
 
 def test_the_product_workspace_holds_no_node_buffer_until_asked():
-    """``Workspace``'s node state is class-level None: a workspace no node step ran on has no buffer and nothing to settle."""
+    """``Workspace``'s table-family state is class-level None: a workspace no node step ran on has no node buffer and nothing
+    to settle -- and the same holds of the robust, peer and pace slots."""
     from nvrx_straggler.backend import Workspace
 
-    assert Workspace._node_buf is None and Workspace._node_last is None
+    assert Workspace._table_state is None
     ws = Workspace.__new__(Workspace)
-    ws.node_settle()  # (nothing in flight: no call into a backend)
-    assert "_node_buf" not in ws.__dict__ and "_node_last" in ws.__dict__ and ws._node_last is None
+    for slot in ("node", "robust", "peer", "pace"):
+        getattr(ws, slot + "_settle")()  # (nothing in flight: no call into a backend)
+        assert "_table_state" not in ws.__dict__ and ws._table_state is None, slot  # no buffer, no step in flight
+    ws.settle_readers()
+    assert ws.__dict__ == {}
 
 
 @pytest.mark.parametrize("emulate_fused,asynchronous", [(False, False), (True, False), (True, True)])

@@ -22,6 +22,8 @@
     ``nvrx_pace_group_score`` on the same tables in the same run: 8 ranks x 64 sections on 2 nodes, 64 ranks x 4096 kernels
     on 8 nodes, 1024 ranks x 128 ids on 128 nodes (``block:N``); under the profiler a run per ``--shape``.  ``report``:
     ``node_scores`` (``node_groups="block:4"``) is what alternates.
+``--families`` (``report`` only; docs/MEASUREMENTS.md, "Table families"): ``robust_scores``, ``pace_scores`` and ``node_scores``
+    (``node_groups="block:4"``) all on is what alternates with a plain generator.
 Prints one JSON line per measurement.
 """
 import argparse
@@ -191,6 +193,10 @@ def report(args):
     if args.node:
         gens = {0: ReportGenerator(["relative_perf_scores"], node_name="n"),
                 1: ReportGenerator(["relative_perf_scores"], node_name="n", node_scores=True, node_groups="block:4")}
+    if args.families:
+        gens = {0: ReportGenerator(["relative_perf_scores"], node_name="n"),
+                1: ReportGenerator(["relative_perf_scores"], node_name="n", robust_scores=True, pace_scores=True,
+                                   node_scores=True, node_groups="block:4")}
     lat, readable = {0: [], 1: []}, []
     try:
         for i in range(2 * (args.reports + args.warmup)):
@@ -201,20 +207,22 @@ def report(args):
             rep.identify_stragglers()
             t1 = time.perf_counter_ns()
             if on:
-                scores = rep.node_scores() if args.node else rep.pace_scores()
+                scores = rep.node_scores() if args.node or args.families else rep.pace_scores()
                 assert len(scores["section_columns"]) == sections
+                if args.families:
+                    assert rep.robust_scores() and rep.pace_scores()
             t2 = time.perf_counter_ns()
             if i >= 2 * args.warmup:
                 lat[on].append((t1 - t0) * 1e-3)
                 if on:
                     readable.append((t2 - t0) * 1e-3)
             be.synchronize()
-        out = {"what": "ring report, call -> flagged set" + (", pace_peer_groups off / on" if args.grouped else ", node_scores off / on" if args.node else ""), "processes": 1, "reports_each": args.reports, "shape": "8 x 64 x 10000"}
+        out = {"what": "ring report, call -> flagged set" + (", pace_peer_groups off / on" if args.grouped else ", node_scores off / on" if args.node else ", robust + pace + node scores off / on" if args.families else ""), "processes": 1, "reports_each": args.reports, "shape": "8 x 64 x 10000"}
         for on, key in ((0, "off"), (1, "on")):
             out[f"{key}_median_us"] = round(float(np.median(lat[on])), 1)
             out[f"{key}_p95_us"] = round(float(np.percentile(lat[on], 95)), 1)
         out["delta_median_us"] = round(out["on_median_us"] - out["off_median_us"], 1)
-        out["node_readable_median_us" if args.node else "pace_readable_median_us"] = round(float(np.median(readable)), 1)
+        out["all_readable_median_us" if args.families else "node_readable_median_us" if args.node else "pace_readable_median_us"] = round(float(np.median(readable)), 1)
         print(json.dumps(out), flush=True)
     finally:
         for g in gens.values():
@@ -231,6 +239,7 @@ def main():
     ap.add_argument("--shape", type=int, default=-1, help="kernels: only that entry of SHAPES (a profiler run per shape)")
     ap.add_argument("--grouped", action="store_true", help="pace scores per peer group (see the module's text)")
     ap.add_argument("--node", action="store_true", help="node scores (see the module's text)")
+    ap.add_argument("--families", action="store_true", help="report: robust, pace and node scores together (see the module's text)")
     args = ap.parse_args()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     {"kernels": kernels_node if args.node else kernels_grouped if args.grouped else kernels, "report": report}[args.what](args)
