@@ -91,6 +91,13 @@ every rank of node 2 is 4 % slower in every kernel -- failed fans, a capped PSU 
 own.  ``identify_pace_stragglers`` names nine ranks and cannot say which of them are one incident; with node scores
 (``ReportGenerator(node_scores=True)``) ``identify_node_stragglers`` names node 2 alone, 8 of its 8 ranks agreeing, and hands
 rank 5 back as a rank that is off pace without its node.
+
+``--work`` plays the ``--peer`` job WITHOUT anybody describing its layout: 8 ranks in two pipeline stages (folded onto one GPU,
+1 % noise, seed 31), 120 kernel keys and 4 sections; 100 keys are shared and run 1600 times a window in stage 0 and 2400 times
+in stage 1, 10 keys only stage 0 has and 10 only stage 1; rank 6 is 1.4x slower in everything.  ``identify_stragglers`` names
+ranks 4-7; with ``ReportGenerator(peer_groups="auto")`` the groups are inferred from the table the report gathers anyway --
+which kernels a rank has and how often each ran, neither of which a slow GPU changes --, ``identify_peer_stragglers`` names
+rank 6 alone, and the inferred groups are printed with every rank's nearest other rank.
 """
 import argparse
 import os
@@ -391,6 +398,46 @@ def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 
         job.close()
 
 
+def work(ranks: int = 8, sections: int = 4, shared: int = 100, own: int = 10, calls=(1600, 2400), slow_rank: int = 6) -> None:
+    """Two pipeline stages nobody described: whom the job-wide rule names, whom ``peer_groups="auto"`` names, and the groups."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    names = [f"kernel_{k:03d}" for k in range(shared + 2 * own)]
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=4096, scores_to_compute=("relative_perf_scores",),
+                    kernel_names=names, peer_groups="auto")
+    rng = np.random.default_rng(31)
+    base = rng.uniform(20.0, 400.0, len(names))
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            stage = r // (ranks // 2)
+            slow = 1.4 if r == slow_rank else 1.0
+            sec = np.full((sections, 33), (1000.0, 1500.0)[stage] * slow) * (1.0 + 0.01 * rng.standard_normal((sections, 33)))
+            job.load(lr, sec.astype(np.float32))
+            mine = list(range(shared)) + list(range(shared + own * stage, shared + own * (stage + 1)))
+            for k in mine:  # (a key of the other stage gets no sample: this rank does not have it)
+                n = calls[stage] if k < shared else 200
+                job.rings.push_many(job._no_kernel_rows[names[k]], (base[k] * slow * (1.0 + 0.01 * rng.standard_normal(n))).astype(np.float32), lr=lr)
+        report = job.report()
+        w, t = report.work_groups(), report.peer_scores()
+        print(f"identify_stragglers(): {named(report.identify_stragglers())}")
+        print(f"identify_peer_stragglers() with peer_groups='auto': {named(report.identify_peer_stragglers())}")
+        print(f"inferred groups: {w['groups']}; rule {w['params']}")
+        for r in sorted(w["ranks"]):
+            d = w["ranks"][r]
+            print(f"  rank {r} (group {w['group_of'][r]} of {d['size']}): {d['kernels']} kernels, {d['sections']} sections; nearest rank "
+                  f"{d['nearest']} differs in {d['nearest_unlike']} of {d['nearest_columns']} columns; relative GPU score against the job "
+                  f"{report.gpu_relative_perf_scores[r]:.3f}, against its peers {t['gpu_relative'][r]:.3f}")
+    finally:
+        job.close()
+
+
 def pace(ranks: int = 8, kernels: int = 120, calls: int = 200, slow_rank: int = 5, slowdown: float = 1.04) -> None:
     """A rank that is a little slower in everything: whom the threshold rules name, and whom the pace scores do."""
     import numpy as np
@@ -541,7 +588,13 @@ def main() -> None:
     ap.add_argument("--node", action="store_true",
                     help="no training: play the node-score scenario (32 ranks on 4 nodes, every rank of node 2 and rank 5 of node "
                          "0 4 %% slower in every kernel) with the pace rule and the node rule, and exit")
+    ap.add_argument("--work", action="store_true",
+                    help="no training: play the work-group scenario (the two pipeline stages of --peer with nobody describing "
+                         "the layout: the groups are inferred from the kernels each rank runs and how often) and exit")
     args = ap.parse_args()
+    if args.work:
+        work()
+        return
     if args.node:
         node()
         return

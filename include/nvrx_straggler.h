@@ -593,6 +593,52 @@ int nvrx_score_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, 
 #define NVRX_SLACK_WORDS(R) (8 + 4 * (size_t)NVRX_SLACK_COLS + 8 * (size_t)(R))
 int nvrx_slack_score(const float *d_slack, const float *d_table, int R, int K, int S, int min_ranks, void *d_out, void *stream);
 
+/* Work groups: WHICH RANKS DO THE SAME WORK, inferred from the table.  Peer-group scores, pace scores per peer group and node
+ * scores take that from the caller (d_groups); the table a report gathers holds a signature of each rank's work that does not
+ * depend on how fast the rank runs: which kernel ids and section ids it has at all, and -- the exchanged weight being NUM * AVG
+ * -- how OFTEN each kernel ran in the window, w / med.  A slow GPU changes durations, neither the set of kernels nor their call
+ * counts, so a rank 1.4 x slower than its peers has exactly its peers' signature.  Every word of the result is an integer, or
+ * one correctly rounded f64 division converted to f32: exact.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_WORK_MAX_RANKS; T = ceil(R / 64).
+ *   Signature sig[r][c], f32, c < K+S, from med = table[r][c] and, for a kernel id, w = table[r][2(K+S) + c]:
+ *      -1.0   absent: unless med >= 0 (the -1 sentinel and NaN are absent, as in the robust scores);
+ *      +0.0   present with an unknown count: every present section id (c >= K), and a present kernel id unless
+ *      q      = (float)((double)w / (double)med), where med > 0, w is finite and > 0 and q is finite and > 0.
+ *   Pair (a, b), a != b, over all K+S columns:
+ *      either  columns present on at least one of the two ranks;
+ *      unlike  columns present on exactly one of them, plus the columns present on both with both counts > 0 where
+ *              (double)hi > (1.0 + (double)count_tol) * (double)lo, hi and lo the larger and the smaller of the two counts;
+ *      the two ranks are ALIKE iff either >= 1 and (uint64)unlike * 1000000 <= (uint64)max_unlike_ppm * either.  Symmetric.
+ *   count_tol f32 in [0, 16], max_unlike_ppm in [0, 1000000].  The Python package's 0.25 and 100000 are defaults, not
+ *   measurements.  NUM is the number of samples a ring row holds: a kernel called more often in a window than its ring has
+ *   slots reads ring_cap on every rank alike, and call counts beyond that do not tell ranks apart (presence still does).
+ *   Groups are the connected components of the alike relation; root[r] is the lowest rank of r's component.  A rank with
+ *   nothing present is alike to nobody and alone.  Single linkage can chain: a component need not be a clique (degree + 1 < size
+ *   says so).
+ *   Nearest of rank a: the other rank b with either >= 1 whose share unlike / either is smallest, shares compared by 64-bit
+ *   cross-multiplication, the lower b on a tie; -1 where there is none.
+ *   d_out  16-byte aligned, nvrx_work_words(R, K, S) 32-bit words; five parts, each starting on a 16-byte boundary (the words
+ *   that pad a part are written as 0):
+ *      A  sig [R][K+S] f32;
+ *      B  adjacency [R][T] u64: bit b of word j of row a stands for rank 64 j + b and is set iff the two are alike; the
+ *         diagonal is set; bits at or beyond R are clear;
+ *      C  partial nearest [R][T], 16 bytes: {u32 unlike, u32 either, i32 rank, 0}, the nearest of rank a among ranks [64 j,
+ *         64 j + 64); {0, 0, -1, 0} where that tile has none;
+ *      D  rank records [R], 32 bytes: {i32 root, u32 size of the component, u32 degree = alike ranks without the rank itself,
+ *         i32 nearest, u32 nearest_unlike, u32 nearest_either, u32 kernels_present, u32 sections_present};
+ *      E  job record, 16 bytes: {u32 groups, u32 singletons (groups of one rank), u32 largest, u32 ranks_with_data (ranks
+ *         with a present column)}.
+ *   All R ranks are always computed.  A, B and C are the hand-over between the kernels and part of the result.
+ * Four launches on `stream` (signatures, pairs -- one workgroup per 64 x 64 tile of rank pairs --, components, ranks); no float
+ * atomics, no atomics on global memory, no scratch.  Argument errors, reported before any device is touched: the table's shape
+ * as for nvrx_robust_score, then NVRX_ERR_RANGE for R > NVRX_WORK_MAX_RANKS, for a count_tol outside [0, 16] (a NaN included)
+ * and for a max_unlike_ppm outside [0, 1000000], then NVRX_ERR_INVALID for a null pointer or a d_out that is not 16-byte
+ * aligned.  nvrx_work_words returns the block's size (it fits an int: below 2^30 words at the largest shape), or the error
+ * nvrx_work_groups reports for that shape (NVRX_ERR_INVALID, NVRX_ERR_RANGE). */
+#define NVRX_WORK_MAX_RANKS 4096
+int nvrx_work_words(int R, int K, int S);
+int nvrx_work_groups(const float *d_table, int R, int K, int S, float count_tol, int max_unlike_ppm, void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a
@@ -832,6 +878,12 @@ int nvrx_report_pace_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const in
  * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_node(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group, int min_members,
                      int min_nodes, int first_rank, int n_ranks, void *d_out);
+/* nvrx_work_groups (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as nvrx_report_peer orders itself: the
+ * context's stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a
+ * D2H on the context's stream, and do not let a later report rewrite the table before the kernels have run.  NVRX_ERR_STATE:
+ * no report was issued through this descriptor. */
+int nvrx_report_work(nvrx_ctx *ctx, const nvrx_report_desc *desc, float count_tol, int max_unlike_ppm, void *d_out);
 /* nvrx_score_history (above) on the result block of the report LAST issued through `desc` on `ctx` (desc->d_scores; R and S
  * from the descriptor).  Ordered behind that report's last kernel exactly as nvrx_report_robust orders itself: the context's
  * stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a D2H on the

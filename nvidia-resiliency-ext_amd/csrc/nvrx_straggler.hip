@@ -3973,3 +3973,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_pace.inl"
 #include "nvrx_pace_group.inl"
 #include "nvrx_node.inl"
+#include "nvrx_work.inl"

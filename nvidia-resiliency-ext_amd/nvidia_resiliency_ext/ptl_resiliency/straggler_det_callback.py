@@ -81,7 +81,8 @@ class StragglerDetectionCallback(Callback):
                 score sees) logs one warning that names the ranks and the microseconds the others wait for each per report
                 window.  A warning only: it never stops the job.
             peer_groups: None (the default): nothing changes.  Otherwise which ranks do the same work, as
-                ``Detector.initialize(peer_groups=...)`` takes it: labels, one per rank, or ``"block:N"`` / ``"mod:N"``.  The
+                ``Detector.initialize(peer_groups=...)`` takes it: labels, one per rank, or ``"block:N"`` / ``"mod:N"``.  ``"auto"``: nobody
+                describes the layout; every report infers the groups from its table (``Report.work_groups()``).  The
                 RELATIVE family's warning, and with ``stop_if_detected`` the halt, then come from
                 ``Report.identify_peer_stragglers`` -- each rank against the fastest rank of its own group -- so that the
                 healthy ranks of a slower pipeline stage do not stop the job.  Ranks without a peer are unrated; they are

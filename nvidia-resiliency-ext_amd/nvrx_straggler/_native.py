@@ -47,6 +47,9 @@ TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, f
 SLACK_COLS = 64  # NVRX_SLACK_COLS: columns the collective keys are folded into (digest % 64)
 SLACK_HEAD_WORDS = 8 + 4 * SLACK_COLS  # the job record and the column records in front of the rank records
 SLACK_RANK_WORDS = 8  # {f32 collective_us, waited_us, compute_us, share, u32 calls, columns, 0, 0} per rank
+WORK_MAX_RANKS = 4096  # NVRX_WORK_MAX_RANKS: the most ranks a work-group step compares pairwise
+WORK_RANK_WORDS = 8  # {i32 root, u32 size, degree, i32 nearest, u32 nearest_unlike, nearest_either, kernels, sections} per rank
+WORK_JOB_WORDS = 4  # {u32 groups, singletons, largest, ranks_with_data}
 
 
 
@@ -106,6 +109,8 @@ SYMBOLS = [
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
     ("nvrx_slack_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("nvrx_work_words", c_int, [c_int, c_int, c_int]),
+    ("nvrx_work_groups", c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     ("nvrx_ctx_destroy", c_int, [c_void_p]),
     ("nvrx_ctx_set_stream", c_int, [c_void_p, c_void_p]),
@@ -153,6 +158,7 @@ SYMBOLS = [
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
+    ("nvrx_report_work", c_int, [c_void_p, POINTER(ReportDesc), c_float, c_int, c_void_p]),
     ("nvrx_slack_local", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
     ("nvrx_report_desc_size", c_int, []),
@@ -295,6 +301,23 @@ def trend_words(n_ranks: int, S: int) -> int:
 def slack_words(R: int) -> int:
     """NVRX_SLACK_WORDS: 32-bit words of a slack score's output -- job record | 64 column records | ``R`` rank records."""
     return SLACK_HEAD_WORDS + SLACK_RANK_WORDS * R
+
+
+def work_offsets(R: int, K: int, S: int):
+    """Where the parts of a work-group block start, in 32-bit words -- ``(adjacency, partial nearest, rank records, job record,
+    size)``; the signature plane starts at 0 and every part on a 16-byte boundary.  The size is ``nvrx_work_words(R, K, S)``."""
+    T = -(-R // 64)
+    adj = (R * (K + S) + 3) & ~3
+    part = adj + ((2 * R * T + 3) & ~3)
+    rank = part + 4 * R * T
+    job = rank + WORK_RANK_WORDS * R
+    return adj, part, rank, job, job + WORK_JOB_WORDS
+
+
+def work_words(R: int, K: int, S: int) -> int:
+    """``nvrx_work_words``: 32-bit words of a work-group block -- signatures | adjacency | partial nearest | ``R`` rank records |
+    job record."""
+    return work_offsets(R, K, S)[4]
 
 
 def tail_q_ppm(q) -> int:

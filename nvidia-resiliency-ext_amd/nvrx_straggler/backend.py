@@ -487,6 +487,36 @@ class Slack:
         return self._host
 
 
+class Work:
+    """The work groups of one report (``nvrx_work_groups`` / ``nvrx_report_work``), enqueued and not waited for: once the four
+    kernels have run, the workspace's device buffer holds the block of include/nvrx_straggler.h -- signatures, adjacency,
+    partial nearest records, rank records, job record.  ``records()`` waits for them and takes the private host copy of the
+    rank records and the job record (one ordered D2H on the backend's stream): when a ``Report`` first asks, when
+    ``peer_groups="auto"`` needs the groups, or -- ``Workspace.work_settle`` -- before the next report on the same workspace
+    rewrites the table the kernels read and the buffer they write."""
+
+    __slots__ = ("backend", "d_ptr", "R", "K", "S", "count_tol", "max_unlike_ppm", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, K: int, S: int, count_tol: float, max_unlike_ppm: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.R, self.K, self.S = R, K, S
+        self.count_tol, self.max_unlike_ppm = count_tol, max_unlike_ppm
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(ranks [R, 8], job [4])`` uint32 (private copies): ``{root, size, degree, nearest, nearest_unlike, nearest_either,
+        kernels_present, sections_present}`` per rank and ``{groups, singletons, largest, ranks_with_data}``; the first call
+        waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.work_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Workspace:
     """Buffers of one report shape (R ranks, K kernel ids, S section ids): the exchange rows and the gathered table in
     device memory, and two result blocks (``ResultBlock``) that successive reports alternate between.  ``ws.meta /
@@ -671,6 +701,27 @@ class Workspace:
             self.trend_settle()
         if self._slack_last is not None:
             self.slack_settle()
+        if self._work_last is not None:
+            self.work_settle()
+
+    # ---- work groups (off unless a ReportGenerator asks: nothing is allocated before) -----------------------------
+    _work_buf = None   # device: the block of the last work-group step on this workspace's table
+    _work_last = None  # the Work whose kernels may still be reading the table / writing _work_buf
+
+    def work_buffers(self):
+        """The block of a work-group step over this workspace's table (cold: allocated once)."""
+        if self._work_buf is None:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._work_buf = torch.empty(max(_native.work_words(self.R, self.K, self.S), 64), dtype=torch.int32,
+                                             device=self._backend.device)
+        return self._work_buf
+
+    def work_settle(self) -> None:
+        """Before anything rewrites this workspace's table or the block: the last work-group step's kernels have run and its
+        records are on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._work_last = self._work_last, None
+        if last is not None:
+            last.records()
 
     # ---- slack scores (off unless a ReportGenerator asks: nothing is allocated before) ----------------------------
     _slack_state = None  # (send, table, out) once a slack step has run on this workspace
@@ -1131,6 +1182,32 @@ class HipBackend:
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, host.nbytes, self._stream_handle))
         return host
 
+    def _work_step(self, ws: Workspace, entry, head: tuple, tail: tuple, count_tol: float, max_unlike_ppm: int) -> Work:
+        """What both routes of the work-group step share: the slot settled, its block, ``entry(*head, count_tol,
+        max_unlike_ppm, d_out, *tail)``, and the handle noted in the workspace."""
+        ws.work_settle()  # (the block is about to be rewritten)
+        buf = ws.work_buffers()
+        rc = entry(*head, float(count_tol), int(max_unlike_ppm), buf.data_ptr(), *tail)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._work_last = Work(self, buf, ws.R, ws.K, ws.S, float(count_tol), int(max_unlike_ppm))
+        return out
+
+    def work_groups(self, ws: Workspace, table: torch.Tensor, count_tol: float = 0.25, max_unlike_ppm: int = 100000) -> Work:
+        """Which ranks of ``table`` ([R, L], the table ``score`` was given) do the same work: ``nvrx_work_groups`` enqueued on
+        the backend's stream behind the score kernel.  All R ranks are computed.  Nothing is waited for."""
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        return self._work_step(ws, self.lib.nvrx_work_groups, (table_ptr, ws.R, ws.K, ws.S), (self._stream_handle,), count_tol,
+                               max_unlike_ppm)
+
+    def work_copy_out(self, w: Work):
+        """The one wait of a report's work groups: a D2H of the rank records and the job record, which end the block, on the
+        backend's stream, behind the kernels."""
+        _, _, rank, job, words = _native.work_offsets(w.R, w.K, w.S)
+        host = np.empty(words - rank, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, w.d_ptr + 4 * rank, host.nbytes, self._stream_handle))
+        return host[: job - rank].reshape(w.R, _native.WORK_RANK_WORDS).copy(), host[job - rank:].copy()
+
     def slack_score(self, ws: Workspace, slack_table: torch.Tensor, table: torch.Tensor, first_rank: int = 0,
                     n_ranks: Optional[int] = None, min_ranks: int = 4) -> Slack:
         """Slack scores from the gathered rows ``slack_table`` ([R, 2 * 64], ``HipRings.slack_local`` and the caller's
@@ -1488,6 +1565,12 @@ class HipRings:
     def report_node(self, ws: Workspace, nodes: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
                     min_members: int = 2, min_nodes: int = 3) -> TableScores:
         return self._table_report(NODE, ws, nodes, first_rank, n_ranks, (min_members, min_nodes))
+
+    def report_work(self, ws: Workspace, count_tol: float = 0.25, max_unlike_ppm: int = 100000) -> Work:
+        """The work groups of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_work``): enqueued
+        behind that report's kernels by the library, nothing is waited for.  (The caller settled the workspace before the
+        report already.)"""
+        return self.backend._work_step(ws, self.lib.nvrx_report_work, (self.ctx, ws.block.desc_ref), (), count_tol, max_unlike_ppm)
 
     def report_history(self, ws: Workspace, state: ScoreHistory, first_rank: int = 0, n_ranks: Optional[int] = None,
                        thresholds: Sequence[float] = DEFAULT_THRESHOLDS) -> History:

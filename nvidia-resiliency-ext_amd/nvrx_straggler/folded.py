@@ -35,7 +35,8 @@ class FoldedJob:
                  pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8, pace_min_effect: float = 0.03,
                  pace_min_breadth: float = 0.9, pace_peer_groups: bool = False, node_scores: bool = False, node_groups=None,
                  node_min_members: int = 2, node_min_nodes: int = 3, node_min_columns: int = 8, node_min_effect: float = 0.03,
-                 node_min_breadth: float = 0.9, node_min_agree: float = 0.75):
+                 node_min_breadth: float = 0.9, node_min_agree: float = 0.75, work_groups: bool = False,
+                 work_count_tol: float = 0.25, work_max_unlike: float = 0.1):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -69,7 +70,10 @@ class FoldedJob:
                                             "node_min_members": node_min_members, "node_min_nodes": node_min_nodes,
                                             "node_min_columns": node_min_columns, "node_min_effect": node_min_effect,
                                             "node_min_breadth": node_min_breadth, "node_min_agree": node_min_agree}
-                                           if node_scores else {}))
+                                           if node_scores else {}),
+                                        **({"work_groups": bool(work_groups), "work_count_tol": work_count_tol,
+                                            "work_max_unlike": work_max_unlike}
+                                           if work_groups or (isinstance(peer_groups, str) and peer_groups == "auto") else {}))
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         # (the same object every report so the reporter's cached plan stays valid)
         self._no_kernel_rows = {name: self.rings.row_for(_native.KIND_KERNEL, name) for name in self.kernel_names}

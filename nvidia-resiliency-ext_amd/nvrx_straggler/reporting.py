@@ -891,11 +891,17 @@ class _NodeSource:
 
 
 def _peer_spec(peer_groups, what: str = "peer_groups"):
-    """``ReportGenerator``'s ``peer_groups`` as the generator keeps it: None (off), a rule (``"block:N"``: label ``rank //
+    """``ReportGenerator``'s ``peer_groups`` as the generator keeps it: None (off), ``"auto"`` (inferred per report: work
+    groups), a rule (``"block:N"``: label ``rank //
     N``, contiguous stages; ``"mod:N"``: label ``rank % N``) or a tuple of ``int`` / ``str`` labels, one per logical rank.
     Nothing else is accepted.  ``node_groups`` is parsed here too: ``what`` is the option's name in the messages."""
     if peer_groups is None:
         return None
+    if isinstance(peer_groups, str) and peer_groups == "auto":
+        if what != "peer_groups":
+            raise ValueError(f"{what}='auto': only peer_groups are inferred from the table (work groups say which ranks do the "
+                             "same work, not which share a host); pass labels, 'block:N' or 'mod:N'")
+        return "auto"  # the groups of every report are the work groups inferred from its table (ReportGenerator._peer_for)
     if isinstance(peer_groups, str):
         kind, sep, num = peer_groups.partition(":")
         if kind not in ("block", "mod") or not sep or not num.strip().isdigit():
@@ -1108,6 +1114,50 @@ class _SlackSource:
         return self._built
 
 
+class _WorkSource:
+    """What a report keeps of its work groups: the backend's handle (``records()`` waits for the kernels and copies the rank
+    records and the job record out on first use), the ranks its rows stand for, the step's parameters and -- where the user
+    also passed labels -- the resolved ``peer_groups`` to hold against the inferred ones."""
+
+    __slots__ = ("handle", "ranks", "params", "labelled", "_built")
+
+    def __init__(self, handle, ranks, params: dict, labelled=None):
+        self.handle, self.ranks, self.params, self.labelled = handle, tuple(ranks), params, labelled
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            rec, job = (np.ascontiguousarray(a, dtype=np.uint32) for a in self.handle.records())
+            root = rec[:, 0].copy().view(np.int32).tolist()
+            nearest = rec[:, 3].copy().view(np.int32).tolist()
+            u = rec.tolist()
+            groups: Dict[int, List[int]] = {}
+            for r, g in enumerate(root):
+                groups.setdefault(g, []).append(r)
+            per_rank = {}
+            for r in self.ranks:
+                _, size, degree, _, n_unlike, n_either, kernels, sections = u[r]
+                per_rank[r] = {"size": size, "degree": degree, "loose": degree + 1 < size,
+                               "nearest": nearest[r] if nearest[r] >= 0 else None, "nearest_unlike": n_unlike,
+                               "nearest_columns": n_either, "kernels": kernels, "sections": sections}
+            built = {"groups": groups, "group_of": {r: root[r] for r in self.ranks},
+                     "singletons": [g for g, members in groups.items() if len(members) == 1], "ranks": per_rank,
+                     "ranks_with_data": int(job[3]), "params": dict(self.params)}
+            if self.labelled is not None:
+                # the user's groups whose members the table puts into more than one inferred group (host arithmetic)
+                conflicts = {}
+                for g, label in enumerate(self.labelled.labels):
+                    split: Dict[int, List[int]] = {}
+                    for r in self.labelled.members(g):
+                        split.setdefault(root[r], []).append(r)
+                    if len(split) > 1:
+                        conflicts[label] = split
+                built["label_conflicts"] = conflicts
+            self._built = built
+            self.handle = self.labelled = None
+        return self._built
+
+
 _LAZY_FIELDS = frozenset((
     "gpu_relative_perf_scores", "section_relative_perf_scores", "gpu_individual_perf_scores",
     "section_individual_perf_scores", "local_section_summaries", "local_kernel_summaries",
@@ -1218,6 +1268,9 @@ class Report:
         slack = self.__dict__.get("_slack")
         if slack is not None:
             state["_slack"] = slack.build() if isinstance(slack, _SlackSource) else slack
+        work = self.__dict__.get("_work")
+        if work is not None:
+            state["_work"] = work.build() if isinstance(work, _WorkSource) else work
         for fam in row_families.FAMILIES:
             scores = self.__dict__.get(fam.slot)
             if scores is not None:
@@ -1625,6 +1678,31 @@ class Report:
             slack = self.__dict__["_slack"] = slack.build()
         return _copy_scores(slack)
 
+    def work_groups(self) -> Dict[str, Any]:
+        """Which ranks do the SAME WORK, inferred from the report's table (``ReportGenerator(work_groups=True)`` or
+        ``peer_groups="auto"``; ``{}`` when the report carries none).  The signature of a rank's work is which kernel ids and
+        section ids it has at all and how often each kernel ran in the window (its weight over its median): a slow GPU changes
+        neither, so a straggler stays in the group of its peers.  Two ranks are alike when at most ``max_unlike`` of the columns
+        either of them has differ -- present on one only, or call counts more than ``1 + count_tol`` apart -- and the groups
+        are the connected components of that relation, named by their lowest rank.
+
+        ``{"groups": {root: [ranks]}`` (every rank of the job), ``"group_of": {rank: root}``, ``"singletons": [roots of groups of
+        one rank]``, ``"ranks": {rank: {"size", "degree" (alike ranks), "loose" (degree + 1 < size: the group is a chain, not a
+        clique -- single linkage joined ranks that are not alike each other), "nearest" (the other rank with the smallest share
+        of differing columns, the lower rank on a tie; None where no other rank has data), "nearest_unlike", "nearest_columns",
+        "kernels", "sections" (present columns)}}, "ranks_with_data", "params": {"count_tol", "max_unlike", "max_unlike_ppm"}}``;
+        with explicit ``peer_groups`` also ``"label_conflicts": {label: {root: [members]}}`` -- the user's groups whose members
+        fall into more than one inferred group.  ``group_of`` and ``ranks`` cover the ranks of the score mappings.  In
+        region-stamp timing mode a rank has few columns and equal presence gives one group; call counts saturate at the ring
+        capacity.  Plain dicts, lists, ints and floats.  The first call waits for the kernels; ``generate_report`` never does
+        (``peer_groups="auto"`` does: the peer step needs the groups)."""
+        work = self.__dict__.get("_work")
+        if work is None:
+            return {}
+        if isinstance(work, _WorkSource):
+            work = self.__dict__["_work"] = work.build()
+        return _copy_peer(work)  # (nested dicts and lists, as the peer scores)
+
     def identify_slack_stragglers(self, min_share: Optional[float] = None, max_ratio: Optional[float] = None) -> Dict[str, Any]:
         """Ranks the others wait for: ``{"straggler_gpus_slack": set[StragglerId]}``.  A rank with data is named iff the job
         as a whole waits (``typical_share >= min_share``, default the generator's 0.05, and ``typical_waited_us > 0``) and
@@ -1826,7 +1904,8 @@ class ReportGenerator:
                  pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9, pace_peer_groups: bool = False,
                  node_scores: bool = False, node_groups=None, node_min_members: int = 2, node_min_nodes: int = 3,
                  node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
-                 node_min_agree: float = 0.75) -> None:
+                 node_min_agree: float = 0.75, work_groups: bool = False, work_count_tol: float = 0.25,
+                 work_max_unlike: float = 0.1) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -1926,6 +2005,33 @@ class ReportGenerator:
                 raise RuntimeError(f"peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no peer-group scores (backend.peer_score)")
             self.peer_min_ranks = int(peer_min_ranks)
+        # work groups: every report also says which ranks do the same work, inferred from the table (Report.work_groups), and
+        # peer_groups="auto" takes its groups from there; off: no buffer, no launch, no backend call.  The step reads the
+        # exchanged table only: no collective, and every rank infers the same groups from the same table.  0.25 and 0.1 are
+        # defaults, not measurements.
+        self.work_groups = bool(work_groups) or self.peer_groups == "auto"
+        self._work_handle = None  # this report's step (peer_groups="auto" waits for it: _peer_for)
+        self._peer_auto_roots = None  # the root array _peer_resolved was built from
+        if self.work_groups:
+            try:
+                tol, share = float(work_count_tol), float(work_max_unlike)
+            except (TypeError, ValueError):
+                raise ValueError(f"work_count_tol and work_max_unlike must be numbers, got {work_count_tol!r} and "
+                                 f"{work_max_unlike!r}") from None
+            if isinstance(work_count_tol, bool) or not 0.0 <= tol <= 16.0:  # (NaN fails both comparisons)
+                raise ValueError(f"work_count_tol must be within [0, 16], got {work_count_tol!r}")
+            if isinstance(work_max_unlike, bool) or not 0.0 <= share <= 1.0:
+                raise ValueError(f"work_max_unlike must be within [0, 1], got {work_max_unlike!r}")
+            option = "peer_groups='auto'" if self.peer_groups == "auto" else "work_groups"
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"{option} needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "work groups compare ranks")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "work_groups"):
+                raise RuntimeError(f"{option}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no work groups (backend.work_groups)")
+            self.work_count_tol, self.work_max_unlike = tol, share
+            self.work_max_unlike_ppm = int(round(share * 1e6))
         # pace scores: every report also says whether a rank is a little slower in nearly all of its kernels
         # (Report.pace_scores); off: no buffer, no launch, no backend call.  They read the exchanged table only: no collective,
         # so a mismatch between ranks cannot hang anything -- but every rank should pass the same value.
@@ -2335,6 +2441,8 @@ class ReportGenerator:
                 names_ok = True
             K, S = mapper.kernel_counter, mapper.section_counter
             world = self.world_size if exchanged else 1
+            if self.work_groups:
+                self._work_refuse(world * local_ranks)  # (before anything of this report is launched)
             ws = be.workspace(world * local_ranks, K, S, local_ranks, stats_rows)
             settle = getattr(ws, "settle_readers", None)  # (the CPU checker backend of the tests has no deferred readers)
             if settle is not None:
@@ -2392,6 +2500,10 @@ class ReportGenerator:
             # likewise: enqueued behind the score kernel, waited for when the report is first asked
             self._attach_robust(report, _backend_mod.get_backend().robust_score(
                 ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor), ws, mapper, view)
+        if self.work_groups:
+            # likewise, ahead of the peer step, which peer_groups="auto" makes wait for it
+            self._attach_work(report, _backend_mod.get_backend().work_groups(
+                ws, ws.table, self.work_count_tol, self.work_max_unlike_ppm), ws, view)
         if self.peer_groups is not None:
             # likewise, behind the robust step
             groups = self._peer_for(ws)
@@ -2498,6 +2610,8 @@ class ReportGenerator:
         plan.key = key
         plan.topology = self._plan_topology(rings, local_ranks)
         plan.mapper = mapper
+        if self.work_groups:
+            self._work_refuse(world * local_ranks)
         plan.ws = be.workspace(world * local_ranks, K, S, local_ranks, total_rows)
         plan.rows_used = rings.rows_used
         # the report's local summaries are those of this process' FIRST logical rank (rank 0 of a folded job): its rows are
@@ -2563,6 +2677,8 @@ class ReportGenerator:
             raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
         if fused and self.robust_scores and not hasattr(rings, "report_robust"):
             raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
+        if fused and self.work_groups and not hasattr(rings, "report_work"):
+            raise RuntimeError("work_groups: these rings run the one-call report but have no report_work")
         if fused and self.peer_groups is not None and not hasattr(rings, "report_peer"):
             raise RuntimeError("peer_groups: these rings run the one-call report but have no report_peer")
         if fused and self.pace_scores and not hasattr(rings, "report_pace_group" if self.pace_peer_groups else "report_pace"):
@@ -2598,6 +2714,8 @@ class ReportGenerator:
                     self._attach_plan_attribution(report, plan, rings, True)
                 if self.robust_scores:
                     self._attach_plan_robust(report, plan, rings, True)
+                if self.work_groups:
+                    self._attach_plan_work(report, plan, rings, True)
                 if self.peer_groups is not None:
                     self._attach_plan_peer(report, plan, rings, True)
                 if self.pace_scores:
@@ -2640,6 +2758,8 @@ class ReportGenerator:
             self._attach_plan_attribution(report, plan, rings, fused)
         if self.robust_scores:
             self._attach_plan_robust(report, plan, rings, fused)
+        if self.work_groups:
+            self._attach_plan_work(report, plan, rings, fused)
         if self.peer_groups is not None:
             self._attach_plan_peer(report, plan, rings, fused)
         if self.pace_scores:
@@ -2689,9 +2809,44 @@ class ReportGenerator:
         """The groups resolved for the logical ranks of ``ws``' table (cold: once per R; a label list of another length
         is refused here, where R is first known)."""
         groups = self._peer_resolved
+        if self.peer_groups == "auto":
+            # the work groups of THIS report's table: one stream wait and one D2H of the rank records and the job record (an
+            # asynchronous report waits here too); the roots are the labels, and the object is kept while they stay the same
+            rec, _ = self._work_handle.records()
+            roots = np.ascontiguousarray(rec[:, 0], dtype=np.uint32).view(np.int32)
+            if groups is None or groups.R != ws.R or not np.array_equal(roots, self._peer_auto_roots):
+                groups = self._peer_resolved = _backend_mod.PeerGroups(roots.tolist())
+                self._peer_auto_roots = roots.copy()
+            return groups
         if groups is None or groups.R != ws.R:
             groups = self._peer_resolved = _backend_mod.PeerGroups.resolve(self.peer_groups, ws.R)
         return groups
+
+    # ---- work groups --------------------------------------------------------------------------------
+    def _work_refuse(self, R: int) -> None:
+        """The step compares every pair of ranks and takes at most ``NVRX_WORK_MAX_RANKS`` of them."""
+        cap = _backend_mod._native.WORK_MAX_RANKS
+        if R > cap:
+            option = "peer_groups='auto'" if self.peer_groups == "auto" else "work_groups"
+            raise ValueError(f"{option}: the job has {R} logical ranks, work groups are inferred for at most {cap}; say which "
+                             "ranks do the same work with peer_groups labels, 'block:N' or 'mod:N' instead")
+
+    def _attach_work(self, report, handle, ws, view) -> None:
+        self._work_handle = handle
+        labelled = self._peer_for(ws) if self.peer_groups is not None and self.peer_groups != "auto" else None
+        report.__dict__["_work"] = _WorkSource(handle, view.ranks, {"count_tol": self.work_count_tol,
+                                                                    "max_unlike": self.work_max_unlike,
+                                                                    "max_unlike_ppm": self.work_max_unlike_ppm}, labelled)
+
+    def _attach_plan_work(self, report, plan, rings, fused: bool) -> None:
+        """Enqueue the work-group step of the planned report that was just issued, as ``_attach_plan_robust`` does (all R
+        ranks: the components need them), and hang it on ``report``.  Nothing is waited for."""
+        ws = plan.ws
+        if fused:
+            handle = rings.report_work(ws, self.work_count_tol, self.work_max_unlike_ppm)
+        else:
+            handle = _backend_mod.get_backend().work_groups(ws, ws.table, self.work_count_tol, self.work_max_unlike_ppm)
+        self._attach_work(report, handle, ws, plan.view)
 
     def _attach_peer(self, report, handle, groups, ws, mapper, view) -> None:
         report.__dict__["_peer"] = _PeerSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), groups,

@@ -164,6 +164,8 @@ class _Lane:
             return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
         if getattr(reporter, "peer_groups", None) is not None:
             return None  # (the peer launch follows the report in the generator's planned path: DESIGN.md, "Peer-group scores")
+        if getattr(reporter, "work_groups", False):
+            return None  # (the work-group launches follow the report in the generator's planned path: DESIGN.md, "Work groups")
         if getattr(reporter, "pace_scores", False):
             return None  # (the pace launches follow the report in the generator's planned path: DESIGN.md, "Pace scores")
         if getattr(reporter, "node_scores", False):
@@ -303,13 +305,13 @@ class _Lane:
 
 
 def _peer_groups_from_env(value: str, name: str = "NVRX_PEER_GROUPS"):
-    """``NVRX_PEER_GROUPS`` (and ``NVRX_NODE_GROUPS``, by ``name``): ``block:N``, ``mod:N`` or a comma-separated list of
+    """``NVRX_PEER_GROUPS`` (and ``NVRX_NODE_GROUPS``, by ``name``): ``auto`` (peer groups only), ``block:N``, ``mod:N`` or a comma-separated list of
     integer labels, one per logical rank; unset or empty: None (off; for the nodes: ``rank_to_node``)."""
     value = value.strip()
     if not value:
         return None
-    if ":" in value:
-        return value  # (ReportGenerator checks the rule)
+    if ":" in value or value == "auto":
+        return value  # (ReportGenerator checks the rule, and says that only peer groups are inferred)
     try:
         return [int(x) for x in value.split(",")]
     except ValueError:
@@ -447,6 +449,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
         node_min_effect: float = 0.03,
         node_min_breadth: float = 0.9,
         node_min_agree: float = 0.75,
+        work_groups: Optional[bool] = None,
+        work_count_tol: Optional[float] = None,
+        work_max_unlike: Optional[float] = None,
     ):
         """
         Args:
@@ -550,8 +555,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 (``Report.peer_scores()``, ``Report.identify_peer_stragglers()``), so that the healthy ranks of a slower
                 stage are not named.  A list, tuple or ndarray of ``int`` or ``str`` labels, one per LOGICAL rank of the job,
                 or ``"block:N"`` (label ``rank // N``: contiguous stages) or ``"mod:N"`` (label ``rank % N``).  Needs
-                ``relative_perf_scores``.  Default: ``NVRX_PEER_GROUPS`` (``block:N``, ``mod:N`` or a comma-separated list
-                of integers), else off.  Same value on every rank (no collective depends on it).
+                ``relative_perf_scores``.  ``"auto"``: nobody describes the layout -- the groups of every report are the work
+                groups inferred from its table (``work_groups`` below, which it implies; at most 4096 logical ranks).  Default:
+                ``NVRX_PEER_GROUPS`` (``auto``, ``block:N``, ``mod:N`` or a comma-separated list of integers), else off.  Same
+                value on every rank (no collective depends on it).
             peer_min_ranks: ranks of a group that must have a section or kernel for the group to have a reference; at the
                 default of 2 (``NVRX_PEER_MIN_RANKS``) a rank alone in its group has no peer and is unrated, not rated 1.0.
             pace_scores: every report also says whether a rank is a LITTLE slower in nearly ALL of its kernels -- a card held a
@@ -587,6 +594,14 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 at least this many columns, a pace of at most ``1 - node_min_effect``, slower than the nodes' centre in at
                 least this share of the columns, and at least this share of the node's rated ranks off pace themselves.
                 8, 0.03, 0.9 and 0.75 are defaults, not measurements.
+            work_groups: every report also says which ranks do the SAME WORK, inferred from the table the report gathers anyway
+                (``Report.work_groups()``): which kernels and sections a rank has at all and how often each kernel ran do not
+                depend on how fast the rank runs.  With explicit ``peer_groups`` the report also lists the labels that
+                contradict the work (``"label_conflicts"``).  Needs ``relative_perf_scores``; at most 4096 logical ranks.
+                Default: ``NVRX_WORK_GROUPS`` ("1"; "0" or unset: off).  No collective depends on it.
+            work_count_tol, work_max_unlike: two ranks are alike when at most the share ``work_max_unlike`` of the columns either
+                of them has differ, a kernel both have differing when its call counts are more than ``1 + work_count_tol`` apart.
+                Defaults: ``NVRX_WORK_COUNT_TOL`` / ``NVRX_WORK_MAX_UNLIKE``, else 0.25 and 0.1 -- defaults, not measurements.
         """
         assert not cls.initialized
         _backend_mod.require_engine()  # no silent CPU path: a box that cannot run the engine says so here
@@ -671,6 +686,23 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 except ValueError:
                     raise ValueError("NVRX_PEER_MIN_RANKS must be an integer >= 1") from None
             peer_options = {"peer_groups": peer_groups, "peer_min_ranks": peer_min_ranks}
+        work_options = {}  # (off: the generator is built exactly as before)
+        if work_groups is None:
+            from_env = os.environ.get("NVRX_WORK_GROUPS", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_WORK_GROUPS must be 0 or 1, got {from_env!r}")
+            work_groups = from_env == "1"
+        if work_groups or (isinstance(peer_groups, str) and peer_groups == "auto"):
+            for name, env, default in (("work_count_tol", "NVRX_WORK_COUNT_TOL", 0.25), ("work_max_unlike", "NVRX_WORK_MAX_UNLIKE", 0.1)):
+                value = work_count_tol if name == "work_count_tol" else work_max_unlike
+                if value is None:
+                    try:
+                        value = float(os.environ.get(env, "") or default)
+                    except ValueError:
+                        raise ValueError(f"{env} must be a number, got {os.environ.get(env)!r}") from None
+                work_options[name] = value
+            if work_groups:
+                work_options["work_groups"] = True
         pace_options = {}  # (off: the generator is built exactly as before)
         if pace_scores is None:
             pace_scores = os.environ.get("NVRX_PACE_SCORES", "0") not in ("", "0")
@@ -710,7 +742,8 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                       slack_max_ratio=slack_max_ratio, **peer_options, **pace_options, **node_options)
+                                       slack_max_ratio=slack_max_ratio, **peer_options, **pace_options, **node_options,
+                                       **work_options)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
