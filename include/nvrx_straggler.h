@@ -37,7 +37,15 @@ extern "C" {
 #define NVRX_ERR_TIMEOUT (-62) /* wait timed out (ETIME) */
 
 /* Row statistics layout: NVRX_STATS_STRIDE floats per row.
- * Mirrors the Statistic enum (statistics.py:19-35) + the kernel weight NUM*AVG (reporting.py:246). */
+ * Mirrors the Statistic enum (statistics.py:19-35) + the kernel weight NUM*AVG (reporting.py:246).
+ * Word 7 has no name: the statistics kernel stores there, as a float, the path its selection of the median took --
+ *   0       nothing was selected (no samples, or all samples equal)
+ *   1       the range estimated from the row's first tile held
+ *   2       the median fell into an edge bin of that estimate: the histogram was rebuilt over the row's exact range
+ *   +4      the median's bin was too heavy to rank and was refined (5 = 1+4, 6 = 2+4, 22 = 18+4)
+ *   18      (16|2) a sample with the sign bit set: the row was re-keyed, which always rebuilds over the exact range
+ * It is a diagnostic and no caller should act on it, but the tests rely on it: tests/test_gpu_row_stats_paths.py compares
+ * it, row by row, with a model of the selection's control flow to show that every path ran in every launch shape. */
 #define NVRX_STATS_STRIDE 8
 #define NVRX_STAT_MIN 0
 #define NVRX_STAT_MAX 1

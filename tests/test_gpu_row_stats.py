@@ -99,7 +99,8 @@ def test_kernel_rows_match_reference_golden(be):
     _check_against_oracle(got, m, counts, kinds, "golden-k1")
 
 
-@pytest.mark.parametrize("stride", [4, 8, 64, 256, 1000, 1024, 2048, 3072, 4096, 5000, 8192, 10000, 16384, 20480, 32768, 65536])
+@pytest.mark.parametrize("stride", [4, 8, 64, 256, 1000, 1024, 2048, 3072, 4096, 5000, 8192, 10000, 12288, 16384, 20480, 24576, 32768,
+                                    49152, 65536])
 def test_random_rows_every_launch_shape(be, stride):
     """Ragged counts (0, 1, 2, odd, even, full) x both kinds for every register-tile variant."""
     rng = np.random.default_rng(stride)
