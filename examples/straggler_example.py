@@ -74,6 +74,14 @@ usual time and the step lasts as long on every rank, so ``identify_stragglers`` 
 peers.  ``identify_stragglers`` names ranks 4-7, three of them healthy; with peer groups (``ReportGenerator(peer_groups=
 "block:4")``) ``identify_peer_stragglers`` names rank 6 alone, and both scores are printed side by side.
 
+``--peer-persist`` plays the ``--peer`` job over 16 reports (8 ranks, ``block:4``, stages of 1000 us and 1500 us, 1 % noise, seed
+37): rank 1 is 1.6x slower in report 6 only, rank 6 is 1.4x slower than its stage from report 10 on.  Per report it prints whom
+each rule names.  Per-report peer flagging (``identify_peer_stragglers``) names rank 1 at report 6 -- with ``stop_if_detected``
+one bad window would end the job -- and rank 6 from report 10; the job-wide history (``identify_persistent_stragglers``) names
+the healthy ranks 4-7 from the third report on, for ever; the peer history (``ReportGenerator(peer_history=8,
+peer_persistence_min_reports=3)``, ``identify_persistent_peer_stragglers``) never names rank 1 and names rank 6 alone from
+report 12 on.
+
 ``--pace`` needs no training loop either: it plays one report of a job of 8 ranks x 120 kernels (folded onto one GPU, lognormal
 kernel times, 1 % noise per entry, seed 2026, 200 calls of every kernel) in which rank 5 is 4 % slower in EVERY kernel -- a card
 held a clock step down.  Its relative GPU score reads about 0.95 and its robust z about 2: ``identify_stragglers`` and
@@ -398,6 +406,53 @@ def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 
         job.close()
 
 
+def peer_persist_windows(reports: int = 16, ranks: int = 8, sections: int = 4, samples: int = 33):
+    """The ``--peer-persist`` job, report by report: ``[ranks, sections, samples]`` f64 microseconds (NumPy only)."""
+    import numpy as np
+
+    for i in range(reports):
+        x = np.repeat(np.array([1000.0] * (ranks // 2) + [1500.0] * (ranks - ranks // 2)), sections * samples)
+        x = x.reshape(ranks, sections, samples) * (1.0 + 0.01 * np.random.default_rng([37, i]).standard_normal((ranks, sections, samples)))
+        if i == 6:
+            x[1] *= 1.6
+        if i >= 10:
+            x[6] *= 1.4
+        yield x
+
+
+def peer_persist_verdicts(report):
+    """``(per-report peer flagging, the job-wide history, the peer history)``: the ranks each rule names, sorted."""
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    return (named(report.identify_peer_stragglers()), named(report.identify_persistent_stragglers()),
+            named(report.identify_persistent_peer_stragglers()))
+
+
+def peer_persist(ranks: int = 8) -> None:
+    """A pipeline job over 16 reports: one bad window and a rank that stays slower than its peers, under three rules."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    job = FoldedJob(total_ranks=ranks, sections=4, ring_cap=64, scores_to_compute=("relative_perf_scores",),
+                    peer_groups=f"block:{ranks // 2}", score_history=8, persistence_min_reports=3, peer_history=8,
+                    peer_persistence_min_reports=3)
+    try:
+        for i, x in enumerate(peer_persist_windows(ranks=ranks)):
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, x[r].astype(np.float32))
+            report = job.report()
+            per_report, job_wide, peers = peer_persist_verdicts(report)
+            rec = report.peer_history()["section_relative"][job.section_names[0]][6]
+            print(f"report {i:2d}: identify_peer_stragglers() {per_report}, identify_persistent_stragglers() {job_wide}, "
+                  f"identify_persistent_peer_stragglers() {peers}; rank 6 against its peers on {job.section_names[0]}: latest "
+                  f"{rec['latest']:.2f}, streak {rec['streak']}, below in {rec['below']} of {rec['present']}")
+    finally:
+        job.close()
+
+
 def work(ranks: int = 8, sections: int = 4, shared: int = 100, own: int = 10, calls=(1600, 2400), slow_rank: int = 6) -> None:
     """Two pipeline stages nobody described: whom the job-wide rule names, whom ``peer_groups="auto"`` names, and the groups."""
     import numpy as np
@@ -579,6 +634,9 @@ def main() -> None:
     ap.add_argument("--peer", action="store_true",
                     help="no training: play the peer-group scenario (two pipeline stages of different length, one rank slow "
                          "within its stage) and exit")
+    ap.add_argument("--peer-persist", action="store_true",
+                    help="no training: play the peer-history scenario (the two stages of --peer over 16 reports: one bad "
+                         "window of rank 1, rank 6 slower than its stage from report 10 on) under three rules, and exit")
     ap.add_argument("--pace", action="store_true",
                     help="no training: play the pace-score scenario (a rank 4 %% slower in every one of its 120 kernels) and "
                          "exit")
@@ -606,6 +664,9 @@ def main() -> None:
         return
     if args.slack:
         slack()
+        return
+    if args.peer_persist:
+        peer_persist()
         return
     if args.peer:
         peer()

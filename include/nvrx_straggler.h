@@ -560,6 +560,35 @@ int nvrx_score_history(const float *d_scores, int R, int S, int first_rank, int 
 #define NVRX_TREND_WORDS(n_ranks, S) ((size_t)(n_ranks) * 2 * (1 + (size_t)(S)) * 4)
 int nvrx_score_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, void *d_out, void *stream);
 
+/* Peer-score history and trends: the two steps above on the PEER-GROUP scores.  Where ranks legitimately differ (pipeline
+ * stages, expert groups) the job-wide relative scores rate a whole stage low in every report; the scores that mean something
+ * are nvrx_peer_score's, and these entries keep a ring of THEM.  One family, not two; the NaN of an unrated rank is an absent
+ * entry (it ends a streak).  There is one definition of every record -- the two contracts above:
+ *   d_peer  the rank part nvrx_peer_score / nvrx_report_peer left: f32 [n_ranks][1 + S] {GPU peer score, section peer
+ *           score[S]}, behind the G (K+S) column records of its block (d_out + 16 G (K+S) bytes there); 4-byte aligned;
+ *   d_hist  f32 [n_ranks][1 + S_cap][Hs], Hs = NVRX_HISTORY_STRIDE(H), 16-byte aligned (NVRX_PEER_HISTORY_FLOATS); a fresh
+ *           ring is bytes 0xFF.  Slot 0 is the GPU peer score, slot 1 + s section id s;
+ *   rows    row r of d_peer, d_hist and d_out is the r-th REPORTED rank: the peer block is already cut to the reported ranks,
+ *           so there is no first_rank;
+ *   thresholds[2]  {gpu, section}, NULL => 0.75 each (finite).
+ * nvrx_peer_history: the record of cell (r, j) is word for word the record nvrx_score_history writes for (r, f = 1, j) on
+ * score rows whose relative columns hold the peer values (column 1 = d_peer[r][0], column 2 + S + s = d_peer[r][1 + s]), with
+ * thresholds[0] and thresholds[1]; the ring cell (r, j) is byte for byte that call's ring cell (r, 1, j).
+ *   d_out  16-byte aligned, NVRX_PEER_HISTORY_WORDS(n_ranks, S) 32-bit words: [n_ranks][1 + S][8].
+ * nvrx_peer_trend: the record of cell (r, j) is the record nvrx_score_trend writes for that ring cell; the ring is only read.
+ *   d_out  16-byte aligned, NVRX_PEER_TREND_WORDS(n_ranks, S) 32-bit words: [n_ranks][1 + S][4].
+ * One launch each; steps on one ring must be ordered against each other and behind the peer step they read (one stream).
+ * Errors as nvrx_score_history's and nvrx_score_trend's, in their order, with R = n_ranks and one family: NVRX_ERR_RANGE for H
+ * outside [2, 64], S_cap above NVRX_MAX_ROWS or more cells than one launch covers (n_ranks * ceil((1 + S) / (64 / Hs)) waves
+ * above 2^31 - 1); NVRX_ERR_INVALID for n_ranks < 1, S < 0, S > S_cap, null or misaligned pointers, non-finite thresholds and
+ * -- the trend -- n_reports == 0; reported before any device is touched. */
+#define NVRX_PEER_HISTORY_FLOATS(n_ranks, S_cap, H) ((size_t)(n_ranks) * (1 + (size_t)(S_cap)) * NVRX_HISTORY_STRIDE(H))
+#define NVRX_PEER_HISTORY_WORDS(n_ranks, S) ((size_t)(n_ranks) * (1 + (size_t)(S)) * 8)
+#define NVRX_PEER_TREND_WORDS(n_ranks, S) ((size_t)(n_ranks) * (1 + (size_t)(S)) * 4)
+int nvrx_peer_history(const float *d_peer, int n_ranks, int S, float *d_hist, int S_cap, int H, uint64_t n_before,
+                      const double *thresholds, void *d_out, void *stream);
+int nvrx_peer_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, void *d_out, void *stream);
+
 /* Slack scores: the rank the others WAIT FOR in collectives.  Every score above compares how long a rank's own work takes; a
  * rank whose host is slow (a busy CPU, a data loader, a GC pause) launches late, computes at the usual speed and ends its
  * sections in a collective like everybody else, so all of them read 1.  The time the ranks spend inside collective kernels
@@ -904,6 +933,14 @@ int nvrx_report_history(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_r
  * wait; copy d_out with a D2H on the context's stream. */
 int nvrx_report_trend(nvrx_ctx *ctx, const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports,
                       void *d_out);
+/* nvrx_peer_history and nvrx_peer_trend (above) on the context's stream -- the stream nvrx_report_peer launched on, so a
+ * step is ordered behind the peer step whose rank part it reads (d_peer: that step's d_out + 16 G (K+S) bytes) and behind the
+ * ring's earlier steps without an event.  The host does not wait; copy d_out with a D2H on the context's stream, and do not
+ * let a later peer step rewrite the block before the kernel has run.  NVRX_ERR_STATE: no report was issued on this context. */
+int nvrx_report_peer_history(nvrx_ctx *ctx, const float *d_peer, int n_ranks, int S, float *d_hist, int S_cap, int H,
+                             uint64_t n_before, const double *thresholds, void *d_out);
+int nvrx_report_peer_trend(nvrx_ctx *ctx, const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports,
+                           void *d_out);
 /* The local step of the slack scores (nvrx_slack_score, above) on the STATISTICS of the report last issued -- it reads the
  * statistics rows, not the rings.  rows[i], cols[i], i < n: host arrays, the collective rows of a logical rank (row within the
  * rank, the same for every logical rank) in ascending order with their columns; the library keeps the list in device memory

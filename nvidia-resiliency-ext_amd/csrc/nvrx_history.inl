@@ -18,6 +18,8 @@
 //   which orders behind all of them: no presence mask goes with the broadcasts.  The lanes at positions 0, (present - 1) >> 1
 //   and present - 1 hand worst, median and best to the lane of age 0, which writes the record as two 16-byte stores.  No LDS
 //   memory, no barrier, no atomics, no scratch, no data-dependent loop; workgroups share nothing.
+// k_peer_history<HS>  the same cell code (history_cell<HS, true>) on the peer-score ring, which has one family: see
+//   nvrx_peer_history.inl.
 
 namespace {
 
@@ -25,9 +27,9 @@ constexpr int HISTORY_THREADS = 256;
 constexpr uint32_t HISTORY_ABSENT = 0xFFFFFFFFu;  // f2key of a NaN: above f2key(+inf), the key of no present value
 
 struct HistoryArgs {
-    const float *scores;  // [R][2 + 2S]
-    float *hist;          // [n_ranks][2][1 + S_cap][HS]
-    uint4 *out;           // [n_ranks][2][1 + S][2]
+    const float *scores;  // [R][2 + 2S]; k_peer_history: the peer step's rank part [n_ranks][1 + S]
+    float *hist;          // [n_ranks][2][1 + S_cap][HS]; k_peer_history: [n_ranks][1 + S_cap][HS]
+    uint4 *out;           // [n_ranks][2][1 + S][2]; k_peer_history: [n_ranks][1 + S][2]
     int S, S_cap, first_rank;
     int H, slot0, depth;  // slot0 = n_before % H, depth = min(n_before + 1, H)
     uint32_t waves_per_fam, total_waves;
@@ -68,15 +70,18 @@ __device__ __forceinline__ uint32_t history_order(uint32_t key, int lane) {
     }
 }
 
-template <int HS>
-__global__ __launch_bounds__(HISTORY_THREADS) void k_score_history(HistoryArgs a) {
+// One cell per segment.  PEER: the peer-score history (nvrx_peer_history) -- one family, so a wave's `rf` is the rank itself,
+// and the lane of age 0 reads x from the rank part the peer step left, [n_ranks][1 + S], one run of consecutive floats per
+// wave; the record is the one family 1 gets, with thr[0] and thr[1].
+template <int HS, bool PEER>
+__device__ __forceinline__ void history_cell(const HistoryArgs &a) {
     constexpr int SPW = 64 / HS;  // slots per wave
     constexpr unsigned long long SEG = HS == 64 ? ~0ull : ((1ull << (HS & 63)) - 1ull);
     const int lane = threadIdx.x & 63;
     const uint32_t gw = blockIdx.x * (HISTORY_THREADS / 64) + (threadIdx.x >> 6);
     if (gw >= a.total_waves) return;  // wave-uniform
     const uint32_t rf = gw / a.waves_per_fam, chunk = gw - rf * a.waves_per_fam;
-    const int f = (int)(rf & 1u), r = (int)(rf >> 1);
+    const int f = PEER ? 1 : (int)(rf & 1u), r = PEER ? (int)rf : (int)(rf >> 1);
     const int S = a.S;
     const int seg = lane / HS, age = lane & (HS - 1), sh = seg * HS;
     const int j = (int)chunk * SPW + seg;
@@ -89,8 +94,12 @@ __global__ __launch_bounds__(HISTORY_THREADS) void k_score_history(HistoryArgs a
     if (live) {
         float *cell = a.hist + ((size_t)rf * (size_t)(1 + a.S_cap) + (size_t)j) * HS;
         if (age == 0) {
-            const int col = j == 0 ? f : 2 + f * S + (j - 1);
-            x = a.scores[(size_t)(a.first_rank + r) * (size_t)NVRX_SCORE_LEN(S) + col];
+            if constexpr (PEER) {
+                x = a.scores[(size_t)r * (size_t)(1 + S) + (size_t)j];
+            } else {
+                const int col = j == 0 ? f : 2 + f * S + (j - 1);
+                x = a.scores[(size_t)(a.first_rank + r) * (size_t)NVRX_SCORE_LEN(S) + col];
+            }
             cell[at] = x;
         } else {
             x = cell[at];
@@ -121,9 +130,20 @@ __global__ __launch_bounds__(HISTORY_THREADS) void k_score_history(HistoryArgs a
     }
 }
 
-// argument checks shared by both entry points; nothing here touches a device
+template <int HS>
+__global__ __launch_bounds__(HISTORY_THREADS) void k_score_history(HistoryArgs a) {
+    history_cell<HS, false>(a);
+}
+
+template <int HS>
+__global__ __launch_bounds__(HISTORY_THREADS) void k_peer_history(HistoryArgs a) {
+    history_cell<HS, true>(a);
+}
+
+// argument checks shared by the entry points; nothing here touches a device.  fams: 2 for the score history (four
+// thresholds), 1 for the peer-score history (two)
 int history_check(int R, int S, int first_rank, int n_ranks, const void *d_hist, int S_cap, int H, const double *thresholds,
-                  const void *d_out) {
+                  const void *d_out, int fams = 2) {
     if (R <= 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad score shape R=%d S=%d", R, S);
     if (H < 2 || H > NVRX_HISTORY_MAX_DEPTH) return fail(NVRX_ERR_RANGE, "history depth H=%d outside [2,%d]", H, NVRX_HISTORY_MAX_DEPTH);
     if (S > S_cap) return fail(NVRX_ERR_INVALID, "S=%d section ids, the history holds S_cap=%d", S, S_cap);
@@ -134,14 +154,15 @@ int history_check(int R, int S, int first_rank, int n_ranks, const void *d_hist,
     if ((reinterpret_cast<uintptr_t>(d_hist) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0)
         return fail(NVRX_ERR_INVALID, "d_hist or d_out is not 16-byte aligned");
     if (thresholds)
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < 2 * fams; i++)
             if (thresholds[i] - thresholds[i] != 0.0) return fail(NVRX_ERR_INVALID, "thresholds[%d] is not finite", i);
     const int per_wave = 64 / NVRX_HISTORY_STRIDE(H);
-    const uint64_t waves = (uint64_t)n_ranks * 2u * (uint64_t)((1 + S + per_wave - 1) / per_wave);
+    const uint64_t waves = (uint64_t)n_ranks * (uint64_t)fams * (uint64_t)((1 + S + per_wave - 1) / per_wave);
     if (waves > 0x7FFFFFFFull) return fail(NVRX_ERR_RANGE, "n_ranks=%d x S=%d is more than one launch covers", n_ranks, S);
     return NVRX_OK;
 }
 
+template <bool PEER = false>
 int history_launch(const float *d_scores, int S, int first_rank, int n_ranks, float *d_hist, int S_cap, int H,
                    uint64_t n_before, const double *thresholds, void *d_out, hipStream_t st) {
     const int HS = NVRX_HISTORY_STRIDE(H), per_wave = 64 / HS;
@@ -150,10 +171,17 @@ int history_launch(const float *d_scores, int S, int first_rank, int n_ranks, fl
     a.S = S, a.S_cap = S_cap, a.first_rank = first_rank;
     a.H = H, a.slot0 = (int)(n_before % (uint64_t)H), a.depth = n_before + 1 < (uint64_t)H ? (int)(n_before + 1) : H;
     a.waves_per_fam = (uint32_t)((1 + S + per_wave - 1) / per_wave);
-    a.total_waves = (uint32_t)n_ranks * 2u * a.waves_per_fam;
-    for (int i = 0; i < 4; i++) a.thr[i] = thresholds ? thresholds[i] : 0.75;
+    a.total_waves = (uint32_t)n_ranks * (PEER ? 1u : 2u) * a.waves_per_fam;
+    for (int i = 0; i < 4; i++) a.thr[i] = thresholds && i < (PEER ? 2 : 4) ? thresholds[i] : 0.75;
     const dim3 grid((a.total_waves + HISTORY_THREADS / 64 - 1) / (HISTORY_THREADS / 64)), block(HISTORY_THREADS);
-    if (HS == 16)
+    if constexpr (PEER) {
+        if (HS == 16)
+            hipLaunchKernelGGL(k_peer_history<16>, grid, block, 0, st, a);
+        else if (HS == 32)
+            hipLaunchKernelGGL(k_peer_history<32>, grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL(k_peer_history<64>, grid, block, 0, st, a);
+    } else if (HS == 16)
         hipLaunchKernelGGL(k_score_history<16>, grid, block, 0, st, a);
     else if (HS == 32)
         hipLaunchKernelGGL(k_score_history<32>, grid, block, 0, st, a);

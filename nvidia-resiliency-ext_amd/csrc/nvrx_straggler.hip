@@ -3974,3 +3974,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_pace_group.inl"
 #include "nvrx_node.inl"
 #include "nvrx_work.inl"
+#include "nvrx_peer_history.inl"

@@ -26,8 +26,8 @@
 namespace {
 
 struct TrendArgs {
-    const float *hist;  // [n_ranks][2][1 + S_cap][HS]
-    uint4 *out;         // [n_ranks][2][1 + S]
+    const float *hist;  // [n_ranks][2][1 + S_cap][HS]; k_peer_trend: [n_ranks][1 + S_cap][HS]
+    uint4 *out;         // [n_ranks][2][1 + S]; k_peer_trend: [n_ranks][1 + S]
     int S, S_cap;
     int H, slot0, depth;  // slot0 = (n_reports - 1) % H, depth = min(n_reports, H)
     uint32_t waves_per_fam, total_waves;
@@ -61,8 +61,10 @@ __device__ __forceinline__ uint32_t trend_seg_sum(uint32_t v) {
     }
 }
 
+// One cell per segment.  A wave's `rf` only indexes the ring and the records, so the same code serves the peer-score ring
+// [n_ranks][1 + S_cap][HS] (k_peer_trend: one family, rf is the rank).
 template <int HS>
-__global__ __launch_bounds__(HISTORY_THREADS) void k_score_trend(TrendArgs a) {
+__device__ __forceinline__ void trend_cell(const TrendArgs &a) {
     constexpr int SPW = 64 / HS;  // slots per wave
     constexpr unsigned long long SEG = HS == 64 ? ~0ull : ((1ull << (HS & 63)) - 1ull);
     const int lane = threadIdx.x & 63;
@@ -158,8 +160,20 @@ __global__ __launch_bounds__(HISTORY_THREADS) void k_score_trend(TrendArgs a) {
     if (slot && age == 0) a.out[(size_t)rf * (size_t)(1 + S) + (size_t)j] = make_uint4(slope_bits, level, mk, p);
 }
 
-// argument checks shared by both entry points; nothing here touches a device
-int trend_check(const void *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, const void *d_out) {
+template <int HS>
+__global__ __launch_bounds__(HISTORY_THREADS) void k_score_trend(TrendArgs a) {
+    trend_cell<HS>(a);
+}
+
+// (a kernel of its own name, so that a trace tells the two rings' steps apart)
+template <int HS>
+__global__ __launch_bounds__(HISTORY_THREADS) void k_peer_trend(TrendArgs a) {
+    trend_cell<HS>(a);
+}
+
+// argument checks shared by the entry points; nothing here touches a device.  fams: 2 for the score history's ring, 1 for
+// the peer-score history's
+int trend_check(const void *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, const void *d_out, int fams = 2) {
     if (n_ranks < 1 || S < 0) return fail(NVRX_ERR_INVALID, "bad trend shape n_ranks=%d S=%d", n_ranks, S);
     if (H < 2 || H > NVRX_HISTORY_MAX_DEPTH) return fail(NVRX_ERR_RANGE, "history depth H=%d outside [2,%d]", H, NVRX_HISTORY_MAX_DEPTH);
     if (S > S_cap) return fail(NVRX_ERR_INVALID, "S=%d section ids, the history holds S_cap=%d", S, S_cap);
@@ -169,11 +183,12 @@ int trend_check(const void *d_hist, int n_ranks, int S, int S_cap, int H, uint64
     if ((reinterpret_cast<uintptr_t>(d_hist) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15u) != 0)
         return fail(NVRX_ERR_INVALID, "d_hist or d_out is not 16-byte aligned");
     const int per_wave = 64 / NVRX_HISTORY_STRIDE(H);
-    const uint64_t waves = (uint64_t)n_ranks * 2u * (uint64_t)((1 + S + per_wave - 1) / per_wave);
+    const uint64_t waves = (uint64_t)n_ranks * (uint64_t)fams * (uint64_t)((1 + S + per_wave - 1) / per_wave);
     if (waves > 0x7FFFFFFFull) return fail(NVRX_ERR_RANGE, "n_ranks=%d x S=%d is more than one launch covers", n_ranks, S);
     return NVRX_OK;
 }
 
+template <bool PEER = false>
 int trend_launch(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, void *d_out, hipStream_t st) {
     const int HS = NVRX_HISTORY_STRIDE(H), per_wave = 64 / HS;
     TrendArgs a{};
@@ -181,9 +196,16 @@ int trend_launch(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint
     a.S = S, a.S_cap = S_cap;
     a.H = H, a.slot0 = (int)((n_reports - 1) % (uint64_t)H), a.depth = n_reports < (uint64_t)H ? (int)n_reports : H;
     a.waves_per_fam = (uint32_t)((1 + S + per_wave - 1) / per_wave);
-    a.total_waves = (uint32_t)n_ranks * 2u * a.waves_per_fam;
+    a.total_waves = (uint32_t)n_ranks * (PEER ? 1u : 2u) * a.waves_per_fam;
     const dim3 grid((a.total_waves + HISTORY_THREADS / 64 - 1) / (HISTORY_THREADS / 64)), block(HISTORY_THREADS);
-    if (HS == 16)
+    if constexpr (PEER) {
+        if (HS == 16)
+            hipLaunchKernelGGL(k_peer_trend<16>, grid, block, 0, st, a);
+        else if (HS == 32)
+            hipLaunchKernelGGL(k_peer_trend<32>, grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL(k_peer_trend<64>, grid, block, 0, st, a);
+    } else if (HS == 16)
         hipLaunchKernelGGL(k_score_trend<16>, grid, block, 0, st, a);
     else if (HS == 32)
         hipLaunchKernelGGL(k_score_trend<32>, grid, block, 0, st, a);

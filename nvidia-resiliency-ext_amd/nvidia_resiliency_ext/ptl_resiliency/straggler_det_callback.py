@@ -54,6 +54,7 @@ class StragglerDetectionCallback(Callback):
         pace_peer_groups: bool = False,
         warn_if_node_off_pace: bool = False,
         node_groups=None,
+        min_consecutive_peer_reports: int = 1,
     ):
         """
         Args:
@@ -104,12 +105,20 @@ class StragglerDetectionCallback(Callback):
                 many of their GPUs are off pace.  A warning only: it never stops the job.
             node_groups: which ranks share a node, for ``warn_if_node_off_pace`` (None: the node names the detector gathers;
                 else ``"block:N"``, ``"mod:N"`` or one label per rank, as ``Detector.initialize(node_groups=...)``).
+            min_consecutive_peer_reports: 1 (the default): nothing changes.  M > 1 (needs ``peer_groups``): the relative
+                family's warning, and with ``stop_if_detected`` the halt, come only once a GPU's PEER score has been below the
+                relative threshold in M reports in a row (``Report.identify_persistent_peer_stragglers``; the detector then
+                keeps a peer history of ``max(8, M)`` reports, ``Detector.initialize(peer_history=...)``): what
+                ``min_consecutive_reports`` does for a job without peer groups.  With ``peer_groups`` use this, not
+                ``min_consecutive_reports``: the job-wide history rates every healthy rank of a slower stage low in every
+                report and would name them all from the M-th report on.
 
         Raises:
             ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64],
                 ``warn_if_waited_for``, ``warn_if_off_pace`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
                 ``min_consecutive_reports`` > 1 (the score history does not hold peer scores), or ``pace_peer_groups`` without
-                ``warn_if_off_pace`` or without ``peer_groups``, or ``warn_if_node_off_pace`` without ``calc_relative_gpu_perf``.
+                ``warn_if_off_pace`` or without ``peer_groups``, or ``warn_if_node_off_pace`` without ``calc_relative_gpu_perf``, or
+                ``min_consecutive_peer_reports`` outside [1, 64] or above 1 without ``peer_groups``.
         """
         self.initialized = False
         self.logger = logging.getLogger(logger_name)
@@ -150,6 +159,13 @@ class StragglerDetectionCallback(Callback):
             if min_consecutive_reports > 1:
                 raise ValueError("peer_groups cannot be combined with min_consecutive_reports > 1: the score history does "
                                  "not hold peer-group scores")
+        if (isinstance(min_consecutive_peer_reports, bool) or not isinstance(min_consecutive_peer_reports, int)
+                or not 1 <= min_consecutive_peer_reports <= 64):
+            raise ValueError(f"min_consecutive_peer_reports must be an integer within [1, 64], "
+                             f"got {min_consecutive_peer_reports!r}")
+        if min_consecutive_peer_reports > 1 and peer_groups is None:
+            raise ValueError("min_consecutive_peer_reports > 1 needs peer_groups: it counts reports of the peer-group scores")
+        self.min_consecutive_peer_reports = min_consecutive_peer_reports
         self.pace_peer_groups = bool(pace_peer_groups)
         if self.pace_peer_groups:
             if not self.warn_if_off_pace:
@@ -182,6 +198,10 @@ class StragglerDetectionCallback(Callback):
             persistence["collective_slack"] = True
         if self.peer_groups is not None:
             persistence["peer_groups"] = self.peer_groups
+        if self.min_consecutive_peer_reports > 1:
+            m = self.min_consecutive_peer_reports
+            persistence.update(peer_history=max(8, m), peer_persistence_min_reports=m,
+                               peer_persistence_thresholds=(self.gpu_relative_perf_threshold, 0.75))
         if self.warn_if_off_pace:
             persistence["pace_scores"] = True
         if self.pace_peer_groups:
@@ -252,9 +272,15 @@ class StragglerDetectionCallback(Callback):
         if self.peer_groups is not None:
             # the relative family's verdict: each rank against its own group
             flagged = dict(flagged)
-            flagged["straggler_gpus_relative"] = report.identify_peer_stragglers(
-                gpu_rel_threshold=self.gpu_relative_perf_threshold)["straggler_gpus_relative"]
-            texts["straggler_gpus_relative"] = "Some GPUs have worse performance than their peer group."
+            pm = self.min_consecutive_peer_reports
+            if pm > 1:
+                flagged["straggler_gpus_relative"] = report.identify_persistent_peer_stragglers()["straggler_gpus_relative"]
+                texts["straggler_gpus_relative"] = (f"Some GPUs have worse performance than their peer group for {pm} "
+                                                    "consecutive reports.")
+            else:
+                flagged["straggler_gpus_relative"] = report.identify_peer_stragglers(
+                    gpu_rel_threshold=self.gpu_relative_perf_threshold)["straggler_gpus_relative"]
+                texts["straggler_gpus_relative"] = "Some GPUs have worse performance than their peer group."
             if not self._unrated_said:
                 self._unrated_said = True
                 unrated = report.peer_scores().get("unrated_ranks", [])

@@ -108,6 +108,9 @@ SYMBOLS = [
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
+    ("nvrx_peer_history", c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double), c_void_p,
+                                  c_void_p]),
+    ("nvrx_peer_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
     ("nvrx_slack_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_work_words", c_int, [c_int, c_int, c_int]),
     ("nvrx_work_groups", c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
@@ -158,6 +161,9 @@ SYMBOLS = [
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
+    ("nvrx_report_peer_history", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
+                                         c_void_p]),
+    ("nvrx_report_peer_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
     ("nvrx_report_work", c_int, [c_void_p, POINTER(ReportDesc), c_float, c_int, c_void_p]),
     ("nvrx_slack_local", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
@@ -296,6 +302,21 @@ def history_words(n_ranks: int, S: int) -> int:
 def trend_words(n_ranks: int, S: int) -> int:
     """NVRX_TREND_WORDS: 32-bit words of a trend step's records ``[n_ranks][2][1 + S][4]``."""
     return n_ranks * 2 * (1 + S) * TREND_RECORD_WORDS
+
+
+def peer_history_floats(n_ranks: int, S_cap: int, H: int) -> int:
+    """NVRX_PEER_HISTORY_FLOATS: floats of a peer-score history ring ``[n_ranks][1 + S_cap][stride]``."""
+    return n_ranks * (1 + S_cap) * history_stride(H)
+
+
+def peer_history_words(n_ranks: int, S: int) -> int:
+    """NVRX_PEER_HISTORY_WORDS: 32-bit words of a peer-history step's records ``[n_ranks][1 + S][8]``."""
+    return n_ranks * (1 + S) * HISTORY_RECORD_WORDS
+
+
+def peer_trend_words(n_ranks: int, S: int) -> int:
+    """NVRX_PEER_TREND_WORDS: 32-bit words of a peer-trend step's records ``[n_ranks][1 + S][4]``."""
+    return n_ranks * (1 + S) * TREND_RECORD_WORDS
 
 
 def slack_words(R: int) -> int:

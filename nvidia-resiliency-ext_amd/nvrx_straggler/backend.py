@@ -408,24 +408,34 @@ class ScoreHistory:
         return max(64, -(-S // 64) * 64)
 
 
+class PeerHistory(ScoreHistory):
+    """The peer-score history of one ``ReportGenerator`` (``nvrx_peer_history`` / ``nvrx_report_peer_history``): a
+    ``ScoreHistory`` whose ring holds the peer step's scores -- one family, ``hist`` f32 ``[n_ranks][1 + S_cap][stride]`` --
+    and whose ``n_before`` counts the reports for which the peer step ran on this rank."""
+
+    __slots__ = ()
+
+
 class History:
     """The score history after one report (``nvrx_score_history`` / ``nvrx_report_history``), enqueued and not waited for: once
     the kernel has run, the workspace's device buffer holds ``[n_ranks][2][1 + S][8]`` 32-bit words ``{latest, median, worst,
     best, streak, below, present, depth}`` (include/nvrx_straggler.h).  ``records()`` waits for it and takes the private host
     copy (one ordered D2H on the backend's stream): when a ``Report`` first asks, or -- ``Workspace.history_settle`` --
-    before the next report on the same workspace rewrites the block the kernel read and the buffer it wrote."""
+    before the next report on the same workspace rewrites the block the kernel read and the buffer it wrote.  ``fams``: 2, or
+    1 for the peer-score history (``nvrx_peer_history``: ``[n_ranks][1][1 + S][8]``, settled by
+    ``Workspace.peer_history_settle``)."""
 
-    __slots__ = ("backend", "d_ptr", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
+    __slots__ = ("backend", "d_ptr", "S", "first_rank", "n_ranks", "fams", "_host", "_lock", "_keep")
 
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, S: int, first_rank: int, n_ranks: int):
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, S: int, first_rank: int, n_ranks: int, fams: int = 2):
         self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.S, self.first_rank, self.n_ranks = S, first_rank, n_ranks
+        self.S, self.first_rank, self.n_ranks, self.fams = S, first_rank, n_ranks, fams
         self._host = None
         self._lock = threading.Lock()
         self._keep = buf  # the device buffer lives at least until the copy is taken
 
     def records(self) -> np.ndarray:
-        """``[n_ranks, 2, 1 + S, 8]`` uint32 (private copy); the first call waits for the kernel."""
+        """``[n_ranks, fams, 1 + S, 8]`` uint32 (private copy); the first call waits for the kernel."""
         if self._host is None:
             with self._lock:
                 if self._host is None:
@@ -439,19 +449,20 @@ class Trend:
     kernel has run, the workspace's device buffer holds ``[n_ranks][2][1 + S][4]`` 32-bit words ``{slope, level, S, usable}``
     (include/nvrx_straggler.h).  ``records()`` waits for it and takes the private host copy (one ordered D2H on the backend's
     stream): when a ``Report`` first asks, or -- ``Workspace.trend_settle`` -- before the next trend step on the same
-    workspace rewrites the buffer."""
+    workspace rewrites the buffer.  ``fams``: 2, or 1 for the peer-score trends (``nvrx_peer_trend``: ``[n_ranks][1][1 + S][4]``,
+    settled by ``Workspace.peer_trend_settle``)."""
 
-    __slots__ = ("backend", "d_ptr", "S", "n_ranks", "_host", "_lock", "_keep")
+    __slots__ = ("backend", "d_ptr", "S", "n_ranks", "fams", "_host", "_lock", "_keep")
 
-    def __init__(self, backend: "HipBackend", buf: torch.Tensor, S: int, n_ranks: int):
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, S: int, n_ranks: int, fams: int = 2):
         self.backend, self.d_ptr = backend, buf.data_ptr()
-        self.S, self.n_ranks = S, n_ranks
+        self.S, self.n_ranks, self.fams = S, n_ranks, fams
         self._host = None
         self._lock = threading.Lock()
         self._keep = buf  # the device buffer lives at least until the copy is taken
 
     def records(self) -> np.ndarray:
-        """``[n_ranks, 2, 1 + S, 4]`` uint32 (private copy); the first call waits for the kernel."""
+        """``[n_ranks, fams, 1 + S, 4]`` uint32 (private copy); the first call waits for the kernel."""
         if self._host is None:
             with self._lock:
                 if self._host is None:
@@ -699,6 +710,10 @@ class Workspace:
             self.history_settle()
         if self._trend_last is not None:
             self.trend_settle()
+        if self._peer_history_last is not None:
+            self.peer_history_settle()
+        if self._peer_trend_last is not None:
+            self.peer_trend_settle()
         if self._slack_last is not None:
             self.slack_settle()
         if self._work_last is not None:
@@ -832,6 +847,42 @@ class Workspace:
         """Before anything rewrites the trend records buffer: the last trend step's kernel has run and its records are on
         the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
         last, self._trend_last = self._trend_last, None
+        if last is not None:
+            last.records()
+
+    # ---- peer-score history and trends (off unless a ReportGenerator asks: nothing is allocated before) ------------
+    _peer_history_buf = None   # device: the records of the last peer-history step issued through this workspace
+    _peer_history_last = None  # the History whose kernel may still be reading the peer slot / writing _peer_history_buf
+    _peer_trend_buf = None     # device: the records of the last peer-trend step issued through this workspace
+    _peer_trend_last = None    # the Trend whose kernel may still be writing _peer_trend_buf
+
+    def _records_buffer(self, attr: str, words: int):
+        buf = getattr(self, attr)
+        if buf is None or buf.numel() < words:
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                buf = torch.empty(max(words, 64), dtype=torch.int32, device=self._backend.device)
+            setattr(self, attr, buf)
+        return buf
+
+    def peer_history_buffers(self, n_ranks: int):
+        """The records buffer for a peer-history step over ``n_ranks`` ranks (cold: allocated once per shape)."""
+        return self._records_buffer("_peer_history_buf", _native.peer_history_words(n_ranks, self.S))
+
+    def peer_history_settle(self) -> None:
+        """Before anything rewrites the peer slot's block or the records buffer: the last peer-history step's kernel has run
+        and its records are on the host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._peer_history_last = self._peer_history_last, None
+        if last is not None:
+            last.records()
+
+    def peer_trend_buffers(self, n_ranks: int):
+        """The records buffer for a peer-trend step over ``n_ranks`` ranks (cold: allocated once per shape)."""
+        return self._records_buffer("_peer_trend_buf", _native.peer_trend_words(n_ranks, self.S))
+
+    def peer_trend_settle(self) -> None:
+        """Before anything rewrites the peer-trend records buffer: the last step's kernel has run and its records are on the
+        host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
+        last, self._peer_trend_last = self._peer_trend_last, None
         if last is not None:
             last.records()
 
@@ -1158,7 +1209,7 @@ class HipBackend:
 
     def history_copy_out(self, h: History) -> np.ndarray:
         """The one wait of a report's score history: a D2H of the records on the backend's stream, behind the kernel."""
-        host = np.empty((h.n_ranks, 2, 1 + h.S, _native.HISTORY_RECORD_WORDS), dtype=np.uint32)
+        host = np.empty((h.n_ranks, h.fams, 1 + h.S, _native.HISTORY_RECORD_WORDS), dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, h.d_ptr, host.nbytes, self._stream_handle))
         return host
 
@@ -1178,9 +1229,61 @@ class HipBackend:
 
     def trend_copy_out(self, t: Trend) -> np.ndarray:
         """The one wait of a report's score trends: a D2H of the records on the backend's stream, behind the kernel."""
-        host = np.empty((t.n_ranks, 2, 1 + t.S, _native.TREND_RECORD_WORDS), dtype=np.uint32)
+        host = np.empty((t.n_ranks, t.fams, 1 + t.S, _native.TREND_RECORD_WORDS), dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, host.nbytes, self._stream_handle))
         return host
+
+    def _peer_history_step(self, ws: Workspace, state: PeerHistory, peer: TableScores, thresholds, entry, head: tuple,
+                           tail: tuple) -> History:
+        """What both routes of a peer-history step share: the ring of ``state`` with room for this workspace's section ids
+        (cold: allocated -- every word a NaN -- or grown on the backend's stream, the old entries copied by slicing), the
+        records buffer settled, ``entry(*head, the rank part of ``peer``'s block, shape, ring, thresholds, d_out, *tail)`` and
+        the handle noted in the workspace.  ``peer`` is the handle of the peer step just issued on ``ws``: its block sits in
+        the workspace's peer slot, which nothing settles or rewrites between that step and this one."""
+        first_rank, n_ranks = peer.first_rank, peer.n_ranks
+        state.begin(first_rank, n_ranks)
+        if state.hist is None or ws.S > state.S_cap:
+            cap = ScoreHistory.capacity(ws.S)
+            with torch.cuda.stream(self.stream):  # (allocated, written and read under the backend's stream)
+                ring = torch.full((n_ranks, 1 + cap, 4 * state.stride), 0xFF, dtype=torch.uint8,
+                                  device=self.device).view(torch.float32)
+                if state.hist is not None:
+                    ring[:, : 1 + state.S_cap] = state.hist
+            state.hist, state.S_cap = ring, cap
+        ws.peer_history_settle()
+        thr = tuple(float(t) for t in thresholds)
+        if len(thr) != 2:
+            raise ValueError(f"a peer-score history takes two thresholds (gpu, section), got {thresholds!r}")
+        buf = ws.peer_history_buffers(n_ranks)
+        d_peer = peer.d_ptr + 16 * peer.G * (peer.K + peer.S)  # behind the G (K+S) column records of 16 bytes
+        rc = entry(*head, d_peer, n_ranks, ws.S, state.hist.data_ptr(), state.S_cap, state.depth, state.n_before,
+                   (ctypes.c_double * 2)(*thr), buf.data_ptr(), *tail)
+        if rc < 0:
+            _native.check(rc)
+        state.n_before += 1
+        out = ws._peer_history_last = History(self, buf, ws.S, first_rank, n_ranks, fams=1)
+        return out
+
+    def peer_history(self, ws: Workspace, state: PeerHistory, peer: TableScores,
+                     thresholds: Sequence[float] = (0.75, 0.75)) -> History:
+        """Append the peer scores ``peer_score`` just left in ``ws``'s peer slot (``peer``: that step's handle) to ``state``'s
+        ring: ``nvrx_peer_history`` enqueued on the backend's stream directly behind that step.  Nothing is waited for."""
+        return self._peer_history_step(ws, state, peer, thresholds, self.lib.nvrx_peer_history, (), (self._stream_handle,))
+
+    def _peer_trend_step(self, ws: Workspace, state: PeerHistory, entry, head: tuple, tail: tuple) -> Trend:
+        ws.peer_trend_settle()
+        n_ranks = state.ranks[1]
+        buf = ws.peer_trend_buffers(n_ranks)
+        rc = entry(*head, state.hist.data_ptr(), n_ranks, ws.S, state.S_cap, state.depth, state.n_before, buf.data_ptr(), *tail)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._peer_trend_last = Trend(self, buf, ws.S, n_ranks, fams=1)
+        return out
+
+    def peer_trend(self, ws: Workspace, state: PeerHistory) -> Trend:
+        """The trends of ``state``'s ring as the peer-history step just issued on ``ws`` leaves it (``state.n_before`` counts
+        that report): ``nvrx_peer_trend`` enqueued on the backend's stream behind that step.  Nothing is waited for."""
+        return self._peer_trend_step(ws, state, self.lib.nvrx_peer_trend, (), (self._stream_handle,))
 
     def _work_step(self, ws: Workspace, entry, head: tuple, tail: tuple, count_tol: float, max_unlike_ppm: int) -> Work:
         """What both routes of the work-group step share: the slot settled, its block, ``entry(*head, count_tol,
@@ -1600,6 +1703,18 @@ class HipRings:
             _native.check(rc)
         out = ws._trend_last = Trend(be, buf, ws.S, n_ranks)
         return out
+
+    def report_peer_history(self, ws: Workspace, state: PeerHistory, peer: TableScores,
+                            thresholds: Sequence[float] = (0.75, 0.75)) -> History:
+        """Append the peer scores ``report_peer`` just left in ``ws``'s peer slot (``peer``: that step's handle) to ``state``'s
+        ring (``nvrx_report_peer_history``): enqueued on the context's stream directly behind that step, nothing is waited
+        for."""
+        return self.backend._peer_history_step(ws, state, peer, thresholds, self.lib.nvrx_report_peer_history, (self.ctx,), ())
+
+    def report_peer_trend(self, ws: Workspace, state: PeerHistory) -> Trend:
+        """The trends of ``state``'s ring as ``report_peer_history`` just left it (``nvrx_report_peer_trend``): enqueued on the
+        context's stream behind that step, nothing is waited for."""
+        return self.backend._peer_trend_step(ws, state, self.lib.nvrx_report_peer_trend, (self.ctx,), ())
 
     _slack_list = None  # (len(kernel_row_names), rows int32, columns int32, {column: keys}): names are only ever added
 

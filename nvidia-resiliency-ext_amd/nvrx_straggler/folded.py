@@ -36,7 +36,8 @@ class FoldedJob:
                  pace_min_breadth: float = 0.9, pace_peer_groups: bool = False, node_scores: bool = False, node_groups=None,
                  node_min_members: int = 2, node_min_nodes: int = 3, node_min_columns: int = 8, node_min_effect: float = 0.03,
                  node_min_breadth: float = 0.9, node_min_agree: float = 0.75, work_groups: bool = False,
-                 work_count_tol: float = 0.25, work_max_unlike: float = 0.1):
+                 work_count_tol: float = 0.25, work_max_unlike: float = 0.1, peer_history: int = 0,
+                 peer_persistence_min_reports: int = 3, peer_persistence_thresholds=None, peer_trends: bool = False):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -66,6 +67,10 @@ class FoldedJob:
                                         pace_min_ranks=pace_min_ranks, pace_min_columns=pace_min_columns,
                                         pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth,
                                         **({"pace_peer_groups": True} if pace_peer_groups else {}),
+                                        **({"peer_history": peer_history,
+                                            "peer_persistence_min_reports": peer_persistence_min_reports,
+                                            "peer_persistence_thresholds": peer_persistence_thresholds,
+                                            "peer_trends": peer_trends} if peer_history or peer_trends else {}),
                                         **({"node_scores": True, "node_groups": node_groups,
                                             "node_min_members": node_min_members, "node_min_nodes": node_min_nodes,
                                             "node_min_columns": node_min_columns, "node_min_effect": node_min_effect,

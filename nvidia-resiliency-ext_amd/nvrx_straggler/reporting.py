@@ -1011,16 +1011,32 @@ class _HistorySource:
 
             built: Dict[str, Any] = {"depth": int(rec[0, 0, 0, 7]) if rec.size else 0, "capacity": self.capacity,
                                      "min_reports": self.min_reports, "thresholds": self.thresholds}
-            for fam, name in _HISTORY_FAMILIES:
-                if self.has_rel if fam else self.has_indiv:
-                    built["gpu_" + name] = {r: record(i, fam, 0) for i, r in enumerate(ranks)}
-            for fam, name in _HISTORY_FAMILIES:
-                if self.has_rel if fam else self.has_indiv:
-                    built["section_" + name] = {n: {r: record(i, fam, 1 + g) for i, r in enumerate(ranks)}
-                                                for n, g in self.sections.items()}
+            families = self.families()
+            for fam, name in families:
+                built["gpu_" + name] = {r: record(i, fam, 0) for i, r in enumerate(ranks)}
+            for fam, name in families:
+                built["section_" + name] = {n: {r: record(i, fam, 1 + g) for i, r in enumerate(ranks)}
+                                            for n, g in self.sections.items()}
             self._built = built
             self.handle = None
         return self._built
+
+    def families(self):
+        """``(family index of the records, name)`` of the families the report shows, in the order the mappings are listed."""
+        return [(fam, name) for fam, name in _HISTORY_FAMILIES if (self.has_rel if fam else self.has_indiv)]
+
+
+class _PeerHistorySource(_HistorySource):
+    """``_HistorySource`` for the peer-score history: the records hold one family, the relative one, and the thresholds are
+    ``(gpu, section)``."""
+
+    __slots__ = ()
+
+    def __init__(self, handle, ranks, sections, capacity: int, min_reports: int, thresholds):
+        super().__init__(handle, ranks, sections, True, False, capacity, min_reports, thresholds)
+
+    def families(self):
+        return [(0, "relative")]
 
 
 class _TrendSource:
@@ -1064,19 +1080,34 @@ class _TrendSource:
 
             built: Dict[str, Any] = {"depth": self.depth, "min_reports": min_reports, "min_tau": min_tau,
                                      "horizon": self.horizon, "thresholds": self.thresholds}
-            g_rel, s_rel, g_ind, s_ind = self.thresholds
-            for fam, name in _HISTORY_FAMILIES:
-                if self.has_rel if fam else self.has_indiv:
-                    thr = g_rel if fam else g_ind
-                    built["gpu_" + name] = {r: record(i, fam, 0, thr) for i, r in enumerate(ranks)}
-            for fam, name in _HISTORY_FAMILIES:
-                if self.has_rel if fam else self.has_indiv:
-                    thr = s_rel if fam else s_ind
-                    built["section_" + name] = {n: {r: record(i, fam, 1 + g, thr) for i, r in enumerate(ranks)}
-                                                for n, g in self.sections.items()}
+            families = self.families()
+            for fam, name, thr, _ in families:
+                built["gpu_" + name] = {r: record(i, fam, 0, thr) for i, r in enumerate(ranks)}
+            for fam, name, _, thr in families:
+                built["section_" + name] = {n: {r: record(i, fam, 1 + g, thr) for i, r in enumerate(ranks)}
+                                            for n, g in self.sections.items()}
             self._built = built
             self.handle = None
         return self._built
+
+    def families(self):
+        """``(family index of the records, name, GPU threshold, section threshold)`` of the families the report shows."""
+        g_rel, s_rel, g_ind, s_ind = self.thresholds
+        return [(fam, name, g_rel if fam else g_ind, s_rel if fam else s_ind) for fam, name in _HISTORY_FAMILIES
+                if (self.has_rel if fam else self.has_indiv)]
+
+
+class _PeerTrendSource(_TrendSource):
+    """``_TrendSource`` for the peer-score trends: the records hold one family, the relative one, and the thresholds are
+    ``(gpu, section)``.  The records and the rule are ``_TrendSource``'s."""
+
+    __slots__ = ()
+
+    def __init__(self, handle, ranks, sections, depth: int, min_reports: int, min_tau: float, horizon: int, thresholds):
+        super().__init__(handle, ranks, sections, True, False, depth, min_reports, min_tau, horizon, thresholds)
+
+    def families(self):
+        return [(0, "relative") + self.thresholds]
 
 
 class _SlackSource:
@@ -1265,6 +1296,10 @@ class Report:
         trends = self.__dict__.get("_trends")
         if trends is not None:
             state["_trends"] = trends.build() if isinstance(trends, _TrendSource) else trends
+        for key, source in (("_peer_history", _HistorySource), ("_peer_trends", _TrendSource)):
+            held = self.__dict__.get(key)
+            if held is not None:
+                state[key] = held.build() if isinstance(held, source) else held
         slack = self.__dict__.get("_slack")
         if slack is not None:
             state["_slack"] = slack.build() if isinstance(slack, _SlackSource) else slack
@@ -1591,7 +1626,10 @@ class Report:
         (default: the generator's ``persistence_min_reports``): the four keys of ``identify_stragglers``, ``StragglerId``
         sets; a section appears only if somebody is flagged for it.  One slow window flags nobody here.  Empty sets when
         the report carries no score history."""
-        t = self.score_history()
+        return self._identify_persistent(self.score_history(), min_reports)
+
+    def _identify_persistent(self, t, min_reports) -> Dict[str, Any]:
+        """The streak rule on a history ``t`` (``score_history()`` or ``peer_history()``): the four keys."""
         m = t.get("min_reports", 1) if min_reports is None else min_reports
         if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
             raise ValueError(f"min_reports must be an integer >= 1, got {min_reports!r}")
@@ -1637,7 +1675,10 @@ class Report:
         ``identify_stragglers``, ``StragglerId`` sets; a section appears only if somebody is flagged for it.  A warning, ahead
         of ``identify_stragglers``: a rank named here may still be above its threshold.  Empty sets when the report carries
         no score trends."""
-        t = self.score_trends()
+        return self._identify_declining(self.score_trends(), horizon)
+
+    def _identify_declining(self, t, horizon) -> Dict[str, Any]:
+        """The horizon rule on trends ``t`` (``score_trends()`` or ``peer_trends()``): the four keys."""
         h = t.get("horizon", 0) if horizon is None else horizon
         if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < 0:
             raise ValueError(f"horizon must be an integer >= 0, got {horizon!r}")
@@ -1655,6 +1696,48 @@ class Report:
         return {"straggler_gpus_relative": gpus("gpu_relative"), "straggler_gpus_individual": gpus("gpu_individual"),
                 "straggler_sections_relative": sections("section_relative"),
                 "straggler_sections_individual": sections("section_individual")}
+
+    def _held(self, key: str, source) -> Dict[str, Any]:
+        held = self.__dict__.get(key)
+        if held is None:
+            return {}
+        if isinstance(held, source):
+            held = self.__dict__[key] = held.build()
+        return _copy_scores(held)
+
+    def peer_history(self) -> Dict[str, Any]:
+        """The history of the PEER scores as it stood after this report (``ReportGenerator(peer_groups=..., peer_history=H)``;
+        ``{}`` when the report carries none): ``score_history()`` for ``peer_scores()``.  In a job whose ranks legitimately
+        differ the job-wide history rates every rank of a slower stage low in every report; this one looks, across reports,
+        at each rank against the ranks doing the same work.
+
+        ``{"depth", "capacity": H, "min_reports": M, "thresholds": (gpu, section), "gpu_relative": {rank: rec},
+        "section_relative": {section: {rank: rec}}}`` with ``rec`` as ``score_history()`` spells it.  A report in which a rank
+        was unrated (alone in its group, a section its group has no reference for) is a report without the score: it ends the
+        streak.  The history is per rank, whatever the rank's group was in each report: it does not notice that a rank's
+        peers changed between reports (``peer_groups="auto"``).  The first call waits for the kernel and copies its records;
+        ``generate_report`` does not."""
+        return self._held("_peer_history", _HistorySource)
+
+    def identify_persistent_peer_stragglers(self, min_reports: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks whose PEER score has been strictly below its threshold for the last ``min_reports`` reports IN A ROW, this
+        one included (default: the generator's ``peer_persistence_min_reports``): the two keys of
+        ``identify_peer_stragglers``.  Empty sets when the report carries no peer history."""
+        out = self._identify_persistent(self.peer_history(), min_reports)
+        return {key: out[key] for key in ("straggler_gpus_relative", "straggler_sections_relative")}
+
+    def peer_trends(self) -> Dict[str, Any]:
+        """Whether each PEER score is falling from report to report (``ReportGenerator(peer_history=H, peer_trends=True)``;
+        ``{}`` when the report carries none): ``score_trends()`` for the peer history, with ``"thresholds": (gpu, section)``
+        and the relative family only.  Records and rule are those of ``score_trends()``."""
+        return self._held("_peer_trends", _TrendSource)
+
+    def identify_declining_peer_stragglers(self, horizon: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks whose PEER score is falling and whose trend line crosses the threshold within ``horizon`` reports (default:
+        the generator's ``trend_horizon``, else ``peer_history``): the two keys of ``identify_peer_stragglers``.  Empty sets
+        when the report carries no peer trends."""
+        out = self._identify_declining(self.peer_trends(), horizon)
+        return {key: out[key] for key in ("straggler_gpus_relative", "straggler_sections_relative")}
 
     def slack_scores(self) -> Dict[str, Any]:
         """Whom the job WAITS FOR in collectives (``ReportGenerator(collective_slack=True)``; ``{}`` when the report carries
@@ -1900,7 +1983,9 @@ class ReportGenerator:
                  score_trends: bool = False, trend_min_reports: int = 6, trend_min_tau: float = 0.6,
                  trend_horizon: Optional[int] = None, collective_slack: bool = False, slack_min_ranks: int = 4,
                  slack_min_share: float = 0.05, slack_max_ratio: float = 0.25, peer_groups=None,
-                 peer_min_ranks: int = 2, pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8,
+                 peer_min_ranks: int = 2, peer_history: int = 0, peer_persistence_min_reports: int = 3,
+                 peer_persistence_thresholds: Optional[Sequence[float]] = None, peer_trends: bool = False,
+                 pace_scores: bool = False, pace_min_ranks: int = 4, pace_min_columns: int = 8,
                  pace_min_effect: float = 0.03, pace_min_breadth: float = 0.9, pace_peer_groups: bool = False,
                  node_scores: bool = False, node_groups=None, node_min_members: int = 2, node_min_nodes: int = 3,
                  node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
@@ -2226,6 +2311,61 @@ class ReportGenerator:
                 raise RuntimeError(f"score_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no score trends (backend.score_trend)")
             self.trend_min_reports, self.trend_min_tau, self.trend_horizon = int(m), tau, int(hz)
+        # peer-score history and trends: the two options above on the PEER scores (Report.peer_history,
+        # Report.identify_persistent_peer_stragglers, Report.peer_trends, Report.identify_declining_peer_stragglers); 0 = off:
+        # no buffer, no launch, no backend call.  The step runs directly behind the peer step and reads its rank part where
+        # that step wrote it: no collective.  The history is per rank: it does not notice that a rank's peers changed.
+        self._peer_history = None  # (backend.PeerHistory while the option is on)
+        depth = peer_history
+        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not (
+                depth == 0 or 2 <= depth <= _backend_mod._native.HISTORY_MAX_DEPTH):
+            raise ValueError(f"peer_history must be 0 (off) or an integer within [2, {_backend_mod._native.HISTORY_MAX_DEPTH}] "
+                             f"reports, got {peer_history!r}")
+        self.peer_history = int(depth)
+        if self.peer_history:
+            if self.peer_groups is None:
+                raise ValueError("peer_history needs peer_groups: it is the history of the peer-group scores")
+            m = peer_persistence_min_reports
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= self.peer_history:
+                raise ValueError(f"peer_persistence_min_reports must be an integer within [1, peer_history={self.peer_history}], "
+                                 f"got {peer_persistence_min_reports!r}")
+            try:
+                thr = (0.75, 0.75) if peer_persistence_thresholds is None else tuple(float(t) for t in peer_persistence_thresholds)
+            except (TypeError, ValueError):
+                thr = ()
+            if len(thr) != 2 or not all(np.isfinite(thr)):
+                raise ValueError(f"peer_persistence_thresholds must be two finite numbers (gpu, section), "
+                                 f"got {peer_persistence_thresholds!r}")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "peer_history"):
+                raise RuntimeError(f"peer_history: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no peer-score history (backend.peer_history)")
+            self.peer_persistence_min_reports, self.peer_persistence_thresholds = int(m), thr
+            self._peer_history = _backend_mod.PeerHistory(self.peer_history)
+        self.peer_trends = bool(peer_trends)
+        if self.peer_trends:
+            if self.peer_history < 4:
+                raise ValueError(f"peer_trends needs a peer history of at least 4 reports (peer_history within [4, "
+                                 f"{_backend_mod._native.HISTORY_MAX_DEPTH}]), got peer_history={self.peer_history!r}")
+            m = trend_min_reports
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 4 <= m <= self.peer_history:
+                raise ValueError(f"trend_min_reports must be an integer within [4, peer_history={self.peer_history}], "
+                                 f"got {trend_min_reports!r}")
+            try:
+                tau = float(trend_min_tau)
+            except (TypeError, ValueError):
+                tau = float("nan")
+            if isinstance(trend_min_tau, bool) or not 0.0 < tau <= 1.0:
+                raise ValueError(f"trend_min_tau must be a number within (0, 1], got {trend_min_tau!r}")
+            hz = self.peer_history if trend_horizon is None else trend_horizon
+            if isinstance(hz, bool) or not isinstance(hz, (int, np.integer)) or hz < 0:
+                raise ValueError(f"trend_horizon must be None (the history's depth) or an integer >= 0 reports, "
+                                 f"got {trend_horizon!r}")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "peer_trend"):
+                raise RuntimeError(f"peer_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no peer-score trends (backend.peer_trend)")
+            self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon = int(m), tau, int(hz)
         # slack scores: every ring report also says whom the job waits for in collectives (Report.slack_scores,
         # Report.identify_slack_stragglers) from the statistics of the collective kernels' rows, which every other score drops;
         # off: no buffer, no launch, no collective, no backend call.  The step adds one collective per report, so EVERY rank
@@ -2507,8 +2647,11 @@ class ReportGenerator:
         if self.peer_groups is not None:
             # likewise, behind the robust step
             groups = self._peer_for(ws)
-            self._attach_peer(report, _backend_mod.get_backend().peer_score(
-                ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks), groups, ws, mapper, view)
+            handle = _backend_mod.get_backend().peer_score(ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks)
+            self._attach_peer(report, handle, groups, ws, mapper, view)
+            if self._peer_history is not None:
+                # ... and the history of the peer scores, directly behind the step that left them
+                self._attach_peer_history(report, ws, handle, view, None)
         if self.pace_scores:
             # likewise, behind the robust and peer steps
             if self.pace_peer_groups:
@@ -2687,6 +2830,10 @@ class ReportGenerator:
             raise RuntimeError("pace_scores: these rings run the one-call report but have no report_pace")
         if fused and self.node_scores and not hasattr(rings, "report_node"):
             raise RuntimeError("node_scores: these rings run the one-call report but have no report_node")
+        if fused and self._peer_history is not None and not hasattr(rings, "report_peer_history"):
+            raise RuntimeError("peer_history: these rings run the one-call report but have no report_peer_history")
+        if fused and self.peer_trends and not hasattr(rings, "report_peer_trend"):
+            raise RuntimeError("peer_trends: these rings run the one-call report but have no report_peer_trend")
         if fused and self._history is not None and not hasattr(rings, "report_history"):
             raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
         if fused and self.score_trends and not hasattr(rings, "report_trend"):
@@ -2863,6 +3010,27 @@ class ReportGenerator:
         else:
             handle = _backend_mod.get_backend().peer_score(ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks)
         self._attach_peer(report, handle, groups, ws, plan.mapper, plan.view)
+        if self._peer_history is not None:
+            self._attach_peer_history(report, ws, handle, plan.view, rings if fused else None)
+
+    def _attach_peer_history(self, report, ws, peer, view, rings) -> None:
+        """Enqueue the peer-history step -- and the peer-trend step behind it -- directly behind the peer step ``peer`` just
+        issued on ``ws``, on the stream that step used (``rings``: the one-call report's, else the backend's), and hang them
+        on ``report``.  Nothing is waited for.  Called once per report for which the peer step ran on this rank, and never
+        otherwise: that is what the history's ``n_before`` counts."""
+        state, be = self._peer_history, _backend_mod.get_backend()
+        thr = self.peer_persistence_thresholds
+        if rings is not None:
+            handle = rings.report_peer_history(ws, state, peer, thr)
+        else:
+            handle = be.peer_history(ws, state, peer, thr)
+        report.__dict__["_peer_history"] = _PeerHistorySource(handle, view.ranks, view.cols, self.peer_history,
+                                                              self.peer_persistence_min_reports, thr)
+        if self.peer_trends:
+            handle = rings.report_peer_trend(ws, state) if rings is not None else be.peer_trend(ws, state)
+            report.__dict__["_peer_trends"] = _PeerTrendSource(handle, view.ranks, view.cols,
+                                                               min(state.n_before, self.peer_history), self.trend_min_reports,
+                                                               self.trend_min_tau, self.peer_trend_horizon, thr)
 
     # ---- pace scores --------------------------------------------------------------------------------
     def _pace_min(self, ws) -> int:
@@ -2973,9 +3141,11 @@ class ReportGenerator:
 
     def reset_score_history(self) -> None:
         """Forget the score history: the next report starts a new one (after a restart from a checkpoint, a change of the
-        job's layout, a node swap).  Reports already handed out keep theirs."""
+        job's layout, a node swap) -- and so does the peer-score history.  Reports already handed out keep theirs."""
         if self._history is not None:
             self._history.reset()
+        if self._peer_history is not None:
+            self._peer_history.reset()
 
     # ---- row families: tail, onset, period, episode scores ------------------------------------------
     def _family_step(self, fam, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:

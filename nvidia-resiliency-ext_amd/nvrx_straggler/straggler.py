@@ -435,6 +435,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
         slack_max_ratio: float = 0.25,
         peer_groups=None,
         peer_min_ranks: Optional[int] = None,
+        peer_history: Optional[int] = None,
+        peer_persistence_min_reports: Optional[int] = None,
+        peer_persistence_thresholds: Optional[Sequence[float]] = None,
+        peer_trends: Optional[bool] = None,
         pace_scores: Optional[bool] = None,
         pace_min_ranks: int = 4,
         pace_min_columns: int = 8,
@@ -561,6 +565,21 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 value on every rank (no collective depends on it).
             peer_min_ranks: ranks of a group that must have a section or kernel for the group to have a reference; at the
                 default of 2 (``NVRX_PEER_MIN_RANKS``) a rank alone in its group has no peer and is unrated, not rated 1.0.
+            peer_history: 0 = off; H in 2..64: ``score_history`` for the PEER scores -- every report also appends its peer scores
+                to a history of the last H reports (``Report.peer_history()``,
+                ``Report.identify_persistent_peer_stragglers()``).  In a job with peer groups the job-wide history names every
+                healthy rank of a slower stage; this one names the rank that stays slower than its peers.  Needs
+                ``peer_groups``.  A rank unrated in a report (alone in its group) has no entry for it, which ends its streak;
+                the history is per rank and does not notice that a rank's peers changed between reports
+                (``peer_groups="auto"``).  Default: ``NVRX_PEER_HISTORY``, else 0.
+            peer_persistence_min_reports: the streak that makes a rank persistently slower than its peers, within
+                [1, peer_history].  Default: ``NVRX_PEER_PERSISTENCE_MIN_REPORTS``, else 3 (never more than ``peer_history``).
+            peer_persistence_thresholds: (gpu, section) a peer score has to be strictly below; default 0.75 each, as
+                ``identify_peer_stragglers``.
+            peer_trends: ``score_trends`` for the peer scores (``Report.peer_trends()``,
+                ``Report.identify_declining_peer_stragglers()``), by ``trend_min_reports``, ``trend_min_tau`` and
+                ``trend_horizon`` (None = ``peer_history``).  Needs ``peer_history`` >= 4.  Default: ``NVRX_PEER_TRENDS`` (set
+                and not "0"), else off.
             pace_scores: every report also says whether a rank is a LITTLE slower in nearly ALL of its kernels -- a card held a
                 clock step down, a throttling HBM stack, a marginal power rail: 3-5 % on every kernel, which no threshold on
                 one row sees (``Report.pace_scores()``, ``Report.identify_pace_stragglers()``).  Needs
@@ -672,6 +691,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
             score_trends = os.environ.get("NVRX_SCORE_TRENDS", "0") not in ("", "0")
         if collective_slack is None:
             collective_slack = os.environ.get("NVRX_COLLECTIVE_SLACK", "0") not in ("", "0")
+        trend_min_reports_defaulted = trend_min_reports is None
         if trend_min_reports is None:
             trend_min_reports = 6
             if isinstance(score_history, int) and 4 <= score_history < 6:
@@ -686,6 +706,27 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 except ValueError:
                     raise ValueError("NVRX_PEER_MIN_RANKS must be an integer >= 1") from None
             peer_options = {"peer_groups": peer_groups, "peer_min_ranks": peer_min_ranks}
+        if peer_history is None:
+            try:
+                peer_history = int(os.environ.get("NVRX_PEER_HISTORY", "0") or 0)
+            except ValueError:
+                raise ValueError("NVRX_PEER_HISTORY must be an integer: 0 (off) or 2..64 reports") from None
+        if peer_trends is None:
+            peer_trends = os.environ.get("NVRX_PEER_TRENDS", "0") not in ("", "0")
+        if peer_history or peer_trends:  # (off: the generator is built exactly as before)
+            if peer_persistence_min_reports is None:
+                from_env = os.environ.get("NVRX_PEER_PERSISTENCE_MIN_REPORTS", "")
+                if from_env:
+                    try:
+                        peer_persistence_min_reports = int(from_env)
+                    except ValueError:
+                        raise ValueError("NVRX_PEER_PERSISTENCE_MIN_REPORTS must be an integer within [1, NVRX_PEER_HISTORY]") from None
+                else:
+                    peer_persistence_min_reports = 2 if peer_history == 2 else 3  # (two reports cannot hold a streak of three)
+            if peer_trends and trend_min_reports_defaulted and isinstance(peer_history, int) and 4 <= peer_history < trend_min_reports:
+                trend_min_reports = peer_history  # (a history of four reports cannot hold six)
+            peer_options.update(peer_history=peer_history, peer_persistence_min_reports=peer_persistence_min_reports,
+                                peer_persistence_thresholds=peer_persistence_thresholds, peer_trends=peer_trends)
         work_options = {}  # (off: the generator is built exactly as before)
         if work_groups is None:
             from_env = os.environ.get("NVRX_WORK_GROUPS", "")
