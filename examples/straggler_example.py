@@ -375,6 +375,57 @@ def slack(ranks: int = 8, calls: int = 200, late_rank: int = 5, late_us: float =
         job.close()
 
 
+def slack_peer(calls: int = 200, late_rank: int = 5, late_us: float = 300.0) -> None:
+    """A pipeline job of two stages (2 + 6 ranks) whose waits in collectives differ per stage, and a rank of the second stage
+    whose host is slow: whom the job-wide slack rule names, and whom the rule per peer group does."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    stage = np.array([0, 0, 1, 1, 1, 1, 1, 1])
+    ranks = stage.size
+    gemm, allreduce = "gemm_kernel<bf16>", "ncclDevKernel_AllReduce_Sum_bf16_RING_LL(ncclDevKernelArgsStorage<4096ul>)"
+    sendrecv = "ncclDevKernel_SendRecv(ncclDevKernelArgsStorage<4096ul>)"
+    rng = np.random.default_rng(17)
+    transfer = 200.0 * (1.0 + 0.02 * rng.standard_normal(calls))
+    arrival = rng.exponential(20.0, (ranks, calls))
+    noise = rng.standard_normal((ranks, calls))
+    arrival[late_rank] += late_us
+    # the all-reduce is stage-local: a rank waits for the last one OF ITS STAGE; the send / receive bubble differs per stage
+    last = np.stack([arrival[stage == stage[r]].max(0) for r in range(ranks)])
+    in_allreduce = transfer[None, :] + last - arrival
+    bubble = np.array([60.0, 420.0])[stage][:, None] * (1.0 + 0.02 * noise)
+    step = 1000.0 + in_allreduce + bubble
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    for on in (False, True):
+        job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                        collective_slack=True, kernel_names=[gemm, allreduce, sendrecv], peer_groups=stage.tolist(),
+                        slack_peer_groups=on)
+        try:
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, step[r][None, :].astype(np.float32))
+                job.load_kernels(lr, np.stack([np.full(calls, 1000.0), in_allreduce[r], bubble[r]]).astype(np.float32))
+            report = job.report()
+            s = report.slack_scores()
+            print(f"identify_slack_stragglers() with slack_peer_groups={on}: {named(report.identify_slack_stragglers())}")
+            if on:
+                for label, g in s["per_group"].items():
+                    print(f"  stage {label} (ranks {s['groups'][label]}): the typical rank waits {g['typical_waited_us']:.0f} us per "
+                          f"window, {100 * g['typical_share']:.1f} % of its traced GPU time")
+            else:
+                print(f"  the typical rank of the job waits {s['typical_waited_us']:.0f} us per window, "
+                      f"{100 * s['typical_share']:.1f} % of its traced GPU time")
+            for r, rec in sorted(s["ranks"].items()):
+                print(f"  rank {r}: in collectives {rec['collective_us']:.0f} us, waited {rec['waited_us']:.0f} us "
+                      f"(share {rec['share']:.3f}), the others wait {rec['lead_us']:.0f} us for it")
+        finally:
+            job.close()
+
+
 def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 6) -> None:
     """Two pipeline stages of different length: whom the job-wide rule names, and whom the peer-group scores do."""
     import numpy as np
@@ -631,6 +682,9 @@ def main() -> None:
     ap.add_argument("--slack", action="store_true",
                     help="no training: play the slack-score scenario (a rank whose host is slow arrives late at every "
                          "collective) and exit")
+    ap.add_argument("--slack-peer", action="store_true",
+                    help="no training: play the slack-score scenario of a pipeline job (stages of 2 and 6 ranks whose waits in "
+                         "collectives differ, rank 5 arriving late) with the job-wide rule and the rule per peer group, and exit")
     ap.add_argument("--peer", action="store_true",
                     help="no training: play the peer-group scenario (two pipeline stages of different length, one rank slow "
                          "within its stage) and exit")
@@ -661,6 +715,9 @@ def main() -> None:
         return
     if args.pace:
         pace()
+        return
+    if args.slack_peer:
+        slack_peer()
         return
     if args.slack:
         slack()

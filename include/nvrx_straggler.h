@@ -630,6 +630,49 @@ int nvrx_peer_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, u
 #define NVRX_SLACK_WORDS(R) (8 + 4 * (size_t)NVRX_SLACK_COLS + 8 * (size_t)(R))
 int nvrx_slack_score(const float *d_slack, const float *d_table, int R, int K, int S, int min_ranks, void *d_out, void *stream);
 
+/* Slack scores per peer group: the rank that the ranks doing the SAME work wait for.  nvrx_slack_score's floor of a column is
+ * taken over all ranks and its typical wait over the whole job: a lockstep model.  In a job of pipeline stages, tensor-parallel
+ * or expert groups the time inside collective kernels is dominated by waits that legitimately differ per stage; the stage
+ * that waits least sets a floor no other stage can reach, and a rank whose host is slow is missed or healthy ranks are named.
+ * Here the score step runs per peer group; the local step, the send rows and the gathered d_slack are nvrx_slack_score's.
+ *   d_groups  nvrx_peer_score's array, unchanged: group[R] | members[R] | start[G+1], 1 <= G <= R and G <=
+ *      NVRX_PEER_MAX_GROUPS.
+ *   max_group  in 1..R: the size of the largest group as the host knows it.  It selects the variant of the group kernel (at
+ *      most 64: one wave, a member per lane; at most 1024: 256 threads; beyond: 1024); a larger value than needed is legal.
+ *   The MEMBERS of group g are members[s .. e), s and e being start[g] and start[g+1] clamped to [0, R], e at least s, and
+ *   e - s clamped to max_group; an entry outside [0, R) is skipped.  size_g is that stretch's length (skipped entries count).
+ *   present, t, n and avg per (rank, column) are nvrx_slack_score's.
+ *   Per pair (group g, column c < 64), over the members of g:
+ *      present_gc  members present in c;
+ *      the pair is REFERENCED iff present_gc >= max(min_peers, min(min_ranks, size_g)) (nvrx_pace_group_score's rule: at
+ *      min_peers = 2 a rank alone in its group has no peer and is unrated);
+ *      floor       the minimum of avg over the present members by raw bit pattern, floor_rank the member that holds it, the
+ *      lower rank on a tie;
+ *      record, 16 bytes: {f32 floor, u32 present_gc, i32 floor_rank, u32 size_g}; floor is the NaN 0x7FC00000 and floor_rank
+ *      -1 where the pair is not referenced.  Exact.
+ *   Per rank r of group g = group[r], over the columns it is present in whose pair (g, c) is referenced: collective_us,
+ *      waited_us = sum (double)n * ((double)avg - (double)floor_gc), calls, columns, compute_us and share exactly as
+ *      nvrx_slack_score spells them (the same f64 sequences);
+ *      record, 32 bytes: {f32 collective_us, f32 waited_us, f32 compute_us, f32 share, u32 calls, u32 columns, u32
+ *      present_columns, i32 group}: present_columns counts the columns the rank is present in at all (what tells "no collective
+ *      rows" from "rows but no peers"), group is g, -1 where group[r] is outside [0, G) -- such a rank has no column.  NaN
+ *      in the four floats and 0 in calls and columns where columns == 0.
+ *   Per group g: record, 32 bytes: {f32 typical_waited, f32 typical_share, u32 ranks_with_data, u32 pairs_referenced, u32
+ *      size_g, 0, 0, 0}: the LOWER medians (rank (m - 1) >> 1 in value order) of waited_us and of share over the records of the
+ *      group's members with data (columns > 0), a NaN not entering, as in nvrx_slack_score's job record; NaN 0x7FC00000 when
+ *      none enters.
+ *   d_out  16-byte aligned, NVRX_SLACK_GROUP_WORDS(G, R) 32-bit words: G group records | G x 64 pair records | R rank records.
+ *      All R ranks are always computed.
+ *   The CONTENTS of d_groups are guarded on the device as stated above; no content makes a kernel read or write outside
+ *   d_slack, d_table, the array or d_out.  With one group of all ranks and min_peers = 1 the pair records' {floor, present},
+ *   words 0-5 of every rank record and the first four words of the group record are nvrx_slack_score's.
+ * Three small launches on `stream` (pairs, ranks, groups); no atomics, no scratch.  Argument errors, reported before any
+ * device is touched: those of nvrx_slack_score in its order, then nvrx_peer_score's checks of G, then NVRX_ERR_RANGE for a
+ * max_group outside 1..R or min_peers < 1, then NVRX_ERR_INVALID for a null d_groups. */
+#define NVRX_SLACK_GROUP_WORDS(G, R) ((8 + 4 * (size_t)NVRX_SLACK_COLS) * (size_t)(G) + 8 * (size_t)(R))
+int nvrx_slack_group_score(const float *d_slack, const float *d_table, int R, int K, int S, const int32_t *d_groups, int G,
+                           int max_group, int min_ranks, int min_peers, void *d_out, void *stream);
+
 /* Work groups: WHICH RANKS DO THE SAME WORK, inferred from the table.  Peer-group scores, pace scores per peer group and node
  * scores take that from the caller (d_groups); the table a report gathers holds a signature of each rank's work that does not
  * depend on how fast the rank runs: which kernel ids and section ids it has at all, and -- the exchanged weight being NUM * AVG

@@ -15,7 +15,8 @@
 // k_slack_cols   one workgroup per column, strided over the ranks: the minimum of the per-call means (as keys) and the number
 //   of present ranks by the wave reductions and one LDS word per wave.
 // k_slack_rank   one wave per rank, lane c = column c: three wave sums in f64 and a strided one over the K kernel weights;
-//   lane 0 writes the 32-byte record as two 16-byte stores.
+//   lane 0 writes the 32-byte record as two 16-byte stores.  A template on GROUPED: <true> is the per-group form's rank kernel
+//   (nvrx_slack_group.inl), <false> what the kernel was.
 // k_slack_job<T> one workgroup: the lower medians of waited_us and share over the rank records.  T == 0 (R <= 64): rank r in
 //   lane r, robust_wave_select; else robust_radix_select over the record words at a stride of 8.  Absent ranks hold NaN in
 //   both words and never enter.
@@ -113,18 +114,46 @@ __global__ __launch_bounds__(SLACK_COLS_THREADS) void k_slack_cols(SlackScoreArg
     }
 }
 
-__global__ __launch_bounds__(256) void k_slack_rank(SlackScoreArgs a) {
+// the per-group form's arguments and layout (nvrx_slack_group.inl): G group records | G x 64 pair records | R rank records
+struct SlackGroupArgs {
+    const float *slack;     // [R][2][64]
+    const float *table;     // [R][L]
+    const int32_t *groups;  // group[R] | members[R] | start[G+1]
+    int R, K, S, G;
+    int max_group;  // in 1..R
+    int min_ranks, min_peers;
+    uint32_t *out;
+};
+constexpr int SLACK_GROUP_WORDS = 8;  // a group record
+__host__ __device__ constexpr size_t slack_group_rank_base(int G) { return (size_t)(SLACK_GROUP_WORDS + 4 * SLACK_COLS) * (size_t)G; }
+
+// GROUPED (a compile-time flag: the job-wide instantiation is what it was): the column records are the pair records of
+// group[r], a pair being referenced iff it names a floor rank; words 6 and 7 of the record say how many columns the rank is
+// present in at all and its group id (-1 outside [0, G): such a rank has no column).
+template <bool GROUPED = false, class Args = SlackScoreArgs>
+__global__ __launch_bounds__(256) void k_slack_rank(Args a) {
     const int lane = threadIdx.x & 63;
     const int r = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (r >= a.R) return;  // wave-uniform
     float t, n, avg;
     const bool present = slack_entry(a.slack, r, lane, &t, &n, &avg);
-    const uint4 col = reinterpret_cast<const uint4 *>(a.out + 8)[lane];
-    const bool in = present && col.y != 0u && (int)col.y >= a.min_ranks;
+    uint4 col;
+    bool in;
+    int g = -1;
+    if constexpr (GROUPED) {
+        g = a.groups[r];
+        g = (uint32_t)g < (uint32_t)a.G ? g : -1;  // wave-uniform
+        col = reinterpret_cast<const uint4 *>(a.out + SLACK_GROUP_WORDS * (size_t)a.G)[(size_t)(g < 0 ? 0 : g) * SLACK_COLS + lane];
+        in = present && g >= 0 && (int)col.z >= 0;
+    } else {
+        col = reinterpret_cast<const uint4 *>(a.out + 8)[lane];
+        in = present && col.y != 0u && (int)col.y >= a.min_ranks;
+    }
     const double coll = wave_sum_f64(in ? (double)t : 0.0);
     const double waited = wave_sum_f64(in ? (double)n * ((double)avg - (double)__uint_as_float(col.x)) : 0.0);
     const double calls = wave_sum_f64(in ? (double)n : 0.0);
     const uint32_t columns = (uint32_t)__popcll(__ballot(in));
+    const uint32_t word6 = GROUPED ? (uint32_t)__popcll(__ballot(present)) : 0u, word7 = GROUPED ? (uint32_t)g : 0u;
     const int K = a.K, KS = K + a.S;
     double comp = 0.0;
     if (K > 0) {  // (no table is needed without kernel ids)
@@ -133,16 +162,18 @@ __global__ __launch_bounds__(256) void k_slack_rank(SlackScoreArgs a) {
     }
     comp = wave_sum_f64(comp);
     if (lane == 0) {
-        uint4 *rec = reinterpret_cast<uint4 *>(a.out + SLACK_HEAD_WORDS) + 2 * (size_t)r;
+        size_t base = SLACK_HEAD_WORDS;
+        if constexpr (GROUPED) base = slack_group_rank_base(a.G);
+        uint4 *rec = reinterpret_cast<uint4 *>(a.out + base) + 2 * (size_t)r;
         if (columns) {
             const float share = (float)(waited / (coll + comp));
             const uint32_t ncalls = calls >= 4294967295.0 ? 0xFFFFFFFFu : calls >= 0.0 ? (uint32_t)calls : 0u;  // (a NaN reads 0)
             rec[0] = make_uint4(__float_as_uint((float)coll), __float_as_uint((float)waited), __float_as_uint((float)comp),
                                 __float_as_uint(share));
-            rec[1] = make_uint4(ncalls, columns, 0u, 0u);
+            rec[1] = make_uint4(ncalls, columns, word6, word7);
         } else {
             rec[0] = make_uint4(SLACK_NAN, SLACK_NAN, SLACK_NAN, SLACK_NAN);
-            rec[1] = make_uint4(0u, 0u, 0u, 0u);
+            rec[1] = make_uint4(0u, 0u, word6, word7);
         }
     }
 }
@@ -227,7 +258,7 @@ int slack_score_launch(const float *d_slack, const float *d_table, int R, int K,
     a.out = static_cast<uint32_t *>(d_out);
     hipLaunchKernelGGL(k_slack_cols, dim3(SLACK_COLS), dim3(SLACK_COLS_THREADS), 0, st, a);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_slack_rank, dim3((R + 3) / 4), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_slack_rank<false, SlackScoreArgs>), dim3((R + 3) / 4), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (R <= 64)
         hipLaunchKernelGGL(k_slack_job<0>, dim3(1), dim3(64), 0, st, a);

@@ -3972,6 +3972,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_peer.inl"
 #include "nvrx_pace.inl"
 #include "nvrx_pace_group.inl"
+#include "nvrx_slack_group.inl"
 #include "nvrx_node.inl"
 #include "nvrx_work.inl"
 #include "nvrx_peer_history.inl"

@@ -55,6 +55,7 @@ class StragglerDetectionCallback(Callback):
         warn_if_node_off_pace: bool = False,
         node_groups=None,
         min_consecutive_peer_reports: int = 1,
+        slack_peer_groups: bool = False,
     ):
         """
         Args:
@@ -112,9 +113,14 @@ class StragglerDetectionCallback(Callback):
                 ``min_consecutive_reports`` does for a job without peer groups.  With ``peer_groups`` use this, not
                 ``min_consecutive_reports``: the job-wide history rates every healthy rank of a slower stage low in every
                 report and would name them all from the M-th report on.
+            slack_peer_groups: False (the default): nothing changes.  True (needs ``warn_if_waited_for`` and ``peer_groups``):
+                the slack scores are taken inside each rank's own peer group
+                (``Detector.initialize(slack_peer_groups=True)``), so that a pipeline job is not warned about the healthy ranks
+                of the stage that waits least at every report, and the warning names the ranks their own peer group waits
+                for.  Still a warning only.
 
         Raises:
-            ValueError: neither score family requested, ``min_consecutive_reports`` outside [1, 64],
+            ValueError: ``slack_peer_groups`` without ``warn_if_waited_for`` or without ``peer_groups``, neither score family requested, ``min_consecutive_reports`` outside [1, 64],
                 ``warn_if_waited_for``, ``warn_if_off_pace`` or ``peer_groups`` without ``calc_relative_gpu_perf``, or ``peer_groups`` together with
                 ``min_consecutive_reports`` > 1 (the score history does not hold peer scores), or ``pace_peer_groups`` without
                 ``warn_if_off_pace`` or without ``peer_groups``, or ``warn_if_node_off_pace`` without ``calc_relative_gpu_perf``, or
@@ -172,6 +178,12 @@ class StragglerDetectionCallback(Callback):
                 raise ValueError("pace_peer_groups needs warn_if_off_pace=True: it changes what the pace scores compare with")
             if peer_groups is None:
                 raise ValueError("pace_peer_groups needs peer_groups: which ranks do the same work")
+        self.slack_peer_groups = bool(slack_peer_groups)
+        if self.slack_peer_groups:
+            if not self.warn_if_waited_for:
+                raise ValueError("slack_peer_groups needs warn_if_waited_for=True: it changes what the slack scores compare with")
+            if peer_groups is None:
+                raise ValueError("slack_peer_groups needs peer_groups: which ranks do the same work")
         self.warn_if_node_off_pace = bool(warn_if_node_off_pace)
         if self.warn_if_node_off_pace and not calc_relative_gpu_perf:
             raise ValueError("warn_if_node_off_pace needs calc_relative_gpu_perf=True: node scores compare nodes")
@@ -206,6 +218,8 @@ class StragglerDetectionCallback(Callback):
             persistence["pace_scores"] = True
         if self.pace_peer_groups:
             persistence["pace_peer_groups"] = True
+        if self.slack_peer_groups:
+            persistence["slack_peer_groups"] = True
         if self.warn_if_node_off_pace:
             persistence["node_scores"] = True
             if self.node_groups is not None:
@@ -327,6 +341,13 @@ class StragglerDetectionCallback(Callback):
         if not named:
             return
         scores = report.slack_scores()
+        if self.slack_peer_groups:
+            parts = [f"rank {rank} (its peer group {scores['ranks'][rank]['group']!r} waits "
+                     f"{scores['ranks'][rank]['lead_us']:.0f} us per window for it)"
+                     for rank in sorted(getattr(s, "rank", s) for s in named)]
+            self.logger.warning("STRAGGLER DETECTION WARNING: Some GPUs' peer groups wait for them in their collectives "
+                                "(slow host?): " + "; ".join(parts))
+            return
         parts = [f"rank {rank} (the others wait {scores['ranks'][rank]['lead_us']:.0f} us per window for it)"
                  for rank in sorted(getattr(s, "rank", s) for s in named)]
         self.logger.warning("STRAGGLER DETECTION WARNING: The job waits for some GPUs in its collectives (slow host?): "

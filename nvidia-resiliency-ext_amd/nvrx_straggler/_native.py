@@ -47,6 +47,7 @@ TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, f
 SLACK_COLS = 64  # NVRX_SLACK_COLS: columns the collective keys are folded into (digest % 64)
 SLACK_HEAD_WORDS = 8 + 4 * SLACK_COLS  # the job record and the column records in front of the rank records
 SLACK_RANK_WORDS = 8  # {f32 collective_us, waited_us, compute_us, share, u32 calls, columns, 0, 0} per rank
+SLACK_GROUP_HEAD_WORDS = 8 + 4 * SLACK_COLS  # per group of nvrx_slack_group_score: its record and its 64 pair records
 WORK_MAX_RANKS = 4096  # NVRX_WORK_MAX_RANKS: the most ranks a work-group step compares pairwise
 WORK_RANK_WORDS = 8  # {i32 root, u32 size, degree, i32 nearest, u32 nearest_unlike, nearest_either, kernels, sections} per rank
 WORK_JOB_WORDS = 4  # {u32 groups, singletons, largest, ranks_with_data}
@@ -112,6 +113,8 @@ SYMBOLS = [
                                   c_void_p]),
     ("nvrx_peer_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
     ("nvrx_slack_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("nvrx_slack_group_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_void_p]),
     ("nvrx_work_words", c_int, [c_int, c_int, c_int]),
     ("nvrx_work_groups", c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -322,6 +325,12 @@ def peer_trend_words(n_ranks: int, S: int) -> int:
 def slack_words(R: int) -> int:
     """NVRX_SLACK_WORDS: 32-bit words of a slack score's output -- job record | 64 column records | ``R`` rank records."""
     return SLACK_HEAD_WORDS + SLACK_RANK_WORDS * R
+
+
+def slack_group_words(G: int, R: int) -> int:
+    """NVRX_SLACK_GROUP_WORDS: 32-bit words of the slack scores per peer group -- ``G`` group records | ``G x 64`` pair records
+    | ``R`` rank records."""
+    return 8 * G + 256 * G + 8 * R
 
 
 def work_offsets(R: int, K: int, S: int):

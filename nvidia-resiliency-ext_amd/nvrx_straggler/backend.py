@@ -498,6 +498,33 @@ class Slack:
         return self._host
 
 
+class SlackGroup:
+    """The slack scores per peer group of one report (``nvrx_slack_group_score``), enqueued and not waited for: ``Slack``'s
+    sibling, in the same slot of the workspace (``Workspace.slack_buffers`` / ``slack_settle``: a report runs one of the
+    two).  Once the kernels have run, the device buffer holds the ``G`` group records, the ``G x 64`` pair records and every
+    rank's record (include/nvrx_straggler.h)."""
+
+    __slots__ = ("backend", "d_ptr", "G", "first_rank", "n_ranks", "min_ranks", "min_peers", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, G: int, first_rank: int, n_ranks: int, min_ranks: int,
+                 min_peers: int):
+        self.backend, self.d_ptr, self.G = backend, buf.data_ptr(), G
+        self.first_rank, self.n_ranks, self.min_ranks, self.min_peers = first_rank, n_ranks, min_ranks, min_peers
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(groups [G, 8], pairs [G, 64, 4], ranks [n_ranks, 8])`` uint32 (private copies), the ranks being ``[first_rank,
+        first_rank + n_ranks)``; the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.slack_group_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class Work:
     """The work groups of one report (``nvrx_work_groups`` / ``nvrx_report_work``), enqueued and not waited for: once the four
     kernels have run, the workspace's device buffer holds the block of include/nvrx_straggler.h -- signatures, adjacency,
@@ -742,15 +769,23 @@ class Workspace:
     _slack_state = None  # (send, table, out) once a slack step has run on this workspace
     _slack_last = None   # the Slack whose kernels may still be reading the tables / writing the records
 
-    def slack_buffers(self):
+    def slack_buffers(self, group_words: int = 0):
         """``(send [local_ranks, 2 * 64] f32, table [R, 2 * 64] f32, out)`` of the slack step (cold: allocated on first
-        use); ``send`` is the table itself when nothing is exchanged; ``out`` takes ``_native.slack_words(R)`` words."""
+        use); ``send`` is the table itself when nothing is exchanged; ``out`` takes ``_native.slack_words(R)`` words, or
+        ``group_words`` (``_native.slack_group_words``: the step per peer group) where that is more -- a report runs one of the
+        two steps.  Only the per-group step passes ``group_words``, behind ``slack_settle``."""
         if self._slack_state is None:
             dev, W = self._backend.device, 2 * _native.SLACK_COLS
             with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
                 table = torch.empty((self.R, W), dtype=torch.float32, device=dev)
                 send = table if self.R == self.local_ranks else torch.empty((self.local_ranks, W), dtype=torch.float32, device=dev)
-                out = torch.empty(_native.slack_words(self.R), dtype=torch.int32, device=dev)
+                out = torch.empty(max(_native.slack_words(self.R), group_words), dtype=torch.int32, device=dev)
+            self._slack_state = (send, table, out)
+        elif self._slack_state[2].numel() < group_words:  # cold: more groups than before (peer_groups="auto")
+            self.slack_settle()
+            send, table, _ = self._slack_state
+            with torch.cuda.stream(self._backend.stream):
+                out = torch.empty(group_words, dtype=torch.int32, device=self._backend.device)
             self._slack_state = (send, table, out)
         return self._slack_state
 
@@ -1337,6 +1372,39 @@ class HipBackend:
         host = np.empty(n, dtype=np.uint32)
         _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, s.d_ptr, n * 4, self._stream_handle))
         return (host[:8].copy(), host[8:head].reshape(_native.SLACK_COLS, 4).copy(),
+                host[head + rw * s.first_rank:].reshape(s.n_ranks, rw).copy())
+
+    def slack_group_score(self, ws: Workspace, slack_table: torch.Tensor, table: torch.Tensor, groups: PeerGroups,
+                          first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 4,
+                          min_peers: int = 2) -> SlackGroup:
+        """Slack scores per peer group from the gathered rows ``slack_table`` and ``table``, as ``slack_score`` takes them,
+        and the resolved ``groups``: ``nvrx_slack_group_score`` enqueued on the backend's stream, in the slot of the job-wide
+        step.  All R ranks are computed; the handle delivers every group's record and pair records and the ranks
+        ``[first_rank, first_rank + n_ranks)``.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if first_rank < 0 or n_ranks < 1 or first_rank + n_ranks > ws.R:
+            raise ValueError(f"ranks [{first_rank}, {first_rank}+{n_ranks}) outside the table's {ws.R}")
+        if groups.R != ws.R:
+            raise ValueError(f"peer groups of {groups.R} ranks for a table of {ws.R}")
+        _, _, out = ws.slack_buffers(_native.slack_group_words(groups.G, ws.R))
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_slack_group_score(slack_table.data_ptr(), table_ptr, ws.R, ws.K, ws.S, groups.device(self).data_ptr(),
+                                             groups.G, groups.max_size, int(min_ranks), int(min_peers), out.data_ptr(),
+                                             self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        handle = ws._slack_last = SlackGroup(self, out, groups.G, first_rank, n_ranks, int(min_ranks), int(min_peers))
+        return handle
+
+    def slack_group_copy_out(self, s: SlackGroup):
+        """The one wait of a report's slack scores per peer group: a D2H of the group and pair records and of the rank records
+        up to the last rank the report covers, on the backend's stream, behind the kernels."""
+        G, rw = s.G, _native.SLACK_RANK_WORDS
+        head = _native.SLACK_GROUP_HEAD_WORDS * G
+        n = head + rw * (s.first_rank + s.n_ranks)
+        host = np.empty(n, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, s.d_ptr, n * 4, self._stream_handle))
+        return (host[: 8 * G].reshape(G, 8).copy(), host[8 * G: head].reshape(G, _native.SLACK_COLS, 4).copy(),
                 host[head + rw * s.first_rank:].reshape(s.n_ranks, rw).copy())
 
     def row_quantile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm: int) -> torch.Tensor:

@@ -1145,6 +1145,50 @@ class _SlackSource:
         return self._built
 
 
+class _SlackGroupSource(_SlackSource):
+    """What a report keeps of its slack scores per peer group (``ReportGenerator(slack_peer_groups=True)``): ``_SlackSource``
+    with the resolved groups and ``min_peers``; the handle's records are per group."""
+
+    __slots__ = ("groups", "min_peers")
+
+    def __init__(self, handle, ranks, keys, groups, min_ranks: int, min_peers: int, min_share: float, max_ratio: float):
+        super().__init__(handle, ranks, keys, min_ranks, min_share, max_ratio)
+        self.groups, self.min_peers = groups, min_peers
+
+    def build(self) -> dict:
+        if self._built is None:
+            grp, pairs, ranks = (np.ascontiguousarray(a, dtype=np.uint32) for a in self.handle.records())
+            labels, group = self.groups.labels, self.groups.group.tolist()
+            G = len(labels)
+            typical = grp[:, :2].copy().view(np.float32).tolist()
+            floors = pairs[:, :, 0].copy().view(np.float32).tolist()
+            present = pairs[:, :, 1].tolist()
+            holder = pairs[:, :, 2].copy().view(np.int32).tolist()
+            f = ranks[:, :4].copy().view(np.float32).tolist()
+            counts = ranks[:, 4:7].tolist()
+            per_rank, unrated = {}, []
+            for i, r in enumerate(self.ranks):
+                if counts[i][1] == 0:
+                    if counts[i][2]:
+                        unrated.append(r)  # (collective rows, and no pair of its group is referenced: no peers)
+                    continue
+                coll, waited, comp, share = f[i]
+                per_rank[r] = {"collective_us": coll, "waited_us": waited, "compute_us": comp, "share": share,
+                               "calls": counts[i][0], "lead_us": typical[group[r]][0] - waited, "group": labels[group[r]]}
+            per_group = {}
+            for g in range(G):
+                columns = {c: {"floor_us": floors[g][c], "ranks": present[g][c], "floor_rank": holder[g][c],
+                               "kernels": list(self.keys.get(c, ()))} for c in range(SLACK_COLS) if holder[g][c] >= 0}
+                per_group[labels[g]] = {"typical_waited_us": typical[g][0], "typical_share": typical[g][1],
+                                        "ranks_with_data": int(grp[g, 2]), "columns": columns}
+            self._built = {"ranks": per_rank, "groups": {labels[g]: self.groups.members(g) for g in range(G)},
+                           "group_of": {r: labels[group[r]] for r in self.ranks}, "unrated_ranks": unrated,
+                           "per_group": per_group, "min_ranks": self.min_ranks, "min_peers": self.min_peers,
+                           "min_share": self.min_share, "max_ratio": self.max_ratio, "peer_groups": True}
+            self.handle = None
+        return self._built
+
+
 class _WorkSource:
     """What a report keeps of its work groups: the backend's handle (``records()`` waits for the kernels and copies the rank
     records and the job record out on first use), the ranks its rows stand for, the step's parameters and -- where the user
@@ -1753,13 +1797,21 @@ class Report:
         "kernels": this process' collective kernels in it}}, "min_ranks", "min_share", "max_ratio"}``.  Only columns that at
         least ``min_ranks`` ranks have are used; a rank without one is left out.  Per-kernel timing only: without collective
         rows (region timing) the result is empty.  Plain dicts, floats and ints.  The first call waits for the kernels and
-        copies their records; ``generate_report`` does not."""
+        copies their records; ``generate_report`` does not.
+
+        With ``ReportGenerator(slack_peer_groups=True)`` the floor of a column is the smallest mean among the rank's OWN peer
+        group (``peer_groups``) and the typical wait is its group's: ``"ranks"`` holds the same record per rank plus
+        ``"group"`` (the label), ``lead_us`` being taken against the group's typical wait; ``"groups"``, ``"group_of"`` and
+        ``"unrated_ranks"`` as ``peer_scores()`` spells them (unrated: ranks with collective rows none of which enough peers
+        have); ``"per_group": {label: {"typical_waited_us", "typical_share", "ranks_with_data", "columns": {column:
+        {"floor_us", "ranks", "floor_rank", "kernels"}}}}``; ``"min_ranks"``, ``"min_peers"``, ``"min_share"``,
+        ``"max_ratio"`` and ``"peer_groups": True``.  There is no job-wide typical wait then."""
         slack = self.__dict__.get("_slack")
         if slack is None:
             return {}
         if isinstance(slack, _SlackSource):
             slack = self.__dict__["_slack"] = slack.build()
-        return _copy_scores(slack)
+        return _copy_peer(slack) if slack.get("peer_groups") else _copy_scores(slack)
 
     def work_groups(self) -> Dict[str, Any]:
         """Which ranks do the SAME WORK, inferred from the report's table (``ReportGenerator(work_groups=True)`` or
@@ -1791,7 +1843,12 @@ class Report:
         as a whole waits (``typical_share >= min_share``, default the generator's 0.05, and ``typical_waited_us > 0``) and
         this rank hardly does (``waited_us <= max_ratio * typical_waited_us``, default 0.25).  If half the ranks or more are
         late the typical wait is about 0 and nobody is named.  0.05 and 0.25 are defaults, not measurements.  An empty set
-        when the report carries no slack scores."""
+        when the report carries no slack scores.
+
+        With ``slack_peer_groups`` the rule is applied inside each peer group: a rank with data is named iff ITS GROUP waits
+        (the group's ``typical_share >= min_share`` and ``typical_waited_us > 0``) and the rank hardly does (``waited_us <=
+        max_ratio *`` the group's typical wait).  The typical wait is a lower median: in a group of two it is the late rank's
+        own wait, about 0, so a group of two names nobody; a rank alone in its group is unrated."""
         s = self.slack_scores()
         share = s.get("min_share", 0.05) if min_share is None else min_share
         ratio = s.get("max_ratio", 0.25) if max_ratio is None else max_ratio
@@ -1799,7 +1856,12 @@ class Report:
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not v >= 0:
                 raise ValueError(f"{name} must be a number >= 0, got {v!r}")
         named = []
-        if s and s["typical_share"] >= share and s["typical_waited_us"] > 0:
+        if s.get("peer_groups"):
+            for r, rec in s["ranks"].items():
+                grp = s["per_group"][rec["group"]]
+                if grp["typical_share"] >= share and grp["typical_waited_us"] > 0 and rec["waited_us"] <= ratio * grp["typical_waited_us"]:
+                    named.append(r)
+        elif s and s["typical_share"] >= share and s["typical_waited_us"] > 0:
             limit = ratio * s["typical_waited_us"]
             named = [r for r, rec in s["ranks"].items() if rec["waited_us"] <= limit]
         return {"straggler_gpus_slack": self._ids(named)}
@@ -1990,7 +2052,7 @@ class ReportGenerator:
                  node_scores: bool = False, node_groups=None, node_min_members: int = 2, node_min_nodes: int = 3,
                  node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
                  node_min_agree: float = 0.75, work_groups: bool = False, work_count_tol: float = 0.25,
-                 work_max_unlike: float = 0.1) -> None:
+                 work_max_unlike: float = 0.1, slack_peer_groups: bool = False) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2391,6 +2453,20 @@ class ReportGenerator:
                 raise RuntimeError(f"collective_slack: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no slack scores (backend.slack_score)")
             self.slack_min_ranks, (self.slack_min_share, self.slack_max_ratio) = int(slack_min_ranks), rule
+        # slack scores per peer group: the score step of the slack scores takes a column's floor and the typical wait inside
+        # the rank's OWN group (nvrx_slack_group_score); off: the step is the job-wide one, whatever peer_groups says.  The
+        # local step and its collective are the same either way.
+        self.slack_peer_groups = bool(slack_peer_groups)
+        if self.slack_peer_groups:
+            if not self.collective_slack or self.peer_groups is None:
+                missing = [name for name, on in (("collective_slack", self.collective_slack),
+                                                 ("peer_groups", self.peer_groups is not None)) if not on]
+                raise ValueError(f"slack_peer_groups needs collective_slack and peer_groups; {' and '.join(missing)} "
+                                 f"{'is' if len(missing) == 1 else 'are'} not set")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "slack_group_score"):
+                raise RuntimeError(f"slack_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no slack scores per peer group (backend.slack_group_score)")
         # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
         # any, that needs the ring-start snapshot
         self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
@@ -3204,6 +3280,16 @@ class ReportGenerator:
             lo = self.rank * local_ranks
             hi = lo + local_ranks
         view = report.__dict__["_src"].view
+        if self.slack_peer_groups:
+            grouped = getattr(be, "slack_group_score", None)
+            if grouped is None:
+                raise RuntimeError("slack_peer_groups: the active backend has no slack scores per peer group "
+                                   "(backend.slack_group_score)")
+            groups = self._peer_for(ws)  # (with "auto": the work groups of this report, whose step has run by now)
+            handle = grouped(ws, table, ws.table, groups, lo, hi - lo, self.slack_min_ranks, self.peer_min_ranks)
+            report.__dict__["_slack"] = _SlackGroupSource(handle, view.ranks, rings.slack_list()[2], groups, self.slack_min_ranks,
+                                                          self.peer_min_ranks, self.slack_min_share, self.slack_max_ratio)
+            return
         min_ranks = min(self.slack_min_ranks, ws.R)
         handle = score(ws, table, ws.table, lo, hi - lo, min_ranks)
         report.__dict__["_slack"] = _SlackSource(handle, view.ranks, rings.slack_list()[2], min_ranks, self.slack_min_share,

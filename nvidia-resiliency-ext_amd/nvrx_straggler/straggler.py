@@ -445,6 +445,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         pace_min_effect: float = 0.03,
         pace_min_breadth: float = 0.9,
         pace_peer_groups: Optional[bool] = None,
+        slack_peer_groups: Optional[bool] = None,
         node_scores: Optional[bool] = None,
         node_groups=None,
         node_min_members: int = 2,
@@ -596,6 +597,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 ``max(peer_min_ranks, min(pace_min_ranks, its size))`` ranks with a kernel for its median to be a reference.
                 Default: ``NVRX_PACE_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank (no collective depends
                 on it).
+            slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
+                peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
+                expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
+                healthy ranks of the stage that waits least, or nobody.  Needs ``collective_slack`` and ``peer_groups``
+                (``"auto"`` is allowed); a (group, collective kernel) pair needs ``max(peer_min_ranks, min(slack_min_ranks,
+                its size))`` ranks to be a reference.  A group of two names nobody; a rank alone in its group is unrated.
+                Default: ``NVRX_SLACK_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank.
             node_scores: every report also says whether a NODE is a little slower in nearly all of its kernels -- failed fans,
                 a capped PSU, a throttling host CPU, the wrong power profile: all GPUs of one host lose a few per cent, the
                 pace scores name every one of them, and only a score per node says that they are one incident
@@ -757,6 +765,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
             pace_peer_groups = from_env == "1"
         if pace_peer_groups:
             pace_options["pace_peer_groups"] = True  # (the generator says which of pace_scores and peer_groups it misses)
+        if slack_peer_groups is None:
+            from_env = os.environ.get("NVRX_SLACK_PEER_GROUPS", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_SLACK_PEER_GROUPS must be 0 or 1, got {from_env!r}")
+            slack_peer_groups = from_env == "1"
+        if slack_peer_groups:
+            pace_options["slack_peer_groups"] = True  # (the generator says which of collective_slack and peer_groups it misses)
         node_options = {}  # (off: the generator is built exactly as before)
         if node_scores is None:
             from_env = os.environ.get("NVRX_NODE_SCORES", "")
