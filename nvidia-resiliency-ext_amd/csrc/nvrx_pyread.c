@@ -18,6 +18,8 @@
  *       the sets identify_stragglers returns, straight from the score kernel's flag bytes ([rows][2+2S] u8 at buf+offset):
  *       no numpy call, no Python frame per column -- what a report read once a minute pays for is cold code and cold
  *       objects, so the fewer of both the better (Report.identify_stragglers: 75 -> ... us cold on the build host).
+ *       memo: None, or the plan's list [flag bytes, master copy, newest result, older result] (a list of two: no results kept);
+ *       an unchanged table's sets are handed out again once their caller has dropped them, as copies otherwise.
  */
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
@@ -469,9 +471,9 @@ static PyObject *pyread_copy_sets(PyObject *self, PyObject *arg) {
     return copy_set_dict(arg);  /* a set built from a set keeps the stored hashes: nothing is re-hashed */
 }
 
-/* one level deep copy of {name: set}; NULL on error */
+/* one level deep copy of {name: set}, created at its final size like the dicts of dict_from; NULL on error */
 static PyObject *copy_set_dict(PyObject *d) {
-    PyObject *out = PyDict_New();
+    PyObject *out = NEW_DICT(PyDict_GET_SIZE(d));
     if (!out) return NULL;
     PyObject *key, *value;
     Py_ssize_t pos = 0;
@@ -497,6 +499,125 @@ static int column_members(const unsigned char *f, int rows, int width, int col, 
     return 0;
 }
 
+/* ---- handing a dropped flagged result out again ---------------------------------------------------------------------------
+ * A straggler stays one for many reports, so the memo below hits report after report, and what a hit costs is the copies:
+ * for 64 flagged sections 128 one-member sets and two dicts are allocated, and as many freed when the caller rebinds its
+ * previous result.  The memo list therefore keeps, behind [key, hit], the last two results (gr, gi, sr, si) it handed out
+ * (two: a loop rebinds `found` after the next call has returned, so during call N result N-1 is alive and N-2 is free).
+ * On a hit a kept result is handed out again instead of a copy when
+ *   - nobody else can see it: the tuple, its four containers and every set inside the two dicts have reference count 1
+ *     (the memo's slot, through the tuple) and no set has a weak reference;
+ *   - it still equals the memo's master copy (the caller may have done anything to it before dropping it): same sizes, the
+ *     dicts' keys the very same objects in the same order, every value an exact set with the same members.
+ * Members are compared by pointer and nothing else: no __hash__ / __eq__ runs (StragglerId.__hash__ is a Python function),
+ * so no code of the caller's runs between the check and the return.  A result that fails any of this is never touched; it
+ * lives on with whoever holds it.  The set layout read here (cpython/setobject.h) is public in the non-limited API; a
+ * free-threaded build, where a reference count of 1 proves nothing, never reuses. */
+#if !defined(PYPY_VERSION) && !defined(Py_GIL_DISABLED) && !defined(Py_LIMITED_API) && PY_VERSION_HEX >= 0x03080000 && \
+    PY_VERSION_HEX < 0x030E0000
+#define NVRX_REUSE_POSSIBLE 1
+#define REUSE_MAX_MEMBERS 16 /* beyond the fast path: sets larger than this, or in a table larger than ... */
+#define REUSE_MAX_TABLE 64   /* ... this, are simply copied */
+
+/* same members by identity; both exact sets */
+static int same_members(PyObject *a_, PyObject *b_) {
+    const PySetObject *a = (const PySetObject *)a_, *b = (const PySetObject *)b_;
+    if (a->used != b->used || a->fill != a->used || b->fill != b->used) return 0;  /* (deleted entries in a table: copy) */
+    if (a->table == a->smalltable && b->table == b->smalltable && a->mask == b->mask) {
+        /* a set copied from a set into an empty table of the same mask keeps its slot layout: every member of b sits in the
+         * same slot of a.  Neither table has deleted entries, so a's `used` non-NULL slots are then all accounted for and the
+         * walk stops at b's last member (one-member sets: half a table read on average, not two) */
+        Py_ssize_t left = b->used;
+        int i = 0;
+        for (; left && i < PySet_MINSIZE; i++) {
+            const PyObject *k = b->smalltable[i].key;
+            if (!k) continue;
+            if (a->smalltable[i].key != k) break;
+            left--;
+        }
+        if (!left) return 1;
+    }
+    if (a->used > REUSE_MAX_MEMBERS || a->mask >= REUSE_MAX_TABLE || b->mask >= REUSE_MAX_TABLE) return 0;
+    for (Py_ssize_t i = 0; i <= a->mask; i++) {  /* equal sizes: every member of a found in b is equality */
+        const PyObject *k = a->table[i].key;
+        if (!k) continue;
+        Py_ssize_t j = 0;
+        while (j <= b->mask && b->table[j].key != k) j++;
+        if (j > b->mask) return 0;
+    }
+    return 1;
+}
+
+/* s is an exact set only its holder refers to, with the members of the exact set master */
+static int set_reusable(PyObject *s, PyObject *master) {
+    return PySet_CheckExact(s) && Py_REFCNT(s) == 1 && ((PySetObject *)s)->weakreflist == NULL && PySet_CheckExact(master) &&
+           same_members(s, master);
+}
+
+static int set_dict_reusable(PyObject *d, PyObject *master) {
+    if (!PyDict_CheckExact(d) || Py_REFCNT(d) != 1 || !PyDict_CheckExact(master) || PyDict_GET_SIZE(d) != PyDict_GET_SIZE(master))
+        return 0;
+    PyObject *k, *v, *mk, *mv;
+    Py_ssize_t pos = 0, mpos = 0;
+    while (PyDict_Next(d, &pos, &k, &v)) {
+        if (!PyDict_Next(master, &mpos, &mk, &mv) || k != mk || !set_reusable(v, mv)) return 0;
+    }
+    return 1;
+}
+
+/* t is a result (gr, gi, sr, si) nobody but the memo's slot holds, equal to the master copies in hit[1..4] */
+static int result_reusable(PyObject *t, PyObject *hit) {
+    return PyTuple_CheckExact(t) && PyTuple_GET_SIZE(t) == 4 && Py_REFCNT(t) == 1 &&
+           set_reusable(PyTuple_GET_ITEM(t, 0), PyTuple_GET_ITEM(hit, 1)) && set_reusable(PyTuple_GET_ITEM(t, 1), PyTuple_GET_ITEM(hit, 2)) &&
+           set_dict_reusable(PyTuple_GET_ITEM(t, 2), PyTuple_GET_ITEM(hit, 3)) &&
+           set_dict_reusable(PyTuple_GET_ITEM(t, 3), PyTuple_GET_ITEM(hit, 4));
+}
+#else
+#define NVRX_REUSE_POSSIBLE 0
+#endif
+
+/* memo[2] (the result handed out last) and memo[3] (the one before) of a memo list with slots; new references are taken, the
+ * old ones dropped only after both slots hold their new objects */
+static void set_slots(PyObject *memo, PyObject *newest, PyObject *older) {
+    if (PyList_GET_SIZE(memo) != 4) return;  /* (somebody's code ran during an allocation and cut the list: nothing is kept) */
+    PyObject *o2 = PyList_GET_ITEM(memo, 2), *o3 = PyList_GET_ITEM(memo, 3);
+    Py_INCREF(newest);
+    Py_INCREF(older);
+    PyList_SET_ITEM(memo, 2, newest);
+    PyList_SET_ITEM(memo, 3, older);
+    Py_DECREF(o2);
+    Py_DECREF(o3);
+}
+
+/* One word-wise pass over the n flag bytes: *any = some byte is set; returns whether they equal key (NULL: no candidate,
+ * returns 0).  The bytes may sit in the pinned result block itself, so they are read once, front to back. */
+static int scan_flags(const unsigned char *f, const unsigned char *key, Py_ssize_t n, int *any) {
+    uint64_t acc = 0, diff = 0;
+    Py_ssize_t i = 0;
+    if (key) {
+        for (; i + 8 <= n; i += 8) {
+            uint64_t a, b;
+            memcpy(&a, f + i, 8);
+            memcpy(&b, key + i, 8);
+            acc |= a;
+            diff |= a ^ b;
+        }
+        for (; i < n; i++) {
+            acc |= f[i];
+            diff |= (uint64_t)(f[i] ^ key[i]);
+        }
+    } else {
+        for (; i + 8 <= n; i += 8) {
+            uint64_t a;
+            memcpy(&a, f + i, 8);
+            acc |= a;
+        }
+        for (; i < n; i++) acc |= f[i];
+    }
+    *any = acc != 0;
+    return key != NULL && diff == 0;
+}
+
 static PyObject *pyread_flagged(PyObject *self, PyObject *args) {
     Py_buffer view;
     Py_ssize_t offset;
@@ -510,7 +631,7 @@ static PyObject *pyread_flagged(PyObject *self, PyObject *args) {
     const Py_ssize_t n = (Py_ssize_t)rows * width;
     if (rows < 0 || S < 0 || width != 2 + 2 * S || offset < 0 || view.len < offset + n ||
         (cols != Py_None && (!PyTuple_Check(cols) || PyTuple_GET_SIZE(cols) != n_names)) ||
-        (memo != Py_None && (!PyList_Check(memo) || PyList_GET_SIZE(memo) != 2))) {
+        (memo != Py_None && (!PyList_Check(memo) || (PyList_GET_SIZE(memo) != 2 && PyList_GET_SIZE(memo) != 4)))) {
         PyErr_SetString(PyExc_ValueError, "nvrx_pyread.flagged: inconsistent shapes");
         goto done;
     }
@@ -523,24 +644,52 @@ static PyObject *pyread_flagged(PyObject *self, PyObject *args) {
     PyObject **ids = PySequence_Fast_ITEMS(ids_fast);
     const unsigned char *f = (const unsigned char *)view.buf + offset;
 
-    unsigned char any = 0;
-    for (Py_ssize_t i = 0; i < n; i++) any |= f[i];
-    if (any && memo != Py_None) {
-        /* a straggler usually stays one for many reports: the sets of an unchanged flag table are handed out as copies
-         * (a set built from a set keeps the stored hashes, StragglerId.__hash__ is a Python function) */
-        PyObject *key = PyList_GET_ITEM(memo, 0), *hit = PyList_GET_ITEM(memo, 1);
+    /* memo: [key, hit], or [key, hit, newest, older] with the two results handed out last ("handing a dropped flagged result
+     * out again" above) */
+    const int slots = memo != Py_None && PyList_GET_SIZE(memo) == 4;
+    const unsigned char *memo_key = NULL;
+    PyObject *hit = NULL;
+    if (memo != Py_None) {
+        PyObject *key = PyList_GET_ITEM(memo, 0);
+        hit = PyList_GET_ITEM(memo, 1);
         /* the hit belongs to one (ids, names, cols, families) combination: a memo list shared across views must miss */
         if (PyBytes_Check(key) && PyBytes_GET_SIZE(key) == n && PyTuple_Check(hit) && PyTuple_GET_SIZE(hit) == 9 &&
             PyTuple_GET_ITEM(hit, 0) == ids_obj && PyTuple_GET_ITEM(hit, 5) == names && PyTuple_GET_ITEM(hit, 6) == cols &&
             PyTuple_GET_ITEM(hit, 7) == (has_rel ? Py_True : Py_False) && PyTuple_GET_ITEM(hit, 8) == (has_indiv ? Py_True : Py_False) &&
-            memcmp(PyBytes_AS_STRING(key), f, (size_t)n) == 0) {
-            gr = PySet_New(PyTuple_GET_ITEM(hit, 1));
-            gi = PySet_New(PyTuple_GET_ITEM(hit, 2));
-            sr = copy_set_dict(PyTuple_GET_ITEM(hit, 3));
-            si = copy_set_dict(PyTuple_GET_ITEM(hit, 4));
-            if (gr && gi && sr && si) result = PyTuple_Pack(4, gr, gi, sr, si);
-            goto done;
+            PyDict_Check(PyTuple_GET_ITEM(hit, 3)) && PyDict_Check(PyTuple_GET_ITEM(hit, 4)))
+            memo_key = (const unsigned char *)PyBytes_AS_STRING(key);
+    }
+    int any = 0, new_master = 0;
+    /* (one pass: is any flag set, and is the table the one the memo holds) */
+    if (scan_flags(f, memo_key, n, &any) && any) {
+        /* a straggler usually stays one for many reports: the sets of an unchanged flag table are handed out again when the
+         * caller has dropped them, as copies otherwise (a set built from a set keeps the stored hashes, StragglerId.__hash__
+         * is a Python function) */
+#if NVRX_REUSE_POSSIBLE
+        if (slots) {
+            PyObject *newest = PyList_GET_ITEM(memo, 2), *older = PyList_GET_ITEM(memo, 3);
+            if (result_reusable(older, hit)) {  /* the usual case: the caller still holds the newest one */
+                result = older;
+                Py_INCREF(result);
+                set_slots(memo, older, newest);
+                goto done;
+            }
+            if (result_reusable(newest, hit)) {
+                result = newest;
+                Py_INCREF(result);
+                goto done;
+            }
         }
+#endif
+        Py_INCREF(hit);  /* (an allocation may run the collector, and with it anybody's code: the master copy stays ours) */
+        gr = PySet_New(PyTuple_GET_ITEM(hit, 1));
+        gi = PySet_New(PyTuple_GET_ITEM(hit, 2));
+        sr = copy_set_dict(PyTuple_GET_ITEM(hit, 3));
+        si = copy_set_dict(PyTuple_GET_ITEM(hit, 4));
+        Py_DECREF(hit);
+        if (gr && gi && sr && si) result = PyTuple_Pack(4, gr, gi, sr, si);
+        if (result && slots) set_slots(memo, result, PyList_GET_ITEM(memo, 2));  /* the older slot's result lives on with its holders */
+        goto done;
     }
     gr = PySet_New(NULL);
     gi = PySet_New(NULL);
@@ -582,7 +731,7 @@ static PyObject *pyread_flagged(PyObject *self, PyObject *args) {
         if (memo != Py_None) {
             PyObject *key = PyBytes_FromStringAndSize((const char *)f, n);
             PyObject *c_gr = PySet_New(gr), *c_gi = PySet_New(gi), *c_sr = copy_set_dict(sr), *c_si = copy_set_dict(si);
-            PyObject *hit = (key && c_gr && c_gi && c_sr && c_si)
+            hit = (key && c_gr && c_gi && c_sr && c_si)
                                 ? PyTuple_Pack(9, ids_obj, c_gr, c_gi, c_sr, c_si, names, cols, has_rel ? Py_True : Py_False,
                                                has_indiv ? Py_True : Py_False)
                                 : NULL;
@@ -595,12 +744,15 @@ static PyObject *pyread_flagged(PyObject *self, PyObject *args) {
                 Py_XDECREF(hit);
                 goto done;
             }
-            /* (memo was checked to be a list of two: these cannot fail; SetItem steals the references) */
+            /* (memo was checked to be a list of two or four: these cannot fail; SetItem steals the references) */
             PyList_SetItem(memo, 0, key);
             PyList_SetItem(memo, 1, hit);
+            new_master = 1;
         }
     }
     result = PyTuple_Pack(4, gr, gi, sr, si);
+    /* the kept results belonged to the table before: this one is the first of the new table */
+    if (result && new_master && slots) set_slots(memo, result, Py_None);
 done:
     Py_XDECREF(gr);
     Py_XDECREF(gi);

@@ -309,13 +309,14 @@ class _View:
             return self._memo
 
     def flag_memo(self) -> list:
-        """[flag bytes, (ids, gpu_rel, gpu_indiv, sec_rel, sec_indiv)] of the last flag table ``_nvrx_pyread.flagged``
-        decoded for this plan (it hands an unchanged table's sets out as copies)."""
+        """[flag bytes, (ids, gpu_rel, gpu_indiv, sec_rel, sec_indiv, ...), newest, older] of the last flag table
+        ``_nvrx_pyread.flagged`` decoded for this plan, and the last two results it handed out: an unchanged table's sets
+        are handed out again once their caller has dropped them, as copies otherwise."""
         m = self.memo()
         try:
             return m["c"]
         except KeyError:
-            m["c"] = [None, None]
+            m["c"] = [None, None, None, None]
             return m["c"]
 
     def rank_list(self) -> list:
