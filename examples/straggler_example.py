@@ -426,6 +426,70 @@ def slack_peer(calls: int = 200, late_rank: int = 5, late_us: float = 300.0) -> 
             job.close()
 
 
+def tail_peer_samples(ranks: int = 8, sections: int = 2, samples: int = 2000, slow_rank: int = 6):
+    """The ``--tail-peer`` job: ``[ranks, sections, samples]`` f64 microseconds (NumPy only).  The two stages of ``--peer``
+    (1000 us and 1500 us, 1 % noise); ``slow_rank`` is 1.5 x slower on every 10th of its samples only."""
+    import numpy as np
+
+    x = np.repeat(np.array([1000.0] * (ranks // 2) + [1500.0] * (ranks - ranks // 2)), sections * samples).reshape(ranks, sections, samples)
+    x *= 1.0 + 0.01 * np.random.default_rng(31).standard_normal(x.shape)
+    x[slow_rank, :, 9::10] *= 1.5
+    return x
+
+
+def period_peer_samples(ranks: int = 8, sections: int = 2, samples: int = 2000, alone: int = 2, every: int = 50):
+    """The ``--period-peer`` job: ``[ranks, sections, samples]`` f64 microseconds (NumPy only).  The two stages of ``--peer``;
+    a stage-local checkpoint shard makes every rank of stage 1 stall 1.5 x on every ``every``-th sample, and rank ``alone`` of
+    stage 0 stalls the same way on its own."""
+    import numpy as np
+
+    x = np.repeat(np.array([1000.0] * (ranks // 2) + [1500.0] * (ranks - ranks // 2)), sections * samples).reshape(ranks, sections, samples)
+    x *= 1.0 + 0.01 * np.random.default_rng(37).standard_normal(x.shape)
+    x[ranks // 2:, :, every - 1::every] *= 1.5
+    x[alone, :, every - 1::every] *= 1.5
+    return x
+
+
+def named_ranks(found) -> list:
+    """The ranks an ``identify_*_stragglers()`` result names, in any of its mappings."""
+    return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+
+def row_peer(family: str) -> None:
+    """A pipeline job of two stages of different length under a row family's job-wide rule and its rule per peer group
+    (``row_peer_groups``): ``tail`` -- rank 6 is slow on a tenth of its samples only; ``period`` -- stage 1 stalls together on a
+    beat, rank 2 of stage 0 stalls alone."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    x = tail_peer_samples() if family == "tail" else period_peer_samples()
+    ranks, sections, samples = x.shape
+    option = {"tail_quantile": 0.95} if family == "tail" else {"period_detection": True}
+    for on in (False, True):
+        job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=2048, scores_to_compute=("relative_perf_scores",),
+                        peer_groups=f"block:{ranks // 2}", row_peer_groups=on, **option)
+        try:
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, x[r].astype(np.float32))
+            report = job.report()
+            scores = getattr(report, family + "_scores")()
+            found = getattr(report, f"identify_{family}_stragglers")()
+            name = job.section_names[0]
+            print(f"identify_{family}_stragglers() with row_peer_groups={on}: {named_ranks(found)}")
+            if family == "tail":
+                print(f"identify_peer_stragglers(): {named_ranks(report.identify_peer_stragglers())}")
+            for r in sorted(scores["section_relative"][name]):
+                against = f"its peers (group {scores['group_of'][r]})" if on else "the job"
+                print(f"  rank {r}: {name} against {against} {scores['section_relative'][name][r]:.3f}")
+            if on:
+                for label, ref in scores["section_reference"][name].items():
+                    print(f"  group {label} (ranks {scores['groups'][label]}): reference {ref['value']:.3f}, held by rank {ref['rank']}")
+        finally:
+            job.close()
+
+
 def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 6) -> None:
     """Two pipeline stages of different length: whom the job-wide rule names, and whom the peer-group scores do."""
     import numpy as np
@@ -685,6 +749,12 @@ def main() -> None:
     ap.add_argument("--slack-peer", action="store_true",
                     help="no training: play the slack-score scenario of a pipeline job (stages of 2 and 6 ranks whose waits in "
                          "collectives differ, rank 5 arriving late) with the job-wide rule and the rule per peer group, and exit")
+    ap.add_argument("--tail-peer", action="store_true",
+                    help="no training: play the tail-score scenario of a pipeline job (the two stages of --peer, rank 6 1.5 x "
+                         "slower on a tenth of its samples) with the job-wide rule and the rule per peer group, and exit")
+    ap.add_argument("--period-peer", action="store_true",
+                    help="no training: play the period-score scenario of a pipeline job (stage 1 stalls together on every 50th "
+                         "sample, rank 2 of stage 0 stalls alone) with the job-wide rule and the rule per peer group, and exit")
     ap.add_argument("--peer", action="store_true",
                     help="no training: play the peer-group scenario (two pipeline stages of different length, one rank slow "
                          "within its stage) and exit")
@@ -706,6 +776,9 @@ def main() -> None:
     args = ap.parse_args()
     if args.work:
         work()
+        return
+    if args.tail_peer or args.period_peer:
+        row_peer("tail" if args.tail_peer else "period")
         return
     if args.node:
         node()

@@ -673,6 +673,46 @@ int nvrx_slack_score(const float *d_slack, const float *d_table, int R, int K, i
 int nvrx_slack_group_score(const float *d_slack, const float *d_table, int R, int K, int S, const int32_t *d_groups, int G,
                            int max_group, int min_ranks, int min_peers, void *d_out, void *stream);
 
+/* Row-family scores per peer group: nvrx_{tail,onset,period,episode}_score with a column's reference taken inside each rank's
+ * OWN group.  The job-wide step takes one reference per column over all R ranks: in a job of pipeline stages the healthy ranks
+ * of the slower stage read as tail stragglers (tails are absolute times), and a step, a beat or a stretch that one whole STAGE
+ * shares flags that stage.  One entry serves all four families: they differ in what plane 0 holds, not in how it is scored.
+ *   d_planes  [R][planes][K+S], a family's gathered table (-1.0: none); only plane 0 is read, at a pitch of planes * (K+S).
+ *      planes in 1..7 (the largest *_PLANES above).
+ *   d_table  [R][L] as for nvrx_score: only the weights w[r][k] = table[r][2(K+S) + k], k < K, are read; it may be NULL only
+ *      at K = 0.  R <= NVRX_ROBUST_MAX_RANKS.
+ *   d_groups  nvrx_peer_score's array, unchanged: group[R] | members[R] | start[G+1], 1 <= G <= R and G <=
+ *      NVRX_PEER_MAX_GROUPS, with that entry's guards: a group[r] outside [0, G) rates rank r NaN, a members entry outside
+ *      [0, R) is skipped, start values are clamped to [0, R]; no content makes a kernel read or write outside the inputs or
+ *      d_out.
+ *   d_out  16-byte aligned, NVRX_ROWFAM_GROUP_WORDS(G, K, S, n_ranks) 32-bit words (nvrx_rowfam_group_words returns the same;
+ *      0 for a negative argument), two blocks:
+ *      A  [G][K+S] records of 16 bytes {f32 floor, u32 present, i32 floor_rank, u32 members}: exactly nvrx_peer_score's column
+ *         record taken over plane 0.  A member is PRESENT iff its value v >= 0 (the -1 sentinel and NaN are absent); floor is
+ *         the present value with the smallest key (raw bit pattern order), floor_rank the lowest rank that holds it; the pair
+ *         is REFERENCED iff present >= min_ranks, else floor is the NaN 0x7FC00000 and floor_rank -1.  min_ranks >= 1 and NOT
+ *         clamped to the group's size: at 2 a rank alone in its group is unrated, not rated 1.0.
+ *      B  [n_ranks][1 + S] f32 per reported rank r in [first_rank, first_rank + n_ranks), g = group[r]:
+ *         slot 1 + s: (float)((double)floor / (double)v) of column K + s of g;
+ *         slot 0: (float)(sum_k w_k * ((double)floor_k / (double)v_k) / sum_k w_k) in f64 over the kernel columns k < K that are
+ *         eligible in the same way; NaN when none is (also at K = 0).  The sum is taken across a wave: its last bits depend on
+ *         that order;
+ *         a slot is NaN where g is outside [0, G), r's value is absent or the pair is not referenced.  Zero and +inf values
+ *         give the IEEE results, as in nvrx_peer_score.
+ *   This rule DIFFERS from the job-wide entries' "NaN if any rank has none": a group's floor is taken over its PRESENT members,
+ *   and min_ranks says how many of them a reference needs.  With one group of all ranks, min_ranks = 1 and every rank holding
+ *   every column, the section slots are nvrx_tail_score's bit for bit.
+ * Two launches on `stream` for every R (k_peer_cols on the planes, k_rowfam_group_rank); no atomics, no scratch.  Argument
+ * errors, reported before any device is touched: NVRX_ERR_INVALID for a bad shape, NVRX_ERR_RANGE for R, K or S beyond their
+ * limits, for a rank range outside the table, for planes outside 1..7 and for min_ranks < 1, then nvrx_peer_score's checks of
+ * G, then NVRX_ERR_INVALID for a null pointer or a d_out that is not 16-byte aligned. */
+#define NVRX_ROWFAM_GROUP_WORDS(G, K, S, n_ranks) \
+    (4 * (size_t)(G) * ((size_t)(K) + (S)) + (size_t)(n_ranks) * (1 + (size_t)(S)))
+int nvrx_rowfam_group_score(const float *d_planes, int planes, const float *d_table, int R, int K, int S,
+                            const int32_t *d_groups, int G, int first_rank, int n_ranks, int min_ranks, void *d_out,
+                            void *stream);
+size_t nvrx_rowfam_group_words(int G, int K, int S, int n_ranks);
+
 /* Work groups: WHICH RANKS DO THE SAME WORK, inferred from the table.  Peer-group scores, pace scores per peer group and node
  * scores take that from the caller (d_groups); the table a report gathers holds a signature of each rank's work that does not
  * depend on how fast the rank runs: which kernel ids and section ids it has at all, and -- the exchanged weight being NUM * AVG

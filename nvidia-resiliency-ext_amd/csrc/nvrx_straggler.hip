@@ -3970,6 +3970,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_period.inl"
 #include "nvrx_episode.inl"
 #include "nvrx_peer.inl"
+#include "nvrx_rowfam_group.inl"
 #include "nvrx_pace.inl"
 #include "nvrx_pace_group.inl"
 #include "nvrx_slack_group.inl"

@@ -115,6 +115,8 @@ SYMBOLS = [
     ("nvrx_slack_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_slack_group_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                        c_void_p]),
+    ("nvrx_rowfam_group_score", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p]),
     ("nvrx_work_words", c_int, [c_int, c_int, c_int]),
     ("nvrx_work_groups", c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     ("nvrx_ctx_create", c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -194,6 +196,11 @@ SYMBOLS = [
     ("nvrx_wait", c_int, [c_void_p]),
 ]
 
+# entry points that return a size, not a code (bound like SYMBOLS)
+SIZE_SYMBOLS = [
+    ("nvrx_rowfam_group_words", c_size_t, [c_int, c_int, c_int, c_int]),
+]
+
 _lib = None
 _lock = threading.Lock()
 
@@ -226,7 +233,7 @@ def load() -> ctypes.CDLL:
             lib = ctypes.CDLL(_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         except OSError as e:  # pragma: no cover
             raise RuntimeError(f"failed to load {_LIB_PATH}: {e}") from e
-        for name, restype, argtypes in SYMBOLS:
+        for name, restype, argtypes in SYMBOLS + SIZE_SYMBOLS:
             fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
             fn.restype = restype
             fn.argtypes = argtypes
@@ -331,6 +338,12 @@ def slack_group_words(G: int, R: int) -> int:
     """NVRX_SLACK_GROUP_WORDS: 32-bit words of the slack scores per peer group -- ``G`` group records | ``G x 64`` pair records
     | ``R`` rank records."""
     return 8 * G + 256 * G + 8 * R
+
+
+def rowfam_group_words(G: int, K: int, S: int, n_ranks: int) -> int:
+    """NVRX_ROWFAM_GROUP_WORDS: 32-bit words of a row family's scores per peer group -- ``[G][K+S][4]`` column records, then
+    ``[n_ranks][1 + S]``."""
+    return 4 * G * (K + S) + n_ranks * (1 + S)
 
 
 def work_offsets(R: int, K: int, S: int):

@@ -271,6 +271,30 @@ class RowScores:
         return self._host
 
 
+class RowGroupScores(RowScores):
+    """One row family's scores per peer group of one report (``nvrx_rowfam_group_score``), ``RowScores``' sibling in the same
+    slot: once the kernels have run, the workspace's buffer of that family holds the gathered table, then -- on a 16-byte
+    boundary -- the ``[G][K+S]`` column records and the scores ``[n_ranks][1 + S]`` of the reported ranks.  ``records()`` waits
+    for them and takes the private host copy by one ordered D2H, as ``RowScores.records`` does."""
+
+    __slots__ = ("G", "min_ranks")
+
+    def __init__(self, backend: "HipBackend", family: RowFamily, buf: torch.Tensor, R: int, K: int, S: int, G: int,
+                 first_rank: int, n_ranks: int, min_ranks: int, params: tuple = ()):
+        super().__init__(backend, family, buf, R, K, S, first_rank, n_ranks, params)
+        self.G, self.min_ranks = G, min_ranks
+
+    def records(self):
+        """``(planes, scores, cols)``: ``RowScores.records``' two arrays and the column records ``[G, K+S, 4]`` uint32 {f32
+        floor, u32 present, i32 floor_rank, u32 members} (private copies); the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.family_group_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class _FamilyBuffers:
     """A workspace's device buffers of one row family, and the handle that may still be using them."""
 
@@ -666,25 +690,39 @@ class Workspace:
     # ---- row families: tail, onset, period, episode scores (off unless a ReportGenerator asks: nothing is allocated before) ----
     _family_state = None  # family name -> _FamilyBuffers, once that family has run on this workspace
 
-    def family_buffers(self, fam: RowFamily):
+    def family_buffers(self, fam: RowFamily, group_words: int = 0):
         """``(send, table, scores, scratch)`` of one row family (cold: allocated on first use): ONE buffer holds the gathered
         table ``[R][P * (K+S)]`` and then the scores ``[R][1 + S]`` (one copy-out); ``send`` are this process' rows
-        ``[local_ranks][P * (K+S)]`` (the table's own rows without an exchange); ``scratch`` takes the column minima."""
+        ``[local_ranks][P * (K+S)]`` (the table's own rows without an exchange); ``scratch`` takes the column minima.
+        ``group_words`` (``_native.rowfam_group_words``: only the score step per peer group passes it): the buffer is ``table
+        | pad to 16 bytes | column records | scores`` instead, and ``scores`` is what follows the pad.  It grows -- behind
+        ``family_settle``, the table's contents carried over -- when there are more groups than before
+        (``peer_groups="auto"``)."""
         if self._family_state is None:
             self._family_state = {}
         st = self._family_state.get(fam.name)
         KS, R, P = self.K + self.S, self.R, fam.planes
+        head = (R * P * KS + 3) & ~3 if group_words else R * P * KS
         if st is None:
             st = self._family_state[fam.name] = _FamilyBuffers()
             dev = self._backend.device
             with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
-                st.buf = torch.empty(max(R * P * KS + R * (1 + self.S), 64), dtype=torch.float32, device=dev)
+                st.buf = torch.empty(max(R * P * KS + R * (1 + self.S), head + group_words, 64), dtype=torch.float32, device=dev)
                 st.table = st.buf[: R * P * KS].view(R, P * KS)
                 st.send = (st.table if R == self.local_ranks
                            else torch.empty((self.local_ranks, P * KS), dtype=torch.float32, device=dev))
                 st.scratch = torch.empty(max(33 * KS, 64), dtype=torch.float32, device=dev)
             st.last = None  # the RowScores whose kernels may still be reading the table / writing the buffers
-        return st.send, st.table, st.buf[R * P * KS:], st.scratch
+        elif st.buf.numel() < head + group_words:  # cold: the first grouped step, or more groups than before
+            self.family_settle(fam)
+            with torch.cuda.stream(self._backend.stream):
+                buf = torch.empty(head + group_words, dtype=torch.float32, device=self._backend.device)
+                buf[: R * P * KS].copy_(st.buf[: R * P * KS])  # (this report's gathered table is in there already)
+            table = buf[: R * P * KS].view(R, P * KS)
+            if st.send is st.table:
+                st.send = table
+            st.buf, st.table = buf, table
+        return st.send, st.table, st.buf[head:], st.scratch
 
     def family_settle(self, fam: RowFamily) -> None:
         """Before anything rewrites this workspace's table or that family's buffers: the family's last step's kernels have
@@ -1075,6 +1113,56 @@ class HipBackend:
         st = ws._family_state[fam.name]
         out = st.last = RowScores(self, fam, st.buf, ws.R, ws.K, ws.S, first_rank, n_ranks, params)
         return out
+
+    def _family_group_score(self, fam: RowFamily, ws: Workspace, planes: torch.Tensor, table: torch.Tensor, groups: PeerGroups,
+                            first_rank: int, n_ranks: Optional[int], min_ranks: int, params: tuple = ()) -> RowGroupScores:
+        """``_family_score`` per peer group: a column's reference is taken inside each rank's own group of the resolved
+        ``groups``, a pair needing ``min_ranks`` present members (``nvrx_rowfam_group_score`` enqueued on the backend's
+        stream, in the slot of the job-wide step).  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        if groups.R != ws.R:
+            raise ValueError(f"peer groups of {groups.R} ranks for a table of {ws.R}")
+        _, before, _, _ = ws.family_buffers(fam)
+        assert planes is before or (planes.data_ptr() == before.data_ptr())
+        _, fam_table, out, _ = ws.family_buffers(fam, _native.rowfam_group_words(groups.G, ws.K, ws.S, n_ranks))
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_rowfam_group_score(fam_table.data_ptr(), fam.planes, table_ptr, ws.R, ws.K, ws.S,
+                                              groups.device(self).data_ptr(), groups.G, first_rank, n_ranks, int(min_ranks),
+                                              out.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        st = ws._family_state[fam.name]
+        handle = st.last = RowGroupScores(self, fam, st.buf, ws.R, ws.K, ws.S, groups.G, first_rank, n_ranks, int(min_ranks), params)
+        return handle
+
+    def family_group_copy_out(self, t: RowGroupScores):
+        """The one wait of a report's row family per peer group: a D2H of its table, column records and scores on the
+        backend's stream, behind the kernels."""
+        KS, P = t.K + t.S, t.family.planes
+        head = (t.R * P * KS + 3) & ~3
+        n = head + _native.rowfam_group_words(t.G, t.K, t.S, t.n_ranks)
+        host = np.empty(n, dtype=np.float32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        shape = (t.R, KS) if P == 1 else (t.R, P, KS)
+        planes = host[: t.R * P * KS].reshape(shape)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        cols = host[head : head + 4 * t.G * KS].view(np.uint32).reshape(t.G, KS, 4).copy()
+        return planes, host[head + 4 * t.G * KS : n].reshape(t.n_ranks, 1 + t.S).copy(), cols
+
+    def tail_group_score(self, ws, tails, table, groups, first_rank: int = 0, n_ranks: Optional[int] = None, min_ranks: int = 2,
+                         q_ppm: int = 0) -> RowGroupScores:
+        return self._family_group_score(TAIL, ws, tails, table, groups, first_rank, n_ranks, min_ranks, (q_ppm,))
+
+    def onset_group_score(self, ws, onsets, table, groups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                          min_ranks: int = 2) -> RowGroupScores:
+        return self._family_group_score(ONSET, ws, onsets, table, groups, first_rank, n_ranks, min_ranks)
+
+    def period_group_score(self, ws, periods, table, groups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                           min_ranks: int = 2) -> RowGroupScores:
+        return self._family_group_score(PERIOD, ws, periods, table, groups, first_rank, n_ranks, min_ranks)
+
+    def episode_group_score(self, ws, episodes, table, groups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                            min_ranks: int = 2) -> RowGroupScores:
+        return self._family_group_score(EPISODE, ws, episodes, table, groups, first_rank, n_ranks, min_ranks)
 
     def family_copy_out(self, t: RowScores):
         """The one wait of a report's row family: a D2H of its table and scores on the backend's stream, behind the kernels."""

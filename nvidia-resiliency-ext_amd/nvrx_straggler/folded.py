@@ -38,7 +38,7 @@ class FoldedJob:
                  node_min_breadth: float = 0.9, node_min_agree: float = 0.75, work_groups: bool = False,
                  work_count_tol: float = 0.25, work_max_unlike: float = 0.1, peer_history: int = 0,
                  peer_persistence_min_reports: int = 3, peer_persistence_thresholds=None, peer_trends: bool = False,
-                 slack_peer_groups: bool = False):
+                 slack_peer_groups: bool = False, row_peer_groups: bool = False):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -69,6 +69,7 @@ class FoldedJob:
                                         pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth,
                                         **({"pace_peer_groups": True} if pace_peer_groups else {}),
                                         **({"slack_peer_groups": True} if slack_peer_groups else {}),
+                                        **({"row_peer_groups": True} if row_peer_groups else {}),
                                         **({"peer_history": peer_history,
                                             "peer_persistence_min_reports": peer_persistence_min_reports,
                                             "peer_persistence_thresholds": peer_persistence_thresholds,

@@ -692,6 +692,59 @@ class _RowFamilySource:
         return self._built
 
 
+class _RowGroupFamilySource(_RowFamilySource):
+    """What a report keeps of one row family's scores per peer group (``ReportGenerator(row_peer_groups=True)``):
+    ``_RowFamilySource``'s, the resolved groups and ``min_peers``.  The handle's ``records()`` delivers the column records
+    ``[G][K+S]`` as well."""
+
+    __slots__ = ("groups", "min_peers")
+
+    def __init__(self, family, handle, ranks, sections, kernels, params: tuple, groups, min_peers: int):
+        super().__init__(family, handle, ranks, sections, kernels, params)
+        self.groups, self.min_peers = groups, min_peers
+
+    def build(self) -> dict:
+        if self._built is None:
+            planes, scores, cols = self.handle.records()
+            self.handle = _Delivered((planes, scores))
+            built = super().build()
+            ranks, labels, min_peers = self.ranks, self.groups.labels, self.min_peers
+            group = self.groups.group.tolist()
+            G, K = len(labels), len(self.kernels)
+            floor = np.ascontiguousarray(cols).view(np.float32)[:, :, 0].tolist()
+            present = cols[:, :, 1].tolist()
+            holder = cols[:, :, 2].view(np.int32).tolist() if cols.size else []
+            sc = scores.tolist()
+
+            def referenced(c):
+                return {labels[g]: {"value": floor[g][c], "rank": holder[g][c], "ranks": present[g][c]}
+                        for g in range(G) if present[g][c] >= min_peers}
+
+            built.update({
+                "peer_groups": True,
+                "min_peers": min_peers,
+                "groups": {labels[g]: self.groups.members(g) for g in range(G)},
+                "group_of": {r: labels[group[r]] for r in ranks},
+                "unrated_ranks": [r for i, r in enumerate(ranks) if all(x != x for x in sc[i])],
+                "section_reference": {name: referenced(K + c) for name, c in self.sections.items()},
+                "kernel_reference": {name: referenced(k) for k, name in enumerate(self.kernels)},
+            })
+            self.groups = None
+        return self._built
+
+
+class _Delivered:
+    """Records that are on the host already, behind a handle's ``records()``."""
+
+    __slots__ = ("_rec",)
+
+    def __init__(self, rec):
+        self._rec = rec
+
+    def records(self):
+        return self._rec
+
+
 def _copy_scores(d: dict) -> dict:
     """A private copy of a report's follow-up scores (plain dicts, floats, ints and bools all the way down)."""
     return {k: _copy_scores(x) if isinstance(x, dict) else x for k, x in d.items()}
@@ -1868,7 +1921,13 @@ class Report:
         return {"straggler_gpus_slack": self._ids(named)}
 
     def _family_scores(self, name: str) -> Dict[str, Any]:
-        """A private copy of one row family's scores (built from the device's planes on first use); ``{}`` without them."""
+        """A private copy of one row family's scores (built from the device's planes on first use); ``{}`` without them.
+
+        With ``ReportGenerator(row_peer_groups=True)`` the reference of a column is the smallest value among the rank's OWN peer
+        group that has the row, and the dict gains ``"peer_groups": True``, ``"min_peers"``, ``"groups"``, ``"group_of"``,
+        ``"unrated_ranks"`` as ``peer_scores()`` spells them, and ``"section_reference"`` / ``"kernel_reference"``: ``{name:
+        {group label: {"value": the group's reference, "rank": the lowest rank that holds it, "ranks": how many of the group
+        have the row}}}`` of the pairs at least ``min_peers`` ranks have."""
         fam = row_families.BY_NAME[name]
         scores = self.__dict__.get(fam.slot)
         if scores is None:
@@ -1878,6 +1937,9 @@ class Report:
         out = _copy_scores(scores)
         for alias, key in fam.aliases:
             out[alias] = out[key]
+        if out.get("peer_groups"):  # (row_peer_groups: the lists are private copies too)
+            out["groups"] = {label: list(members) for label, members in out["groups"].items()}
+            out["unrated_ranks"] = list(out["unrated_ranks"])
         return out
 
     def _identify_relative(self, scores: Mapping[str, Any], gpu_thr: float, sec_thr: float) -> Dict[str, Any]:
@@ -2053,7 +2115,7 @@ class ReportGenerator:
                  node_scores: bool = False, node_groups=None, node_min_members: int = 2, node_min_nodes: int = 3,
                  node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
                  node_min_agree: float = 0.75, work_groups: bool = False, work_count_tol: float = 0.25,
-                 work_max_unlike: float = 0.1, slack_peer_groups: bool = False) -> None:
+                 work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2472,6 +2534,22 @@ class ReportGenerator:
         # any, that needs the ring-start snapshot
         self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
         self._starts_family = next((f for f in self._row_families if f.needs_starts), None)
+        # row families per peer group: the score step of every row family that is on takes a column's reference inside the
+        # rank's OWN group (nvrx_rowfam_group_score); off: the step is the job-wide one, whatever peer_groups says.  The ring
+        # kernels, the send rows and the collectives are the same either way.
+        self.row_peer_groups = bool(row_peer_groups)
+        if self.row_peer_groups:
+            if not self._row_families or self.peer_groups is None:
+                missing = [name for name, on in (("a row family (" + ", ".join(f.option for f in row_families.FAMILIES) + ")",
+                                                  bool(self._row_families)),
+                                                 ("peer_groups", self.peer_groups is not None)) if not on]
+                raise ValueError(f"row_peer_groups needs a row family and peer_groups; {' and '.join(missing)} "
+                                 f"{'is' if len(missing) == 1 else 'are'} not set")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            lacks = [f.name + "_group_score" for f in self._row_families if be is not None and not hasattr(be, f.name + "_group_score")]
+            if lacks:
+                raise RuntimeError(f"row_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   f"has no row-family scores per peer group (backend.{lacks[0]})")
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -3249,6 +3327,16 @@ class ReportGenerator:
             lo = self.rank * local_ranks
             hi = lo + local_ranks
         view = report.__dict__["_src"].view
+        if self.row_peer_groups:
+            grouped = getattr(be, fam.name + "_group_score", None)
+            if grouped is None:
+                raise RuntimeError(f"row_peer_groups: the active backend has no {fam.name} scores per peer group "
+                                   f"(backend.{fam.name}_group_score)")
+            groups = self._peer_for(ws)  # (with "auto": the work groups of this report, whose step has run by now)
+            handle = grouped(ws, table, ws.table, groups, lo, hi - lo, self.peer_min_ranks, *params[:fam.score_params])
+            report.__dict__[fam.slot] = _RowGroupFamilySource(fam, handle, view.ranks, view.cols,
+                                                              self._attr_names(mapper, ws.K), params, groups, self.peer_min_ranks)
+            return
         handle = score(ws, table, ws.table, lo, hi - lo, *params[:fam.score_params])
         report.__dict__[fam.slot] = _RowFamilySource(fam, handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
 

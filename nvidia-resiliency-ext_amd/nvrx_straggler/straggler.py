@@ -446,6 +446,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         pace_min_breadth: float = 0.9,
         pace_peer_groups: Optional[bool] = None,
         slack_peer_groups: Optional[bool] = None,
+        row_peer_groups: Optional[bool] = None,
         node_scores: Optional[bool] = None,
         node_groups=None,
         node_min_members: int = 2,
@@ -604,6 +605,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 (``"auto"`` is allowed); a (group, collective kernel) pair needs ``max(peer_min_ranks, min(slack_min_ranks,
                 its size))`` ranks to be a reference.  A group of two names nobody; a rank alone in its group is unrated.
                 Default: ``NVRX_SLACK_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank.
+            row_peer_groups: every row family that is on (``tail_quantile``, ``onset_detection``, ``period_detection``,
+                ``episode_detection``) takes a column's reference inside each rank's OWN peer group instead of the whole job:
+                tails are absolute times, so the job-wide rule names the healthy ranks of a slower pipeline stage, and a step,
+                a beat or a stretch that one whole stage shares flags that stage.  Needs ``peer_groups`` (``"auto"`` is
+                allowed) and at least one row family; a (group, column) pair needs ``peer_min_ranks`` ranks to be a reference,
+                so a rank alone in its group is unrated.  Nothing else is exchanged.  Default: ``NVRX_ROW_PEER_GROUPS`` ("1";
+                "0" or unset: off).  Same value on every rank.
             node_scores: every report also says whether a NODE is a little slower in nearly all of its kernels -- failed fans,
                 a capped PSU, a throttling host CPU, the wrong power profile: all GPUs of one host lose a few per cent, the
                 pace scores name every one of them, and only a score per node says that they are one incident
@@ -772,6 +780,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
             slack_peer_groups = from_env == "1"
         if slack_peer_groups:
             pace_options["slack_peer_groups"] = True  # (the generator says which of collective_slack and peer_groups it misses)
+        if row_peer_groups is None:
+            from_env = os.environ.get("NVRX_ROW_PEER_GROUPS", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_ROW_PEER_GROUPS must be 0 or 1, got {from_env!r}")
+            row_peer_groups = from_env == "1"
+        if row_peer_groups:
+            pace_options["row_peer_groups"] = True  # (the generator says which of a row family and peer_groups it misses)
         node_options = {}  # (off: the generator is built exactly as before)
         if node_scores is None:
             from_env = os.environ.get("NVRX_NODE_SCORES", "")
