@@ -3,8 +3,8 @@ small exact window they play -- TEST INFRASTRUCTURE, lives outside the product.
 
 ``row_group_records`` restates the contract of include/nvrx_straggler.h (``nvrx_rowfam_group_score``) in NumPy and plain
 Python: block A is ``peer_oracle_backend.peer_columns`` over plane 0, block B one f64 quotient per slot and, for the GPU slot,
-a sequential f64 sum in ascending kernel id.  It shares nothing with the kernels.  ``RowGroupOracleBackend`` is the checker
-with everything a report can carry plus the four ``*_group_score`` methods built on it; ``CountingRowGroupBackend`` has
+a sequential f64 sum in ascending kernel id.  It shares nothing with the kernels.  ``RowGroupOracleBackend`` is
+``PeerHistoryOracleBackend`` plus the four ``*_group_score`` methods built on it (it lacks the slack scores per peer group); ``CountingRowGroupBackend`` has
 grouped methods that only count and raise.
 
 The window (``make`` / ``report``) is tests/row_family_script.py's, doubled: four logical ranks folded into one process, stages
@@ -12,6 +12,9 @@ The window (``make`` / ``report``) is tests/row_family_script.py's, doubled: fou
 beat, stretch); BOTH ranks of stage 1 share a beat (a stage-local stall), and rank 3 alone has the stretch.  Each stage also
 runs a kernel of its own (``gemm_a`` / ``gemm_b``, flat): what ``peer_groups="auto"`` tells the stages apart by, and columns
 that half of the ranks lack.
+
+``RowGroupOracleBackend`` has no ``slack_group_score``: the checker that serves a report with every option on is
+tests/full_oracle_backend.py's ``FullOracleBackend``, and the all-options run is tests/full_report_script.py.
 """
 import numpy as np
 
@@ -71,8 +74,8 @@ class _OracleRowGroup:
 
 
 class RowGroupOracleBackend(PeerHistoryOracleBackend):
-    """The CPU checker with everything a report can carry, the row families per peer group included (computed at enqueue
-    time)."""
+    """The CPU checker up to the peer-score history plus the row families per peer group (computed at enqueue time).  It
+    lacks ``slack_group_score``: a report with ``slack_peer_groups`` too needs ``full_oracle_backend.FullOracleBackend``."""
 
     name = "oracle-test+row-group"
 

@@ -4,8 +4,9 @@ INFRASTRUCTURE, lives outside the product.
 ``slack_group_records`` restates the contract of include/nvrx_straggler.h (``nvrx_slack_group_score``) in NumPy and plain
 Python, the guards of hostile ``d_groups`` contents included: every sum is a SEQUENTIAL f64 sum in ascending column order,
 floors and medians are taken by sorting keys -- nothing is shared with the kernels' wave reductions and selections, and nothing
-reads their output.  ``SlackGroupOracleBackend`` is the checker with everything a report can carry plus
-``slack_group_score``; ``CountingSlackGroupBackend`` has a grouped method that only counts and raises: with the option off
+reads their output.  ``SlackGroupOracleBackend`` is ``PeerHistoryOracleBackend`` plus
+``slack_group_score`` (it lacks the four ``*_group_score`` methods of the row families: the checker that serves a report with
+every option on is tests/full_oracle_backend.py's ``FullOracleBackend``); ``CountingSlackGroupBackend`` has a grouped method that only counts and raises: with the option off
 nobody may call it.  ``stage_scenario`` / ``play_stages`` are the issue's sketch: 8 ranks in two pipeline stages, a
 stage-local all-reduce and a send / receive bubble that differs per stage.
 """
@@ -124,8 +125,9 @@ class _OracleSlackGroup(_OracleSlack):
 
 
 class SlackGroupOracleBackend(PeerHistoryOracleBackend):
-    """The CPU checker with everything a report can carry, the slack scores per peer group included (computed at enqueue
-    time)."""
+    """The CPU checker up to the peer-score history plus the slack scores per peer group (computed at enqueue time).  It
+    lacks the row families' ``*_group_score`` methods: a report with ``row_peer_groups`` too needs
+    ``full_oracle_backend.FullOracleBackend``."""
 
     name = "oracle-test+slack-group"
 

@@ -298,8 +298,8 @@ def test_the_buffer_grows_behind_a_settle_when_there_are_more_groups(be):
         gen2, rings2, rows2 = rg.make(be, KERNELS, peer_groups=(0, 1, 2, 3), peer_min_ranks=1)
         second = rg.report(gen2, rings2, rows2, KERNELS, 1)
         ws2 = gen2._ring_plan.ws
-        if ws2 is ws:
-            assert all(ws._family_state[f.name].buf.numel() > before[f.name] for f in row_families.FAMILIES)
+        assert ws2 is ws  # (the cache is per table shape, across generators: were it not, the growth below would check nothing)
+        assert all(ws._family_state[f.name].buf.numel() > before[f.name] for f in row_families.FAMILIES)
         t1, t2 = first.tail_scores(), second.tail_scores()
         assert t1["groups"] == {0: [0, 1, 2, 3]} and t2["groups"] == {g: [g] for g in range(4)}
         assert t1["section_relative"]["step"] == {0: 1.0, 1: 1.0, 2: float(np.float32(1000.0 / 1500.0)), 3: float(np.float32(1000.0 / 1500.0))}
