@@ -823,7 +823,11 @@ int nvrx_ring_counts(const nvrx_ctx *ctx, int32_t *out, int n);
  * leaves out what holds no samples -- only need rebuilding when this says so.  One call, nothing copied. */
 int nvrx_ring_occupancy_changed(nvrx_ctx *ctx, int n);
 /* Drop all samples of every row: deque.clear (straggler.py:223-225) / reset (CuptiProfiler.cpp:148-152).
- * History minima and row configuration are kept, as in the reference (reporting.py:186-191). */
+ * History minima and row configuration are kept, as in the reference (reporting.py:186-191).
+ * Host state only: nothing is launched and no staging buffer is waited for.  That makes it the ONE ring call allowed while a
+ * report is pending between nvrx_report_issue and nvrx_report_wait: the statistics kernel has its counts already -- as the
+ * uniform-count argument of its launch, or in the device's count table behind the scatter that was enqueued in front of it
+ * on the same stream from a staging buffer this call does not touch. */
 int nvrx_ring_reset(nvrx_ctx *ctx);
 /* Forget the history minima too (new Detector.initialize). */
 int nvrx_history_reset(nvrx_ctx *ctx, void *stream);
@@ -916,6 +920,25 @@ typedef struct nvrx_report_desc {
                                  report's statistics kernel */
 } nvrx_report_desc;
 int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *desc, void *stream);
+/* The synchronous report in two calls, for a caller that has host work of its own to do while the GPU runs (building the
+ * object that will read the result block, emptying the rings): nvrx_report(ctx, desc, stream) with h_seq_word set IS
+ * nvrx_report_issue followed by nvrx_report_wait.
+ * nvrx_report_issue does everything up to the last launch -- re-homing, the resident score kernel's stream, flush,
+ * statistics kernel, the exchange, score kernel -- and decides all of it as a SYNCHRONOUS report (no ring guards, resident
+ * scorer allowed); desc->seq is advanced on return.  NVRX_ERR_INVALID, before any device is touched: a null context or
+ * descriptor, a null buffer, an exchange without a table of its own, or a descriptor without h_seq_word (asynchronous reports
+ * go through nvrx_report).  NVRX_ERR_STATE: a report is already pending on the context.  After a failed issue nothing is
+ * pending.
+ * nvrx_report_wait waits for that report's completion word (desc->timeout_s, NVRX_ERR_TIMEOUT) and does the bookkeeping the
+ * one-call form does behind its wait.  NVRX_ERR_INVALID: null argument; NVRX_ERR_STATE: nothing is pending, or `desc` is not
+ * the pending report's descriptor (that report is given up: its results are not to be read).  After any return nothing is
+ * pending.
+ * Between the two calls the descriptor, the result block and the context's streams are the report's: of this context's
+ * entry points only nvrx_ring_reset may be called (see there), and nothing that enqueues on the context's stream -- the
+ * wait takes the completion word as proof that the context's stream has drained, which holds for nothing enqueued later.
+ * The follow-ups (nvrx_report_attribute, ...) come after the wait. */
+int nvrx_report_issue(nvrx_ctx *ctx, nvrx_report_desc *desc, void *stream);
+int nvrx_report_wait(nvrx_ctx *ctx, nvrx_report_desc *desc);
 /* nvrx_attribute (reporting.py:219-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or
  * d_send without an exchange; shape and families from the descriptor).  The library orders the kernel behind that report's
  * kernels itself: it is enqueued on the context's stream (nvrx_ctx_set_stream), behind an event of the stream the report's

@@ -2101,6 +2101,18 @@ struct nvrx_ctx {
     std::vector<int32_t> slack_list;  // {row, column} pairs as uploaded last
     bool slack_list_up = false;
 
+    // a synchronous report that has been issued and not waited for yet (nvrx_report_issue -> nvrx_report_wait): what the
+    // wait needs -- the descriptor and its sequence number, which of the two tails it takes (resident or queued score kernel,
+    // re-homed or not), the stream the statistics kernel went to, the granule epoch, and the side-work count at the issue
+    // (the completion word vouches for nothing that was enqueued on the context's stream after it)
+    struct PendingReport {
+        nvrx_report_desc *desc = nullptr;
+        uint32_t seq = 0, gran_epoch = 0;
+        bool resident = false, rehomed = false;
+        hipStream_t stream = nullptr;
+        uint64_t side_gen = 0;
+    } pending_report;
+
     std::mutex mu;
 };
 
@@ -3375,13 +3387,20 @@ int nvrx_report_clocks(double *out8) {
     return NVRX_OK;
 }
 
-int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
-    report_clk(0);
+// What every form of the report checks first, before any device is touched.
+static int report_check_args(const nvrx_ctx *ctx, const nvrx_report_desc *d) {
     if (!ctx || !d) return fail(NVRX_ERR_INVALID, "null argument");
     if (!d->d_stats || !d->d_send || !d->d_scores || !d->d_meta) return fail(NVRX_ERR_INVALID, "null buffer in the report descriptor");
-    const bool exchanging = d->allgather_fn != nullptr;
-    if (exchanging && (!d->d_table || d->d_table == d->d_send || d->send_count <= 0))
+    if (d->allgather_fn != nullptr && (!d->d_table || d->d_table == d->d_send || d->send_count <= 0))
         return fail(NVRX_ERR_INVALID, "an exchange needs a separate table buffer and a positive send_count");
+    return NVRX_OK;
+}
+
+// Everything of a report up to its last launch (clocks 1..5): the re-homing decision, the resident-scorer decision and its
+// stream, the statistics kernel, the exchange or the peer prologue, the score kernel.  `out` says what was decided -- what
+// the wait of a synchronous report (nvrx_report_wait) and the tail of an asynchronous one (nvrx_report) go by.
+static int report_enqueue(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream, nvrx_ctx::PendingReport *out) {
+    const bool exchanging = d->allgather_fn != nullptr;
     // Re-homing.  A synchronous report that has to follow the work of exactly ONE other stream -- the stream the
     // region stamps of this window were launched on and / or the caller's current stream -- is enqueued ON that stream:
     // the stream order is the dependency, and the report issues nothing but kernel launches.  The event record +
@@ -3532,17 +3551,7 @@ int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
         ctx->attr_desc = d, ctx->attr_stream = ctx->score_stream;  // (for nvrx_report_attribute)
         report_clk(4);
         report_clk(5);
-        rc2 = nvrx_poll_u32(d->h_seq_word, d->seq, d->timeout_s > 0.0 ? d->timeout_s : 1e30);
-        report_clk(6);
-        if (rc2) return rc2;
-        if (*static_cast<volatile uint32_t *>(ctx->h_gather_err) == ctx->gran_epoch)
-            return fail(NVRX_ERR_TIMEOUT, "the score kernel gave up waiting for the statistics kernel's rows (epoch %u)", ctx->gran_epoch);
-        if (as_stream(stream) == ctx->default_stream) {
-            // every row's granules were consumed: the statistics kernel, last on the context's in-order stream, is done
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            ctx->side_work = false;
-            ctx->async_on_ctx = false;
-        }
+        out->resident = true, out->rehomed = rehomed, out->stream = as_stream(stream), out->gran_epoch = ctx->gran_epoch;
         return NVRX_OK;
     }
     int rc = report_local_impl(ctx, d->d_stats, d->d_send, d->K, d->S, d->names_ok, d->rows_active, stream, nullptr, 0);
@@ -3590,19 +3599,70 @@ int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
     if (rc) return rc;
     ctx->attr_desc = d, ctx->attr_stream = as_stream(stream);  // (for nvrx_report_attribute)
     report_clk(5);
-    if (d->h_seq_word) {
-        rc = nvrx_poll_u32(d->h_seq_word, d->seq, d->timeout_s > 0.0 ? d->timeout_s : 1e30);
-        report_clk(6);
-        if (rc == NVRX_OK && !rehomed && as_stream(stream) == ctx->default_stream) {
-            // the completion word was stored by the last kernel of this report on the context's own in-order stream:
-            // everything of ours enqueued there before it has finished
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            ctx->side_work = false;
-            ctx->async_on_ctx = false;
-        }
-        return rc;
+    out->resident = false, out->rehomed = rehomed, out->stream = as_stream(stream), out->gran_epoch = 0;
+    return NVRX_OK;
+}
+
+int nvrx_report_issue(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
+    report_clk(0);
+    int rc = report_check_args(ctx, d);
+    if (rc) return rc;
+    if (!d->h_seq_word)
+        return fail(NVRX_ERR_INVALID, "nvrx_report_issue needs a completion word (h_seq_word): asynchronous reports go through nvrx_report");
+    if (ctx->pending_report.desc) return fail(NVRX_ERR_STATE, "a report is pending on this context: nvrx_report_wait comes first");
+    nvrx_ctx::PendingReport p;
+    {
+        // (the completion word will vouch for the side work counted so far, not for what is enqueued behind the report)
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        p.side_gen = ctx->side_gen;
     }
-    if (!rehomed) {
+    rc = report_enqueue(ctx, d, stream, &p);
+    if (rc) return rc;
+    p.desc = d, p.seq = d->seq;
+    ctx->pending_report = p;
+    return NVRX_OK;
+}
+
+int nvrx_report_wait(nvrx_ctx *ctx, nvrx_report_desc *d) {
+    if (!ctx || !d) return fail(NVRX_ERR_INVALID, "null argument");
+    if (!ctx->pending_report.desc) return fail(NVRX_ERR_STATE, "no report is pending on this context");
+    const nvrx_ctx::PendingReport p = ctx->pending_report;
+    ctx->pending_report = nvrx_ctx::PendingReport();  // whatever this call returns, nothing is pending afterwards
+    if (p.desc != d) return fail(NVRX_ERR_STATE, "the report pending on this context was issued through another descriptor");
+    const int rc = nvrx_poll_u32(d->h_seq_word, p.seq, d->timeout_s > 0.0 ? d->timeout_s : 1e30);
+    report_clk(6);
+    if (rc) return rc;
+    if (p.resident) {
+        if (*static_cast<volatile uint32_t *>(ctx->h_gather_err) == p.gran_epoch)
+            return fail(NVRX_ERR_TIMEOUT, "the score kernel gave up waiting for the statistics kernel's rows (epoch %u)", p.gran_epoch);
+        // every row's granules were consumed: the statistics kernel, last on the context's in-order stream, is done
+        if (p.stream != ctx->default_stream) return NVRX_OK;
+    } else if (p.rehomed || p.stream != ctx->default_stream) {
+        return NVRX_OK;
+    }
+    // the completion word was stored by the last kernel of this report on the context's own in-order stream (the resident
+    // scorer's: behind the last row of the statistics kernel there): everything of ours enqueued there before the report has
+    // finished -- and nothing is known of what went there since the issue
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->side_gen == p.side_gen) {
+        ctx->side_work = false;
+        ctx->async_on_ctx = false;
+    }
+    return NVRX_OK;
+}
+
+int nvrx_report(nvrx_ctx *ctx, nvrx_report_desc *d, void *stream) {
+    if (ctx && d && d->h_seq_word) {  // synchronous: the two phases back to back
+        const int rc = nvrx_report_issue(ctx, d, stream);
+        return rc ? rc : nvrx_report_wait(ctx, d);
+    }
+    report_clk(0);
+    int rc = report_check_args(ctx, d);
+    if (rc) return rc;
+    nvrx_ctx::PendingReport p;
+    rc = report_enqueue(ctx, d, stream, &p);
+    if (rc) return rc;
+    if (!p.rehomed) {
         std::lock_guard<std::mutex> lk(ctx->mu);
         ctx->async_on_ctx = true;  // an asynchronous report is in flight on the context's own stream,
         ctx->async_gen = ctx->side_gen;  // behind all the side work counted so far

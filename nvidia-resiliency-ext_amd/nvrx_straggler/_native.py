@@ -151,6 +151,8 @@ SYMBOLS = [
     ("nvrx_stamp_end", c_int, [c_void_p, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_local", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report", c_int, [c_void_p, POINTER(ReportDesc), c_void_p]),
+    ("nvrx_report_issue", c_int, [c_void_p, POINTER(ReportDesc), c_void_p]),
+    ("nvrx_report_wait", c_int, [c_void_p, POINTER(ReportDesc)]),
     ("nvrx_report_attribute", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_tail_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_onset_enable", c_int, [c_void_p, c_int]),

@@ -1751,14 +1751,11 @@ class HipRings:
         d.resident = 1 if (wait and resident) else 0
         blk.desc_key = key
 
-    def report_fused(self, ws: Workspace, rows_active: int, stats_rows: int, do_indiv: bool, do_rel: bool,
-                     thresholds: Sequence[float], direct=None, names_ok: bool = True, wait: bool = True,
-                     order_after: Optional[int] = None, resident: bool = True, prev_settled: bool = False) -> int:
-        """The whole report in one C call (``nvrx_report``): flush -> statistics kernel -> [``ncclAllGather`` of the
-        exchange rows through ``direct``] -> score kernel -> wait for the completion word.  On return
-        ``ws.scores / flags / meta / stats`` hold this report's values.  ``wait=False`` only enqueues (asynchronous
-        report): the caller waits for the returned sequence number with ``backend.wait_seq`` later, and ring writers on
-        other streams are ordered after the statistics kernel on the device."""
+    def _report_prepare(self, ws: Workspace, rows_active: int, stats_rows: int, do_indiv: bool, do_rel: bool,
+                        thresholds: Sequence[float], direct, names_ok: bool, wait: bool, order_after: Optional[int],
+                        resident: bool, prev_settled: bool) -> ResultBlock:
+        """What every form of the one-call report does before its C call: flip to this report's result block, bring its
+        descriptor up to date, initialise the exchange rows when they are new.  Returns the block."""
         blk = ws.flip()  # this report's result block; the previous report's block stays readable for one more report
         d = blk.desc
         key = (rows_active, stats_rows, do_indiv, do_rel, thresholds, direct, names_ok, wait, resident)
@@ -1777,13 +1774,50 @@ class HipRings:
             self.backend.send_init(ws)
             self.backend.synchronize()  # cold: a resident score kernel touches the exchange rows from its own stream
         d.seq = ws.seq
+        return blk
+
+    def report_fused(self, ws: Workspace, rows_active: int, stats_rows: int, do_indiv: bool, do_rel: bool,
+                     thresholds: Sequence[float], direct=None, names_ok: bool = True, wait: bool = True,
+                     order_after: Optional[int] = None, resident: bool = True, prev_settled: bool = False) -> int:
+        """The whole report in one C call (``nvrx_report``): flush -> statistics kernel -> [``ncclAllGather`` of the
+        exchange rows through ``direct``] -> score kernel -> wait for the completion word.  On return
+        ``ws.scores / flags / meta / stats`` hold this report's values.  ``wait=False`` only enqueues (asynchronous
+        report): the caller waits for the returned sequence number with ``backend.wait_seq`` later, and ring writers on
+        other streams are ordered after the statistics kernel on the device."""
+        blk = self._report_prepare(ws, rows_active, stats_rows, do_indiv, do_rel, thresholds, direct, names_ok, wait,
+                                   order_after, resident, prev_settled)
         rc = self.lib.nvrx_report(self.ctx, blk.desc_ref, self.backend._stream_handle)
-        ws.seq = d.seq
+        ws.seq = blk.desc.seq
         if rc < 0:
             if rc == _native.ERR_TIMEOUT:
                 self.backend.retire_workspace(ws)
             _native.check(rc)
         return ws.seq
+
+    def report_issue(self, ws: Workspace, rows_active: int, stats_rows: int, do_indiv: bool, do_rel: bool,
+                     thresholds: Sequence[float], direct=None, names_ok: bool = True, order_after: Optional[int] = None,
+                     resident: bool = True) -> int:
+        """The synchronous ``report_fused`` up to its last launch (``nvrx_report_issue``): everything is enqueued, nothing is
+        waited for.  Returns the report's sequence number; ``report_wait(ws)`` must follow, and between the two the caller
+        does host work only -- of these rings nothing but ``reset()`` may be called (include/nvrx_straggler.h)."""
+        blk = self._report_prepare(ws, rows_active, stats_rows, do_indiv, do_rel, thresholds, direct, names_ok, True,
+                                   order_after, resident, False)
+        rc = self.lib.nvrx_report_issue(self.ctx, blk.desc_ref, self.backend._stream_handle)
+        ws.seq = blk.desc.seq
+        if rc < 0:
+            _native.check(rc)
+        return ws.seq
+
+    def report_wait(self, ws: Workspace) -> None:
+        """Wait for the report ``report_issue`` enqueued on ``ws`` (``nvrx_report_wait``).  On return ``ws.scores / flags /
+        meta / stats`` hold its values.  When it raises, the block is nobody's -- whatever the caller attached to it in
+        between is let go, as if ``report_fused`` had raised -- and a timeout retires the workspace."""
+        rc = self.lib.nvrx_report_wait(self.ctx, ws.block.desc_ref)
+        if rc < 0:
+            ws.block._live = None
+            if rc == _native.ERR_TIMEOUT:
+                self.backend.retire_workspace(ws)
+            _native.check(rc)
 
     def report_attribute(self, ws: Workspace, top_n: int, first_rank: int = 0, n_ranks: Optional[int] = None) -> Attribution:
         """Kernel attribution of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_attribute``):

@@ -115,11 +115,9 @@ class FoldedJob:
         self.rings.set_count_all(n)
 
     def report(self, reset: bool = True):
-        rep = self.reporter.generate_report_from_rings(self.rings, self.rows, self._no_kernel_rows,
-                                                       local_ranks=self.local_ranks)
-        if reset:
-            self.rings.reset()
-        return rep
+        # (reset: the generator empties the rings itself, while the GPU runs where the report allows it)
+        return self.reporter.generate_report_from_rings(self.rings, self.rows, self._no_kernel_rows,
+                                                        local_ranks=self.local_ranks, reset_rings=reset)
 
     def close(self) -> None:
         self.reporter.close()

@@ -2153,6 +2153,11 @@ class ReportGenerator:
         self._resync_pending = False  # some rank's table said "ids missing": no plan, no lane; the general path syncs names first
         self._had_ring_report = False  # a ring report has reached its score round (collective: the same on every rank)
         self._unreported_rows: list = []  # see take_unreported_rows
+        # a synchronous one-call report is issued, its Report built (and the rings emptied, when the caller asked) while the
+        # GPU runs, and only then waited for -- where the rings can (report_issue / report_wait) and no exchange runs inside
+        # the call; NVRX_DEBUG_REPORT_SPLIT=0 (read here, once) keeps the one call
+        self._report_split = os.environ.get("NVRX_DEBUG_REPORT_SPLIT", "1") != "0"
+        self._rings_were_reset = False  # the planned report that just ran emptied the rings itself (reset_rings)
         # kernel attribution: every report also names the top-N kernels behind each GPU score (Report.explain_gpu_scores); 0 = off:
         # no buffer, no launch, no backend call.  Every rank should pass the same value (it changes no collective, so a
         # mismatch cannot hang anything: a rank's own reports simply carry what that rank asked for)
@@ -2959,9 +2964,11 @@ class ReportGenerator:
         if check is not None:
             check()
 
-    def _report_from_plan(self, plan, rings, t0, order_after=None, names_ok: bool = True):
+    def _report_from_plan(self, plan, rings, t0, order_after=None, names_ok: bool = True, reset_rings: bool = False):
         """The steady-state report: ONE C call (statistics kernel, the collective, score kernel, wait), one host
-        copy of the result block, mappings built on first read.  Asynchronous generators only enqueue."""
+        copy of the result block, mappings built on first read.  Asynchronous generators only enqueue.  A synchronous
+        report without an exchange is issued and waited for in two calls where the rings can, with the Report built in
+        between (``_report_split``)."""
         be = _backend_mod.get_backend()
         ws = plan.ws
         multi = self.world_size > 1 and self._exchanged()
@@ -2996,6 +3003,10 @@ class ReportGenerator:
         if fused:
             # ONE C call: flush -> statistics kernel -> [ncclAllGather] -> score kernel -> completion word
             wait = not self.asynchronous
+            if wait and not multi and self._report_split:
+                issue = getattr(rings, "report_issue", None)  # (the CPU checker backends of the tests have the one call only)
+                if issue is not None:
+                    return self._report_split_from_plan(plan, rings, be, t0, issue, names_ok, reset_rings)
             seq = rings.report_fused(ws, plan.rows_used, plan.stats_needed, self.is_computing_indiv_scores,
                                      self.is_computing_rel_scores, self.thresholds, self._direct if multi else None,
                                      names_ok=names_ok, wait=wait, order_after=order_after if multi else None,
@@ -3070,6 +3081,54 @@ class ReportGenerator:
             self._attach_plan_node(report, plan, rings, fused)
         if self._history is not None:
             self._attach_plan_history(report, plan, rings, fused)
+        return report
+
+    def _report_split_from_plan(self, plan, rings, be, t0, issue, names_ok: bool, reset_rings: bool):
+        """``_report_from_plan`` for a synchronous one-call report of a single process, in two C calls: issue (both launches),
+        build on the host what needs none of the results -- the live block, the Report, the emptied rings -- while the GPU
+        runs, wait, look at ``meta[0]``.  Every way out leaves what the one-call path leaves: a wait that raises leaves the
+        block nobody's (``rings.report_wait``) and the caller drops the plan; "ids missing" leaves it as ``mark_live`` does.
+        The follow-up kernels of the per-report options are enqueued behind the wait, where the one-call path enqueues them:
+        the library takes the completion word as proof that its stream has drained, which holds for nothing enqueued
+        in between."""
+        ws = plan.ws
+        seq = issue(ws, plan.rows_used, plan.stats_needed, self.is_computing_indiv_scores, self.is_computing_rel_scores,
+                    self.thresholds, None, names_ok=names_ok, order_after=None, resident=True)
+        report = None
+        if not (self.gather_on_rank0 and self.rank != 0):
+            pending = _LiveBlock(be, ws, seq, plan.stats_needed)
+            ws.attach(pending)  # the workspace collects it (if still held) before the block is reused by anybody
+            report = Report._from_device(_ScoreSource(plan.view, pending), self._shared_rank_to_node(), 0.0,
+                                         self.gather_on_rank0, self.rank)
+        if reset_rings and not self._row_families and not self.collective_slack:
+            # the statistics kernel has its counts (include/nvrx_straggler.h, nvrx_ring_reset); the steps that read the
+            # rings again after the report -- row families, slack -- are off, and so is the general path: "ids missing" comes
+            # out of another process' row or out of names_ok=False, which only an asynchronous report passes
+            rings.reset()
+            self._rings_were_reset = True
+        rings.report_wait(ws)
+        if report is None or ws.meta[0] != 1:
+            mark = getattr(ws, "mark_live", None)
+            if mark is not None:
+                mark(seq)  # nobody holds this report: the block's next user still has to see its statistics rows land
+            if ws.meta[0] != 1:
+                return False  # (a name without an id: the general path; the Report built above is let go here)
+            return None
+        report.__dict__["generate_report_elapsed_time"] = (time.perf_counter_ns() - t0) * 1e-6
+        if self.kernel_attribution:
+            self._attach_plan_attribution(report, plan, rings, True)
+        if self.robust_scores:
+            self._attach_plan_robust(report, plan, rings, True)
+        if self.work_groups:
+            self._attach_plan_work(report, plan, rings, True)
+        if self.peer_groups is not None:
+            self._attach_plan_peer(report, plan, rings, True)
+        if self.pace_scores:
+            self._attach_plan_pace(report, plan, rings, True)
+        if self.node_scores:
+            self._attach_plan_node(report, plan, rings, True)
+        if self._history is not None:
+            self._attach_plan_history(report, plan, rings, True)
         return report
 
     def _attach_plan_attribution(self, report, plan, rings, fused: bool) -> None:
@@ -3436,7 +3495,7 @@ class ReportGenerator:
 
     # ---- internal: summaries never leave the device (Detector path) -----------------------------------
     def generate_report_from_rings(self, rings, section_rows: Mapping[str, int], kernel_rows: Mapping[str, int],
-                                   local_ranks: int = 1, order_after: Optional[int] = None):
+                                   local_ranks: int = 1, order_after: Optional[int] = None, reset_rings: bool = False):
         """Report straight from the device rings: statistics kernel -> exchange -> score kernel.
 
         ``section_rows`` / ``kernel_rows`` map the names that hold samples this window to their ring
@@ -3444,6 +3503,8 @@ class ReportGenerator:
         of the reference (straggler.py:236-239) without materialising per-section Python objects.
         ``order_after``: raw ``hipStream_t`` of the caller's current stream; a multi-rank report is ordered after the
         work already enqueued there (the collectives of the training step) on the device, without a host wait.
+        ``reset_rings``: empty the rings (``rings.reset()``) once the report has what it needs of them -- while the GPU
+        runs, where the report is issued and waited for in two calls; before returning, on every other path.
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
@@ -3464,15 +3525,22 @@ class ReportGenerator:
         plan = self._ring_plan
         if plan is not None and plan.key == self._plan_key(rings, section_rows, kernel_rows, local_ranks):
             try:
-                out = self._report_from_plan(plan, rings, t0, order_after)
+                out = self._report_from_plan(plan, rings, t0, order_after, True, reset_rings)
             except Exception:
+                self._rings_were_reset = False
                 self._drop_plan()
                 raise
             if out is not False:
                 self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 if self.collective_slack:
                     self._slack_step(out, rings, plan.ws, plan.rows_used, self._last_plan_fused, local_ranks)
+                if reset_rings:
+                    if self._rings_were_reset:
+                        self._rings_were_reset = False
+                    else:
+                        rings.reset()
                 return out
+            self._rings_were_reset = False  # (the general path below empties them at its end)
             self._sync_names_first()  # some OTHER rank met a new name during this report's exchange
         elif (plan is not None and self.enqueue_only() and plan.fused and plan.topology == self._plan_topology(rings, local_ranks)
               and not plan.mapper.has_all_names(list(kernel_rows.keys()), list(section_rows.keys()))):
@@ -3488,6 +3556,8 @@ class ReportGenerator:
             self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             if self.collective_slack:
                 self._slack_step(out, rings, plan.ws, plan.rows_used, self._last_plan_fused, local_ranks)
+            if reset_rings:
+                rings.reset()
             return out
         kernel_rows = {k: r for k, r in kernel_rows.items() if not is_collective_kernel(k)} if any(
             is_collective_kernel(k) for k in kernel_rows) else kernel_rows
@@ -3521,4 +3591,6 @@ class ReportGenerator:
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)
+        if reset_rings:
+            rings.reset()
         return report
