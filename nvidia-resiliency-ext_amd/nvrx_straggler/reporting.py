@@ -2078,6 +2078,19 @@ class _DeviceFlags:
         return gr, gi, sr, si
 
 
+def steps_behind_report(generator) -> tuple:
+    """Whether steps follow a report of ``generator``: ``(any table follow-up, any ring step)``, by its options alone
+    (``peer_history``, the trends and the per-peer-group variants need one of these).  The generator asks once, in its
+    ``__init__``; ``straggler._Lane.build`` asks for whatever it is handed, so an option that is not there counts as off."""
+    table = bool(getattr(generator, "kernel_attribution", 0) or getattr(generator, "robust_scores", False)
+                 or getattr(generator, "work_groups", False) or getattr(generator, "peer_groups", None) is not None
+                 or getattr(generator, "pace_scores", False) or getattr(generator, "node_scores", False)
+                 or getattr(generator, "score_history", 0))
+    ring = bool(any(getattr(generator, fam.param_attrs[0], 0) for fam in row_families.FAMILIES)
+                or getattr(generator, "collective_slack", False))
+    return table, ring
+
+
 class ReportGenerator:
     """Builds :class:`Report` objects; every rank of the group must call ``generate_report`` together.
 
@@ -2555,6 +2568,17 @@ class ReportGenerator:
             if lacks:
                 raise RuntimeError(f"row_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    f"has no row-family scores per peer group (backend.{lacks[0]})")
+        # what follows a report, decided here once (nothing assigns the options later): whether any table follow-up
+        # (_follow_ups) is on, whether any ring step (_ring_steps) is, and what the one-call route needs of its rings
+        self._table_steps_on, self._ring_steps_on = steps_behind_report(self)
+        pace = ("pace_peer_groups", "report_pace_group") if self.pace_peer_groups else ("pace_scores", "report_pace")
+        self._one_call_needs = tuple((option, method) for on, option, method in (
+            (self.kernel_attribution, f"kernel_attribution={self.kernel_attribution}", "report_attribute"),
+            (self.robust_scores, "robust_scores", "report_robust"),
+            (self.work_groups, "work_groups", "report_work"), (self.peer_groups is not None, "peer_groups", "report_peer"),
+            (self.pace_scores,) + pace, (self.node_scores, "node_scores", "report_node"),
+            (self.peer_history, "peer_history", "report_peer_history"), (self.peer_trends, "peer_trends", "report_peer_trend"),
+            (self.score_history, "score_history", "report_history"), (self.score_trends, "score_trends", "report_trend")) if on)
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
 
@@ -2620,7 +2644,7 @@ class ReportGenerator:
         from . import peer_exchange, rccl_direct
 
         mode = peer_exchange.exchange_mode()
-        if self._row_families or self.collective_slack:
+        if self._ring_steps_on:
             # a row family's collective -- and the slack step's -- is a torch.distributed call between two kernels: reports
             # with one stay on that route as a whole (the option has the same value on every rank, so every rank decides alike
             # -- no collective here).  A row family that is on is the one named.
@@ -2791,48 +2815,8 @@ class ReportGenerator:
         src.stats = stats
         report = Report._from_device(src, self._shared_rank_to_node(), (time.perf_counter_ns() - t_start_ns) * 1e-6,
                                      self.gather_on_rank0, self.rank)
-        if self.kernel_attribution:
-            # enqueued behind the score kernel on the backend's stream; waited for when the report is first asked
-            handle = _backend_mod.get_backend().attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
-                                                          self.is_computing_rel_scores, lo, hi - lo)
-            report.__dict__["_attr"] = self._attr_source(handle, ws, mapper, lo, hi, view.ranks)
-        if self.robust_scores:
-            # likewise: enqueued behind the score kernel, waited for when the report is first asked
-            self._attach_robust(report, _backend_mod.get_backend().robust_score(
-                ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor), ws, mapper, view)
-        if self.work_groups:
-            # likewise, ahead of the peer step, which peer_groups="auto" makes wait for it
-            self._attach_work(report, _backend_mod.get_backend().work_groups(
-                ws, ws.table, self.work_count_tol, self.work_max_unlike_ppm), ws, view)
-        if self.peer_groups is not None:
-            # likewise, behind the robust step
-            groups = self._peer_for(ws)
-            handle = _backend_mod.get_backend().peer_score(ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks)
-            self._attach_peer(report, handle, groups, ws, mapper, view)
-            if self._peer_history is not None:
-                # ... and the history of the peer scores, directly behind the step that left them
-                self._attach_peer_history(report, ws, handle, view, None)
-        if self.pace_scores:
-            # likewise, behind the robust and peer steps
-            if self.pace_peer_groups:
-                groups = self._peer_for(ws)
-                self._attach_pace(report, _backend_mod.get_backend().pace_group_score(
-                    ws, ws.table, groups, lo, hi - lo, self._pace_min(ws), self.peer_min_ranks), ws, mapper, view, groups)
-            else:
-                self._attach_pace(report, _backend_mod.get_backend().pace_score(
-                    ws, ws.table, lo, hi - lo, self._pace_min(ws)), ws, mapper, view)
-        if self.node_scores:
-            # likewise, behind the pace step
-            nodes = self._node_for(ws)
-            self._attach_node(report, _backend_mod.get_backend().node_score(
-                ws, ws.table, nodes, lo, hi - lo, self.node_min_members, self._node_min(nodes)), nodes, ws, mapper, view)
-        if self._history is not None:
-            # likewise; the ring takes the scores of every report this rank holds, once, behind its last score kernel
-            self._attach_history(report, _backend_mod.get_backend().score_history(
-                ws, self._history, lo, hi - lo, self.persistence_thresholds), view)
-            if self.score_trends:
-                # ... and the trends of the ring as that step leaves it, behind it
-                self._attach_trends(report, _backend_mod.get_backend().score_trend(ws, self._history), view)
+        if self._table_steps_on:
+            self._follow_ups(report, ws, mapper, view, lo, hi, None)
         if stats is None:
             # the caller's own summaries travel with the report, untouched
             report.__dict__["local_section_summaries"] = section_summaries
@@ -2973,33 +2957,15 @@ class ReportGenerator:
         ws = plan.ws
         multi = self.world_size > 1 and self._exchanged()
         fused = plan.fused and (not multi or self._direct is not None)
-        attr_n = self.kernel_attribution
+        follow_ups = self._table_steps_on
         settle = getattr(ws, "settle_readers", None)  # (the CPU checker backend of the tests has no deferred readers)
         if settle is not None:
             settle()  # a follow-up kernel of the last report may still be reading the table that is about to be rewritten
         self._last_plan_fused = fused
-        if fused and attr_n and not hasattr(rings, "report_attribute"):
-            raise RuntimeError(f"kernel_attribution={attr_n}: these rings run the one-call report but have no report_attribute")
-        if fused and self.robust_scores and not hasattr(rings, "report_robust"):
-            raise RuntimeError("robust_scores: these rings run the one-call report but have no report_robust")
-        if fused and self.work_groups and not hasattr(rings, "report_work"):
-            raise RuntimeError("work_groups: these rings run the one-call report but have no report_work")
-        if fused and self.peer_groups is not None and not hasattr(rings, "report_peer"):
-            raise RuntimeError("peer_groups: these rings run the one-call report but have no report_peer")
-        if fused and self.pace_scores and not hasattr(rings, "report_pace_group" if self.pace_peer_groups else "report_pace"):
-            if self.pace_peer_groups:
-                raise RuntimeError("pace_peer_groups: these rings run the one-call report but have no report_pace_group")
-            raise RuntimeError("pace_scores: these rings run the one-call report but have no report_pace")
-        if fused and self.node_scores and not hasattr(rings, "report_node"):
-            raise RuntimeError("node_scores: these rings run the one-call report but have no report_node")
-        if fused and self._peer_history is not None and not hasattr(rings, "report_peer_history"):
-            raise RuntimeError("peer_history: these rings run the one-call report but have no report_peer_history")
-        if fused and self.peer_trends and not hasattr(rings, "report_peer_trend"):
-            raise RuntimeError("peer_trends: these rings run the one-call report but have no report_peer_trend")
-        if fused and self._history is not None and not hasattr(rings, "report_history"):
-            raise RuntimeError("score_history: these rings run the one-call report but have no report_history")
-        if fused and self.score_trends and not hasattr(rings, "report_trend"):
-            raise RuntimeError("score_trends: these rings run the one-call report but have no report_trend")
+        if follow_ups and fused:
+            for option, method in self._one_call_needs:  # (before anything of this report is issued)
+                if not hasattr(rings, method):
+                    raise RuntimeError(f"{option}: these rings run the one-call report but have no {method}")
         if fused:
             # ONE C call: flush -> statistics kernel -> [ncclAllGather] -> score kernel -> completion word
             wait = not self.asynchronous
@@ -3023,20 +2989,9 @@ class ReportGenerator:
                     _ScoreSource(plan.view, pend),
                     self._shared_rank_to_node(),
                     (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
-                if attr_n:
-                    self._attach_plan_attribution(report, plan, rings, True)
-                if self.robust_scores:
-                    self._attach_plan_robust(report, plan, rings, True)
-                if self.work_groups:
-                    self._attach_plan_work(report, plan, rings, True)
-                if self.peer_groups is not None:
-                    self._attach_plan_peer(report, plan, rings, True)
-                if self.pace_scores:
-                    self._attach_plan_pace(report, plan, rings, True)
-                if self.node_scores:
-                    self._attach_plan_node(report, plan, rings, True)
-                if self._history is not None:
-                    self._attach_plan_history(report, plan, rings, True)
+                if follow_ups:
+                    view = plan.view
+                    self._follow_ups(report, ws, plan.mapper, view, view.layout[5], view.layout[6], rings)
                 return report
         else:
             rings.report_local(ws, True, rows_active=plan.rows_used)
@@ -3067,20 +3022,9 @@ class ReportGenerator:
             _ScoreSource(plan.view, pending),
             self._shared_rank_to_node(),
             (time.perf_counter_ns() - t0) * 1e-6, self.gather_on_rank0, self.rank)
-        if attr_n:
-            self._attach_plan_attribution(report, plan, rings, fused)
-        if self.robust_scores:
-            self._attach_plan_robust(report, plan, rings, fused)
-        if self.work_groups:
-            self._attach_plan_work(report, plan, rings, fused)
-        if self.peer_groups is not None:
-            self._attach_plan_peer(report, plan, rings, fused)
-        if self.pace_scores:
-            self._attach_plan_pace(report, plan, rings, fused)
-        if self.node_scores:
-            self._attach_plan_node(report, plan, rings, fused)
-        if self._history is not None:
-            self._attach_plan_history(report, plan, rings, fused)
+        if follow_ups:
+            view = plan.view
+            self._follow_ups(report, ws, plan.mapper, view, view.layout[5], view.layout[6], rings if fused else None)
         return report
 
     def _report_split_from_plan(self, plan, rings, be, t0, issue, names_ok: bool, reset_rings: bool):
@@ -3100,7 +3044,7 @@ class ReportGenerator:
             ws.attach(pending)  # the workspace collects it (if still held) before the block is reused by anybody
             report = Report._from_device(_ScoreSource(plan.view, pending), self._shared_rank_to_node(), 0.0,
                                          self.gather_on_rank0, self.rank)
-        if reset_rings and not self._row_families and not self.collective_slack:
+        if reset_rings and not self._ring_steps_on:
             # the statistics kernel has its counts (include/nvrx_straggler.h, nvrx_ring_reset); the steps that read the
             # rings again after the report -- row families, slack -- are off, and so is the general path: "ids missing" comes
             # out of another process' row or out of names_ok=False, which only an asynchronous report passes
@@ -3115,55 +3059,111 @@ class ReportGenerator:
                 return False  # (a name without an id: the general path; the Report built above is let go here)
             return None
         report.__dict__["generate_report_elapsed_time"] = (time.perf_counter_ns() - t0) * 1e-6
-        if self.kernel_attribution:
-            self._attach_plan_attribution(report, plan, rings, True)
-        if self.robust_scores:
-            self._attach_plan_robust(report, plan, rings, True)
-        if self.work_groups:
-            self._attach_plan_work(report, plan, rings, True)
-        if self.peer_groups is not None:
-            self._attach_plan_peer(report, plan, rings, True)
-        if self.pace_scores:
-            self._attach_plan_pace(report, plan, rings, True)
-        if self.node_scores:
-            self._attach_plan_node(report, plan, rings, True)
-        if self._history is not None:
-            self._attach_plan_history(report, plan, rings, True)
+        if self._table_steps_on:
+            view = plan.view
+            self._follow_ups(report, ws, plan.mapper, view, view.layout[5], view.layout[6], rings)
         return report
 
-    def _attach_plan_attribution(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the attribution of the planned report that was just issued (the one-call report: ordered behind its
-        kernels by the library; the stepwise one: behind the score kernel on the backend's stream) and hang it on
-        ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        lo, hi = plan.view.layout[5], plan.view.layout[6]
-        if fused:
-            handle = rings.report_attribute(ws, self.kernel_attribution, lo, hi - lo)
-        else:
-            handle = _backend_mod.get_backend().attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
-                                                          self.is_computing_rel_scores, lo, hi - lo)
-        report.__dict__["_attr"] = self._attr_source(handle, ws, plan.mapper, lo, hi, plan.view.ranks)
+    # ---- the table follow-ups of a report: every route's, in the one order ----------------------------
+    def _follow_ups(self, report, ws, mapper, view, lo: int, hi: int, rings) -> None:
+        """Enqueue every table follow-up that is switched on behind the report that was just issued on ``ws``, for the ranks
+        ``[lo, hi)`` it covers, and hang each on ``report`` unread.  Nothing is waited for (but ``peer_groups="auto"``: its
+        groups are the work step's records).  ``rings``: the one-call report's rings, whose ``report_<x>`` entries the library
+        orders behind that report's kernels; None: the backend's stepwise entries on ``ws.table``, behind the score kernel on
+        the backend's stream.  The order below is the contract ("The follow-ups' order"): ``settle_readers``
+        delivers in it, the peer step needs the work step's handle, the histories run directly behind what they record."""
+        be, d, n = _backend_mod.get_backend(), report.__dict__, hi - lo
+        if self.kernel_attribution:
+            if rings is not None:
+                handle = rings.report_attribute(ws, self.kernel_attribution, lo, n)
+            else:
+                handle = be.attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
+                                      self.is_computing_rel_scores, lo, n)
+            d["_attr"] = self._attr_source(handle, ws, mapper, lo, hi, view.ranks)
+        if self.robust_scores:
+            least = self._robust_min(ws)
+            if rings is not None:
+                handle = rings.report_robust(ws, lo, n, least, self.robust_floor)
+            else:
+                handle = be.robust_score(ws, ws.table, lo, n, least, self.robust_floor)
+            d["_robust"] = _RobustSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), least, self.robust_floor)
+        if self.work_groups:
+            # all R ranks (the components need them); ahead of the peer step, which peer_groups="auto" makes wait for it
+            if rings is not None:
+                handle = rings.report_work(ws, self.work_count_tol, self.work_max_unlike_ppm)
+            else:
+                handle = be.work_groups(ws, ws.table, self.work_count_tol, self.work_max_unlike_ppm)
+            self._work_handle = handle  # (before anything of this report asks _peer_for)
+            labelled = self._peer_for(ws) if self.peer_groups is not None and self.peer_groups != "auto" else None
+            d["_work"] = _WorkSource(handle, view.ranks, {"count_tol": self.work_count_tol, "max_unlike": self.work_max_unlike,
+                                                          "max_unlike_ppm": self.work_max_unlike_ppm}, labelled)
+        if self.peer_groups is not None:
+            groups = self._peer_for(ws)
+            if rings is not None:
+                peer = rings.report_peer(ws, groups, lo, n, self.peer_min_ranks)
+            else:
+                peer = be.peer_score(ws, ws.table, groups, lo, n, self.peer_min_ranks)
+            d["_peer"] = _PeerSource(peer, view.ranks, view.cols, self._attr_names(mapper, ws.K), groups, self.peer_min_ranks)
+            if self._peer_history is not None:
+                # directly behind the peer step, on the stream it used, once per report for which that step ran on this rank
+                # and never otherwise: that is what the history's n_before counts
+                state, thr = self._peer_history, self.peer_persistence_thresholds
+                if rings is not None:
+                    handle = rings.report_peer_history(ws, state, peer, thr)
+                else:
+                    handle = be.peer_history(ws, state, peer, thr)
+                d["_peer_history"] = _PeerHistorySource(handle, view.ranks, view.cols, self.peer_history,
+                                                        self.peer_persistence_min_reports, thr)
+                if self.peer_trends:
+                    handle = rings.report_peer_trend(ws, state) if rings is not None else be.peer_trend(ws, state)
+                    d["_peer_trends"] = _PeerTrendSource(handle, view.ranks, view.cols, min(state.n_before, self.peer_history),
+                                                         self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon, thr)
+        if self.pace_scores:
+            least = self._pace_min(ws)
+            params = {"min_ranks": least, "min_columns": self.pace_min_columns, "min_effect": self.pace_min_effect,
+                      "min_breadth": self.pace_min_breadth}
+            if self.pace_peer_groups:
+                groups = self._peer_for(ws)
+                if rings is not None:
+                    handle = rings.report_pace_group(ws, groups, lo, n, least, self.peer_min_ranks)
+                else:
+                    handle = be.pace_group_score(ws, ws.table, groups, lo, n, least, self.peer_min_ranks)
+                params.update(min_peers=self.peer_min_ranks, peer_groups=True)
+                d["_pace"] = _PaceGroupSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, groups)
+            else:
+                handle = rings.report_pace(ws, lo, n, least) if rings is not None else be.pace_score(ws, ws.table, lo, n, least)
+                d["_pace"] = _PaceSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
+        if self.node_scores:
+            nodes = self._node_for(ws)
+            least = self._node_min(nodes)
+            if rings is not None:
+                handle = rings.report_node(ws, nodes, lo, n, self.node_min_members, least)
+            else:
+                handle = be.node_score(ws, ws.table, nodes, lo, n, self.node_min_members, least)
+            params = {"min_members": self.node_min_members, "min_nodes": least, "min_columns": self.node_min_columns,
+                      "min_effect": self.node_min_effect, "min_breadth": self.node_min_breadth, "min_agree": self.node_min_agree}
+            d["_node"] = _NodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, nodes)
+        if self._history is not None:
+            # the ring takes the scores of every report this rank holds, once, behind its last score kernel
+            state, thr = self._history, self.persistence_thresholds
+            if rings is not None:
+                handle = rings.report_history(ws, state, lo, n, thr)
+            else:
+                handle = be.score_history(ws, state, lo, n, thr)
+            d["_history"] = _HistorySource(handle, view.ranks, view.cols, self.is_computing_rel_scores,
+                                           self.is_computing_indiv_scores, self.score_history, self.persistence_min_reports, thr)
+            if self.score_trends:
+                # ... and the trends of the ring as that step leaves it, behind it
+                handle = rings.report_trend(ws, state) if rings is not None else be.score_trend(ws, state)
+                d["_trends"] = _TrendSource(handle, view.ranks, view.cols, self.is_computing_rel_scores,
+                                            self.is_computing_indiv_scores, min(state.n_before, self.score_history),
+                                            self.trend_min_reports, self.trend_min_tau, self.trend_horizon, thr)
 
     # ---- robust scores ------------------------------------------------------------------------------
     def _robust_min(self, ws) -> int:
         """``robust_min_ranks``, but never more than the ranks the table has: a job smaller than that is rated against its own
         median all the same (one rank: ratio 1, z 0)."""
         return min(self.robust_min_ranks, ws.R)
-
-    def _attach_robust(self, report, handle, ws, mapper, view) -> None:
-        report.__dict__["_robust"] = _RobustSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K),
-                                                   self._robust_min(ws), self.robust_floor)
-
-    def _attach_plan_robust(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the robust scores of the planned report that was just issued, as ``_attach_plan_attribution`` does, for the
-        ranks the report covers, and hang them on ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        lo, hi = plan.view.layout[5], plan.view.layout[6]
-        if fused:
-            handle = rings.report_robust(ws, lo, hi - lo, self._robust_min(ws), self.robust_floor)
-        else:
-            handle = _backend_mod.get_backend().robust_score(ws, ws.table, lo, hi - lo, self._robust_min(ws), self.robust_floor)
-        self._attach_robust(report, handle, ws, plan.mapper, plan.view)
 
     # ---- peer-group scores --------------------------------------------------------------------------
     def _peer_for(self, ws):
@@ -3192,94 +3192,10 @@ class ReportGenerator:
             raise ValueError(f"{option}: the job has {R} logical ranks, work groups are inferred for at most {cap}; say which "
                              "ranks do the same work with peer_groups labels, 'block:N' or 'mod:N' instead")
 
-    def _attach_work(self, report, handle, ws, view) -> None:
-        self._work_handle = handle
-        labelled = self._peer_for(ws) if self.peer_groups is not None and self.peer_groups != "auto" else None
-        report.__dict__["_work"] = _WorkSource(handle, view.ranks, {"count_tol": self.work_count_tol,
-                                                                    "max_unlike": self.work_max_unlike,
-                                                                    "max_unlike_ppm": self.work_max_unlike_ppm}, labelled)
-
-    def _attach_plan_work(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the work-group step of the planned report that was just issued, as ``_attach_plan_robust`` does (all R
-        ranks: the components need them), and hang it on ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        if fused:
-            handle = rings.report_work(ws, self.work_count_tol, self.work_max_unlike_ppm)
-        else:
-            handle = _backend_mod.get_backend().work_groups(ws, ws.table, self.work_count_tol, self.work_max_unlike_ppm)
-        self._attach_work(report, handle, ws, plan.view)
-
-    def _attach_peer(self, report, handle, groups, ws, mapper, view) -> None:
-        report.__dict__["_peer"] = _PeerSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), groups,
-                                               self.peer_min_ranks)
-
-    def _attach_plan_peer(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the peer-group scores of the planned report that was just issued, as ``_attach_plan_robust`` does, for the
-        ranks the report covers, and hang them on ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        lo, hi = plan.view.layout[5], plan.view.layout[6]
-        groups = self._peer_for(ws)
-        if fused:
-            handle = rings.report_peer(ws, groups, lo, hi - lo, self.peer_min_ranks)
-        else:
-            handle = _backend_mod.get_backend().peer_score(ws, ws.table, groups, lo, hi - lo, self.peer_min_ranks)
-        self._attach_peer(report, handle, groups, ws, plan.mapper, plan.view)
-        if self._peer_history is not None:
-            self._attach_peer_history(report, ws, handle, plan.view, rings if fused else None)
-
-    def _attach_peer_history(self, report, ws, peer, view, rings) -> None:
-        """Enqueue the peer-history step -- and the peer-trend step behind it -- directly behind the peer step ``peer`` just
-        issued on ``ws``, on the stream that step used (``rings``: the one-call report's, else the backend's), and hang them
-        on ``report``.  Nothing is waited for.  Called once per report for which the peer step ran on this rank, and never
-        otherwise: that is what the history's ``n_before`` counts."""
-        state, be = self._peer_history, _backend_mod.get_backend()
-        thr = self.peer_persistence_thresholds
-        if rings is not None:
-            handle = rings.report_peer_history(ws, state, peer, thr)
-        else:
-            handle = be.peer_history(ws, state, peer, thr)
-        report.__dict__["_peer_history"] = _PeerHistorySource(handle, view.ranks, view.cols, self.peer_history,
-                                                              self.peer_persistence_min_reports, thr)
-        if self.peer_trends:
-            handle = rings.report_peer_trend(ws, state) if rings is not None else be.peer_trend(ws, state)
-            report.__dict__["_peer_trends"] = _PeerTrendSource(handle, view.ranks, view.cols,
-                                                               min(state.n_before, self.peer_history), self.trend_min_reports,
-                                                               self.trend_min_tau, self.peer_trend_horizon, thr)
-
     # ---- pace scores --------------------------------------------------------------------------------
     def _pace_min(self, ws) -> int:
         """``pace_min_ranks``, but never more than the ranks the table has, as ``_robust_min``."""
         return min(self.pace_min_ranks, ws.R)
-
-    def _attach_pace(self, report, handle, ws, mapper, view, groups=None) -> None:
-        params = {"min_ranks": self._pace_min(ws), "min_columns": self.pace_min_columns, "min_effect": self.pace_min_effect,
-                  "min_breadth": self.pace_min_breadth}
-        if groups is not None:  # per peer group
-            params.update(min_peers=self.peer_min_ranks, peer_groups=True)
-            report.__dict__["_pace"] = _PaceGroupSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params,
-                                                        groups)
-            return
-        report.__dict__["_pace"] = _PaceSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
-
-    def _attach_plan_pace(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the pace scores of the planned report that was just issued, as ``_attach_plan_robust`` does, for the ranks
-        the report covers, and hang them on ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        lo, hi = plan.view.layout[5], plan.view.layout[6]
-        if self.pace_peer_groups:
-            groups = self._peer_for(ws)
-            if fused:
-                handle = rings.report_pace_group(ws, groups, lo, hi - lo, self._pace_min(ws), self.peer_min_ranks)
-            else:
-                handle = _backend_mod.get_backend().pace_group_score(ws, ws.table, groups, lo, hi - lo, self._pace_min(ws),
-                                                                     self.peer_min_ranks)
-            self._attach_pace(report, handle, ws, plan.mapper, plan.view, groups)
-            return
-        if fused:
-            handle = rings.report_pace(ws, lo, hi - lo, self._pace_min(ws))
-        else:
-            handle = _backend_mod.get_backend().pace_score(ws, ws.table, lo, hi - lo, self._pace_min(ws))
-        self._attach_pace(report, handle, ws, plan.mapper, plan.view)
 
     # ---- node scores --------------------------------------------------------------------------------
     def _node_for(self, ws):
@@ -3306,53 +3222,7 @@ class ReportGenerator:
         """``node_min_nodes``, but never more than the nodes the job has, as ``_pace_min``."""
         return min(self.node_min_nodes, nodes.G)
 
-    def _attach_node(self, report, handle, nodes, ws, mapper, view) -> None:
-        params = {"min_members": self.node_min_members, "min_nodes": self._node_min(nodes), "min_columns": self.node_min_columns,
-                  "min_effect": self.node_min_effect, "min_breadth": self.node_min_breadth, "min_agree": self.node_min_agree}
-        report.__dict__["_node"] = _NodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, nodes)
-
-    def _attach_plan_node(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the node scores of the planned report that was just issued, as ``_attach_plan_pace`` does, for the ranks
-        the report covers, and hang them on ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        lo, hi = plan.view.layout[5], plan.view.layout[6]
-        nodes = self._node_for(ws)
-        if fused:
-            handle = rings.report_node(ws, nodes, lo, hi - lo, self.node_min_members, self._node_min(nodes))
-        else:
-            handle = _backend_mod.get_backend().node_score(ws, ws.table, nodes, lo, hi - lo, self.node_min_members,
-                                                           self._node_min(nodes))
-        self._attach_node(report, handle, nodes, ws, plan.mapper, plan.view)
-
     # ---- score history ------------------------------------------------------------------------------
-    def _attach_history(self, report, handle, view) -> None:
-        report.__dict__["_history"] = _HistorySource(handle, view.ranks, view.cols, self.is_computing_rel_scores,
-                                                     self.is_computing_indiv_scores, self.score_history,
-                                                     self.persistence_min_reports, self.persistence_thresholds)
-
-    def _attach_plan_history(self, report, plan, rings, fused: bool) -> None:
-        """Enqueue the history step of the planned report that was just issued, as ``_attach_plan_robust`` does, for the ranks
-        the report covers, and hang it on ``report``.  Nothing is waited for."""
-        ws = plan.ws
-        lo, hi = plan.view.layout[5], plan.view.layout[6]
-        if fused:
-            handle = rings.report_history(ws, self._history, lo, hi - lo, self.persistence_thresholds)
-        else:
-            handle = _backend_mod.get_backend().score_history(ws, self._history, lo, hi - lo, self.persistence_thresholds)
-        self._attach_history(report, handle, plan.view)
-        if self.score_trends:
-            if fused:
-                handle = rings.report_trend(ws, self._history)
-            else:
-                handle = _backend_mod.get_backend().score_trend(ws, self._history)
-            self._attach_trends(report, handle, plan.view)
-
-    def _attach_trends(self, report, handle, view) -> None:
-        report.__dict__["_trends"] = _TrendSource(handle, view.ranks, view.cols, self.is_computing_rel_scores,
-                                                  self.is_computing_indiv_scores, min(self._history.n_before, self.score_history),
-                                                  self.trend_min_reports, self.trend_min_tau, self.trend_horizon,
-                                                  self.persistence_thresholds)
-
     def reset_score_history(self) -> None:
         """Forget the score history: the next report starts a new one (after a restart from a checkpoint, a change of the
         job's layout, a node swap) -- and so does the peer-score history.  Reports already handed out keep theirs."""
@@ -3374,17 +3244,10 @@ class ReportGenerator:
         if local is None or score is None:
             raise RuntimeError(f"{fam.label(params)}: the active backend has no {fam.name} scores "
                                f"(rings.{fam.name}_local / backend.{fam.name}_score)")
-        send, table = local(ws, *params, rows_active, fused)
-        if self.world_size > 1:
-            with be.stream_context():  # (behind the family's ring kernel)
-                table = dist_utils.all_gather_rows(send, table, self.group)
+        table = self._gather_step_rows(be, *local(ws, *params, rows_active, fused))
         if report is None or report is False:
             return
-        if self.gather_on_rank0:
-            lo, hi = 0, ws.R
-        else:
-            lo = self.rank * local_ranks
-            hi = lo + local_ranks
+        lo, hi = self._covered(ws, local_ranks)
         view = report.__dict__["_src"].view
         if self.row_peer_groups:
             grouped = getattr(be, fam.name + "_group_score", None)
@@ -3399,10 +3262,30 @@ class ReportGenerator:
         handle = score(ws, table, ws.table, lo, hi - lo, *params[:fam.score_params])
         report.__dict__[fam.slot] = _RowFamilySource(fam, handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params)
 
-    def _family_steps(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
-        """The steps of the families that are switched on, in the table's order: the order of their collectives."""
+    def _ring_steps(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The ring steps of one ``generate_report_from_rings`` call: the families that are switched on, in the table's order,
+        then slack -- the order of their collectives, the same on every rank whatever ``report`` is."""
+        if not self._ring_steps_on:
+            return
         for fam in self._row_families:
             self._family_step(fam, report, rings, ws, mapper, rows_active, fused, local_ranks)
+        if self.collective_slack:
+            self._slack_step(report, rings, ws, rows_active, fused, local_ranks)
+
+    def _gather_step_rows(self, be, send, table):
+        """Exchange a ring step's rows behind its local kernel: its one collective, on the backend's stream."""
+        if self.world_size > 1:
+            with be.stream_context():
+                table = dist_utils.all_gather_rows(send, table, self.group)
+        return table
+
+    def _covered(self, ws, local_ranks: int):
+        """The ranks ``[lo, hi)`` a ring step scores for the report this rank holds.  (Not ``_view``'s rule: a step's table
+        is exchanged whether or not the report's is, so this rank's rows always sit at ``rank * local_ranks``.)"""
+        if self.gather_on_rank0:
+            return 0, ws.R
+        lo = self.rank * local_ranks
+        return lo, lo + local_ranks
 
     # ---- slack scores -------------------------------------------------------------------------------
     def _slack_step(self, report, rings, ws, rows_active: int, fused: bool, local_ranks: int) -> None:
@@ -3416,17 +3299,10 @@ class ReportGenerator:
         if local is None or score is None or not hasattr(rings, "slack_list"):
             raise RuntimeError("collective_slack: the active backend has no slack scores (rings.slack_local, rings.slack_list / "
                                "backend.slack_score)")
-        send, table = local(ws, rows_active, fused)
-        if self.world_size > 1:
-            with be.stream_context():  # (behind the local kernel)
-                table = dist_utils.all_gather_rows(send, table, self.group)
+        table = self._gather_step_rows(be, *local(ws, rows_active, fused))
         if report is None or report is False:
             return
-        if self.gather_on_rank0:
-            lo, hi = 0, ws.R
-        else:
-            lo = self.rank * local_ranks
-            hi = lo + local_ranks
+        lo, hi = self._covered(ws, local_ranks)
         view = report.__dict__["_src"].view
         if self.slack_peer_groups:
             grouped = getattr(be, "slack_group_score", None)
@@ -3531,9 +3407,7 @@ class ReportGenerator:
                 self._drop_plan()
                 raise
             if out is not False:
-                self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-                if self.collective_slack:
-                    self._slack_step(out, rings, plan.ws, plan.rows_used, self._last_plan_fused, local_ranks)
+                self._ring_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
                 if reset_rings:
                     if self._rings_were_reset:
                         self._rings_were_reset = False
@@ -3553,9 +3427,7 @@ class ReportGenerator:
             self._unreported_rows = ([r for n, r in kernel_rows.items() if n not in known_k and not is_collective_kernel(n)]
                                      + [r for n, r in section_rows.items() if n not in known_s])
             out = self._report_from_plan(plan, rings, t0, order_after, names_ok=False)
-            self._family_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
-            if self.collective_slack:
-                self._slack_step(out, rings, plan.ws, plan.rows_used, self._last_plan_fused, local_ranks)
+            self._ring_steps(out, rings, plan.ws, plan.mapper, plan.rows_used, self._last_plan_fused, local_ranks)
             if reset_rings:
                 rings.reset()
             return out
@@ -3584,10 +3456,9 @@ class ReportGenerator:
                                        stats_rows_used=stats_needed, sync_first=self._take_resync(), may_defer_sync=not_the_first)
         report = self._assemble(ws, mapper, snames, dict(section_rows), dict(kernel_rows), t0, local_ranks=local_ranks,
                                 stats=ws.stats[:stats_needed].copy())
-        self._family_steps(report, rings, ws, mapper, rows_used, False, local_ranks)  # (before the plan below re-points the ring rows)
-        if self.collective_slack:
-            # (its list is built from the rings' own table of kernel rows: the collective ones were filtered out of kernel_rows above)
-            self._slack_step(report, rings, ws, rows_used, False, local_ranks)
+        # before the plan below re-points the ring rows (the slack step's list is built from the rings' own table of kernel
+        # rows: the collective ones were filtered out of kernel_rows above)
+        self._ring_steps(report, rings, ws, mapper, rows_used, False, local_ranks)
         # names are settled now: the next report with the same tables takes the planned path
         self._ring_plan = self._build_ring_plan(self._plan_key(rings, section_rows, kernel_rows, local_ranks), rings,
                                                 section_rows, kernel_rows, local_ranks)

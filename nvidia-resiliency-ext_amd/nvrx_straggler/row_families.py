@@ -7,7 +7,7 @@ All four are ONE pipeline with a different ring kernel in front ("Row
 
 ``FAMILIES`` says what differs, once, in the fixed order the families run in (and issue their collectives in).  The backend
 (``Workspace.family_buffers``, ``HipBackend._family_score``, ``HipRings._family_local``) and the reports
-(``reporting._RowFamilySource``, ``ReportGenerator._family_steps``) are written against these records; a further family is
+(``reporting._RowFamilySource``, ``ReportGenerator._ring_steps``) are written against these records; a further family is
 a kernel file, one record here, its two public ``Report`` methods and the one-line delegations by name on the backend, the
 workspace and the rings.
 """

@@ -35,13 +35,13 @@ from collections.abc import Callable
 from contextlib import contextmanager
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Union
 
-from . import _native, row_families
+from . import _native
 from . import backend as _backend_mod
 from . import dist_utils as _dist_utils
 from . import ktrace as _ktrace
 from .cupti import CuptiManager
 from .interval_tracker import ReportIntervalTracker
-from .reporting import Report, ReportGenerator, _LiveBlock, _PendingBlock, _ScoreSource
+from .reporting import Report, ReportGenerator, _LiveBlock, _PendingBlock, _ScoreSource, steps_behind_report
 from .statistics import Statistic  # noqa: F401  (re-exported for callers that poke summaries)
 
 GPU_KEY_PREFIX = "hipevent::"  # kernel-summary key of a section's GPU-time row
@@ -156,24 +156,9 @@ class _Lane:
             return None  # (a host-driven exchange: the report is three calls with a collective between them)
         if reporter.asynchronous and not reporter.enqueue_only():
             return None
-        if reporter.kernel_attribution:
-            return None  # (the attribution launch follows the report in the generator's planned path: DESIGN.md, "Kernel attribution")
-        if any(getattr(reporter, fam.param_attrs[0], 0) for fam in row_families.FAMILIES):
-            return None  # (a row family's step follows the report in the generator's paths: DESIGN.md, "Row families")
-        if getattr(reporter, "robust_scores", False):
-            return None  # (the robust launch follows the report in the generator's planned path: DESIGN.md, "Robust scores")
-        if getattr(reporter, "peer_groups", None) is not None:
-            return None  # (the peer launch follows the report in the generator's planned path: DESIGN.md, "Peer-group scores")
-        if getattr(reporter, "work_groups", False):
-            return None  # (the work-group launches follow the report in the generator's planned path: DESIGN.md, "Work groups")
-        if getattr(reporter, "pace_scores", False):
-            return None  # (the pace launches follow the report in the generator's planned path: DESIGN.md, "Pace scores")
-        if getattr(reporter, "node_scores", False):
-            return None  # (the node launches follow the report in the generator's planned path: DESIGN.md, "Node scores")
-        if getattr(reporter, "score_history", 0):
-            return None  # (the history step follows the report in the generator's planned path: DESIGN.md, "Score history")
-        if getattr(reporter, "collective_slack", False):
-            return None  # (the slack step follows the report in the generator's paths: DESIGN.md, "Slack scores")
+        if any(steps_behind_report(reporter)):
+            # (a table follow-up or a ring step follows the report in the generator's paths: DESIGN.md, "The follow-ups' order")
+            return None
         ext = manager.cupti_ext
         ws = plan.ws
         if ws.block.desc_key is None or not ws.send_initialised:

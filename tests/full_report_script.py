@@ -127,7 +127,7 @@ FEATURES = {
     "slack": (lambda ranks: dict(_peer(ranks), collective_slack=True, slack_peer_groups=True),
               lambda rep: rep.slack_scores(), ("_slack",)),
     # by design work_groups() gains the labelled comparison ("label_conflicts") when peer_groups labels are set
-    # (ReportGenerator._attach_work): "alone" is work_groups=True WITH the labels
+    # (ReportGenerator._follow_ups): "alone" is work_groups=True WITH the labels
     "work": (lambda ranks: dict(_peer(ranks), work_groups=True), lambda rep: rep.work_groups(), ("_work",)),
 }
 

@@ -140,7 +140,7 @@ def test_no_comparison_is_vacuous():
 def test_every_feature_says_composed_what_it_says_alone(emulate_fused, asynchronous):
     """For every entry of ``FEATURES``: the six composed reports say exactly (``same``: NaN equal to NaN) what six reports of a
     generator with only that feature's options say, on the same pushes.  One exception by design: ``work_groups()`` gains the
-    labelled comparison when ``peer_groups`` labels are set (``ReportGenerator._attach_work``), so "alone" for it is
+    labelled comparison when ``peer_groups`` labels are set (``ReportGenerator._follow_ups``), so "alone" for it is
     ``work_groups=True`` WITH the labels (``FEATURES["work"]``), not ``work_groups=True`` alone -- which differs, as asserted."""
     composed, composed_named, _, _ = _composed(emulate_fused, asynchronous)
     for feature in fs.FEATURES:

@@ -190,3 +190,34 @@ def test_wait_and_issue_out_of_turn(monkeypatch):
             assert _read(a.report()) == _read(b.report()), t
     finally:
         a.close(), b.close()
+
+
+def test_every_option_on_the_split_report_equals_the_one_call(monkeypatch):
+    """The job of tests/full_report_script.py -- 8 folded ranks, 3 sections, rings 256 deep, every option on, synchronous --
+    for three windows, once on the two-call route and once with NVRX_DEBUG_REPORT_SPLIT=0, each in a generator and a
+    workspace of its own (the backend caches workspaces per shape: the two jobs differ in their rows per rank).  The same
+    kernels run on the same table behind either route's report, in the same order, so every reader says the same bit for bit
+    (``same``: NaN equal to NaN) and the same ranks are identified."""
+    import full_report_script as fs
+    from nvrx_straggler.backend import get_backend
+
+    be, said = get_backend(), {}
+    for split, rows_per_rank in ((True, fs.ROWS_PER_RANK + 2), (False, fs.ROWS_PER_RANK + 3)):
+        monkeypatch.setenv("NVRX_DEBUG_REPORT_SPLIT", "1" if split else "0")
+        job = fs.Job(be, rows_per_rank=rows_per_rank)
+        try:
+            assert job.gen._report_split is split
+            issued, issue = [], job.rings.report_issue
+            monkeypatch.setattr(job.rings, "report_issue", lambda *a, **kw: issued.append(1) or issue(*a, **kw))
+            said[split] = []
+            for w in range(3):
+                rep = job.report(w)
+                said[split].append((fs.read(rep), fs.identified(rep)))
+            assert len(issued) == (2 if split else 0)  # (window 0 learns the names on the general path)
+        finally:
+            job.close()
+    for w in range(3):
+        assert fs.same(said[True][w][0], said[False][w][0]), (w, said[True][w][0], said[False][w][0])
+        assert said[True][w][1] == said[False][w][1], w
+    assert all(said[True][2][1][m] for m in ("identify_slack_stragglers", "identify_pace_stragglers", "identify_onset_stragglers"))
+    assert not fs.same(said[True][1][0], said[True][2][0])  # (the windows differ: equal results are not one result twice)
