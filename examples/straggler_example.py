@@ -51,6 +51,12 @@ of it) and normal again afterwards: no median, no 0.95-quantile, no step and no 
 row's mean (``Report.episode_scores()``) and the example prints whoever ``identify_episode_stragglers`` flags, with how long
 the rank's strongest episode lasted and how many samples ago it ended.
 
+``--ramp`` needs no training loop: it plays one report of a job of 8 ranks (folded onto one GPU, 2 sections x 10 000 samples,
+1 % noise, seed 41) in which rank 5 rises linearly by 50 % over the last 40 % of the window and rank 2 is 1.5x slower from 70 %
+of it on, with tail, onset, episode and ramp scores on (``ReportGenerator(ramp_detection=True)``), and prints whom each
+``identify_*_stragglers`` names and what each score reads for the two ranks next to their onset and ramp records
+(``Report.ramp_scores()``): for how many samples the row has been rising, from where to where.
+
 ``--persist`` needs no training loop: it plays 20 reports of a job of 8 ranks (folded onto one GPU, 1 % noise, seed 17) in which
 rank 2 is 1.6x slower in report 6 only and rank 5 is 1.45x slower from report 10 on, with a score history of 8 reports
 (``ReportGenerator(score_history=8, persistence_min_reports=3)``), and prints per report whom ``identify_stragglers`` flags and
@@ -450,6 +456,51 @@ def period_peer_samples(ranks: int = 8, sections: int = 2, samples: int = 2000, 
     return x
 
 
+def ramp_samples(ranks: int = 8, sections: int = 2, samples: int = 10000, rising: int = 5, stepped: int = 2):
+    """The ``--ramp`` job: ``[ranks, sections, samples]`` f64 microseconds (NumPy only), 1000 us with 1 % noise; rank ``rising``
+    rises linearly by 50 % over the last 40 % of the window, rank ``stepped`` is 1.5 x slower from 70 % of the window on."""
+    import numpy as np
+
+    x = 1000.0 * (1.0 + 0.01 * np.random.default_rng(41).standard_normal((ranks, sections, samples)))
+    knot = samples - (4 * samples) // 10
+    x[rising] += np.maximum(0, np.arange(samples) - knot) * (500.0 / (samples - knot))
+    x[stepped, :, (7 * samples) // 10:] *= 1.5
+    return x
+
+
+def ramp(rising: int = 5, stepped: int = 2) -> None:
+    """A rank that keeps getting slower, and one that stepped, under every score that reads a window: what the relative,
+    tail, onset and episode scores say of the rising rank, next to its ramp record."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    x = ramp_samples(rising=rising, stepped=stepped)
+    ranks, sections, samples = x.shape
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=samples, scores_to_compute=("relative_perf_scores",),
+                    tail_quantile=0.95, onset_detection=True, episode_detection=True, ramp_detection=True)
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, x[r].astype(np.float32))
+        report = job.report()
+        name = job.section_names[0]
+        print(f"identify_stragglers(): {named_ranks({k: v for k, v in report.identify_stragglers().items() if 'relative' in k})}")
+        for family in ("tail", "onset", "episode", "ramp"):
+            print(f"identify_{family}_stragglers(): {named_ranks(getattr(report, f'identify_{family}_stragglers')())}")
+        for r in (rising, stepped):
+            print(f"rank {r}, {name}: relative {report.section_relative_perf_scores[name][r]:.3f}, "
+                  + ", ".join(f"{family} {getattr(report, family + '_scores')()['section_relative'][name][r]:.3f}"
+                              for family in ("tail", "onset", "episode", "ramp")))
+            onset, rec = report.onset_scores()["section_onsets"][name][r], report.ramp_scores()["section_ramps"][name][r]
+            print(f"  onset record: {onset['samples_ago']} samples ago, {onset['before']:.0f} -> {onset['after']:.0f} us, "
+                  f"strength {onset['strength']:.2f}")
+            print(f"  ramp record:  rising for {rec['samples_ago']} of {rec['window']} samples, {rec['base']:.0f} -> "
+                  f"{rec['end']:.0f} us, strength {rec['strength']:.2f}, rise {rec['rise']:.3f}")
+    finally:
+        job.close()
+
+
 def named_ranks(found) -> list:
     """The ranks an ``identify_*_stragglers()`` result names, in any of its mappings."""
     return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
@@ -773,7 +824,13 @@ def main() -> None:
     ap.add_argument("--work", action="store_true",
                     help="no training: play the work-group scenario (the two pipeline stages of --peer with nobody describing "
                          "the layout: the groups are inferred from the kernels each rank runs and how often) and exit")
+    ap.add_argument("--ramp", action="store_true",
+                    help="no training: play the ramp-score scenario (8 ranks, rank 5 rises by 50 %% over the last 40 %% of the "
+                         "window, rank 2 stepped) under the relative, tail, onset, episode and ramp scores, and exit")
     args = ap.parse_args()
+    if args.ramp:
+        ramp()
+        return
     if args.work:
         work()
         return

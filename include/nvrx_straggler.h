@@ -315,6 +315,58 @@ int nvrx_row_episode(const float *d_samples, const uint32_t *d_counts, const uin
 int nvrx_episode_score(const float *d_episode, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                        float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Ramp of timing rows: whether a row KEEPS GETTING SLOWER -- a card heating up after a fan or coolant fault, an allocator
+ * fragmenting, a leak on the host that slows every launch a little more, a link retraining down step by step.  Extends the
+ * statistics of straggler.py:172-197: a step fitted to a ramp puts its `after` at the ramp's mean, not at where the row has got
+ * to, and the median stays in the flat part as long as the ramp covers less than half the window.  Per row with n valid samples:
+ *   time order  as for nvrx_row_onset: sample i lives in slot (start + i) mod n;
+ *   pivoting    d_i = (f64)x_i - (f64)x_0; all sums below are f64 sums; T = sum of all d_i, W = sum of i * d_i,
+ *               SST = sum of (d_i - T / n)^2; prefixes C_t = sum of d_i and V_t = sum of i * d_i over i < t;
+ *   m           max(8, (min_seg_ppm * n + 999999) / 1000000) (64-bit integers), min_seg_ppm in [1, 500000]: nvrx_row_onset's;
+ *   model       at knot t: d_i ~ a + b * h_i, h_i = max(0, i - t) -- flat up to sample t, linear from there to the window's
+ *               end: a least-squares hinge;
+ *   candidates  every t in [0, n - m]: the rising part L = n - t holds at least m samples, t = 0 is a line through the whole
+ *               window (needs n >= 2m);
+ *   at knot t   A = T - C_t, B = W - V_t; Shd = B - t * A; Sh = L(L-1)/2 and Shh = (L-1)L(2L-1)/6 (integers, exact in f64 up
+ *               to NVRX_MAX_RING_CAP); Shd_c = Shd - Sh * T / n; Shh_c = Shh - Sh^2 / n; R_t = Shd_c^2 / Shh_c;
+ *   t*          the knot with the largest R_t, the lowest t on ties; a NaN never wins;
+ *   at t*       b = Shd_c / Shh_c; a = (T - b * Sh) / n; base = x_0 + a; end = base + b * (L - 1) (both f64, each rounded to
+ *               f32 for the record); strength = R_t* / SST, the share of the row's variance that the hinge explains, in
+ *               [0, 1]; ago = L: "the rise began `ago` samples ago".
+ * Row record, 16 bytes: {u32 ago, f32 base, f32 end, f32 strength}.
+ *   n == 0 (an absent row)        {0, -1, -1, -1};
+ *   T, W or SST not finite        {0, NaN, NaN, NaN};
+ *   0 < n < 2m (no ramp)          {0, mean, mean, 0}, mean = x_0 + T / n;
+ *   SST == 0 (a constant row)     {n, x_0, x_0, 0}: t* = 0.
+ * Effective rise of a record: e = f32 of the f64 quotient end / base (the record's f32 values) where strength >= min_strength
+ * and end > base > 0; 1.0 otherwise ("did not rise": a falling ramp is fitted and reported, and counts as a step down does for
+ * onsets); -1.0 for an absent row.
+ * Rules, not defects: a row that STEPPED UP reads as a steep, short ramp (a pure 1.5 x step 70 % into a noise-free window of
+ * 2000 samples reads "rising for 900 samples, from 1000 to 1666", strength 0.84; 0.78 for a step half way; onset scores are
+ * the better reading there); a pulse or a beat reads weak; only the strongest hinge of a
+ * row is reported.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_starts [rows] or NULL (0 everywhere); d_out [rows] records, 16-byte aligned.  Stateless, like nvrx_row_onset.
+ * Rows of at most NVRX_RAMP_LDS_SAMPLES samples are read from device memory once (the kernel keeps them in LDS, in time
+ * order); longer ones twice.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_RAMP_LDS_SAMPLES 15360
+int nvrx_row_ramp(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride,
+                  uint32_t min_seg_ppm, void *d_out, void *stream);
+/* Relative ramp scores.  d_ramp [R][NVRX_RAMP_PLANES][K+S]: per rank six planes {e, base, end, strength, ago as f32, n as f32}
+ * per kernel id and section id (-1.0: none); only plane 0 is read.  Reference per column = the minimum of e over all R ranks,
+ * NaN if any rank has none.  Per reported rank [first_rank, first_rank + n_ranks), nvrx_tail_score's arithmetic on e, exactly
+ * as nvrx_onset_score:
+ *   d_out [n_ranks][1 + S] = {GPU ramp score, section ramp score[S]}
+ * Scores are in (0, 1]: 1 = "rose no more than the steadiest rank"; a warm-up the whole job shares flags nobody.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(K+S) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched.
+ * (An enumerator, not a macro: the row-family table of the Python layer is checked against the header's *_PLANES macros, and
+ * ramp runs behind that table's four families as a fifth step of its own.) */
+enum { NVRX_RAMP_PLANES = 6 };
+int nvrx_ramp_score(const float *d_ramp, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                    float *d_colmin_scratch, float *d_out, void *stream);
+
 /* Robust scores: every rank against the job's median and spread. Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
@@ -987,6 +1039,15 @@ int nvrx_period_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, int max_perio
  * nvrx_onset_local.  NVRX_ERR_STATE: the snapshot is not enabled, or no report was issued through this descriptor. */
 int nvrx_episode_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_len_ppm, float min_strength,
                        float *d_episode_send, int K, int S, int rows_active, void *stream);
+/* Ramp scores on the rings (straggler.py:172-197 on the window in time order; reporting.py:196-253 follows with
+ * nvrx_ramp_score): nvrx_row_ramp on the rings as the report just issued saw them -- its counts, its ring starts (the snapshot
+ * of nvrx_onset_enable), whatever has been pushed since -- packed by gid into d_ramp_send [local_ranks][NVRX_RAMP_PLANES][K+S]
+ * (planes {e, base, end, strength, ago as f32, n as f32}; kernel ids first, then section ids; every slot is written, -1.0
+ * where no row with samples has that gid).  min_seg_ppm in [1, 500000], min_strength in [0, 1].  Ordering, desc, rows_active
+ * and the caller's duty to wait are those of nvrx_onset_local.  NVRX_ERR_STATE: the snapshot is not enabled, or no report was
+ * issued through this descriptor. */
+int nvrx_ramp_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_seg_ppm, float min_strength,
+                    float *d_ramp_send, int K, int S, int rows_active, void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

@@ -41,6 +41,8 @@ PERIOD_PLANES = 7  # NVRX_PERIOD_PLANES: {e, peak, rest, strength, period, ago, 
 EPISODE_LEN_PPM_MIN, EPISODE_LEN_PPM_MAX = 1, 333333  # the accepted range of an episode's minimum length, in parts per million
 EPISODE_MIN_SAMPLES = 8  # ... and the length's floor in samples
 EPISODE_PLANES = 7  # NVRX_EPISODE_PLANES: {e, inside, outside, strength, length, ago, n} per kernel id and section id
+RAMP_PLANES = 6  # NVRX_RAMP_PLANES: {e, base, end, strength, ago, n} per kernel id and section id
+RAMP_LDS_SAMPLES = 15360  # NVRX_RAMP_LDS_SAMPLES: the longest row k_row_ramp keeps in LDS between its two passes
 HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
 HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
 TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, family, slot)
@@ -99,6 +101,8 @@ SYMBOLS = [
     ("nvrx_period_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_episode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_episode_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_ramp", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_ramp_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -159,6 +163,7 @@ SYMBOLS = [
     ("nvrx_onset_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_period_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_ramp_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
@@ -401,6 +406,18 @@ def onset_min_segment(seg_ppm: int, n: int) -> int:
     """Samples either side of an onset in a row of ``n``: ``max(8, ceil(seg_ppm * n / 1e6))`` in integers, exactly as
     k_row_onset computes it.  A row shorter than twice that has no onset."""
     return max(ONSET_MIN_SEG_SAMPLES, (seg_ppm * n + 999999) // 1000000)
+
+
+def ramp_seg_ppm(frac) -> int:
+    """A ramp's minimum rising segment as the library carries it: ``round(frac * 1e6)``, within [0.000001, 0.5] -- an onset's
+    bounds.  ``ValueError`` for anything else."""
+    try:
+        ppm = int(round(float(frac) * 1e6))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"ramp_min_segment must be a number within [0.000001, 0.5], got {frac!r}") from None
+    if not ONSET_SEG_PPM_MIN <= ppm <= ONSET_SEG_PPM_MAX:
+        raise ValueError(f"ramp_min_segment must be within [0.000001, 0.5], got {frac!r}")
+    return ppm
 
 
 def period_max(value) -> int:

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .row_families import EPISODE, FAMILIES, ONSET, PERIOD, TAIL, RowFamily
+from .row_families import EPISODE, ONSET, PERIOD, RAMP, ROW_STEPS, TAIL, RowFamily
 from .table_families import NODE, PACE, PACE_GROUP, PEER, ROBUST, SLOTS, TableFamily
 
 DEFAULT_THRESHOLDS = (0.75, 0.75, 0.75, 0.75)  # gpu_rel, section_rel, gpu_indiv, section_indiv
@@ -757,9 +757,15 @@ class Workspace:
     def episode_settle(self) -> None:
         self.family_settle(EPISODE)
 
+    def ramp_buffers(self):
+        return self.family_buffers(RAMP)
+
+    def ramp_settle(self) -> None:
+        self.family_settle(RAMP)
+
     def settle_readers(self) -> None:
         """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
-        reading it -- attribution, tails, robust scores, onsets, periods, episodes -- has run and delivered; and so has the
+        reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps -- has run and delivered; and so has the
         score history's step, which read the result block and wrote the records buffer."""
         if self._attr_last is not None:
             self.attr_settle()
@@ -769,7 +775,7 @@ class Workspace:
             for fam in SLOTS:
                 self.table_settle(fam)
         if self._family_state:
-            for fam in FAMILIES[1:]:
+            for fam in ROW_STEPS[1:]:
                 self.family_settle(fam)
         if self._history_last is not None:
             self.history_settle()
@@ -1164,6 +1170,10 @@ class HipBackend:
                             min_ranks: int = 2) -> RowGroupScores:
         return self._family_group_score(EPISODE, ws, episodes, table, groups, first_rank, n_ranks, min_ranks)
 
+    def ramp_group_score(self, ws, ramps, table, groups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                         min_ranks: int = 2) -> RowGroupScores:
+        return self._family_group_score(RAMP, ws, ramps, table, groups, first_rank, n_ranks, min_ranks)
+
     def family_copy_out(self, t: RowScores):
         """The one wait of a report's row family: a D2H of its table and scores on the backend's stream, behind the kernels."""
         KS, P = t.K + t.S, t.family.planes
@@ -1187,6 +1197,9 @@ class HipBackend:
     def episodes_copy_out(self, t: RowScores):
         return self.family_copy_out(t)
 
+    def ramps_copy_out(self, t: RowScores):
+        return self.family_copy_out(t)
+
     def tail_score(self, ws, tails, table, first_rank: int = 0, n_ranks: Optional[int] = None, q_ppm: int = 0) -> RowScores:
         return self._family_score(TAIL, ws, tails, table, first_rank, n_ranks, (q_ppm,))
 
@@ -1198,6 +1211,9 @@ class HipBackend:
 
     def episode_score(self, ws, episodes, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
         return self._family_score(EPISODE, ws, episodes, table, first_rank, n_ranks)
+
+    def ramp_score(self, ws, ramps, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
+        return self._family_score(RAMP, ws, ramps, table, first_rank, n_ranks)
 
     def _row_op(self, fam: RowFamily, samples: torch.Tensor, counts: torch.Tensor, param: int,
                 starts: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1224,6 +1240,10 @@ class HipBackend:
     def row_episode(self, samples, counts, min_len_ppm: int, starts=None) -> torch.Tensor:
         """Records ``{ago | length << 16, inside, outside, strength}``."""
         return self._row_op(EPISODE, samples, counts, min_len_ppm, starts)
+
+    def row_ramp(self, samples, counts, min_seg_ppm: int, starts=None) -> torch.Tensor:
+        """Records ``{ago, base, end, strength}``."""
+        return self._row_op(RAMP, samples, counts, min_seg_ppm, starts)
 
     def _table_step(self, fam: TableFamily, ws: Workspace, entry, head: tuple, tail: tuple, groups: Optional[PeerGroups],
                     first_rank: int, n_ranks: Optional[int], params: tuple) -> TableScores:
@@ -1972,6 +1992,9 @@ class HipRings:
 
     def episode_local(self, ws: Workspace, min_len_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
         return self._family_local(EPISODE, ws, (min_len_ppm, min_strength), rows_active, fused)
+
+    def ramp_local(self, ws: Workspace, min_seg_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
+        return self._family_local(RAMP, ws, (min_seg_ppm, min_strength), rows_active, fused)
 
     def peek_stats(self) -> np.ndarray:
         """Statistics of every used row right now ([rows_used, 8] on the host); exchanges nothing and

@@ -647,7 +647,7 @@ def _copy_explanation(d: dict) -> dict:
 
 
 class _RowFamilySource:
-    """What a report keeps of one row family's scores (row_families.py: tail, onset, period, episode): the backend's handle
+    """What a report keeps of one row family's scores (row_families.py: tail, onset, period, episode, ramp): the backend's handle
     (``records()`` waits for the kernels and copies the planes and scores out on first use), the ranks its rows stand for,
     the sections it shows with their ids, the kernel names by id as the report's mapper had them at report time, and the
     family's parameters."""
@@ -1404,7 +1404,7 @@ class Report:
         work = self.__dict__.get("_work")
         if work is not None:
             state["_work"] = work.build() if isinstance(work, _WorkSource) else work
-        for fam in row_families.FAMILIES:
+        for fam in row_families.ROW_STEPS:
             scores = self.__dict__.get(fam.slot)
             if scores is not None:
                 state[fam.slot] = scores.build() if isinstance(scores, _RowFamilySource) else scores
@@ -1520,6 +1520,31 @@ class Report:
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no episode scores."""
         return self._identify_relative(self.episode_scores(), gpu_rel_threshold, section_rel_threshold)
+
+    def ramp_scores(self) -> Dict[str, Any]:
+        """Ramp scores (``ReportGenerator(ramp_detection=True)``; ``{}`` when the report carries none).  Whether a rank KEEPS
+        GETTING SLOWER within the window -- which a step fitted to it understates, a median misses while the rise covers less
+        than half the window, and trends across reports see only several reports later: per timing row the least-squares
+        hinge of its samples, in time order -- flat up to a knot, linear from there to the window's end, with at least
+        ``min_segment`` of the row (never fewer than 8 samples) rising.
+
+        ``{"gpu_relative": {rank: score}, "section_relative": {section: {rank: score}}, "section_ramps": {section: {rank:
+        {"rise", "base", "end", "strength", "samples_ago", "window", "whole_window"}}}, "kernel_ramps": {kernel: {rank:
+        {...}}}, "min_segment": x, "min_strength": x}`` -- the row has been rising for ``samples_ago`` of its ``window``
+        samples (``whole_window``: for all of them), from ``base`` to ``end`` on the fitted line; ``strength`` is the share of
+        the row's variance the hinge explains, ``rise`` is ``end / base`` where the row rose and the strength is at least
+        ``min_strength``, 1.0 otherwise (a falling ramp is reported and counts as "did not rise").  Scores are the steadiest
+        rank's rise over this rank's (NaN where a rank lacks the row): 1 = rose no more than the steadiest rank, so a warm-up the
+        whole job shares flags nobody.  A row that stepped up reads as a steep, short ramp: ``onset_scores()`` is the better
+        reading there.  Ranks and sections as in the score mappings, rows without samples are left out.  Plain dicts and
+        floats.  The first call waits for the ramp kernels and copies their results; ``generate_report`` does not."""
+        return self._family_scores("ramp")
+
+    def identify_ramp_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose RAMP scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no ramp scores."""
+        return self._identify_relative(self.ramp_scores(), gpu_rel_threshold, section_rel_threshold)
 
     def robust_scores(self) -> Dict[str, Any]:
         """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
@@ -2086,7 +2111,7 @@ def steps_behind_report(generator) -> tuple:
                  or getattr(generator, "work_groups", False) or getattr(generator, "peer_groups", None) is not None
                  or getattr(generator, "pace_scores", False) or getattr(generator, "node_scores", False)
                  or getattr(generator, "score_history", 0))
-    ring = bool(any(getattr(generator, fam.param_attrs[0], 0) for fam in row_families.FAMILIES)
+    ring = bool(any(getattr(generator, fam.param_attrs[0], 0) for fam in row_families.ROW_STEPS)
                 or getattr(generator, "collective_slack", False))
     return table, ring
 
@@ -2128,7 +2153,8 @@ class ReportGenerator:
                  node_scores: bool = False, node_groups=None, node_min_members: int = 2, node_min_nodes: int = 3,
                  node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
                  node_min_agree: float = 0.75, work_groups: bool = False, work_count_tol: float = 0.25,
-                 work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False) -> None:
+                 work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False,
+                 ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2395,6 +2421,27 @@ class ReportGenerator:
                 raise RuntimeError(f"episode_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no episode scores (backend.episode_score)")
             self.episode_len_ppm, self.episode_min_strength = len_ppm, strength
+        # ramp scores: every ring report also carries, per row, the hinge (flat, then linear to the window's end) that explains
+        # most of the window's variance and relative scores built from the rises (Report.ramp_scores); off: no buffer, no
+        # launch, no collective, no backend call.  The step adds one collective per report, so EVERY rank must pass the same
+        # value.
+        self.ramp_seg_ppm = 0  # (0 = off)
+        if ramp_detection:
+            seg_ppm = _backend_mod._native.ramp_seg_ppm(ramp_min_segment)
+            try:
+                strength = float(ramp_min_strength)
+            except (TypeError, ValueError):
+                raise ValueError(f"ramp_min_strength must be a number within [0, 1], got {ramp_min_strength!r}") from None
+            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"ramp_min_strength must be within [0, 1], got {ramp_min_strength!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"ramp_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "ramp scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "ramp_score"):
+                raise RuntimeError(f"ramp_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no ramp scores (backend.ramp_score)")
+            self.ramp_seg_ppm, self.ramp_min_strength = seg_ppm, strength
         # score history: every report also appends its scores to a device ring of the last H reports and says, per rank and
         # score, for how many reports in a row the score has been below its threshold (Report.score_history,
         # Report.identify_persistent_stragglers); 0 = off: no buffer, no launch, no backend call.  It reads what the score
@@ -2550,7 +2597,7 @@ class ReportGenerator:
                                    "has no slack scores per peer group (backend.slack_group_score)")
         # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
         # any, that needs the ring-start snapshot
-        self._row_families = tuple(f for f in row_families.FAMILIES if f.params(self))
+        self._row_families = tuple(f for f in row_families.ROW_STEPS if f.params(self))
         self._starts_family = next((f for f in self._row_families if f.needs_starts), None)
         # row families per peer group: the score step of every row family that is on takes a column's reference inside the
         # rank's OWN group (nvrx_rowfam_group_score); off: the step is the job-wide one, whatever peer_groups says.  The ring
@@ -3231,7 +3278,7 @@ class ReportGenerator:
         if self._peer_history is not None:
             self._peer_history.reset()
 
-    # ---- row families: tail, onset, period, episode scores ------------------------------------------
+    # ---- row families: tail, onset, period, episode and ramp scores ----------------------------------
     def _family_step(self, fam, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
         """One row family's step of a ring report, once per ``generate_report_from_rings`` call behind its last score round
         (and behind the steps of the families before it), on that round's workspace: the family's ring kernel on the window
@@ -3329,8 +3376,8 @@ class ReportGenerator:
         host; exchange and scoring run on the device exactly as in the ring path.  Summaries hold no samples: a report
         of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``), no onset scores
         (``onset_detection``; ``Report.onset_scores()`` is ``{}``), no period scores (``period_detection``;
-        ``Report.period_scores()`` is ``{}``) and no episode scores (``episode_detection``; ``Report.episode_scores()`` is
-        ``{}``).
+        ``Report.period_scores()`` is ``{}``), no episode scores (``episode_detection``; ``Report.episode_scores()`` is
+        ``{}``) and no ramp scores (``ramp_detection``; ``Report.ramp_scores()`` is ``{}``).
         """
         t0 = time.perf_counter_ns()
         self.world_size = dist_utils.get_world_size(self.group)

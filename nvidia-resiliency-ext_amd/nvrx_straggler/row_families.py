@@ -1,11 +1,13 @@
-"""The row families: score families computed from the ring rows of a report's window -- tail, onset, period, episode.
+"""The row families: score families computed from the ring rows of a report's window -- tail, onset, period, episode, and
+ramp behind them.
 
-All four are ONE pipeline with a different ring kernel in front ("Row families")::
+All of them are ONE pipeline with a different ring kernel in front ("Row families")::
 
     ring kernel by gid into [local_ranks][P][K+S] behind a -1 fill -> [all-gather] -> score kernel on plane 0 with pitch
     P * (K+S) -> one buffer, one ordered D2H on first read -> per-rank records + gpu_relative / section_relative
 
-``FAMILIES`` says what differs, once, in the fixed order the families run in (and issue their collectives in).  The backend
+``FAMILIES`` (and ``ROW_STEPS``: the four and ramp) says what differs, once, in the fixed order the families run in (and
+issue their collectives in).  The backend
 (``Workspace.family_buffers``, ``HipBackend._family_score``, ``HipRings._family_local``) and the reports
 (``reporting._RowFamilySource``, ``ReportGenerator._ring_steps``) are written against these records; a further family is
 a kernel file, one record here, its two public ``Report`` methods and the one-line delegations by name on the backend, the
@@ -47,6 +49,15 @@ def _episode_record(v, params):
     return {"length": length, "samples_ago": ago, "began_ago": ago + length if length else 0, "window": n,
             "inside": inside, "outside": outside, "strength": strength, "excess": e,
             "open_ended": bool(length) and ago == _native.episode_min_samples(params[0], n)}
+
+
+def _ramp_record(v, params):
+    e, base, end, strength, ago, n = v
+    if e == -1.0:  # (-1: the rank has no samples in this row)
+        return None
+    ago, n = int(ago), int(n)
+    return {"rise": e, "base": base, "end": end, "strength": strength, "samples_ago": ago, "window": n,
+            "whole_window": ago == n}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -93,5 +104,11 @@ FAMILIES: Tuple[RowFamily, ...] = (
               lambda p: {"min_length": p[0] / 1e6, "min_strength": p[1]},
               aliases=(("section_scores", "section_relative"), ("gpu_scores", "gpu_relative"))),
 )
-BY_NAME = {f.name: f for f in FAMILIES}
+# the fifth row shape runs behind the four (and ahead of slack): the same pipeline with k_row_ramp in front.  FAMILIES stays
+# the four-tuple it is; the product iterates ROW_STEPS.
+RAMP = RowFamily("ramp", _native.RAMP_PLANES, "nvrx_row_ramp", "nvrx_ramp_score", "nvrx_ramp_local", "ramp_detection",
+                 ("ramp_seg_ppm", "ramp_min_strength"), True, "_ramp", "ramps", _ramp_record,
+                 lambda p: {"min_segment": p[0] / 1e6, "min_strength": p[1]})
+ROW_STEPS: Tuple[RowFamily, ...] = FAMILIES + (RAMP,)
+BY_NAME = {f.name: f for f in ROW_STEPS}
 TAIL, ONSET, PERIOD, EPISODE = FAMILIES

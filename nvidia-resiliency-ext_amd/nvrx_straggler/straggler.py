@@ -443,6 +443,9 @@ class Detector(metaclass=_DeviceSideOnDemand):
         work_groups: Optional[bool] = None,
         work_count_tol: Optional[float] = None,
         work_max_unlike: Optional[float] = None,
+        ramp_detection: Optional[bool] = None,
+        ramp_min_segment: float = 0.05,
+        ramp_min_strength: float = 0.5,
     ):
         """
         Args:
@@ -512,6 +515,18 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 row's samples, within [0.000001, 0.333333]; never fewer than 8 samples.
             episode_min_strength: an episode counts when its two levels explain at least this share of the row's variance,
                 within [0, 1].  0.5 is a default, not a measurement.
+            ramp_detection: every report also says whether a rank KEEPS GETTING SLOWER within the window (a card heating up, an
+                allocator fragmenting, a link retraining down): per section and kernel row the least-squares hinge of its
+                samples, in time order -- flat, then linear to the window's end -- for how many samples the row has been
+                rising, from where to where, the share of the row's variance the hinge explains, and relative scores built
+                from ``end / base`` (``Report.ramp_scores()``, ``Report.identify_ramp_stragglers()``).  A step fitted to a
+                ramp reads its mean, not where the row has got to, and trends across reports notice several reports later.
+                Needs ``relative_perf_scores``.  Default: ``NVRX_RAMP_DETECTION``, else off.  Pass the same values on EVERY
+                rank (the step adds one collective per report).
+            ramp_min_segment: the rising part of a hinge holds at least this share of the row's samples, within
+                [0.000001, 0.5]; never fewer than 8 samples.  0.05 is a default, not a measurement.
+            ramp_min_strength: a ramp counts when its hinge explains at least this share of the row's variance, within
+                [0, 1].  0.5 is a default, not a measurement.
             score_history: 0 = off; H in 2..64: every report also appends its scores to a history of the last H reports and
                 says, per rank and score, for how many reports in a row the score has been below its threshold
                 (``Report.score_history()``, ``Report.identify_persistent_stragglers()``): a rank that was slow in one window
@@ -785,6 +800,11 @@ class Detector(metaclass=_DeviceSideOnDemand):
                             "node_min_nodes": node_min_nodes, "node_min_columns": node_min_columns,
                             "node_min_effect": node_min_effect, "node_min_breadth": node_min_breadth,
                             "node_min_agree": node_min_agree}
+        ramp_options = {}  # (off: the generator is built exactly as before)
+        if ramp_detection is None:
+            ramp_detection = os.environ.get("NVRX_RAMP_DETECTION", "0") not in ("", "0")
+        if ramp_detection:
+            ramp_options = {"ramp_detection": True, "ramp_min_segment": ramp_min_segment, "ramp_min_strength": ramp_min_strength}
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
@@ -799,7 +819,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
                                        slack_max_ratio=slack_max_ratio, **peer_options, **pace_options, **node_options,
-                                       **work_options)
+                                       **work_options, **ramp_options)
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
