@@ -100,6 +100,13 @@ every rank of the slower stage is slower in 120 of 120 kernels and ``identify_pa
 healthy; with ``ReportGenerator(pace_peer_groups=True)`` each rank is rated against the median of its own stage and rank 6 is
 named alone.  Both are printed.
 
+``--robust-peer`` plays a report of a pipeline job with an anomalously FAST rank in it: 8 ranks x 64 sections in two stages
+(``block:4``) of 1000 us and 1500 us, 1 % noise, rank 6 1.4 x slower than its stage's peers and rank 4 at 0.6 x its stage's time.
+The job-wide robust rule (``robust_scores=True``) takes its median from the fast stage and names the healthy ranks of the slow
+one; the peer scores divide by the group's fastest rank, so rank 4 flags all of its stage-mates; with
+``ReportGenerator(robust_peer_groups=True)`` each rank is rated against the median and spread of its own stage and rank 6 is
+named alone.  All three are printed.
+
 ``--node`` plays a report of 32 ranks x 120 kernels on 4 nodes of 8 (``node_groups="block:8"``; 1 % noise, seed 2026) in which
 every rank of node 2 is 4 % slower in every kernel -- failed fans, a capped PSU -- and rank 5 on node 0 is 4 % slower on its
 own.  ``identify_pace_stragglers`` names nine ranks and cannot say which of them are one incident; with node scores
@@ -733,6 +740,44 @@ def pace_peer(ranks: int = 8, kernels: int = 120, calls: int = 200, stage: int =
             job.close()
 
 
+def robust_peer(ranks: int = 8, sections: int = 64, calls: int = 64, stage: int = 4, slow_rank: int = 6, slowdown: float = 1.4,
+                fast_rank: int = 4, speedup: float = 0.6, seed: int = 2026) -> None:
+    """A slow and an anomalously fast rank in one stage of a pipeline job: whom the job-wide robust rule names, whom the peer
+    scores name, and whom the robust rule per peer group does."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    names = [f"section_{s:03d}" for s in range(sections)]
+    rng = np.random.default_rng(seed)
+    med = np.where((np.arange(ranks) // stage) % 2 == 1, 1500.0, 1000.0)[:, None] * (1.0 + 0.01 * rng.standard_normal((ranks, sections)))
+    med[slow_rank] *= slowdown
+    med[fast_rank] *= speedup
+    med = med.astype(np.float32)
+
+    def named(found):
+        return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
+
+    for title, grouped in (("job-wide", False), ("per-peer-group", True)):
+        job = FoldedJob(total_ranks=ranks, section_names=names, ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                        robust_scores=True, peer_groups=f"block:{stage}", robust_peer_groups=grouped)
+        try:
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, np.repeat(med[r][:, None], calls, axis=1))
+            report = job.report()
+            t = report.robust_scores()
+            print(f"identify_robust_stragglers() {title}: {named(report.identify_robust_stragglers())}")
+            if not grouped:
+                print(f"identify_peer_stragglers(): {named(report.identify_peer_stragglers())}")
+            for r in sorted(t["gpu_z"]):
+                z = [t["section_z"][n][r] for n in names]
+                against = f"group {t['group_of'][r]}'s" if grouped else "the job's"
+                print(f"  rank {r}: section z against {against} median and spread from {min(z):+.1f} to {max(z):+.1f}")
+        finally:
+            job.close()
+
+
 def node(ranks: int = 32, per_node: int = 8, kernels: int = 120, calls: int = 200, slow_node: int = 2, slow_rank: int = 5,
          slowdown: float = 1.04, seed: int = 2026) -> None:
     """A slow host and a slow GPU in one job: whom the pace rule names, and what the node rule makes of them."""
@@ -818,6 +863,10 @@ def main() -> None:
     ap.add_argument("--pace-peer", action="store_true",
                     help="no training: play the pace-score scenario of a pipeline job (two stages, the second 1.5 x slower, rank 6 "
                          "4 %% slower than its stage in every kernel) with the job-wide rule and the rule per peer group, and exit")
+    ap.add_argument("--robust-peer", action="store_true",
+                    help="no training: play the robust-score scenario of a pipeline job (two stages of 1000 us and 1500 us, rank "
+                         "6 1.4 x slower than its stage, rank 4 at 0.6 x its stage's time) with the job-wide robust rule, the peer "
+                         "scores and the robust rule per peer group, and exit")
     ap.add_argument("--node", action="store_true",
                     help="no training: play the node-score scenario (32 ranks on 4 nodes, every rank of node 2 and rank 5 of node "
                          "0 4 %% slower in every kernel) with the pace rule and the node rule, and exit")
@@ -842,6 +891,9 @@ def main() -> None:
         return
     if args.pace_peer:
         pace_peer()
+        return
+    if args.robust_peer:
+        robust_peer()
         return
     if args.pace:
         pace()

@@ -505,6 +505,38 @@ int nvrx_pace_score(const float *d_table, int R, int K, int S, int first_rank, i
 int nvrx_pace_group_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group,
                           int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out, void *stream);
 
+/* Robust scores per peer group: nvrx_robust_score with the lower median and the MAD of the rank's OWN group as centre and
+ * spread.  The median of the whole job is the wrong centre in a job of pipeline stages, tensor-parallel or expert groups: it lies
+ * in one of the groups, the MAD is that group's scatter, and every healthy rank of a slower group gets a huge z.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_ROBUST_MAX_RANKS.
+ *   d_groups, G, max_group  as nvrx_pace_group_score takes them, and the MEMBERS of group g and size_g are that entry's: start
+ *      values clamped to [0, R], a stretch clamped to max_group, an entry outside [0, R) skipped.  max_group selects the kernel
+ *      variant: at most 64, SLOT is the smallest power of two >= max_group (at least 2), a wave holds 64 / SLOT groups and a
+ *      group owns SLOT lanes; at most 1024, 256 threads per pair; beyond, 1024.
+ *   Per pair (group g, column c < K+S of the table's med part), over the members of g; a member is PRESENT iff its value
+ *   v >= 0:
+ *      n      present values;
+ *      ctr    their LOWER median: the element of rank (n-1) >> 1 sorted by raw bit pattern (ties: the lower slot first);
+ *      mad    the lower median of the f32 bit patterns of |v - ctr| (f32 subtraction) over the same members;
+ *      scale  max(1.4826f * mad, floor_rel * ctr), in f32, as nvrx_robust_score spells it;
+ *      the pair is REFERENCED iff n >= max(min_peers, min(min_ranks, size_g)) (nvrx_pace_group_score's rule);
+ *      record, 16 bytes: {f32 ctr, f32 mad, f32 scale (the canonical NaN 0x7FC00000 in all three where not referenced), u32 n},
+ *      at d_out[g * (K+S) + c] in 16-byte units; n is always written.
+ *   Per reported rank r in [first_rank, first_rank + n_ranks): exactly nvrx_robust_score's two rows {gpu, section[S]} of ratio
+ *   and z, in f64, over the columns where r is present and the pair (group[r], c) is referenced, ctr and scale being the
+ *   group's.  A rank whose group[r] is outside [0, G) gets NaN throughout.
+ *   d_out  16-byte aligned, NVRX_ROBUST_GROUP_WORDS(G, n_ranks, K, S) 32-bit words: [G][K+S] column records, then
+ *   [n_ranks][2][1 + S] f32.
+ *   The CONTENTS of d_groups are guarded on the device as stated above; no content makes a kernel read or write outside the
+ *   table, the array or d_out.  With one group of all ranks and min_peers = 1 every record and score is nvrx_robust_score's.
+ * Two launches on `stream` (columns, ranks); no atomics on global memory, no scratch.  Argument errors, reported before any
+ * device is touched: those of nvrx_pace_group_score in its order (up to min_peers), then nvrx_robust_score's of floor_rel, then
+ * NVRX_ERR_INVALID for a null pointer or a d_out that is not 16-byte aligned. */
+#define NVRX_ROBUST_GROUP_WORDS(G, n_ranks, K, S) (4 * (size_t)(G) * ((size_t)(K) + (S)) + (size_t)(n_ranks) * 2 * (1 + (size_t)(S)))
+int nvrx_robust_group_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group,
+                            int first_rank, int n_ranks, int min_ranks, int min_peers, float floor_rel, void *d_out,
+                            void *stream);
+
 /* Node scores: tell a slow HOST from a slow GPU.  Every score above rates a rank; an operator cordons a node.  A chassis whose
  * fans failed, a capped PSU or a throttling host CPU makes every GPU of one node a few per cent slower in everything: the pace
  * scores name all of its ranks and cannot say that they are one incident.  Here a node votes once per column, with the lower
@@ -1075,6 +1107,13 @@ int nvrx_report_pace(nvrx_ctx *ctx, const nvrx_report_desc *desc, int first_rank
  * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_pace_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group,
                            int first_rank, int n_ranks, int min_ranks, int min_peers, void *d_out);
+/* nvrx_robust_group_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor; d_groups sized for the descriptor's R).  Ordered behind that report's kernels exactly as
+ * nvrx_report_pace_group orders itself: the context's stream, with an event when the report was re-homed or scored resident.
+ * The host does not wait; copy d_out with a D2H on the context's stream, and do not let a later report rewrite the table before
+ * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_robust_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group,
+                             int first_rank, int n_ranks, int min_ranks, int min_peers, float floor_rel, void *d_out);
 /* nvrx_node_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
  * exchange; shape from the descriptor; d_groups sized for the descriptor's R).  Ordered behind that report's kernels exactly as
  * nvrx_report_pace_group orders itself: the context's stream, with an event when the report was re-homed or scored resident.

@@ -21,6 +21,8 @@
 //   never enter a histogram.  Exact, ties and all, no data-dependent path.
 // k_robust_rank  one workgroup per reported rank, shaped like k_tail_score.
 
+#include <type_traits>
+
 namespace {
 
 constexpr int ROBUST_TILE = 64;       // columns per workgroup of the small kernel
@@ -207,8 +209,26 @@ struct RobustRankArgs {
     float *out;  // [n_ranks][2][1 + S]
 };
 
-// one workgroup per reported rank: {gpu, section[S]} ratios, then the same of z
-__global__ __launch_bounds__(ROBUST_THREADS) void k_robust_rank(RobustRankArgs a) {
+// k_robust_rank's GROUPED form (nvrx_robust_group.inl): the records of the rank's own group
+struct RobustGroupRankArgs {
+    const float *table;     // [R][L]
+    const uint4 *cols;      // [G][KS]
+    const int32_t *groups;  // group[R] | ...
+    int K, S, G;
+    int first_rank;
+    float *out;  // [n_ranks][2][1 + S]
+};
+
+// the grouped records' rule: the centre is a number exactly where the pair is referenced
+__device__ __forceinline__ bool robust_referenced(const uint4 rec) {
+    const float ctr = __uint_as_float(rec.x);
+    return ctr == ctr;
+}
+
+// one workgroup per reported rank: {gpu, section[S]} ratios, then the same of z.  GROUPED (a compile-time flag: the job-wide
+// instantiation is what it was): the records at cols + group[r] * (K+S); a rank whose group id is outside [0, G) gets NaN.
+template <bool GROUPED = false>
+__global__ __launch_bounds__(ROBUST_THREADS) void k_robust_rank(std::conditional_t<GROUPED, RobustGroupRankArgs, RobustRankArgs> a) {
     constexpr int NW = ROBUST_THREADS / 64;
     __shared__ double s_sum[3][NW];
     __shared__ uint32_t s_cnt[NW];
@@ -220,28 +240,53 @@ __global__ __launch_bounds__(ROBUST_THREADS) void k_robust_rank(RobustRankArgs a
     float *__restrict__ ratio = a.out + (size_t)blockIdx.x * 2 * (size_t)(1 + S);
     float *__restrict__ z = ratio + (1 + S);
     const float NaN = __builtin_nanf("");
-
-    for (int s = tid; s < S; s += ROBUST_THREADS) {
-        const float v = row[K + s];
-        const uint4 rec = a.cols[K + s];
-        const bool ok = v >= 0.0f && rec.w != 0u && (int)rec.w >= a.min_ranks;
-        const double ctr = (double)__uint_as_float(rec.x), scale = (double)__uint_as_float(rec.z);
-        ratio[1 + s] = ok ? (float)(ctr / (double)v) : NaN;
-        z[1 + s] = ok ? (float)(((double)v - ctr) / scale) : NaN;
-    }
     double ws = 0.0, sr = 0.0, sz = 0.0;
     uint32_t cnt = 0;
-    for (int k = tid; k < K; k += ROBUST_THREADS) {
-        const float v = row[k];
-        if (!(v >= 0.0f)) continue;
-        const uint4 rec = a.cols[k];
-        if (rec.w == 0u || (int)rec.w < a.min_ranks) continue;
-        const double ctr = (double)__uint_as_float(rec.x), scale = (double)__uint_as_float(rec.z);
-        const double w = (double)row[2 * KS + k];
-        sr += w * (ctr / (double)v);
-        sz += w * (((double)v - ctr) / scale);
-        ws += w;
-        cnt++;
+    if constexpr (GROUPED) {
+        const int g = a.groups[r];
+        const bool has_group = (uint32_t)g < (uint32_t)a.G;  // block-uniform
+        const uint4 *__restrict__ cols = a.cols + (size_t)(has_group ? g : 0) * (size_t)KS;
+        for (int s = tid; s < S; s += ROBUST_THREADS) {
+            const float v = row[K + s];
+            const uint4 rec = cols[K + s];
+            const bool ok = v >= 0.0f && has_group && robust_referenced(rec);
+            const double ctr = (double)__uint_as_float(rec.x), scale = (double)__uint_as_float(rec.z);
+            ratio[1 + s] = ok ? (float)(ctr / (double)v) : NaN;
+            z[1 + s] = ok ? (float)(((double)v - ctr) / scale) : NaN;
+        }
+        for (int k = tid; k < K; k += ROBUST_THREADS) {
+            const float v = row[k];
+            if (!(v >= 0.0f) || !has_group) continue;
+            const uint4 rec = cols[k];
+            if (!robust_referenced(rec)) continue;
+            const double ctr = (double)__uint_as_float(rec.x), scale = (double)__uint_as_float(rec.z);
+            const double w = (double)row[2 * KS + k];
+            sr += w * (ctr / (double)v);
+            sz += w * (((double)v - ctr) / scale);
+            ws += w;
+            cnt++;
+        }
+    } else {  // (the job-wide loops, spelled as they always were: this instantiation is the kernel it was)
+        for (int s = tid; s < S; s += ROBUST_THREADS) {
+            const float v = row[K + s];
+            const uint4 rec = a.cols[K + s];
+            const bool ok = v >= 0.0f && rec.w != 0u && (int)rec.w >= a.min_ranks;
+            const double ctr = (double)__uint_as_float(rec.x), scale = (double)__uint_as_float(rec.z);
+            ratio[1 + s] = ok ? (float)(ctr / (double)v) : NaN;
+            z[1 + s] = ok ? (float)(((double)v - ctr) / scale) : NaN;
+        }
+        for (int k = tid; k < K; k += ROBUST_THREADS) {
+            const float v = row[k];
+            if (!(v >= 0.0f)) continue;
+            const uint4 rec = a.cols[k];
+            if (rec.w == 0u || (int)rec.w < a.min_ranks) continue;
+            const double ctr = (double)__uint_as_float(rec.x), scale = (double)__uint_as_float(rec.z);
+            const double w = (double)row[2 * KS + k];
+            sr += w * (ctr / (double)v);
+            sz += w * (((double)v - ctr) / scale);
+            ws += w;
+            cnt++;
+        }
     }
     ws = wave_sum_f64(ws);
     sr = wave_sum_f64(sr);
@@ -305,7 +350,7 @@ int robust_launch(const float *d_table, int R, int K, int S, int first_rank, int
     a.table = d_table, a.cols = static_cast<const uint4 *>(d_out);
     a.K = K, a.S = S, a.first_rank = first_rank, a.min_ranks = min_ranks;
     a.out = static_cast<float *>(d_out) + 4 * (size_t)KS;
-    hipLaunchKernelGGL(k_robust_rank, dim3(n_ranks), dim3(ROBUST_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_robust_rank<false>, dim3(n_ranks), dim3(ROBUST_THREADS), 0, st, a);
     HIP_TRY(hipGetLastError());
     return NVRX_OK;
 }

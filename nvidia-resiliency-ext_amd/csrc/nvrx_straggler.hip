@@ -4034,6 +4034,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_rowfam_group.inl"
 #include "nvrx_pace.inl"
 #include "nvrx_pace_group.inl"
+#include "nvrx_robust_group.inl"
 #include "nvrx_slack_group.inl"
 #include "nvrx_node.inl"
 #include "nvrx_work.inl"

@@ -108,6 +108,8 @@ SYMBOLS = [
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_group_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p]),
+    ("nvrx_robust_group_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                        c_void_p, c_void_p]),
     ("nvrx_node_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
@@ -169,6 +171,8 @@ SYMBOLS = [
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace_group", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p]),
+    ("nvrx_report_robust_group", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_float, c_void_p]),
     ("nvrx_report_node", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
@@ -293,6 +297,12 @@ def pace_group_words(G: int, n_ranks: int, K: int, S: int) -> int:
     """NVRX_PACE_GROUP_WORDS: 32-bit words of a block of pace scores per peer group: ``[G][K+S][4]`` column records, then
     ``[n_ranks][2][8]``."""
     return 4 * G * (K + S) + 16 * n_ranks
+
+
+def robust_group_words(G: int, n_ranks: int, K: int, S: int) -> int:
+    """NVRX_ROBUST_GROUP_WORDS: 32-bit words of a block of robust scores per peer group: ``[G][K+S][4]`` column records, then
+    ``[n_ranks][2][1 + S]``."""
+    return 4 * G * (K + S) + n_ranks * 2 * (1 + S)
 
 
 def node_words(G: int, n_ranks: int, K: int, S: int) -> int:

@@ -30,7 +30,7 @@ import torch
 
 from . import _native
 from .row_families import EPISODE, ONSET, PERIOD, RAMP, ROW_STEPS, TAIL, RowFamily
-from .table_families import NODE, PACE, PACE_GROUP, PEER, ROBUST, SLOTS, TableFamily
+from .table_families import NODE, PACE, PACE_GROUP, PEER, ROBUST, ROBUST_GROUP, SLOTS, TableFamily
 
 DEFAULT_THRESHOLDS = (0.75, 0.75, 0.75, 0.75)  # gpu_rel, section_rel, gpu_indiv, section_indiv
 
@@ -1297,6 +1297,11 @@ class HipBackend:
                          n_ranks: Optional[int] = None, min_ranks: int = 4, min_peers: int = 2) -> TableScores:
         return self._table_score(PACE_GROUP, ws, table, groups, first_rank, n_ranks, (min_ranks, min_peers))
 
+    def robust_group_score(self, ws: Workspace, table: torch.Tensor, groups: PeerGroups, first_rank: int = 0,
+                           n_ranks: Optional[int] = None, min_ranks: int = 4, min_peers: int = 2,
+                           floor_rel: float = 0.02) -> TableScores:
+        return self._table_score(ROBUST_GROUP, ws, table, groups, first_rank, n_ranks, (min_ranks, min_peers, floor_rel))
+
     def node_score(self, ws: Workspace, table: torch.Tensor, nodes: PeerGroups, first_rank: int = 0,
                    n_ranks: Optional[int] = None, min_members: int = 2, min_nodes: int = 3) -> TableScores:
         return self._table_score(NODE, ws, table, nodes, first_rank, n_ranks, (min_members, min_nodes))
@@ -1311,6 +1316,9 @@ class HipBackend:
         return self.table_copy_out(t)
 
     def pace_group_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
+
+    def robust_group_copy_out(self, t: TableScores):
         return self.table_copy_out(t)
 
     def node_copy_out(self, t: TableScores):
@@ -1874,6 +1882,10 @@ class HipRings:
     def report_pace_group(self, ws: Workspace, groups: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
                           min_ranks: int = 4, min_peers: int = 2) -> TableScores:
         return self._table_report(PACE_GROUP, ws, groups, first_rank, n_ranks, (min_ranks, min_peers))
+
+    def report_robust_group(self, ws: Workspace, groups: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                            min_ranks: int = 4, min_peers: int = 2, floor_rel: float = 0.02) -> TableScores:
+        return self._table_report(ROBUST_GROUP, ws, groups, first_rank, n_ranks, (min_ranks, min_peers, floor_rel))
 
     def report_node(self, ws: Workspace, nodes: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
                     min_members: int = 2, min_nodes: int = 3) -> TableScores:

@@ -39,7 +39,7 @@ class FoldedJob:
                  work_count_tol: float = 0.25, work_max_unlike: float = 0.1, peer_history: int = 0,
                  peer_persistence_min_reports: int = 3, peer_persistence_thresholds=None, peer_trends: bool = False,
                  slack_peer_groups: bool = False, row_peer_groups: bool = False, ramp_detection: bool = False,
-                 ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5):
+                 ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5, robust_peer_groups: bool = False):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -70,6 +70,7 @@ class FoldedJob:
                                         pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth,
                                         **({"pace_peer_groups": True} if pace_peer_groups else {}),
                                         **({"slack_peer_groups": True} if slack_peer_groups else {}),
+                                        **({"robust_peer_groups": True} if robust_peer_groups else {}),
                                         **({"row_peer_groups": True} if row_peer_groups else {}),
                                         **({"ramp_detection": True, "ramp_min_segment": ramp_min_segment,
                                             "ramp_min_strength": ramp_min_strength} if ramp_detection else {}),

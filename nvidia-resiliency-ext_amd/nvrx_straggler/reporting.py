@@ -789,6 +789,53 @@ class _RobustSource:
         return self._built
 
 
+class _RobustGroupSource(_RobustSource):
+    """``_RobustSource`` for robust scores per peer group: the handle's column records come per group, and the report also says
+    which ranks form which group."""
+
+    __slots__ = ("groups", "min_peers")
+
+    def __init__(self, handle, ranks, sections, kernels, min_ranks: int, floor: float, groups, min_peers: int):
+        super().__init__(handle, ranks, sections, kernels, min_ranks, floor)
+        self.groups, self.min_peers = groups, min_peers
+
+    def build(self) -> dict:
+        if self._built is None:
+            cols, scores = self.handle.records()
+            K = len(self.kernels)
+            ranks, labels = self.ranks, self.groups.labels
+            group = self.groups.group.tolist()
+            G = len(labels)
+            f = np.ascontiguousarray(cols).view(np.float32)[:, :, :3].tolist()
+            n = cols[:, :, 3].tolist()
+            sc = scores.tolist()
+
+            def per_group(c, word):
+                return {labels[g]: (n[g][c] if word == 3 else f[g][c][word]) for g in range(G)}
+
+            with_data = {name: per_group(k, 3) for k, name in enumerate(self.kernels)}
+            with_data.update((name, per_group(K + g, 3)) for name, g in self.sections.items())
+            self._built = {
+                "gpu_ratio": {r: sc[i][0][0] for i, r in enumerate(ranks)},
+                "gpu_z": {r: sc[i][1][0] for i, r in enumerate(ranks)},
+                "section_ratio": {name: {r: sc[i][0][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_z": {name: {r: sc[i][1][1 + g] for i, r in enumerate(ranks)} for name, g in self.sections.items()},
+                "section_center": {name: per_group(K + g, 0) for name, g in self.sections.items()},
+                "section_spread": {name: per_group(K + g, 2) for name, g in self.sections.items()},
+                "kernel_center": {name: per_group(k, 0) for k, name in enumerate(self.kernels)},
+                "ranks_with_data": with_data,
+                "min_ranks": self.min_ranks,
+                "floor": self.floor,
+                "peer_groups": True,
+                "min_peers": self.min_peers,
+                "groups": {labels[g]: self.groups.members(g) for g in range(G)},
+                "group_of": {r: labels[group[r]] for r in ranks},
+                "unrated_ranks": [r for i, r in enumerate(ranks) if all(x != x for row in sc[i] for x in row)],
+            }
+            self.handle = self.groups = None
+        return self._built
+
+
 def _pace_rank_parts(recs, ranks) -> dict:
     """``{rank: {"gpu": {...}, "sections": {...}}}`` of ``[n_ranks][2][8]`` pace rank records (uint32 bit patterns)."""
     recs = np.ascontiguousarray(recs)
@@ -1558,13 +1605,18 @@ class Report:
         n, "floor": x}`` -- a ratio above 1 is faster than the median, a positive z slower; the GPU entries are the means of
         the per-kernel ratios and z weighted by the microseconds spent in each kernel; NaN where a rank lacks the row or
         fewer than ``min_ranks`` ranks have it.  Ranks and sections as in the score mappings.  Plain dicts and floats.  The
-        first call waits for the robust kernels and copies their results; ``generate_report`` does not."""
+        first call waits for the robust kernels and copies their results; ``generate_report`` does not.
+
+        With ``ReportGenerator(robust_peer_groups=True)`` centre and spread are those of the rank's OWN peer group:
+        ``section_center``, ``section_spread``, ``kernel_center`` and ``ranks_with_data`` map each name to ``{group label:
+        value}``, and ``peer_groups`` (True), ``min_peers``, ``groups``, ``group_of`` and ``unrated_ranks`` are added, spelled as
+        ``peer_scores()`` spells them."""
         robust = self.__dict__.get("_robust")
         if robust is None:
             return {}
         if isinstance(robust, _RobustSource):
             robust = self.__dict__["_robust"] = robust.build()
-        return _copy_scores(robust)
+        return _copy_peer(robust) if "peer_groups" in robust else _copy_scores(robust)  # (the grouped form holds lists)
 
     def identify_robust_stragglers(self, gpu_z_threshold: float = 3.5, section_z_threshold: float = 3.5) -> Dict[str, Any]:
         """Ranks whose robust z-scores lie strictly ABOVE the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
@@ -2154,7 +2206,8 @@ class ReportGenerator:
                  node_min_columns: int = 8, node_min_effect: float = 0.03, node_min_breadth: float = 0.9,
                  node_min_agree: float = 0.75, work_groups: bool = False, work_count_tol: float = 0.25,
                  work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False,
-                 ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5) -> None:
+                 ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5,
+                 robust_peer_groups: bool = False) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2326,6 +2379,19 @@ class ReportGenerator:
             if be is not None and not hasattr(be, "pace_group_score"):
                 raise RuntimeError(f"pace_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no pace scores per peer group (backend.pace_group_score)")
+        # robust scores per peer group: the robust step rates each rank against the lower median and MAD of its OWN group
+        # (nvrx_robust_group_score), behind the peer step; off: the robust step is the job-wide one, whatever peer_groups says
+        self.robust_peer_groups = bool(robust_peer_groups)
+        if self.robust_peer_groups:
+            if not self.robust_scores or self.peer_groups is None:
+                missing = [name for name, on in (("robust_scores", self.robust_scores), ("peer_groups", self.peer_groups is not None))
+                           if not on]
+                raise ValueError(f"robust_peer_groups needs robust_scores and peer_groups; {' and '.join(missing)} "
+                                 f"{'is' if len(missing) == 1 else 'are'} not set")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "robust_group_score"):
+                raise RuntimeError(f"robust_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no robust scores per peer group (backend.robust_group_score)")
         # node scores: every report also says whether a NODE is a little slower in nearly all of its kernels (Report.node_scores);
         # off: nothing is allocated, resolved, launched or called.  They read the exchanged table and rank_to_node only: no
         # collective, so ranks need not agree on the option.
@@ -2621,8 +2687,9 @@ class ReportGenerator:
         pace = ("pace_peer_groups", "report_pace_group") if self.pace_peer_groups else ("pace_scores", "report_pace")
         self._one_call_needs = tuple((option, method) for on, option, method in (
             (self.kernel_attribution, f"kernel_attribution={self.kernel_attribution}", "report_attribute"),
-            (self.robust_scores, "robust_scores", "report_robust"),
+            (self.robust_scores and not self.robust_peer_groups, "robust_scores", "report_robust"),
             (self.work_groups, "work_groups", "report_work"), (self.peer_groups is not None, "peer_groups", "report_peer"),
+            (self.robust_peer_groups, "robust_peer_groups", "report_robust_group"),
             (self.pace_scores,) + pace, (self.node_scores, "node_scores", "report_node"),
             (self.peer_history, "peer_history", "report_peer_history"), (self.peer_trends, "peer_trends", "report_peer_trend"),
             (self.score_history, "score_history", "report_history"), (self.score_trends, "score_trends", "report_trend")) if on)
@@ -3127,7 +3194,7 @@ class ReportGenerator:
                 handle = be.attribute(ws, ws.table, self.kernel_attribution, self.is_computing_indiv_scores,
                                       self.is_computing_rel_scores, lo, n)
             d["_attr"] = self._attr_source(handle, ws, mapper, lo, hi, view.ranks)
-        if self.robust_scores:
+        if self.robust_scores and not self.robust_peer_groups:
             least = self._robust_min(ws)
             if rings is not None:
                 handle = rings.report_robust(ws, lo, n, least, self.robust_floor)
@@ -3165,6 +3232,15 @@ class ReportGenerator:
                     handle = rings.report_peer_trend(ws, state) if rings is not None else be.peer_trend(ws, state)
                     d["_peer_trends"] = _PeerTrendSource(handle, view.ranks, view.cols, min(state.n_before, self.peer_history),
                                                          self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon, thr)
+        if self.robust_peer_groups:
+            # behind the peer step and its history and trend (peer_groups="auto" has its groups by then), ahead of pace
+            groups, least = self._peer_for(ws), self._robust_min(ws)
+            if rings is not None:
+                handle = rings.report_robust_group(ws, groups, lo, n, least, self.peer_min_ranks, self.robust_floor)
+            else:
+                handle = be.robust_group_score(ws, ws.table, groups, lo, n, least, self.peer_min_ranks, self.robust_floor)
+            d["_robust"] = _RobustGroupSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), least,
+                                              self.robust_floor, groups, self.peer_min_ranks)
         if self.pace_scores:
             least = self._pace_min(ws)
             params = {"min_ranks": least, "min_columns": self.pace_min_columns, "min_effect": self.pace_min_effect,

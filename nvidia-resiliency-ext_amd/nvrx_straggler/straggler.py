@@ -432,6 +432,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         pace_peer_groups: Optional[bool] = None,
         slack_peer_groups: Optional[bool] = None,
         row_peer_groups: Optional[bool] = None,
+        robust_peer_groups: Optional[bool] = None,
         node_scores: Optional[bool] = None,
         node_groups=None,
         node_min_members: int = 2,
@@ -598,6 +599,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 ``max(peer_min_ranks, min(pace_min_ranks, its size))`` ranks with a kernel for its median to be a reference.
                 Default: ``NVRX_PACE_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank (no collective depends
                 on it).
+            robust_peer_groups: the robust scores rate each rank against the lower median and the MAD of its OWN peer group
+                instead of the whole job's -- in a job of pipeline stages, tensor-parallel or expert groups the job's median lies
+                in one group and every healthy rank of a slower one gets a huge z.  Needs ``robust_scores`` and ``peer_groups``
+                (``"auto"`` is allowed); a group needs ``max(peer_min_ranks, min(robust_min_ranks, its size))`` ranks with a
+                kernel for its median to be a reference.  Default: ``NVRX_ROBUST_PEER_GROUPS`` ("1"; "0" or unset: off).  Same
+                value on every rank (no collective depends on it).
             slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
                 peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
                 expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
@@ -773,6 +780,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
             pace_peer_groups = from_env == "1"
         if pace_peer_groups:
             pace_options["pace_peer_groups"] = True  # (the generator says which of pace_scores and peer_groups it misses)
+        if robust_peer_groups is None:
+            from_env = os.environ.get("NVRX_ROBUST_PEER_GROUPS", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_ROBUST_PEER_GROUPS must be 0 or 1, got {from_env!r}")
+            robust_peer_groups = from_env == "1"
+        if robust_peer_groups:
+            pace_options["robust_peer_groups"] = True  # (the generator says which of robust_scores and peer_groups it misses)
         if slack_peer_groups is None:
             from_env = os.environ.get("NVRX_SLACK_PEER_GROUPS", "")
             if from_env not in ("", "0", "1"):

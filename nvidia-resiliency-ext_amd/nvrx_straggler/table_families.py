@@ -6,7 +6,8 @@ The device kernels differ; the host path is ONE (DESIGN.md, "Table families")::
     settle the slot's last step -> the slot's records buffer -> nvrx_<name>_score on the caller's table, or
     nvrx_report_<name> behind the report just issued -> one uint32 block, one ordered D2H on first read -> cut into arrays
 
-``FAMILIES`` says what differs, once, in the fixed order the families run in.  The backend (``Workspace.table_buffers`` /
+``FAMILIES`` (and ``ROBUST_GROUP`` beside it: robust scores per peer group) says what differs, once, in the fixed order the
+families run in.  The backend (``Workspace.table_buffers`` /
 ``table_settle``, ``HipBackend._table_score`` / ``table_copy_out``, ``HipRings._table_report``, ``TableScores``) is written
 against these records; a further family is a kernel file, one record here, its ``Report`` methods and the one-line
 delegations by name on the backend, the workspace and the rings.
@@ -93,3 +94,10 @@ FAMILIES: Tuple[TableFamily, ...] = (
 BY_NAME = {f.name: f for f in FAMILIES}
 ROBUST, PEER, PACE, PACE_GROUP, NODE = FAMILIES
 SLOTS: Tuple[TableFamily, ...] = (ROBUST, PEER, PACE, NODE)  # one family per slot, in the order the slots settle
+
+# robust scores per peer group run in robust's slot (a report runs one of the two) with a records block of their own.  FAMILIES
+# stays the five the slots were written for (the backend names its families by these constants, not by a lookup).
+# (cols [G, K+S, 4] uint32 {ctr, mad, scale, n}, scores [n_ranks, 2, 1 + S] f32 {ratio, z})
+ROBUST_GROUP = TableFamily("robust_group", "nvrx_robust_group_score", "nvrx_report_robust_group", "robust",
+                           _native.robust_group_words, "peer", True, _RANKS + ("min_ranks", "min_peers", "floor_rel"),
+                           lambda G, n, KS, S: (((G, KS, 4), _U32), ((n, 2, 1 + S), _F32)))
