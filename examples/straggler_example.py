@@ -57,6 +57,12 @@ of it on, with tail, onset, episode and ramp scores on (``ReportGenerator(ramp_d
 ``identify_*_stragglers`` names and what each score reads for the two ranks next to their onset and ramp records
 (``Report.ramp_scores()``): for how many samples the row has been rising, from where to where.
 
+``--stall`` needs no training loop: it plays one report of a job of 8 ranks (folded onto one GPU, 2 sections x 10 000 samples,
+1 % noise, seed 43) in which rank 5 has ten samples of 50 x at fixed pseudo-random positions and rank 2 has one (0.5 % of its
+window, below ``stall_min_share``), with every row family on (``ReportGenerator(stall_detection=True)``), and prints whom each
+``identify_*_stragglers`` names and what every family reads for rank 5 next to its stall record (``Report.stall_scores()``):
+how many events, how long ago the last one, what share of the window they cost.
+
 ``--persist`` needs no training loop: it plays 20 reports of a job of 8 ranks (folded onto one GPU, 1 % noise, seed 17) in which
 rank 2 is 1.6x slower in report 6 only and rank 5 is 1.45x slower from report 10 on, with a score history of 8 reports
 (``ReportGenerator(score_history=8, persistence_min_reports=3)``), and prints per report whom ``identify_stragglers`` flags and
@@ -508,6 +514,55 @@ def ramp(rising: int = 5, stepped: int = 2) -> None:
         job.close()
 
 
+STALL_FAMILIES = ("tail", "onset", "period", "episode", "ramp", "stall")
+STALL_OPTIONS = dict(tail_quantile=0.95, onset_detection=True, period_detection=True, episode_detection=True,
+                     ramp_detection=True, stall_detection=True)
+
+
+def stall_samples(ranks: int = 8, sections: int = 2, samples: int = 10000, stalled: int = 5, once: int = 2):
+    """The ``--stall`` job: ``[ranks, sections, samples]`` f64 microseconds (NumPy only), 1000 us with 1 % noise; rank
+    ``stalled`` has ten samples of 50 x at fixed pseudo-random positions of every row, rank ``once`` has one."""
+    import numpy as np
+
+    rng = np.random.default_rng(43)
+    x = 1000.0 * (1.0 + 0.01 * rng.standard_normal((ranks, sections, samples)))
+    at = np.sort(rng.choice(np.arange(0, samples, 3), 10, replace=False))  # (no two of them adjacent: ten events)
+    x[stalled][:, at] *= 50.0
+    x[once, :, at[3]] *= 50.0
+    return x
+
+
+def stall(stalled: int = 5, once: int = 2) -> None:
+    """Ten isolated stalls in a window of 10 000 under every score that reads a window: what each family says of the stalled
+    rank, next to its stall record."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    x = stall_samples(stalled=stalled, once=once)
+    ranks, sections, samples = x.shape
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=samples, scores_to_compute=("relative_perf_scores",),
+                    **STALL_OPTIONS)
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, x[r].astype(np.float32))
+        report = job.report()
+        name = job.section_names[0]
+        print(f"identify_stragglers(): {named_ranks({k: v for k, v in report.identify_stragglers().items() if 'relative' in k})}")
+        for family in STALL_FAMILIES:
+            print(f"identify_{family}_stragglers(): {named_ranks(getattr(report, f'identify_{family}_stragglers')())}")
+        for r in (stalled, once):
+            print(f"rank {r}, {name}: relative {report.section_relative_perf_scores[name][r]:.3f}, "
+                  + ", ".join(f"{family} {getattr(report, family + '_scores')()['section_relative'][name][r]:.3f}"
+                              for family in STALL_FAMILIES))
+            rec = report.stall_scores()["section_stalls"][name][r]
+            print(f"  stall record: {rec['events']} events in {rec['window']} samples, the last {rec['last_samples_ago']} samples ago, "
+                  f"{rec['pace']:.0f} -> {rec['level']:.0f} us, {100 * rec['share']:.1f} % of the window lost, excess {rec['excess']:.3f}")
+    finally:
+        job.close()
+
+
 def named_ranks(found) -> list:
     """The ranks an ``identify_*_stragglers()`` result names, in any of its mappings."""
     return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
@@ -873,10 +928,16 @@ def main() -> None:
     ap.add_argument("--work", action="store_true",
                     help="no training: play the work-group scenario (the two pipeline stages of --peer with nobody describing "
                          "the layout: the groups are inferred from the kernels each rank runs and how often) and exit")
+    ap.add_argument("--stall", action="store_true",
+                    help="no training: play the stall-score scenario (8 ranks, rank 5 with ten samples of 50 x in 10 000, rank 2 "
+                         "with one) under the relative scores and every row family, and exit")
     ap.add_argument("--ramp", action="store_true",
                     help="no training: play the ramp-score scenario (8 ranks, rank 5 rises by 50 %% over the last 40 %% of the "
                          "window, rank 2 stepped) under the relative, tail, onset, episode and ramp scores, and exit")
     args = ap.parse_args()
+    if args.stall:
+        stall()
+        return
     if args.ramp:
         ramp()
         return

@@ -367,6 +367,62 @@ enum { NVRX_RAMP_PLANES = 6 };
 int nvrx_ramp_score(const float *d_ramp, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                     float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Stalls of timing rows: RARE, ISOLATED, LARGE samples at irregular times -- a page-fault storm, a collective's retry, a host
+ * thread descheduled for 50 ms, a PCIe replay: what precedes a collective timeout.  Extends the statistics of
+ * straggler.py:172-197: ten samples of 50 x among 10 000 move neither the median nor the 0.95-quantile, form no step, no beat,
+ * and no stretch or hinge that explains more than a few thousandths of the row's variance -- and cost 4.7 % of the window,
+ * which in a lockstep job every other rank waits for too.
+ * Per row with n valid samples:
+ *   time order  as for nvrx_row_onset: sample i lives in slot (start + i) mod n;
+ *   pace        the lower median: the element of rank (500000 * n + 999999) / 1000000 - 1 by raw-bit key order, exactly
+ *               nvrx_row_quantile at q_ppm = 500000;
+ *   spread      the lower median, by the same rank rule, of a_i = fabsf(x_i - pace): one rounded f32 subtraction, sorted by the
+ *               same key map, so a NaN goes to the top;
+ *   cut         (float) max((double)pace * ratio_ppm / 1e6, (double)pace + (double)min_z * 1.4826 * (double)spread), every
+ *               product, quotient and sum rounded on its own (no fused multiply-add); ratio_ppm in [1000001, 1000000000],
+ *               min_z finite and >= 0;
+ *   stall sample  x_i > cut, an f32 compare: a NaN sample is never one;
+ *   event       a maximal run of consecutive stall samples in TIME order, NOT circular: a run that crosses the ring's physical
+ *               wrap point is one event; the window's last and first samples, neighbours in a wrapped ring, are two events
+ *               if both are stall samples;
+ *   events, samples  the two counts; last_ago = n - 1 - (time index of the newest stall sample), 0 when there is none;
+ *   f64 sums    T = sum of (double)x_i; lost = sum over the stall samples of ((double)x_i - (double)pace);
+ *               level = (float)((double)pace + lost / samples); share = (float)(lost / T): the share of the row's time in the
+ *               window that stalls cost above its pace.
+ * Row record, 32 bytes: {u32 events, u32 samples, u32 last_ago, f32 pace, f32 spread, f32 cut, f32 level, f32 share}.
+ *   n == 0 (an absent row)                              ints 0, floats -1;
+ *   T or lost not finite                                ints 0, floats NaN;
+ *   0 < n < NVRX_STALL_MIN_SAMPLES, or no stall sample  {0, 0, 0, pace, spread, cut, pace, 0}.
+ * Effective excess of a record: e = f32 of the f64 quotient level / pace (the record's f32 values) where events >= 1,
+ * share >= min_share (f32, in [0, 1)) and level > pace > 0; 1.0 otherwise ("did not stall"); -1.0 for an absent row.
+ * Rules, not defects: a stall that every rank shares scores 1 (the reference is the minimum of e); a row in which a quarter or
+ * more of the samples are slow has a spread that swallows them (the tail and episode scores' case); share is of the row's own
+ * time, not of the step's.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_starts [rows] or NULL (0 everywhere); d_out [rows] 32-byte records, 16-byte aligned.  Stateless, like nvrx_row_onset.
+ * Rows of at most NVRX_STALL_LDS_SAMPLES samples are read from device memory once (the kernel keeps them in LDS, in time order,
+ * next to its 16 KB selection histogram: 47 KB + 16 KB + the workgroup's bookkeeping words is what 64 KB hold); longer ones
+ * seven times, six of them from the L2.  The order of the two f64 sums follows from n and the time index alone: a rotated ring gives
+ * the same bits in every field.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+#define NVRX_STALL_LDS_SAMPLES 12032
+#define NVRX_STALL_MIN_SAMPLES 8
+int nvrx_row_stall(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride,
+                   uint32_t ratio_ppm, float min_z, void *d_out, void *stream);
+/* Relative stall scores.  d_stall [R][NVRX_STALL_PLANES][K+S]: per rank seven planes {e, pace, level, share, events as f32,
+ * last_ago as f32, n as f32} per kernel id and section id (-1.0: none); only plane 0 is read.  Reference per column = the
+ * minimum of e over all R ranks, NaN if any rank has none.  Per reported rank [first_rank, first_rank + n_ranks),
+ * nvrx_tail_score's arithmetic on e, exactly as nvrx_onset_score:
+ *   d_out [n_ranks][1 + S] = {GPU stall score, section stall score[S]}
+ * Scores are in (0, 1]: 1 = "stalled no more than the steadiest rank"; a stall the whole job shares flags nobody.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(K+S) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched.
+ * (An enumerator, not a macro, as NVRX_RAMP_PLANES is: stall runs behind ramp as a sixth step of its own.  Seven planes are the
+ * most nvrx_rowfam_group_score accepts.) */
+enum { NVRX_STALL_PLANES = 7 };
+int nvrx_stall_score(const float *d_stall, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                     float *d_colmin_scratch, float *d_out, void *stream);
+
 /* Robust scores: every rank against the job's median and spread. Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
@@ -1080,6 +1136,15 @@ int nvrx_episode_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min
  * issued through this descriptor. */
 int nvrx_ramp_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_seg_ppm, float min_strength,
                     float *d_ramp_send, int K, int S, int rows_active, void *stream);
+/* Stall scores on the rings (straggler.py:172-197 on the window in time order; reporting.py:196-253 follows with
+ * nvrx_stall_score): nvrx_row_stall on the rings as the report just issued saw them -- its counts, its ring starts (the snapshot
+ * of nvrx_onset_enable), whatever has been pushed since -- packed by gid into d_stall_send [local_ranks][NVRX_STALL_PLANES][K+S]
+ * (planes {e, pace, level, share, events as f32, last_ago as f32, n as f32}; kernel ids first, then section ids; every slot is
+ * written, -1.0 where no row with samples has that gid).  ratio_ppm in [1000001, 1000000000], min_z finite and >= 0, min_share
+ * in [0, 1).  Ordering, desc, rows_active and the caller's duty to wait are those of nvrx_onset_local.  NVRX_ERR_STATE: the
+ * snapshot is not enabled, or no report was issued through this descriptor. */
+int nvrx_stall_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t ratio_ppm, float min_z, float min_share,
+                     float *d_stall_send, int K, int S, int rows_active, void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

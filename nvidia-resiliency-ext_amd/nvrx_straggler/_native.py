@@ -43,6 +43,10 @@ EPISODE_MIN_SAMPLES = 8  # ... and the length's floor in samples
 EPISODE_PLANES = 7  # NVRX_EPISODE_PLANES: {e, inside, outside, strength, length, ago, n} per kernel id and section id
 RAMP_PLANES = 6  # NVRX_RAMP_PLANES: {e, base, end, strength, ago, n} per kernel id and section id
 RAMP_LDS_SAMPLES = 15360  # NVRX_RAMP_LDS_SAMPLES: the longest row k_row_ramp keeps in LDS between its two passes
+STALL_PLANES = 7  # NVRX_STALL_PLANES: {e, pace, level, share, events, last_ago, n} per kernel id and section id
+STALL_LDS_SAMPLES = 12032  # NVRX_STALL_LDS_SAMPLES: the longest row k_row_stall keeps in LDS next to its selection histogram
+STALL_MIN_SAMPLES = 8  # NVRX_STALL_MIN_SAMPLES: shorter rows have a pace, a spread and a cut, and no stalls
+STALL_RATIO_PPM_MIN, STALL_RATIO_PPM_MAX = 1000001, 1000000000  # the accepted range of a stall's minimum ratio to the pace
 HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
 HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
 TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, family, slot)
@@ -103,6 +107,8 @@ SYMBOLS = [
     ("nvrx_episode_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_ramp", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_ramp_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_stall", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_float, c_void_p, c_void_p]),
+    ("nvrx_stall_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -166,6 +172,7 @@ SYMBOLS = [
     ("nvrx_period_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_ramp_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_stall_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
@@ -427,6 +434,18 @@ def ramp_seg_ppm(frac) -> int:
         raise ValueError(f"ramp_min_segment must be a number within [0.000001, 0.5], got {frac!r}") from None
     if not ONSET_SEG_PPM_MIN <= ppm <= ONSET_SEG_PPM_MAX:
         raise ValueError(f"ramp_min_segment must be within [0.000001, 0.5], got {frac!r}")
+    return ppm
+
+
+def stall_ratio_ppm(ratio) -> int:
+    """A stall's minimum ratio to the row's pace as the library carries it: ``round(ratio * 1e6)``, within [1.000001, 1000].
+    ``ValueError`` for anything else."""
+    try:
+        ppm = int(round(float(ratio) * 1e6))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"stall_min_ratio must be a number within [1.000001, 1000], got {ratio!r}") from None
+    if not STALL_RATIO_PPM_MIN <= ppm <= STALL_RATIO_PPM_MAX:
+        raise ValueError(f"stall_min_ratio must be within [1.000001, 1000], got {ratio!r}")
     return ppm
 
 

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .row_families import EPISODE, ONSET, PERIOD, RAMP, ROW_STEPS, TAIL, RowFamily
+from .row_families import EPISODE, ONSET, PERIOD, RAMP, ROW_STEPS, STALL, TAIL, RowFamily
 from .table_families import NODE, PACE, PACE_GROUP, PEER, ROBUST, ROBUST_GROUP, SLOTS, TableFamily
 
 DEFAULT_THRESHOLDS = (0.75, 0.75, 0.75, 0.75)  # gpu_rel, section_rel, gpu_indiv, section_indiv
@@ -763,9 +763,15 @@ class Workspace:
     def ramp_settle(self) -> None:
         self.family_settle(RAMP)
 
+    def stall_buffers(self):
+        return self.family_buffers(STALL)
+
+    def stall_settle(self) -> None:
+        self.family_settle(STALL)
+
     def settle_readers(self) -> None:
         """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
-        reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps -- has run and delivered; and so has the
+        reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps, stalls -- has run and delivered; and so has the
         score history's step, which read the result block and wrote the records buffer."""
         if self._attr_last is not None:
             self.attr_settle()
@@ -1174,6 +1180,10 @@ class HipBackend:
                          min_ranks: int = 2) -> RowGroupScores:
         return self._family_group_score(RAMP, ws, ramps, table, groups, first_rank, n_ranks, min_ranks)
 
+    def stall_group_score(self, ws, stalls, table, groups, first_rank: int = 0, n_ranks: Optional[int] = None,
+                          min_ranks: int = 2) -> RowGroupScores:
+        return self._family_group_score(STALL, ws, stalls, table, groups, first_rank, n_ranks, min_ranks)
+
     def family_copy_out(self, t: RowScores):
         """The one wait of a report's row family: a D2H of its table and scores on the backend's stream, behind the kernels."""
         KS, P = t.K + t.S, t.family.planes
@@ -1200,6 +1210,9 @@ class HipBackend:
     def ramps_copy_out(self, t: RowScores):
         return self.family_copy_out(t)
 
+    def stalls_copy_out(self, t: RowScores):
+        return self.family_copy_out(t)
+
     def tail_score(self, ws, tails, table, first_rank: int = 0, n_ranks: Optional[int] = None, q_ppm: int = 0) -> RowScores:
         return self._family_score(TAIL, ws, tails, table, first_rank, n_ranks, (q_ppm,))
 
@@ -1214,6 +1227,9 @@ class HipBackend:
 
     def ramp_score(self, ws, ramps, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
         return self._family_score(RAMP, ws, ramps, table, first_rank, n_ranks)
+
+    def stall_score(self, ws, stalls, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
+        return self._family_score(STALL, ws, stalls, table, first_rank, n_ranks)
 
     def _row_op(self, fam: RowFamily, samples: torch.Tensor, counts: torch.Tensor, param: int,
                 starts: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1244,6 +1260,19 @@ class HipBackend:
     def row_ramp(self, samples, counts, min_seg_ppm: int, starts=None) -> torch.Tensor:
         """Records ``{ago, base, end, strength}``."""
         return self._row_op(RAMP, samples, counts, min_seg_ppm, starts)
+
+    def row_stall(self, samples, counts, ratio_ppm: int, min_z: float, starts=None) -> torch.Tensor:
+        """``nvrx_row_stall`` on caller tensors (``_row_op``'s) -> [rows, 8] int32 records ``{events, samples, last_ago, pace,
+        spread, cut, level, share}``, the last five words f32 bit patterns."""
+        rows, stride = samples.shape
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((max(rows, 1), 8), dtype=torch.int32, device=samples.device)
+            _native.check(self.lib.nvrx_row_stall(samples.data_ptr(), counts.data_ptr(),
+                                                  starts.data_ptr() if starts is not None else None, rows, stride,
+                                                  int(ratio_ppm), float(min_z), out.data_ptr(), self.stream_handle))
+        self.stream.synchronize()
+        return out[:rows]
 
     def _table_step(self, fam: TableFamily, ws: Workspace, entry, head: tuple, tail: tuple, groups: Optional[PeerGroups],
                     first_rank: int, n_ranks: Optional[int], params: tuple) -> TableScores:
@@ -2007,6 +2036,9 @@ class HipRings:
 
     def ramp_local(self, ws: Workspace, min_seg_ppm: int, min_strength: float, rows_active: int = 0, fused: bool = False):
         return self._family_local(RAMP, ws, (min_seg_ppm, min_strength), rows_active, fused)
+
+    def stall_local(self, ws: Workspace, ratio_ppm: int, min_z: float, min_share: float, rows_active: int = 0, fused: bool = False):
+        return self._family_local(STALL, ws, (ratio_ppm, min_z, min_share), rows_active, fused)
 
     def peek_stats(self) -> np.ndarray:
         """Statistics of every used row right now ([rows_used, 8] on the host); exchanges nothing and

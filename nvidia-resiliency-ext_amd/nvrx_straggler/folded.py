@@ -39,7 +39,9 @@ class FoldedJob:
                  work_count_tol: float = 0.25, work_max_unlike: float = 0.1, peer_history: int = 0,
                  peer_persistence_min_reports: int = 3, peer_persistence_thresholds=None, peer_trends: bool = False,
                  slack_peer_groups: bool = False, row_peer_groups: bool = False, ramp_detection: bool = False,
-                 ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5, robust_peer_groups: bool = False):
+                 ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5, robust_peer_groups: bool = False,
+                 stall_detection: bool = False, stall_min_ratio: float = 1.5, stall_min_z: float = 6.0,
+                 stall_min_share: float = 0.01):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -74,6 +76,9 @@ class FoldedJob:
                                         **({"row_peer_groups": True} if row_peer_groups else {}),
                                         **({"ramp_detection": True, "ramp_min_segment": ramp_min_segment,
                                             "ramp_min_strength": ramp_min_strength} if ramp_detection else {}),
+                                        **({"stall_detection": True, "stall_min_ratio": stall_min_ratio,
+                                            "stall_min_z": stall_min_z, "stall_min_share": stall_min_share}
+                                           if stall_detection else {}),
                                         **({"peer_history": peer_history,
                                             "peer_persistence_min_reports": peer_persistence_min_reports,
                                             "peer_persistence_thresholds": peer_persistence_thresholds,

@@ -647,7 +647,7 @@ def _copy_explanation(d: dict) -> dict:
 
 
 class _RowFamilySource:
-    """What a report keeps of one row family's scores (row_families.py: tail, onset, period, episode, ramp): the backend's handle
+    """What a report keeps of one row family's scores (row_families.py: tail, onset, period, episode, ramp, stall): the backend's handle
     (``records()`` waits for the kernels and copies the planes and scores out on first use), the ranks its rows stand for,
     the sections it shows with their ids, the kernel names by id as the report's mapper had them at report time, and the
     family's parameters."""
@@ -1593,6 +1593,32 @@ class Report:
         for it.  Empty sets when the report carries no ramp scores."""
         return self._identify_relative(self.ramp_scores(), gpu_rel_threshold, section_rel_threshold)
 
+    def stall_scores(self) -> Dict[str, Any]:
+        """Stall scores (``ReportGenerator(stall_detection=True)``; ``{}`` when the report carries none).  A rank's RARE,
+        ISOLATED, LARGE samples at irregular times -- which move no median and no quantile short of 0.999, form no step, beat,
+        stretch or hinge, and are what precedes a collective timeout: per timing row the samples above ``max(pace *
+        min_ratio, pace + min_z * 1.4826 * spread)``, ``pace`` being the row's lower median and ``spread`` the lower median
+        of the absolute deviations from it.
+
+        ``{"gpu_relative": {rank: score}, "section_relative": {section: {rank: score}}, "section_stalls": {section: {rank:
+        {"excess", "pace", "level", "share", "events", "last_samples_ago", "window"}}}, "kernel_stalls": {kernel: {rank:
+        {...}}}, "min_ratio": x, "min_z": x, "min_share": x}`` -- the row's stall samples form ``events`` runs in time order,
+        the newest of them ``last_samples_ago`` samples before the end of its ``window``; ``level`` is their mean, ``share``
+        the share of the row's OWN time in the window that they cost above its ``pace`` (not of the step's), ``excess`` is
+        ``level / pace`` where the row stalled and the share is at least ``min_share``, 1.0 otherwise.  Scores are the
+        steadiest rank's excess over this rank's (NaN where a rank lacks the row): 1 = stalled no more than the steadiest
+        rank, so a stall the whole job shares flags nobody.  A row in which a quarter or more of the samples are slow has a
+        spread that swallows them: ``tail_scores()`` and ``episode_scores()`` are the reading there.  Ranks and sections as
+        in the score mappings, rows without samples are left out.  Plain dicts and floats.  The first call waits for the
+        stall kernels and copies their results; ``generate_report`` does not."""
+        return self._family_scores("stall")
+
+    def identify_stall_stragglers(self, gpu_rel_threshold: float = 0.75, section_rel_threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose STALL scores fall strictly below the thresholds (NaN is never flagged): ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
+        for it.  Empty sets when the report carries no stall scores."""
+        return self._identify_relative(self.stall_scores(), gpu_rel_threshold, section_rel_threshold)
+
     def robust_scores(self) -> Dict[str, Any]:
         """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
         of a report divides the FASTEST rank's median by this rank's; these rate a rank against the job's own middle and
@@ -2207,7 +2233,8 @@ class ReportGenerator:
                  node_min_agree: float = 0.75, work_groups: bool = False, work_count_tol: float = 0.25,
                  work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False,
                  ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5,
-                 robust_peer_groups: bool = False) -> None:
+                 robust_peer_groups: bool = False, stall_detection: bool = False, stall_min_ratio: float = 1.5,
+                 stall_min_z: float = 6.0, stall_min_share: float = 0.01) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2508,6 +2535,30 @@ class ReportGenerator:
                 raise RuntimeError(f"ramp_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no ramp scores (backend.ramp_score)")
             self.ramp_seg_ppm, self.ramp_min_strength = seg_ppm, strength
+        # stall scores: every ring report also carries, per row, the count, the timing and the cost of the samples far above the
+        # row's pace and relative scores built from their excess (Report.stall_scores); off: no buffer, no launch, no
+        # collective, no backend call.  The step adds one collective per report, so EVERY rank must pass the same value.
+        # 1.5, 6.0 and 0.01 are defaults, not measurements.
+        self.stall_ratio_ppm = 0  # (0 = off)
+        if stall_detection:
+            ratio_ppm = _backend_mod._native.stall_ratio_ppm(stall_min_ratio)
+            try:
+                min_z, min_share = float(stall_min_z), float(stall_min_share)
+            except (TypeError, ValueError):
+                raise ValueError(f"stall_min_z must be a finite number >= 0 and stall_min_share a number within [0, 1), got "
+                                 f"{stall_min_z!r} and {stall_min_share!r}") from None
+            if not 0.0 <= min_z < float("inf"):  # (NaN fails both comparisons)
+                raise ValueError(f"stall_min_z must be a finite number >= 0, got {stall_min_z!r}")
+            if not 0.0 <= min_share < 1.0:
+                raise ValueError(f"stall_min_share must be within [0, 1), got {stall_min_share!r}")
+            if not self.is_computing_rel_scores:
+                raise ValueError(f"stall_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
+                                 "stall scores are relative scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "stall_score"):
+                raise RuntimeError(f"stall_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no stall scores (backend.stall_score)")
+            self.stall_ratio_ppm, self.stall_min_z, self.stall_min_share = ratio_ppm, min_z, min_share
         # score history: every report also appends its scores to a device ring of the last H reports and says, per rank and
         # score, for how many reports in a row the score has been below its threshold (Report.score_history,
         # Report.identify_persistent_stragglers); 0 = off: no buffer, no launch, no backend call.  It reads what the score
@@ -3354,7 +3405,7 @@ class ReportGenerator:
         if self._peer_history is not None:
             self._peer_history.reset()
 
-    # ---- row families: tail, onset, period, episode and ramp scores ----------------------------------
+    # ---- row families: tail, onset, period, episode, ramp and stall scores ----------------------------
     def _family_step(self, fam, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
         """One row family's step of a ring report, once per ``generate_report_from_rings`` call behind its last score round
         (and behind the steps of the families before it), on that round's workspace: the family's ring kernel on the window
@@ -3453,7 +3504,8 @@ class ReportGenerator:
         of this path carries no tail scores (``tail_quantile``; ``Report.tail_scores()`` is ``{}``), no onset scores
         (``onset_detection``; ``Report.onset_scores()`` is ``{}``), no period scores (``period_detection``;
         ``Report.period_scores()`` is ``{}``), no episode scores (``episode_detection``; ``Report.episode_scores()`` is
-        ``{}``) and no ramp scores (``ramp_detection``; ``Report.ramp_scores()`` is ``{}``).
+        ``{}``), no ramp scores (``ramp_detection``; ``Report.ramp_scores()`` is ``{}``) and no stall scores (``stall_detection``;
+        ``Report.stall_scores()`` is ``{}``).
         """
         t0 = time.perf_counter_ns()
         self.world_size = dist_utils.get_world_size(self.group)

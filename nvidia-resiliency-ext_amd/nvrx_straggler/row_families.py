@@ -1,12 +1,12 @@
 """The row families: score families computed from the ring rows of a report's window -- tail, onset, period, episode, and
-ramp behind them.
+ramp and stall behind them.
 
 All of them are ONE pipeline with a different ring kernel in front ("Row families")::
 
     ring kernel by gid into [local_ranks][P][K+S] behind a -1 fill -> [all-gather] -> score kernel on plane 0 with pitch
     P * (K+S) -> one buffer, one ordered D2H on first read -> per-rank records + gpu_relative / section_relative
 
-``FAMILIES`` (and ``ROW_STEPS``: the four and ramp) says what differs, once, in the fixed order the families run in (and
+``FAMILIES`` (and ``ROW_STEPS``: the four, ramp and stall) says what differs, once, in the fixed order the families run in (and
 issue their collectives in).  The backend
 (``Workspace.family_buffers``, ``HipBackend._family_score``, ``HipRings._family_local``) and the reports
 (``reporting._RowFamilySource``, ``ReportGenerator._ring_steps``) are written against these records; a further family is
@@ -60,6 +60,14 @@ def _ramp_record(v, params):
             "whole_window": ago == n}
 
 
+def _stall_record(v, params):
+    e, pace, level, share, events, ago, n = v
+    if e == -1.0:  # (-1: the rank has no samples in this row)
+        return None
+    return {"excess": e, "pace": pace, "level": level, "share": share, "events": int(events), "last_samples_ago": int(ago),
+            "window": int(n)}
+
+
 @dataclasses.dataclass(frozen=True)
 class RowFamily:
     name: str                 # "tail": Report.tail_scores / identify_tail_stragglers, rings.tail_local, backend.tail_score
@@ -109,6 +117,10 @@ FAMILIES: Tuple[RowFamily, ...] = (
 RAMP = RowFamily("ramp", _native.RAMP_PLANES, "nvrx_row_ramp", "nvrx_ramp_score", "nvrx_ramp_local", "ramp_detection",
                  ("ramp_seg_ppm", "ramp_min_strength"), True, "_ramp", "ramps", _ramp_record,
                  lambda p: {"min_segment": p[0] / 1e6, "min_strength": p[1]})
-ROW_STEPS: Tuple[RowFamily, ...] = FAMILIES + (RAMP,)
+# ... and the sixth behind it: k_row_stall in front, three parameters (the cut's two and the share a row must have lost)
+STALL = RowFamily("stall", _native.STALL_PLANES, "nvrx_row_stall", "nvrx_stall_score", "nvrx_stall_local", "stall_detection",
+                  ("stall_ratio_ppm", "stall_min_z", "stall_min_share"), True, "_stall", "stalls", _stall_record,
+                  lambda p: {"min_ratio": p[0] / 1e6, "min_z": p[1], "min_share": p[2]})
+ROW_STEPS: Tuple[RowFamily, ...] = FAMILIES + (RAMP, STALL)
 BY_NAME = {f.name: f for f in ROW_STEPS}
 TAIL, ONSET, PERIOD, EPISODE = FAMILIES

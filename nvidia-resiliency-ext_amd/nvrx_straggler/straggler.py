@@ -447,6 +447,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
         ramp_detection: Optional[bool] = None,
         ramp_min_segment: float = 0.05,
         ramp_min_strength: float = 0.5,
+        stall_detection: Optional[bool] = None,
+        stall_min_ratio: float = 1.5,
+        stall_min_z: float = 6.0,
+        stall_min_share: float = 0.01,
     ):
         """
         Args:
@@ -528,6 +532,22 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 [0.000001, 0.5]; never fewer than 8 samples.  0.05 is a default, not a measurement.
             ramp_min_strength: a ramp counts when its hinge explains at least this share of the row's variance, within
                 [0, 1].  0.5 is a default, not a measurement.
+            stall_detection: every report also counts a rank's RARE, ISOLATED, LARGE samples at irregular times (a page-fault
+                storm, a collective's retry, a descheduled host thread, a PCIe replay -- what precedes a collective timeout):
+                per section and kernel row the samples above ``max(pace * stall_min_ratio, pace + stall_min_z * 1.4826 *
+                spread)``, pace and spread being the row's lower median and the lower median of the absolute deviations from
+                it -- how many events they form in time order, how many samples ago the last one hit, their mean level, the
+                share of the row's time they cost above its pace -- and relative scores built from ``level / pace``
+                (``Report.stall_scores()``, ``Report.identify_stall_stragglers()``).  Ten samples of 50 x among 10 000 move
+                no median, no 0.95-quantile, no step, beat, stretch or hinge, and cost 4.7 % of the window.  Needs
+                ``relative_perf_scores``.  Default: ``NVRX_STALL_DETECTION``, else off.  Pass the same values on EVERY rank
+                (the step adds one collective per report).
+            stall_min_ratio: a stall sample is at least this many times the row's pace, within [1.000001, 1000].  1.5 is a
+                default, not a measurement.
+            stall_min_z: ... and at least this many robust standard deviations (1.4826 x the spread) above it, finite and
+                >= 0.  6.0 is a default, not a measurement.
+            stall_min_share: a row counts as stalled when its stalls cost at least this share of its time in the window,
+                within [0, 1).  0.01 is a default, not a measurement.
             score_history: 0 = off; H in 2..64: every report also appends its scores to a history of the last H reports and
                 says, per rank and score, for how many reports in a row the score has been below its threshold
                 (``Report.score_history()``, ``Report.identify_persistent_stragglers()``): a rank that was slow in one window
@@ -819,6 +839,11 @@ class Detector(metaclass=_DeviceSideOnDemand):
             ramp_detection = os.environ.get("NVRX_RAMP_DETECTION", "0") not in ("", "0")
         if ramp_detection:
             ramp_options = {"ramp_detection": True, "ramp_min_segment": ramp_min_segment, "ramp_min_strength": ramp_min_strength}
+        if stall_detection is None:
+            stall_detection = os.environ.get("NVRX_STALL_DETECTION", "0") not in ("", "0")
+        if stall_detection:
+            ramp_options.update(stall_detection=True, stall_min_ratio=stall_min_ratio, stall_min_z=stall_min_z,
+                                stall_min_share=stall_min_share)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
