@@ -119,6 +119,12 @@ own.  ``identify_pace_stragglers`` names nine ranks and cannot say which of them
 (``ReportGenerator(node_scores=True)``) ``identify_node_stragglers`` names node 2 alone, 8 of its 8 ranks agreeing, and hands
 rank 5 back as a rank that is off pace without its node.
 
+``--node-peer`` plays a report of a PIPELINE job on nodes: 64 ranks x 120 kernels on 8 nodes of 8 (``node_groups="block:8"``) in
+two stages of four nodes (``peer_groups="block:32"``) of 1000 us and 1500 us, 1 % noise (seed 2026), node 5 4 % slower in
+everything and rank 3 4 % slower on its own.  The job-wide node rule takes a column's centre across all eight nodes -- a node
+of the fast stage -- and names every node of the slow stage; with ``ReportGenerator(node_peer_groups=True)`` a node is compared
+with the nodes of its own stage.  Both are printed.
+
 ``--work`` plays the ``--peer`` job WITHOUT anybody describing its layout: 8 ranks in two pipeline stages (folded onto one GPU,
 1 % noise, seed 31), 120 kernel keys and 4 sections; 100 keys are shared and run 1600 times a window in stage 0 and 2400 times
 in stage 1, 10 keys only stage 0 has and 10 only stage 1; rank 6 is 1.4x slower in everything.  ``identify_stragglers`` names
@@ -873,6 +879,46 @@ def node(ranks: int = 32, per_node: int = 8, kernels: int = 120, calls: int = 20
         job.close()
 
 
+def node_peer(ranks: int = 64, per_node: int = 8, stage: int = 32, kernels: int = 120, calls: int = 50, slow_node: int = 5,
+              slow_rank: int = 3, slowdown: float = 1.04, seed: int = 2026) -> None:
+    """A slow host in a pipeline job: whom the job-wide node rule names, and whom the rule per peer group."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    names = [f"kernel_{k:03d}" for k in range(kernels)]
+    rng = np.random.default_rng(seed)
+    med = rng.lognormal(np.log(1000.0 / kernels), 0.5, kernels)[None, :] * (1.0 + 0.01 * rng.standard_normal((ranks, kernels)))
+    med[stage:] *= 1.5                                                  # the second stage's work
+    med[slow_node * per_node : (slow_node + 1) * per_node] *= slowdown  # the whole node
+    med[slow_rank] *= slowdown                                          # one card elsewhere
+    med = med.astype(np.float32)
+    for grouped in (False, True):
+        job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=64, scores_to_compute=("relative_perf_scores",),
+                        kernel_names=names, node_scores=True, node_groups=f"block:{per_node}", peer_groups=f"block:{stage}",
+                        node_peer_groups=grouped)
+        try:
+            for lr, r in enumerate(job.logical_ranks()):
+                job.load(lr, np.full((1, calls), med[r].sum(), dtype=np.float32))
+                job.load_kernels(lr, np.repeat(med[r][:, None], calls, axis=1))
+            report = job.report()
+            t = report.node_scores()
+            found = report.identify_node_stragglers()
+            rule = "node_peer_groups=True" if grouped else "job-wide"
+            print(f"{rule}: identify_node_stragglers() nodes: {sorted(found['straggler_nodes'])}; ranks off pace alone: "
+                  f"{sorted(s.rank for s in found['ranks_off_pace_alone'])}; unrated nodes: {t['unrated_nodes']}")
+            for label in sorted(t["node_scores"]):
+                d = t["node_scores"][label]
+                gpu = d["gpu"]
+                where = f", stage {t['cells'][label]}" if grouped else ""
+                print(f"  node {label} (ranks {t['nodes'][label][0]}-{t['nodes'][label][-1]}{where}): pace {gpu['pace']:.4f}, slower / "
+                      f"faster than its reference in {gpu['slower']} / {gpu['faster']} of {gpu['columns']} kernels, "
+                      f"{d['members_off_pace']} of {d['members_rated']} ranks off pace")
+        finally:
+            job.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-processes", type=int, default=1)
@@ -925,6 +971,10 @@ def main() -> None:
     ap.add_argument("--node", action="store_true",
                     help="no training: play the node-score scenario (32 ranks on 4 nodes, every rank of node 2 and rank 5 of node "
                          "0 4 %% slower in every kernel) with the pace rule and the node rule, and exit")
+    ap.add_argument("--node-peer", action="store_true",
+                    help="no training: play the node-score scenario of a pipeline job (64 ranks on 8 nodes in two stages of 1000 "
+                         "us and 1500 us, node 5 and rank 3 4 %% slower in every kernel) with the job-wide node rule and the rule "
+                         "per peer group, and exit")
     ap.add_argument("--work", action="store_true",
                     help="no training: play the work-group scenario (the two pipeline stages of --peer with nobody describing "
                          "the layout: the groups are inferred from the kernels each rank runs and how often) and exit")
@@ -949,6 +999,9 @@ def main() -> None:
         return
     if args.node:
         node()
+        return
+    if args.node_peer:
+        node_peer()
         return
     if args.pace_peer:
         pace_peer()

@@ -632,6 +632,63 @@ int nvrx_robust_group_score(const float *d_table, int R, int K, int S, const int
 int nvrx_node_score(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, int max_group, int min_members,
                     int min_nodes, int first_rank, int n_ranks, void *d_out, void *stream);
 
+/* Node scores per peer group: nvrx_node_score with a node compared to the nodes doing the SAME work.  The centre across all
+ * nodes of the job is the wrong one in a job of pipeline stages, tensor-parallel or expert groups: it lies in the fast stage,
+ * and every node of a slower stage is slower than it in all of its kernels.  A CELL is a non-empty intersection of a node and a
+ * peer group; C cells, Gp peer groups, Gn nodes.
+ *   d_table [R][L] as for nvrx_score; R <= NVRX_ROBUST_MAX_RANKS.
+ *   d_cells  ONE device array of NVRX_NODE_GROUP_CELLS_LEN(R, C, Gp, Gn) int32 words, in this order:
+ *      cell[R] | members[R] | cstart[C+1]  nvrx_peer_score's array, a cell being a group: cell[r] is rank r's cell, members holds
+ *                    the ranks sorted by (peer group, node, rank), cstart[j] .. cstart[j+1] is cell j's stretch of members; the
+ *                    cells are numbered in that order, so a peer group's cells are consecutive;
+ *      gstart[Gp+1]  group p's cells are the cell ids gstart[p] .. gstart[p+1];
+ *      nstart[Gn+1] | ncells[C]  node n's cells are ncells[nstart[n] .. nstart[n+1]);
+ *      cgroup[C]     the peer group of each cell;
+ *      rgroup[R]     the peer group of each rank.
+ *      1 <= Gp <= C, 1 <= Gn <= C, C <= R and C <= NVRX_PEER_MAX_GROUPS.
+ *   max_cell in 1..R, max_group_cells and max_node_cells in 1..C: the largest cell's size, the most cells of one peer group and
+ *      the most cells of one node as the host knows them.  They select the kernel variants.
+ *   min_members >= 1: present members a (cell, column) pair needs; min_nodes >= 1: referenced cells a (group, column) pair
+ *      needs, clamped to the group's cells; min_peers >= 1: the floor of that clamp.
+ *   Presence (v >= 0), keys (raw bit pattern order), the lower median (rank (n-1) >> 1 by key) and the canonical NaN 0x7FC00000
+ *   are the pace scores' own.
+ *   Block A, [C][K+S] pair records {f32 med, u32 n, u32 above, u32 below}: exactly nvrx_pace_group_score's column block with the
+ *      cells as groups, min_ranks = min_members and min_peers = 1, and its guards: cstart values clamped to [0, R], a stretch cut
+ *      to max_cell, a member outside [0, R) skipped.
+ *   Block B, [Gp][K+S] records {f32 N_gc, u32 nodes, u32 above, u32 below} across the cells of ONE peer group, one cell one vote.
+ *      The CELLS of group g are gstart[g] .. gstart[g+1] clamped to [0, C], the end at least the start, the stretch cut to
+ *      max_group_cells; cells_g is that stretch's length.  nodes counts the group's referenced pairs of the column; N_gc is the
+ *      lower median of their med by key; the pair (g, c) is REFERENCED iff nodes >= max(min_peers, min(min_nodes, cells_g)),
+ *      else N_gc is NaN; above / below count the referenced cells whose key of med is greater / less than the key of that lower
+ *      median (both 0 at nodes = 0).  The three counts are always written.  At min_peers = 2 a peer group that sits on one node
+ *      gives that node no reference: a slow host cannot be told from the stage's own work there.
+ *   Block C, [Gn][2] node records, 32 bytes each: nvrx_pace_score's rank record without the three sums (+0.0 in both parts).  The
+ *      CELLS of node n are the entries ncells[nstart[n] .. nstart[n+1]), the starts clamped to [0, C], the stretch cut to
+ *      max_node_cells; an entry outside [0, C), or one whose cgroup is outside [0, Gp), is skipped.  The record runs over all
+ *      pairs (cell j of the node, column c of the part) where A[j][c] and B[cgroup[j]][c] are both numbers: q = (float)((double)
+ *      N_gc / (double)med) with g = cgroup[j]; pace, spread, columns, slower and faster as defined for nvrx_pace_score.  columns
+ *      counts PAIRS: a node with two cells can have up to twice K.
+ *   So every word of A, B and C is exact, ties included.
+ *   Block D, [n_ranks][2] rank records: exactly nvrx_pace_group_score's rank record of each reported rank with the records of B
+ *      as its group's column records and rgroup as the group ids (a rank whose rgroup is outside [0, Gp) has no eligible
+ *      column); part 0 keeps the three f64 sums (taken across a workgroup: their last bits depend on that order).
+ *   d_out  16-byte aligned, NVRX_NODE_GROUP_WORDS(C, Gp, Gn, n_ranks, K, S) 32-bit words: A, B, C, D in this order.
+ *   The CONTENTS of d_cells are guarded on the device as stated above; no content makes a kernel read or write outside the
+ *   table, the array or d_out.  (cell[R] is not read.)  With one peer group of all ranks and min_peers = 1 every word of A, B and
+ *   C is nvrx_node_score's (min_nodes at most the number of nodes); with every rank its own node B and D are
+ *   nvrx_pace_group_score's blocks with min_ranks = min_nodes.
+ * R <= 64: three launches on `stream` (A and B in one, C, D); beyond: four.  No atomics on global memory, no scratch.  Argument
+ * errors, reported before any device is touched: those of nvrx_node_score in its order with C as its G and max_cell as its
+ * max_group, then NVRX_ERR_RANGE for Gp or Gn outside 1..C, max_group_cells or max_node_cells outside 1..C, or min_peers < 1,
+ * then NVRX_ERR_INVALID for a null pointer or a d_out that is not 16-byte aligned. */
+#define NVRX_NODE_GROUP_CELLS_LEN(R, C, Gp, Gn) (3 * (size_t)(R) + 3 * (size_t)(C) + (size_t)(Gp) + (size_t)(Gn) + 3)
+#define NVRX_NODE_GROUP_WORDS(C, Gp, Gn, n_ranks, K, S)                                                                     \
+    (4 * (size_t)(C) * ((size_t)(K) + (S)) + 4 * (size_t)(Gp) * ((size_t)(K) + (S)) + 16 * (size_t)(Gn) + \
+     16 * (size_t)(n_ranks))
+int nvrx_node_group_score(const float *d_table, int R, int K, int S, const int32_t *d_cells, int C, int Gp, int Gn, int max_cell,
+                          int max_group_cells, int max_node_cells, int min_members, int min_nodes, int min_peers, int first_rank,
+                          int n_ranks, void *d_out, void *stream);
+
 /* Score history: how each score behaved over the last H reports.  Every score above looks inside one report window; the one
  * thing a report carries over from its predecessors is the running minimum of MED.  Here a device ring keeps the last H
  * reports' scores per reported rank, family f (0 individual, 1 relative: the parity of the score row's first two columns)
@@ -1186,6 +1243,13 @@ int nvrx_report_robust_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const 
  * the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
 int nvrx_report_node(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G, int max_group, int min_members,
                      int min_nodes, int first_rank, int n_ranks, void *d_out);
+/* nvrx_node_group_score (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor; d_cells sized for the descriptor's R).  Ordered behind that report's kernels exactly as
+ * nvrx_report_node orders itself.  The host does not wait; copy d_out with a D2H on the context's stream, and do not let a later
+ * report rewrite the table before the kernels have run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_node_group(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_cells, int C, int Gp, int Gn, int max_cell,
+                           int max_group_cells, int max_node_cells, int min_members, int min_nodes, int min_peers, int first_rank,
+                           int n_ranks, void *d_out);
 /* nvrx_work_groups (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
  * exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as nvrx_report_peer orders itself: the
  * context's stream, with an event when the report was re-homed or scored resident.  The host does not wait; copy d_out with a

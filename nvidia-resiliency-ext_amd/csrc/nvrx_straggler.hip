@@ -4038,5 +4038,6 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_robust_group.inl"
 #include "nvrx_slack_group.inl"
 #include "nvrx_node.inl"
+#include "nvrx_node_group.inl"
 #include "nvrx_work.inl"
 #include "nvrx_peer_history.inl"

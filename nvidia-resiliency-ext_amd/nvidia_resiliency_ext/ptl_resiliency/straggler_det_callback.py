@@ -56,6 +56,7 @@ class StragglerDetectionCallback(Callback):
         node_groups=None,
         min_consecutive_peer_reports: int = 1,
         slack_peer_groups: bool = False,
+        node_peer_groups: bool = False,
     ):
         """
         Args:
@@ -106,6 +107,9 @@ class StragglerDetectionCallback(Callback):
                 many of their GPUs are off pace.  A warning only: it never stops the job.
             node_groups: which ranks share a node, for ``warn_if_node_off_pace`` (None: the node names the detector gathers;
                 else ``"block:N"``, ``"mod:N"`` or one label per rank, as ``Detector.initialize(node_groups=...)``).
+            node_peer_groups: False (the default): nothing changes.  True (needs ``warn_if_node_off_pace`` and ``peer_groups``):
+                a node is compared with the nodes doing the SAME work (``Detector.initialize(node_peer_groups=True)``), so that
+                the healthy nodes of a slower pipeline stage are not warned about at every report.  Still a warning only.
             min_consecutive_peer_reports: 1 (the default): nothing changes.  M > 1 (needs ``peer_groups``): the relative
                 family's warning, and with ``stop_if_detected`` the halt, come only once a GPU's PEER score has been below the
                 relative threshold in M reports in a row (``Report.identify_persistent_peer_stragglers``; the detector then
@@ -188,6 +192,12 @@ class StragglerDetectionCallback(Callback):
         if self.warn_if_node_off_pace and not calc_relative_gpu_perf:
             raise ValueError("warn_if_node_off_pace needs calc_relative_gpu_perf=True: node scores compare nodes")
         self.node_groups = node_groups
+        self.node_peer_groups = bool(node_peer_groups)
+        if self.node_peer_groups:
+            if not self.warn_if_node_off_pace:
+                raise ValueError("node_peer_groups needs warn_if_node_off_pace=True: it changes what the node scores compare with")
+            if peer_groups is None:
+                raise ValueError("node_peer_groups needs peer_groups: which ranks do the same work")
         self._unrated_said = False
         self.interval_est_was_reset = False
 
@@ -224,6 +234,8 @@ class StragglerDetectionCallback(Callback):
             persistence["node_scores"] = True
             if self.node_groups is not None:
                 persistence["node_groups"] = self.node_groups
+        if self.node_peer_groups:
+            persistence["node_peer_groups"] = True
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,

@@ -118,6 +118,7 @@ SYMBOLS = [
                                         c_void_p, c_void_p]),
     ("nvrx_node_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_void_p]),
+    ("nvrx_node_group_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p] + [c_int] * 11 + [c_void_p, c_void_p]),
     ("nvrx_score_history", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                    c_void_p, c_void_p]),
     ("nvrx_score_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
@@ -181,6 +182,7 @@ SYMBOLS = [
     ("nvrx_report_robust_group", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                          c_float, c_void_p]),
     ("nvrx_report_node", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_report_node_group", c_int, [c_void_p, POINTER(ReportDesc), c_void_p] + [c_int] * 11 + [c_void_p]),
     ("nvrx_report_history", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                                     POINTER(c_double), c_void_p]),
     ("nvrx_report_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
@@ -316,6 +318,17 @@ def node_words(G: int, n_ranks: int, K: int, S: int) -> int:
     """NVRX_NODE_WORDS: 32-bit words of a node-score block: ``[G][K+S][4]`` pair records, ``[K+S][4]`` column records across
     the nodes, ``[G][2][8]`` node records, then ``[n_ranks][2][8]`` rank records."""
     return 4 * G * (K + S) + 4 * (K + S) + 16 * G + 16 * n_ranks
+
+
+def node_group_words(C: int, Gp: int, Gn: int, n_ranks: int, K: int, S: int) -> int:
+    """NVRX_NODE_GROUP_WORDS: 32-bit words of a block of node scores per peer group: ``[C][K+S][4]`` pair records of the cells,
+    ``[Gp][K+S][4]`` records across each peer group's cells, ``[Gn][2][8]`` node records, then ``[n_ranks][2][8]`` rank records."""
+    return 4 * C * (K + S) + 4 * Gp * (K + S) + 16 * Gn + 16 * n_ranks
+
+
+def node_group_cells_len(R: int, C: int, Gp: int, Gn: int) -> int:
+    """NVRX_NODE_GROUP_CELLS_LEN: int32 words of ``nvrx_node_group_score``'s ``d_cells``."""
+    return 3 * R + 3 * C + Gp + Gn + 3
 
 
 def history_stride(H: int) -> int:

@@ -30,7 +30,7 @@ import torch
 
 from . import _native
 from .row_families import EPISODE, ONSET, PERIOD, RAMP, ROW_STEPS, STALL, TAIL, RowFamily
-from .table_families import NODE, PACE, PACE_GROUP, PEER, ROBUST, ROBUST_GROUP, SLOTS, TableFamily
+from .table_families import NODE, NODE_GROUP, PACE, PACE_GROUP, PEER, ROBUST, ROBUST_GROUP, SLOTS, TableFamily
 
 DEFAULT_THRESHOLDS = (0.75, 0.75, 0.75, 0.75)  # gpu_rel, section_rel, gpu_indiv, section_indiv
 
@@ -390,6 +390,49 @@ class PeerGroups:
     def members(self, g: int) -> List[int]:
         start = self.host[2 * self.R :]
         return self.host[self.R + start[g] : self.R + start[g + 1]].tolist()
+
+    def device(self, backend: "HipBackend") -> torch.Tensor:
+        if self._dev is None:
+            with torch.cuda.stream(backend.stream):  # (allocated, written and read under the backend's stream)
+                self._dev = torch.from_numpy(self.host).to(backend.device)
+        return self._dev
+
+
+class NodeCells:
+    """The CELLS of node scores per peer group -- the non-empty intersections of a node and a peer group -- resolved from the two
+    ``PeerGroups`` of one table: the array ``nvrx_node_group_score`` takes (``d_cells``, include/nvrx_straggler.h: ``cell[R] |
+    members[R] | cstart[C+1] | gstart[Gp+1] | nstart[Gn+1] | ncells[C] | cgroup[C] | rgroup[R]`` int32) on the host and, uploaded
+    once, on the device.  Cells are numbered by (peer group, node), so a group's cells are consecutive.  ``G`` is the family's
+    three counts ``(C, Gp, Gn)`` and ``maxima`` the largest cell's size and the most cells of one group and of one node, as the C
+    entry takes them.  A ``ReportGenerator`` resolves it again when either side changes."""
+
+    __slots__ = ("R", "G", "maxima", "nodes", "peers", "host", "cell_group", "cell_node", "_dev")
+
+    def __init__(self, nodes: PeerGroups, peers: PeerGroups):
+        if nodes.R != peers.R:
+            raise ValueError(f"node groups resolved for {nodes.R} ranks, peer groups for {peers.R}")
+        self.R, self.nodes, self.peers = nodes.R, nodes, peers
+        key = peers.group.astype(np.int64) * nodes.G + nodes.group
+        uniq, cell = np.unique(key, return_inverse=True)  # ascending by (peer group, node)
+        C = len(uniq)
+        if C > _native.PEER_MAX_GROUPS:
+            raise ValueError(f"node_peer_groups: {C} cells (node x peer group), at most {_native.PEER_MAX_GROUPS}")
+        self.cell_group, self.cell_node = (uniq // nodes.G).astype(np.int32), (uniq % nodes.G).astype(np.int32)
+
+        def starts(ids, n):
+            out = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(np.bincount(ids, minlength=n), out=out[1:])
+            return out
+
+        cstart, gstart, nstart = starts(cell, C), starts(self.cell_group, peers.G), starts(self.cell_node, nodes.G)
+        self.G = (C, peers.G, nodes.G)
+        self.maxima = (int(np.diff(cstart).max()), int(np.diff(gstart).max()), int(np.diff(nstart).max()))
+        self.host = np.concatenate((cell, np.argsort(cell, kind="stable"), cstart, gstart, nstart,
+                                    np.argsort(self.cell_node, kind="stable"), self.cell_group, peers.group)).astype(np.int32)
+        self._dev = None
+
+    def cells_of_node(self, n: int) -> List[int]:
+        return np.flatnonzero(self.cell_node == n).tolist()
 
     def device(self, backend: "HipBackend") -> torch.Tensor:
         if self._dev is None:
@@ -896,6 +939,9 @@ class Workspace:
     def node_settle(self) -> None:
         self.table_settle(NODE)
 
+    def node_group_buffers(self, G: tuple, n_ranks: int):
+        return self.table_buffers(NODE_GROUP, n_ranks, G)
+
     # ---- score history (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------
     _history_buf = None  # device: the records of the last history step on this workspace's result blocks
     _history_last = None  # the History whose kernel may still be reading a result block / writing _history_buf
@@ -1284,7 +1330,10 @@ class HipBackend:
             if groups.R != ws.R:
                 raise ValueError(f"{fam.groups} groups resolved for {groups.R} ranks, the table has {ws.R}")
             G = groups.G
-            lead = (groups.device(self).data_ptr(), G, groups.max_size) if fam.max_size else (groups.device(self).data_ptr(), G)
+            if isinstance(G, tuple):  # NodeCells: the three counts, then the three maxima
+                lead = (groups.device(self).data_ptr(),) + G + groups.maxima
+            else:
+                lead = (groups.device(self).data_ptr(), G, groups.max_size) if fam.max_size else (groups.device(self).data_ptr(), G)
         ws.table_settle(fam)  # (the records buffer is about to be rewritten)
         buf = ws.table_buffers(fam, n_ranks, G)
         rc = entry(*head, *lead, *fam.rank_args(first_rank, n_ranks, params), buf.data_ptr(), *tail)
@@ -1335,6 +1384,10 @@ class HipBackend:
                    n_ranks: Optional[int] = None, min_members: int = 2, min_nodes: int = 3) -> TableScores:
         return self._table_score(NODE, ws, table, nodes, first_rank, n_ranks, (min_members, min_nodes))
 
+    def node_group_score(self, ws: Workspace, table: torch.Tensor, cells: NodeCells, first_rank: int = 0,
+                         n_ranks: Optional[int] = None, min_members: int = 2, min_nodes: int = 3, min_peers: int = 2) -> TableScores:
+        return self._table_score(NODE_GROUP, ws, table, cells, first_rank, n_ranks, (min_members, min_nodes, min_peers))
+
     def robust_copy_out(self, t: TableScores):
         return self.table_copy_out(t)
 
@@ -1351,6 +1404,9 @@ class HipBackend:
         return self.table_copy_out(t)
 
     def node_copy_out(self, t: TableScores):
+        return self.table_copy_out(t)
+
+    def node_group_copy_out(self, t: TableScores):
         return self.table_copy_out(t)
 
     def history_prepare(self, ws: Workspace, state: ScoreHistory, first_rank: int, n_ranks: int, thresholds):
@@ -1919,6 +1975,10 @@ class HipRings:
     def report_node(self, ws: Workspace, nodes: PeerGroups, first_rank: int = 0, n_ranks: Optional[int] = None,
                     min_members: int = 2, min_nodes: int = 3) -> TableScores:
         return self._table_report(NODE, ws, nodes, first_rank, n_ranks, (min_members, min_nodes))
+
+    def report_node_group(self, ws: Workspace, cells: NodeCells, first_rank: int = 0, n_ranks: Optional[int] = None,
+                          min_members: int = 2, min_nodes: int = 3, min_peers: int = 2) -> TableScores:
+        return self._table_report(NODE_GROUP, ws, cells, first_rank, n_ranks, (min_members, min_nodes, min_peers))
 
     def report_work(self, ws: Workspace, count_tol: float = 0.25, max_unlike_ppm: int = 100000) -> Work:
         """The work groups of the table of the report ``report_fused`` just issued on ``ws`` (``nvrx_report_work``): enqueued

@@ -991,6 +991,66 @@ class _NodeSource:
         return self._built
 
 
+class _NodeGroupSource(_NodeSource):
+    """``_NodeSource`` for node scores per peer group: ``nodes`` is a ``backend.NodeCells``, the handle's pair records come per
+    cell (node x peer group) and its column records per peer group."""
+
+    __slots__ = ()
+
+    def build(self) -> dict:
+        if self._built is None:
+            pairs, cols, nrecs, rrecs = self.handle.records()
+            cells = self.nodes
+            nodes, peers = cells.nodes, cells.peers
+            K = len(self.kernels)
+            nlabels, glabels = nodes.labels, peers.labels
+            node, group = nodes.group.tolist(), peers.group.tolist()
+            cell_group = cells.cell_group.tolist()
+            of_node = [cells.cells_of_node(g) for g in range(nodes.G)]
+            center = np.ascontiguousarray(cols).view(np.float32)[:, :, 0].tolist()
+            counts = cols[:, :, 1:].tolist()
+            median = np.ascontiguousarray(pairs).view(np.float32)[:, :, 0].tolist()
+            present = pairs[:, :, 1].tolist()
+
+            def column(c):
+                return {glabels[p]: {"center": center[p][c], "nodes": counts[p][c][0], "above": counts[p][c][1],
+                                     "below": counts[p][c][2]} for p in range(peers.G)}
+
+            def per_node(c):
+                return {nlabels[g]: {glabels[cell_group[j]]: {"median": median[j][c], "ranks": present[j][c]} for j in of_node[g]}
+                        for g in range(nodes.G)}
+
+            rated = _pace_rank_parts(nrecs, nlabels)
+            for d in rated.values():  # (a node record has no weights: its three sums are empty)
+                for key in ("total_us", "slower_us", "excess_us"):
+                    del d["gpu"][key]
+            t = self._built = {
+                "nodes": {nlabels[g]: nodes.members(g) for g in range(nodes.G)},
+                "node_of": {r: nlabels[g] for r, g in enumerate(node)},
+                "kernels": {name: column(k) for k, name in enumerate(self.kernels)},
+                "section_columns": {name: column(K + g) for name, g in self.sections.items()},
+                "per_node": {"kernels": {name: per_node(k) for k, name in enumerate(self.kernels)},
+                             "section_columns": {name: per_node(K + g) for name, g in self.sections.items()}},
+                "node_scores": rated,
+                "ranks": _pace_rank_parts(rrecs, self.ranks),
+                "unrated_nodes": [lab for lab, d in rated.items() if d["gpu"]["columns"] == 0 and d["sections"]["columns"] == 0],
+                "params": dict(self.params),
+                "peer_groups": True,
+                "groups": {glabels[p]: peers.members(p) for p in range(peers.G)},
+                "group_of": {r: glabels[group[r]] for r in self.ranks},
+                "cells": {nlabels[g]: [glabels[cell_group[j]] for j in of_node[g]] for g in range(nodes.G)},
+            }
+            p = self.params
+            for lab, d in rated.items():
+                for part in ("gpu", "sections"):
+                    d[part]["members_rated"], d[part]["members_off_pace"], d[part]["agree"] = _node_agreement(
+                        t, part, lab, p["min_columns"], p["min_effect"], p["min_breadth"])
+                for key in ("members_rated", "members_off_pace", "agree"):
+                    d[key] = d["gpu"][key]
+            self.handle = None
+        return self._built
+
+
 def _peer_spec(peer_groups, what: str = "peer_groups"):
     """``ReportGenerator``'s ``peer_groups`` as the generator keeps it: None (off), ``"auto"`` (inferred per report: work
     groups), a rule (``"block:N"``: label ``rank //
@@ -1758,7 +1818,15 @@ class Report:
         (``gather_on_rank0=False``) still holds every node's record, with ``agree`` over what it sees.  ``ranks`` holds every
         reported rank's record against the nodes' centre, spelled as in ``pace_scores()``: ``excess_us`` is the microseconds
         above the pace of the job's nodes.  ``unrated_nodes``: nodes without a column in either part.  Plain dicts, lists,
-        floats and ints.  The first call waits for the node kernels and copies their results; ``generate_report`` does not."""
+        floats and ints.  The first call waits for the node kernels and copies their results; ``generate_report`` does not.
+
+        With ``ReportGenerator(node_peer_groups=True)`` a node is compared with the nodes doing the SAME work.  A CELL is a
+        node's share of one peer group: a kernel or section then maps to ``{group label: {"center", "nodes", "above",
+        "below"}}`` (the lower median across the group's cells, one cell one vote), the cells' records stand under ``per_node``:
+        ``{"kernels" / "section_columns": {name: {node: {group label: {"median", "ranks"}}}}}``, a node's record runs over all its
+        (cell, column) pairs, each against its own group's centre (``columns`` counts pairs), a rank's record is taken against its
+        own group's centre, and ``peer_groups`` (True), ``groups``, ``group_of`` and ``cells`` (``{node: [group labels]}``) are
+        added.  A peer group that sits on one node gives that node no reference: it is listed under ``unrated_nodes``."""
         node = self.__dict__.get("_node")
         if node is None:
             return {}
@@ -2234,7 +2302,7 @@ class ReportGenerator:
                  work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False,
                  ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5,
                  robust_peer_groups: bool = False, stall_detection: bool = False, stall_min_ratio: float = 1.5,
-                 stall_min_z: float = 6.0, stall_min_share: float = 0.01) -> None:
+                 stall_min_z: float = 6.0, stall_min_share: float = 0.01, node_peer_groups: bool = False) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2453,6 +2521,20 @@ class ReportGenerator:
             self.node_min_members, self.node_min_nodes = int(node_min_members), int(node_min_nodes)
             self.node_min_columns = int(node_min_columns)
             self.node_min_effect, self.node_min_breadth, self.node_min_agree = effect, breadth, agree
+        # node scores per peer group: the node step compares a node with the nodes doing the SAME work (nvrx_node_group_score),
+        # behind the peer step; off: the node step is the job-wide one, whatever peer_groups says
+        self.node_peer_groups = bool(node_peer_groups)
+        self._cells_resolved = None  # backend.NodeCells of the (nodes, peer groups) pair the last report ran on
+        if self.node_peer_groups:
+            if not self.node_scores or self.peer_groups is None:
+                missing = [name for name, on in (("node_scores", self.node_scores), ("peer_groups", self.peer_groups is not None))
+                           if not on]
+                raise ValueError(f"node_peer_groups needs node_scores and peer_groups; {' and '.join(missing)} "
+                                 f"{'is' if len(missing) == 1 else 'are'} not set")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "node_group_score"):
+                raise RuntimeError(f"node_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
+                                   "has no node scores per peer group (backend.node_group_score)")
         # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
         # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
         # call.  The step adds one collective per report, so EVERY rank must pass the same value.
@@ -2741,7 +2823,8 @@ class ReportGenerator:
             (self.robust_scores and not self.robust_peer_groups, "robust_scores", "report_robust"),
             (self.work_groups, "work_groups", "report_work"), (self.peer_groups is not None, "peer_groups", "report_peer"),
             (self.robust_peer_groups, "robust_peer_groups", "report_robust_group"),
-            (self.pace_scores,) + pace, (self.node_scores, "node_scores", "report_node"),
+            (self.pace_scores,) + pace, (self.node_scores and not self.node_peer_groups, "node_scores", "report_node"),
+            (self.node_peer_groups, "node_peer_groups", "report_node_group"),
             (self.peer_history, "peer_history", "report_peer_history"), (self.peer_trends, "peer_trends", "report_peer_trend"),
             (self.score_history, "score_history", "report_history"), (self.score_trends, "score_trends", "report_trend")) if on)
         self._last_plan_fused = False
@@ -3310,13 +3393,22 @@ class ReportGenerator:
         if self.node_scores:
             nodes = self._node_for(ws)
             least = self._node_min(nodes)
-            if rings is not None:
-                handle = rings.report_node(ws, nodes, lo, n, self.node_min_members, least)
-            else:
-                handle = be.node_score(ws, ws.table, nodes, lo, n, self.node_min_members, least)
             params = {"min_members": self.node_min_members, "min_nodes": least, "min_columns": self.node_min_columns,
                       "min_effect": self.node_min_effect, "min_breadth": self.node_min_breadth, "min_agree": self.node_min_agree}
-            d["_node"] = _NodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, nodes)
+            if self.node_peer_groups:
+                # in place of the job-wide step, behind the peer step (peer_groups="auto" has its groups by then)
+                cells = self._cells_for(nodes, self._peer_for(ws))
+                args = (lo, n, self.node_min_members, least, self.peer_min_ranks)
+                handle = rings.report_node_group(ws, cells, *args) if rings is not None else \
+                    be.node_group_score(ws, ws.table, cells, *args)
+                params.update(min_peers=self.peer_min_ranks, peer_groups=True)
+                d["_node"] = _NodeGroupSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, cells)
+            else:
+                if rings is not None:
+                    handle = rings.report_node(ws, nodes, lo, n, self.node_min_members, least)
+                else:
+                    handle = be.node_score(ws, ws.table, nodes, lo, n, self.node_min_members, least)
+                d["_node"] = _NodeSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), params, nodes)
         if self._history is not None:
             # the ring takes the scores of every report this rank holds, once, behind its last score kernel
             state, thr = self._history, self.persistence_thresholds
@@ -3391,6 +3483,15 @@ class ReportGenerator:
             nodes = self._node_resolved = _backend_mod.PeerGroups([r2n[r] for r in range(ws.R)])
             self._node_source = r2n
         return nodes
+
+    def _cells_for(self, nodes, peers):
+        """The cells (node x peer group) of the two resolved sides (cold: built again when either object is replaced -- with
+        ``peer_groups="auto"`` that is whenever a report's work groups differ from the last one's).  More cells than
+        ``NVRX_PEER_MAX_GROUPS`` are refused here, at the first report."""
+        cells = self._cells_resolved
+        if cells is None or cells.nodes is not nodes or cells.peers is not peers:
+            cells = self._cells_resolved = _backend_mod.NodeCells(nodes, peers)
+        return cells
 
     def _node_min(self, nodes) -> int:
         """``node_min_nodes``, but never more than the nodes the job has, as ``_pace_min``."""

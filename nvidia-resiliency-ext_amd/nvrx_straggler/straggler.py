@@ -433,6 +433,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         slack_peer_groups: Optional[bool] = None,
         row_peer_groups: Optional[bool] = None,
         robust_peer_groups: Optional[bool] = None,
+        node_peer_groups: Optional[bool] = None,
         node_scores: Optional[bool] = None,
         node_groups=None,
         node_min_members: int = 2,
@@ -625,6 +626,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 (``"auto"`` is allowed); a group needs ``max(peer_min_ranks, min(robust_min_ranks, its size))`` ranks with a
                 kernel for its median to be a reference.  Default: ``NVRX_ROBUST_PEER_GROUPS`` ("1"; "0" or unset: off).  Same
                 value on every rank (no collective depends on it).
+            node_peer_groups: the node scores compare a node with the nodes doing the SAME work: per (node, peer group) cell
+                the lower median of its ranks, per peer group the lower median of its cells, and a node's pace over all its
+                cells, each against its own group's centre -- in a job of pipeline stages the centre across all nodes lies in
+                the fast stage and every node of a slower one is named.  Needs ``node_scores`` and ``peer_groups`` (``"auto"``
+                is allowed); a peer group needs ``max(peer_min_ranks, min(node_min_nodes, its cells))`` nodes with a kernel
+                for their median to be a reference, so a group that sits on one node leaves that node unrated.  Default:
+                ``NVRX_NODE_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank (no collective depends on it).
             slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
                 peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
                 expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
@@ -834,6 +842,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
                             "node_min_nodes": node_min_nodes, "node_min_columns": node_min_columns,
                             "node_min_effect": node_min_effect, "node_min_breadth": node_min_breadth,
                             "node_min_agree": node_min_agree}
+        if node_peer_groups is None:
+            from_env = os.environ.get("NVRX_NODE_PEER_GROUPS", "")
+            if from_env not in ("", "0", "1"):
+                raise ValueError(f"NVRX_NODE_PEER_GROUPS must be 0 or 1, got {from_env!r}")
+            node_peer_groups = from_env == "1"
+        if node_peer_groups:
+            node_options["node_peer_groups"] = True  # (the generator says which of node_scores and peer_groups it misses)
         ramp_options = {}  # (off: the generator is built exactly as before)
         if ramp_detection is None:
             ramp_detection = os.environ.get("NVRX_RAMP_DETECTION", "0") not in ("", "0")

@@ -6,7 +6,7 @@ The device kernels differ; the host path is ONE (DESIGN.md, "Table families")::
     settle the slot's last step -> the slot's records buffer -> nvrx_<name>_score on the caller's table, or
     nvrx_report_<name> behind the report just issued -> one uint32 block, one ordered D2H on first read -> cut into arrays
 
-``FAMILIES`` (and ``ROBUST_GROUP`` beside it: robust scores per peer group) says what differs, once, in the fixed order the
+``FAMILIES`` (and ``ROBUST_GROUP`` and ``NODE_GROUP`` beside it: robust and node scores per peer group) says what differs, once, in the fixed order the
 families run in.  The backend (``Workspace.table_buffers`` /
 ``table_settle``, ``HipBackend._table_score`` / ``table_copy_out``, ``HipRings._table_report``, ``TableScores``) is written
 against these records; a further family is a kernel file, one record here, its ``Report`` methods and the one-line
@@ -101,3 +101,12 @@ SLOTS: Tuple[TableFamily, ...] = (ROBUST, PEER, PACE, NODE)  # one family per sl
 ROBUST_GROUP = TableFamily("robust_group", "nvrx_robust_group_score", "nvrx_report_robust_group", "robust",
                            _native.robust_group_words, "peer", True, _RANKS + ("min_ranks", "min_peers", "floor_rel"),
                            lambda G, n, KS, S: (((G, KS, 4), _U32), ((n, 2, 1 + S), _F32)))
+
+# node scores per peer group run in node's slot (a report runs one of the two).  They take a NodeCells, whose ``G`` is the three
+# counts (C cells, Gp peer groups, Gn nodes): the counts and the three maxima follow d_cells in the C arguments.
+# (pairs [C, K+S, 4] {med, n, above, below}, cols [Gp, K+S, 4] {center, nodes, above, below}, nodes [Gn, 2, 8], ranks
+# [n_ranks, 2, 8]) uint32; the thresholds come BEFORE the rank range
+NODE_GROUP = TableFamily("node_group", "nvrx_node_group_score", "nvrx_report_node_group", "node",
+                         lambda G, n, K, S: _native.node_group_words(*G, n, K, S), "node", True,
+                         ("min_members", "min_nodes", "min_peers") + _RANKS,
+                         lambda G, n, KS, S: (((G[0], KS, 4), _U32), ((G[1], KS, 4), _U32), ((G[2], 2, 8), _U32), ((n, 2, 8), _U32)))
