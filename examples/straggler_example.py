@@ -86,6 +86,12 @@ usual time and the step lasts as long on every rank, so ``identify_stragglers`` 
 peers.  ``identify_stragglers`` names ranks 4-7, three of them healthy; with peer groups (``ReportGenerator(peer_groups=
 "block:4")``) ``identify_peer_stragglers`` names rank 6 alone, and both scores are printed side by side.
 
+``--peer-explain`` asks "which kernels?" of the ``--peer`` job in per-kernel shape: 8 ranks x 120 kernel keys (``block:4``, the
+second stage 1.5 x slower in every kernel, 0.5 % noise, seed 2026), rank 6 1.4 x slower than its stage in six named kernels only.
+Against the job (``kernel_attribution=6``, ``explain_gpu_scores``) rank 6's list is the stage's heaviest kernels, much the same
+as healthy rank 5's; against its peers (``ReportGenerator(peer_attribution=6)``, ``explain_peer_gpu_scores``) it is the six
+kernels, each with the peer whose pace it is measured against.  Both are printed for both ranks.
+
 ``--peer-persist`` plays the ``--peer`` job over 16 reports (8 ranks, ``block:4``, stages of 1000 us and 1500 us, 1 % noise, seed
 37): rank 1 is 1.6x slower in report 6 only, rank 6 is 1.4x slower than its stage from report 10 on.  Per report it prints whom
 each rule names.  Per-report peer flagging (``identify_peer_stragglers``) names rank 1 at report 6 -- with ``stop_if_detected``
@@ -640,6 +646,71 @@ def peer(ranks: int = 8, sections: int = 4, samples: int = 33, slow_rank: int = 
         job.close()
 
 
+PEER_EXPLAIN_SLOW = (7, 23, 42, 58, 77, 101)  # the kernel ids in which rank 6 of --peer-explain is slower than its peers
+
+
+def peer_explain_medians(ranks: int = 8, kernels: int = 120, stage: int = 4, slow_rank: int = 6, slowdown: float = 1.4,
+                         seed: int = 2026):
+    """The ``--peer-explain`` job: ``(kernel names, [ranks, kernels] f32 microseconds per call)`` (NumPy only).  The ``--peer``
+    job in per-kernel shape: lognormal kernel times, the second stage 1.5 x slower in every kernel, and the slow rank
+    ``slowdown`` x slower in the kernels ``PEER_EXPLAIN_SLOW`` only.  0.5 % noise: against the fastest of four peers a healthy
+    rank then misses about half a percent of its peer score (the minimum of four normal draws lies a standard deviation low)."""
+    import numpy as np
+
+    names = [f"kernel_{k:03d}" for k in range(kernels)]
+    rng = np.random.default_rng(seed)
+    med = rng.lognormal(np.log(100.0), 0.5, kernels)[None, :] * (1.0 + 0.005 * rng.standard_normal((ranks, kernels)))
+    med[(np.arange(ranks) // stage) % 2 == 1] *= 1.5
+    med[slow_rank, list(PEER_EXPLAIN_SLOW)] *= slowdown
+    return names, med.astype(np.float32)
+
+
+def peer_explain_job(kernel_attribution: int = 6, peer_attribution: int = 6, calls: int = 200, stage: int = 4, **options):
+    """A folded job loaded with one window of the ``--peer-explain`` table, both attributions on (the caller reports and
+    closes it; ``peer_explain_load`` fills a further window)."""
+    from nvrx_straggler.folded import FoldedJob
+
+    names, med = peer_explain_medians(stage=stage)
+    job = FoldedJob(total_ranks=len(med), section_names=["step"], ring_cap=256, scores_to_compute=("relative_perf_scores",),
+                    kernel_names=names, peer_groups=f"block:{stage}", kernel_attribution=kernel_attribution,
+                    peer_attribution=peer_attribution, **options)
+    peer_explain_load(job, calls, stage)
+    return job
+
+
+def peer_explain_load(job, calls: int = 200, stage: int = 4) -> None:
+    import numpy as np
+
+    _, med = peer_explain_medians(stage=stage)
+    for lr, r in enumerate(job.logical_ranks()):
+        job.load(lr, np.full((1, calls), med[r].sum(), dtype=np.float32))
+        job.load_kernels(lr, np.repeat(med[r][:, None], calls, axis=1))
+
+
+def peer_explain(slow_rank: int = 6, healthy_rank: int = 5) -> None:
+    """Which kernels?  The job-wide attribution of the slow rank of a pipeline job next to its peer attribution."""
+    torch.cuda.set_device(0)
+    job = peer_explain_job()
+    try:
+        report = job.report()
+        gpu = report.peer_scores()["gpu_relative"]
+        print(f"peer GPU scores: rank {slow_rank} {gpu[slow_rank]:.3f}, rank {healthy_rank} {gpu[healthy_rank]:.3f}; slow on rank "
+              f"{slow_rank} only: {', '.join(f'kernel_{k:03d}' for k in PEER_EXPLAIN_SLOW)}")
+        wide, peers = report.explain_gpu_scores()["relative"], report.explain_peer_gpu_scores()
+        for r in (slow_rank, healthy_rank):
+            w, p = wide[r], peers[r]
+            print(f"rank {r} against the job: {w['deficit']:.3f} of its GPU score is missing, {w['explained']:.3f} of it in:")
+            for k in w["kernels"]:
+                print(f"    {k['kernel']}: share {k['share']:.3f}, score {k['score']:.3f}, {k['lost_us']:.0f} us above the job's pace")
+            print(f"rank {r} against its peers (group {p['group']}): {p['deficit']:.3f} of its peer GPU score is missing, "
+                  f"{p['explained']:.3f} of it in:")
+            for k in p["kernels"]:
+                print(f"    {k['name']}: share {k['share']:.3f}, score {k['score']:.3f}, {k['lost_us']:.0f} us above rank "
+                      f"{k['floor_rank']}'s pace ({k['floor_us']:.1f} us a call), {k['peers_with_kernel']} peers have it")
+    finally:
+        job.close()
+
+
 def peer_persist_windows(reports: int = 16, ranks: int = 8, sections: int = 4, samples: int = 33):
     """The ``--peer-persist`` job, report by report: ``[ranks, sections, samples]`` f64 microseconds (NumPy only)."""
     import numpy as np
@@ -955,6 +1026,9 @@ def main() -> None:
     ap.add_argument("--peer", action="store_true",
                     help="no training: play the peer-group scenario (two pipeline stages of different length, one rank slow "
                          "within its stage) and exit")
+    ap.add_argument("--peer-explain", action="store_true",
+                    help="no training: play the peer-attribution scenario (the two stages of --peer as 8 ranks x 120 kernels, "
+                         "rank 6 1.4 x slower in six kernels only): its job-wide kernel list next to its peer list, and exit")
     ap.add_argument("--peer-persist", action="store_true",
                     help="no training: play the peer-history scenario (the two stages of --peer over 16 reports: one bad "
                          "window of rank 1, rank 6 slower than its stage from report 10 on) under three rules, and exit")
@@ -1020,6 +1094,9 @@ def main() -> None:
         return
     if args.peer_persist:
         peer_persist()
+        return
+    if args.peer_explain:
+        peer_explain()
         return
     if args.peer:
         peer()

@@ -786,6 +786,35 @@ int nvrx_peer_history(const float *d_peer, int n_ranks, int S, float *d_hist, in
                       const double *thresholds, void *d_out, void *stream);
 int nvrx_peer_trend(const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports, void *d_out, void *stream);
 
+/* Peer attribution: which kernels carry a rank's PEER GPU score deficit.  nvrx_attribute (above) measures every kernel against
+ * the fastest rank of the whole job; where ranks legitimately differ that list names the kernels a slow STAGE runs, on its
+ * healthy ranks too.  Here the reference of kernel k is the floor of the rank's own group, as in nvrx_peer_score: with
+ * s_k = floor[g][k] / med[r][k], w_k = table[r][2(K+S) + k] and n_k = w_k * (1 - s_k), all in f64, 1 - (GPU peer score) =
+ * sum_k(n_k) / W over the ELIGIBLE kernels k < K -- med[r][k] >= 0 and the pair (g, k) referenced (present >= min_ranks):
+ * exactly the set nvrx_peer_score sums.  Per reported rank the top_n eligible kernels by n_k, descending, in nvrx_attribute's
+ * order (by value: -0.0 ties with +0.0 and is recorded as +0.0, NaN after -inf; ties to the lower kernel id).
+ *   d_table, d_groups, G, min_ranks  as for nvrx_peer_score; ranks [first_rank, first_rank + n_ranks) are reported;
+ *   d_peer_cols  the [G][K+S] column records nvrx_peer_score / nvrx_report_peer wrote at the head of its block for the SAME
+ *      table, groups and min_ranks; 16-byte aligned; only read.  The step must be ordered behind that peer step;
+ *   top_n in [1, NVRX_ATTR_MAX_TOP];
+ *   d_out [n_ranks][1 + top_n] records of 32 bytes (two 16-byte words), 16-byte aligned (NVRX_PEER_ATTR_WORDS 32-bit words):
+ *      header {f32 deficit = sum(n_k)/W, f32 explained = sum of the listed n_k / W, u32 eligible kernels, f32 W} {0, 0, 0, 0}
+ *      entry  {i32 kernel id, f32 share = n_k/W, f32 score = s_k, f32 lost_us = n_k}
+ *             {f32 floor, i32 floor_rank, u32 present, u32 0}: the pair's column record, copied
+ *      no eligible kernel (a group id outside [0, G), a rank alone in its group under min_ranks >= 2, K = 0): header {NaN, NaN,
+ *      0, 0}, every id -1; fewer than top_n eligible kernels: the remaining ids are -1 (floats NaN, floor_rank -1, present 0).
+ *      s_k and n_k are the f64 formula rounded to f32; the sums are taken across a wave: their last bits depend on that order.
+ *   The row is walked once, in tiles of NVRX_PEER_ATTR_TILE kernel ids above 1024 ids (a shorter row is one tile).
+ *   The CONTENTS of d_groups and d_peer_cols are guarded on the device as in nvrx_peer_score: no content makes the kernel read
+ *   or write outside the table, the records or d_out.
+ * One launch on `stream`; no atomics, no scratch.  Argument errors, reported before any device is touched: nvrx_attribute's in
+ * its order, then NVRX_ERR_RANGE for R > NVRX_ROBUST_MAX_RANKS, S > NVRX_MAX_ROWS or min_ranks < 1, nvrx_peer_score's checks
+ * of G, then NVRX_ERR_INVALID for a null pointer or a d_out or d_peer_cols that is not 16-byte aligned. */
+#define NVRX_PEER_ATTR_TILE 4096
+#define NVRX_PEER_ATTR_WORDS(n_ranks, top_n) ((size_t)(n_ranks) * (1 + (size_t)(top_n)) * 8)
+int nvrx_peer_attribute(const float *d_table, int R, int K, int S, const int32_t *d_groups, int G, const void *d_peer_cols,
+                        int first_rank, int n_ranks, int min_ranks, int top_n, void *d_out, void *stream);
+
 /* Slack scores: the rank the others WAIT FOR in collectives.  Every score above compares how long a rank's own work takes; a
  * rank whose host is slow (a busy CPU, a data loader, a GC pause) launches late, computes at the usual speed and ends its
  * sections in a collective like everybody else, so all of them read 1.  The time the ranks spend inside collective kernels
@@ -1276,6 +1305,13 @@ int nvrx_report_peer_history(nvrx_ctx *ctx, const float *d_peer, int n_ranks, in
                              uint64_t n_before, const double *thresholds, void *d_out);
 int nvrx_report_peer_trend(nvrx_ctx *ctx, const float *d_hist, int n_ranks, int S, int S_cap, int H, uint64_t n_reports,
                            void *d_out);
+/* nvrx_peer_attribute (above) on the table of the report LAST issued through `desc` on `ctx` (d_table, or d_send without an
+ * exchange; shape from the descriptor) and the column records nvrx_report_peer wrote for that report (d_peer_cols: that
+ * step's d_out).  On the context's stream, ordered as nvrx_report_peer orders itself and so behind that step without an event.
+ * The host does not wait; copy d_out with a D2H on the context's stream, and do not let a later report rewrite the table, or a
+ * later peer step the records, before the kernel has run.  NVRX_ERR_STATE: no report was issued through this descriptor. */
+int nvrx_report_peer_attribute(nvrx_ctx *ctx, const nvrx_report_desc *desc, const int32_t *d_groups, int G,
+                               const void *d_peer_cols, int first_rank, int n_ranks, int min_ranks, int top_n, void *d_out);
 /* The local step of the slack scores (nvrx_slack_score, above) on the STATISTICS of the report last issued -- it reads the
  * statistics rows, not the rings.  rows[i], cols[i], i < n: host arrays, the collective rows of a logical rank (row within the
  * rank, the same for every logical rank) in ascending order with their columns; the library keeps the list in device memory

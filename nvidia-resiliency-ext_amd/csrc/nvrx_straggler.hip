@@ -4041,3 +4041,4 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_node_group.inl"
 #include "nvrx_work.inl"
 #include "nvrx_peer_history.inl"
+#include "nvrx_peer_attribute.inl"

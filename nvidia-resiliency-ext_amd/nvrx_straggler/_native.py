@@ -125,6 +125,8 @@ SYMBOLS = [
     ("nvrx_peer_history", c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double), c_void_p,
                                   c_void_p]),
     ("nvrx_peer_trend", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p, c_void_p]),
+    ("nvrx_peer_attribute", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p]),
     ("nvrx_slack_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_slack_group_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                        c_void_p]),
@@ -189,6 +191,8 @@ SYMBOLS = [
     ("nvrx_report_peer_history", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_uint64, POINTER(c_double),
                                          c_void_p]),
     ("nvrx_report_peer_trend", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_void_p]),
+    ("nvrx_report_peer_attribute", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_void_p]),
     ("nvrx_report_work", c_int, [c_void_p, POINTER(ReportDesc), c_float, c_int, c_void_p]),
     ("nvrx_slack_local", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     ("nvrx_report_clocks", c_int, [POINTER(c_double)]),
@@ -290,6 +294,14 @@ def attr_words(n_ranks: int, top_n: int) -> int:
 def robust_words(n_ranks: int, K: int, S: int) -> int:
     """NVRX_ROBUST_WORDS: 32-bit words of a robust-score block: ``[K+S][4]`` column records, then ``[n_ranks][2][1 + S]``."""
     return 4 * (K + S) + n_ranks * 2 * (1 + S)
+
+
+PEER_ATTR_TILE = 4096  # NVRX_PEER_ATTR_TILE: kernel ids per tile of k_peer_attribute's walk above 1024 ids
+
+
+def peer_attr_words(n_ranks: int, top_n: int) -> int:
+    """NVRX_PEER_ATTR_WORDS: 32-bit words of a peer-attribution block ``[n_ranks][1 + top_n][8]``."""
+    return n_ranks * (1 + top_n) * 8
 
 
 def peer_words(G: int, n_ranks: int, K: int, S: int) -> int:

@@ -241,6 +241,32 @@ class Attribution:
         return self._host
 
 
+class PeerAttribution:
+    """Peer attribution of one report (``nvrx_peer_attribute`` / ``nvrx_report_peer_attribute``), enqueued and not waited
+    for: the records -- ``[n_ranks][1 + top_n][8]`` 32-bit words, include/nvrx_straggler.h -- are in the workspace's device
+    buffer once the kernel has run.  ``records()`` waits for it and takes the private host copy (one ordered D2H on the
+    backend's stream): when a ``Report`` first asks, or -- ``Workspace.peer_attr_settle`` -- before the next report on the
+    same workspace rewrites the table and the peer block the kernel reads and the buffer it writes."""
+
+    __slots__ = ("backend", "d_ptr", "first_rank", "n_ranks", "top_n", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, first_rank: int, n_ranks: int, top_n: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.first_rank, self.n_ranks, self.top_n = first_rank, n_ranks, top_n
+        self._host: Optional[np.ndarray] = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self) -> np.ndarray:
+        """``[n_ranks, 1 + top_n, 8]`` uint32 (private copy); the first call waits for the kernel."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.peer_attribution_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class RowScores:
     """One row family's scores of one report (``nvrx_<family>_local`` -> exchange -> ``nvrx_<family>_score``;
     row_families.py), enqueued and not waited for: once the score kernel has run, the workspace's buffer of that family
@@ -834,6 +860,8 @@ class Workspace:
             self.peer_history_settle()
         if self._peer_trend_last is not None:
             self.peer_trend_settle()
+        if self._peer_attr_last is not None:
+            self.peer_attr_settle()
         if self._slack_last is not None:
             self.slack_settle()
         if self._work_last is not None:
@@ -1014,6 +1042,22 @@ class Workspace:
         """Before anything rewrites the peer-trend records buffer: the last step's kernel has run and its records are on the
         host (a ``Report`` still alive keeps them; an unread one costs this one small copy)."""
         last, self._peer_trend_last = self._peer_trend_last, None
+        if last is not None:
+            last.records()
+
+    # ---- peer attribution (off unless a ReportGenerator asks: nothing is allocated before) -------------------------
+    _peer_attr_buf = None   # device: the records of the last peer attribution issued through this workspace
+    _peer_attr_last = None  # the PeerAttribution whose kernel may still be reading the table and the peer slot
+
+    def peer_attr_buffers(self, n_ranks: int, top_n: int):
+        """The records buffer for a peer attribution of ``n_ranks`` ranks (cold: allocated once per shape)."""
+        return self._records_buffer("_peer_attr_buf", _native.peer_attr_words(n_ranks, top_n))
+
+    def peer_attr_settle(self) -> None:
+        """Before anything rewrites this workspace's table, the peer slot's block or the records buffer: the last peer
+        attribution's kernel has run and its records are on the host (a ``Report`` still alive keeps them; an unread one
+        costs this one small copy)."""
+        last, self._peer_attr_last = self._peer_attr_last, None
         if last is not None:
             last.records()
 
@@ -1521,6 +1565,44 @@ class HipBackend:
         that report): ``nvrx_peer_trend`` enqueued on the backend's stream behind that step.  Nothing is waited for."""
         return self._peer_trend_step(ws, state, self.lib.nvrx_peer_trend, (), (self._stream_handle,))
 
+    def _peer_attribute_step(self, ws: Workspace, groups: PeerGroups, peer: TableScores, top_n: int, first_rank: int,
+                             n_ranks: Optional[int], min_ranks: Optional[int], entry, head: tuple, tail: tuple) -> PeerAttribution:
+        """What both routes of a peer attribution share: the records buffer settled, ``entry(*head, d_groups, G, the column
+        records at the head of ``peer``'s block, rank range, min_ranks, top_n, d_out, *tail)`` and the handle noted in the
+        workspace.  ``peer`` is the handle of the peer step just issued on ``ws`` with ``groups``: its block sits in the
+        workspace's peer slot, which nothing settles or rewrites between that step and this one.  The rank range and
+        ``min_ranks`` default to that step's."""
+        if groups.R != ws.R or groups.G != peer.G:
+            raise ValueError(f"peer groups resolved for {groups.R} ranks in {groups.G} groups; the table has {ws.R} ranks, the "
+                             f"peer step had {peer.G} groups")
+        first_rank = peer.first_rank if first_rank is None else first_rank
+        n_ranks = peer.n_ranks if n_ranks is None else n_ranks
+        min_ranks = peer.min_ranks if min_ranks is None else min_ranks
+        ws.peer_attr_settle()  # (the records buffer is about to be rewritten)
+        buf = ws.peer_attr_buffers(n_ranks, top_n)
+        rc = entry(*head, groups.device(self).data_ptr(), groups.G, peer.d_ptr, first_rank, n_ranks, min_ranks, top_n,
+                   buf.data_ptr(), *tail)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._peer_attr_last = PeerAttribution(self, buf, first_rank, n_ranks, top_n)
+        return out
+
+    def peer_attribute(self, ws: Workspace, table: torch.Tensor, groups: PeerGroups, peer: TableScores, top_n: int,
+                       first_rank: Optional[int] = None, n_ranks: Optional[int] = None,
+                       min_ranks: Optional[int] = None) -> PeerAttribution:
+        """Peer attribution of ``table`` ([R, L], the table ``peer_score`` was given) against the column records ``peer_score``
+        just left in ``ws``'s peer slot (``peer``: that step's handle): ``nvrx_peer_attribute`` enqueued on the backend's
+        stream directly behind that step.  Nothing is waited for."""
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        return self._peer_attribute_step(ws, groups, peer, top_n, first_rank, n_ranks, min_ranks, self.lib.nvrx_peer_attribute,
+                                         (table_ptr, ws.R, ws.K, ws.S), (self._stream_handle,))
+
+    def peer_attribution_copy_out(self, attr: PeerAttribution) -> np.ndarray:
+        """The one wait of a peer attribution: a D2H of its records on the backend's stream, behind its kernel."""
+        host = np.empty((attr.n_ranks, 1 + attr.top_n, 8), dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, attr.d_ptr, host.nbytes, self._stream_handle))
+        return host
+
     def _work_step(self, ws: Workspace, entry, head: tuple, tail: tuple, count_tol: float, max_unlike_ppm: int) -> Work:
         """What both routes of the work-group step share: the slot settled, its block, ``entry(*head, count_tol,
         max_unlike_ppm, d_out, *tail)``, and the handle noted in the workspace."""
@@ -2026,6 +2108,15 @@ class HipRings:
         """The trends of ``state``'s ring as ``report_peer_history`` just left it (``nvrx_report_peer_trend``): enqueued on the
         context's stream behind that step, nothing is waited for."""
         return self.backend._peer_trend_step(ws, state, self.lib.nvrx_report_peer_trend, (self.ctx,), ())
+
+    def report_peer_attribute(self, ws: Workspace, groups: PeerGroups, peer: TableScores, top_n: int,
+                              first_rank: Optional[int] = None, n_ranks: Optional[int] = None,
+                              min_ranks: Optional[int] = None) -> PeerAttribution:
+        """Peer attribution of the table of the report ``report_fused`` just issued on ``ws`` against the column records
+        ``report_peer`` just left in ``ws``'s peer slot (``peer``: that step's handle; ``nvrx_report_peer_attribute``):
+        enqueued on the context's stream directly behind that step, nothing is waited for."""
+        return self.backend._peer_attribute_step(ws, groups, peer, top_n, first_rank, n_ranks, min_ranks,
+                                                 self.lib.nvrx_report_peer_attribute, (self.ctx, ws.block.desc_ref), ())
 
     _slack_list = None  # (len(kernel_row_names), rows int32, columns int32, {column: keys}): names are only ever added
 

@@ -41,7 +41,7 @@ class FoldedJob:
                  slack_peer_groups: bool = False, row_peer_groups: bool = False, ramp_detection: bool = False,
                  ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5, robust_peer_groups: bool = False,
                  stall_detection: bool = False, stall_min_ratio: float = 1.5, stall_min_z: float = 6.0,
-                 stall_min_share: float = 0.01, node_peer_groups: bool = False):
+                 stall_min_share: float = 0.01, node_peer_groups: bool = False, peer_attribution: int = 0):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")
@@ -75,6 +75,7 @@ class FoldedJob:
                                         **({"robust_peer_groups": True} if robust_peer_groups else {}),
                                         **({"row_peer_groups": True} if row_peer_groups else {}),
                                         **({"node_peer_groups": True} if node_peer_groups else {}),
+                                        **({"peer_attribution": peer_attribution} if peer_attribution else {}),
                                         **({"ramp_detection": True, "ramp_min_segment": ramp_min_segment,
                                             "ramp_min_strength": ramp_min_strength} if ramp_detection else {}),
                                         **({"stall_detection": True, "stall_min_ratio": stall_min_ratio,

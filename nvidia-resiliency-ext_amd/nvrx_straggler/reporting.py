@@ -646,6 +646,35 @@ def _copy_explanation(d: dict) -> dict:
     return {fam: {r: dict(v, kernels=[dict(k) for k in v["kernels"]]) for r, v in ranks.items()} for fam, ranks in d.items()}
 
 
+class _PeerAttrSource:
+    """What a report keeps of its peer attribution: the backend's handle (``records()`` waits for the kernel and copies the
+    records out on first use), the ranks its rows stand for, the kernel names by id as the report's mapper had them at
+    report time, and the resolved groups."""
+
+    __slots__ = ("handle", "ranks", "names", "groups", "_built")
+
+    def __init__(self, handle, ranks, names, groups):
+        self.handle, self.ranks, self.names, self.groups = handle, tuple(ranks), names, groups
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            rec = np.ascontiguousarray(self.handle.records(), dtype=np.uint32)  # [n_ranks, 1 + top_n, 8]
+            f32, i32 = rec.view(np.float32), rec.view(np.int32)
+            labels, group = self.groups.labels, self.groups.group.tolist()
+            out: Dict[int, Any] = {}
+            for i, rank in enumerate(self.ranks):
+                head = f32[i, 0]
+                kernels = [{"name": self.names[k], "share": float(e[1]), "score": float(e[2]), "lost_us": float(e[3]),
+                            "floor_us": float(e[4]), "floor_rank": int(j[5]), "peers_with_kernel": int(j[6])}
+                           for k, e, j in zip(i32[i, 1:, 0].tolist(), f32[i, 1:], i32[i, 1:]) if k >= 0]
+                out[rank] = {"group": labels[group[rank]], "deficit": float(head[0]), "explained": float(head[1]),
+                             "eligible": int(rec[i, 0, 2]), "total_us": float(head[3]), "kernels": kernels}
+            self._built = out
+            self.handle = None
+        return self._built
+
+
 class _RowFamilySource:
     """What a report keeps of one row family's scores (row_families.py: tail, onset, period, episode, ramp, stall): the backend's handle
     (``records()`` waits for the kernels and copies the planes and scores out on first use), the ranks its rows stand for,
@@ -1501,7 +1530,7 @@ class Report:
         trends = self.__dict__.get("_trends")
         if trends is not None:
             state["_trends"] = trends.build() if isinstance(trends, _TrendSource) else trends
-        for key, source in (("_peer_history", _HistorySource), ("_peer_trends", _TrendSource)):
+        for key, source in (("_peer_history", _HistorySource), ("_peer_trends", _TrendSource), ("_peer_attr", _PeerAttrSource)):
             held = self.__dict__.get(key)
             if held is not None:
                 state[key] = held.build() if isinstance(held, source) else held
@@ -1537,6 +1566,27 @@ class Report:
         if isinstance(attr, _AttrSource):
             attr = self.__dict__["_attr"] = attr.build()
         return _copy_explanation(attr)
+
+    def explain_peer_gpu_scores(self) -> Dict[int, Dict[str, Any]]:
+        """The kernels behind each rank's PEER GPU score (``ReportGenerator(peer_groups=..., peer_attribution=N)``; ``{}`` when
+        the report carries none).  ``explain_gpu_scores()`` measures every kernel against the fastest rank of the whole job,
+        which in a job of stages names what a slow STAGE runs; here the reference of a kernel is the fastest rank of the
+        rank's own group, as in ``peer_scores()``: ``s_k = floor_k / med_k``, and the deficit ``1 - peer score`` splits into
+        the shares ``w_k * (1 - s_k) / W``.
+
+        ``{rank: {"group": label, "deficit": 1 - peer score, "explained": sum of the listed shares, "eligible": kernels the
+        score covers, "total_us": W, "kernels": [{"name", "share", "score": s_k, "lost_us": w_k * (1 - s_k), "floor_us": the
+        group's fastest median, "floor_rank": who holds it, "peers_with_kernel": members of the group that ran it}, ...]}}``
+        -- the N kernels with the largest ``lost_us``, largest first (ties: the kernel that got its id first); ranks as in
+        the score mappings.  Where the peer score is NaN (a rank alone in its group) the deficit is NaN and the list is empty.
+        Plain dicts, lists, floats and strings.  The first call waits for the kernel and copies its records once;
+        ``generate_report`` never does."""
+        held = self.__dict__.get("_peer_attr")
+        if held is None:
+            return {}
+        if isinstance(held, _PeerAttrSource):
+            held = self.__dict__["_peer_attr"] = held.build()
+        return {r: dict(v, kernels=[dict(k) for k in v["kernels"]]) for r, v in held.items()}
 
     def tail_scores(self) -> Dict[str, Any]:
         """Tail scores (``ReportGenerator(tail_quantile=q)``; ``{}`` when the report carries none).  Every score of a report
@@ -2302,7 +2352,8 @@ class ReportGenerator:
                  work_max_unlike: float = 0.1, slack_peer_groups: bool = False, row_peer_groups: bool = False,
                  ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5,
                  robust_peer_groups: bool = False, stall_detection: bool = False, stall_min_ratio: float = 1.5,
-                 stall_min_z: float = 6.0, stall_min_share: float = 0.01, node_peer_groups: bool = False) -> None:
+                 stall_min_z: float = 6.0, stall_min_share: float = 0.01, node_peer_groups: bool = False,
+                 peer_attribution: int = 0) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2755,6 +2806,22 @@ class ReportGenerator:
                 raise RuntimeError(f"peer_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
                                    "has no peer-score trends (backend.peer_trend)")
             self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon = int(m), tau, int(hz)
+        # peer attribution: every report also names the top-N kernels behind each PEER GPU score
+        # (Report.explain_peer_gpu_scores); 0 = off: no buffer, no launch, no backend call.  The step runs behind the peer
+        # step and reads its column records where that step wrote them: no collective.  (peer_groups already makes
+        # steps_behind_report say "table follow-ups", so the lane declines as it does for kernel_attribution.)
+        n = peer_attribution
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 16:
+            raise ValueError(f"peer_attribution must be 0 (off) or 1..16 kernels per peer GPU score, got {peer_attribution!r}")
+        self.peer_attribution = int(n)
+        if self.peer_attribution:
+            if self.peer_groups is None:  # (which in turn needs relative_perf_scores, and said so above)
+                raise ValueError(f"peer_attribution={self.peer_attribution} needs peer_groups (and with it relative_perf_scores): "
+                                 "it explains the peer-group scores")
+            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
+            if be is not None and not hasattr(be, "peer_attribute"):
+                raise RuntimeError(f"peer_attribution={self.peer_attribution}: the active backend "
+                                   f"({getattr(be, 'name', type(be).__name__)}) has no peer attribution (backend.peer_attribute)")
         # slack scores: every ring report also says whom the job waits for in collectives (Report.slack_scores,
         # Report.identify_slack_stragglers) from the statistics of the collective kernels' rows, which every other score drops;
         # off: no buffer, no launch, no collective, no backend call.  The step adds one collective per report, so EVERY rank
@@ -2826,6 +2893,7 @@ class ReportGenerator:
             (self.pace_scores,) + pace, (self.node_scores and not self.node_peer_groups, "node_scores", "report_node"),
             (self.node_peer_groups, "node_peer_groups", "report_node_group"),
             (self.peer_history, "peer_history", "report_peer_history"), (self.peer_trends, "peer_trends", "report_peer_trend"),
+            (self.peer_attribution, f"peer_attribution={self.peer_attribution}", "report_peer_attribute"),
             (self.score_history, "score_history", "report_history"), (self.score_trends, "score_trends", "report_trend")) if on)
         self._last_plan_fused = False
         self._wr_cache: list = [None]  # this generator's remembered (default group, group, (world, rank)): dist_utils.world_and_rank
@@ -3366,6 +3434,13 @@ class ReportGenerator:
                     handle = rings.report_peer_trend(ws, state) if rings is not None else be.peer_trend(ws, state)
                     d["_peer_trends"] = _PeerTrendSource(handle, view.ranks, view.cols, min(state.n_before, self.peer_history),
                                                          self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon, thr)
+            if self.peer_attribution:
+                # behind the peer step (and its history), on the stream it used: it reads that step's column records in place
+                if rings is not None:
+                    handle = rings.report_peer_attribute(ws, groups, peer, self.peer_attribution, lo, n, self.peer_min_ranks)
+                else:
+                    handle = be.peer_attribute(ws, ws.table, groups, peer, self.peer_attribution, lo, n, self.peer_min_ranks)
+                d["_peer_attr"] = _PeerAttrSource(handle, view.ranks, self._attr_names(mapper, ws.K), groups)
         if self.robust_peer_groups:
             # behind the peer step and its history and trend (peer_groups="auto" has its groups by then), ahead of pace
             groups, least = self._peer_for(ws), self._robust_min(ws)

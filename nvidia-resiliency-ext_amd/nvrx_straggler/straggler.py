@@ -434,6 +434,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         row_peer_groups: Optional[bool] = None,
         robust_peer_groups: Optional[bool] = None,
         node_peer_groups: Optional[bool] = None,
+        peer_attribution: Optional[int] = None,
         node_scores: Optional[bool] = None,
         node_groups=None,
         node_min_members: int = 2,
@@ -633,6 +634,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 is allowed); a peer group needs ``max(peer_min_ranks, min(node_min_nodes, its cells))`` nodes with a kernel
                 for their median to be a reference, so a group that sits on one node leaves that node unrated.  Default:
                 ``NVRX_NODE_PEER_GROUPS`` ("1"; "0" or unset: off).  Same value on every rank (no collective depends on it).
+            peer_attribution: 0 = off; N in 1..16: every report also carries, per rank, the N kernels with the largest share of
+                the PEER GPU score's deficit -- each kernel against the fastest rank of the rank's own group, with that rank
+                and the number of peers that ran the kernel (``Report.explain_peer_gpu_scores()``).  In a job of stages
+                ``kernel_attribution`` names what the slow stage runs; this names what is slow on one rank and not on its
+                peers.  Needs ``peer_groups`` (``"auto"`` is allowed) and relative scores.  Default:
+                ``NVRX_PEER_ATTRIBUTION``, else 0.  Same value on every rank (no collective depends on it).
             slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
                 peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
                 expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
@@ -849,6 +856,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
             node_peer_groups = from_env == "1"
         if node_peer_groups:
             node_options["node_peer_groups"] = True  # (the generator says which of node_scores and peer_groups it misses)
+        if peer_attribution is None:
+            try:
+                peer_attribution = int(os.environ.get("NVRX_PEER_ATTRIBUTION", "0") or 0)
+            except ValueError:
+                raise ValueError("NVRX_PEER_ATTRIBUTION must be an integer: 0 (off) or 1..16") from None
+        if peer_attribution:
+            node_options["peer_attribution"] = peer_attribution  # (the generator validates it and says what it misses)
         ramp_options = {}  # (off: the generator is built exactly as before)
         if ramp_detection is None:
             ramp_detection = os.environ.get("NVRX_RAMP_DETECTION", "0") not in ("", "0")
