@@ -15,7 +15,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _native, dist_utils
+from . import _native, dist_utils, report_options
 from .backend import get_backend
 from .reporting import ReportGenerator
 
@@ -53,46 +53,9 @@ class FoldedJob:
         self.kernel_names = list(kernel_names)  # per-kernel rows next to the sections (``load_kernels``); none by default
         self.rings = self.backend.make_rings(self.local_ranks, len(self.section_names) + len(self.kernel_names), ring_cap)
         self.ring_cap = ring_cap
+        # (report_options.GROUPS: the options that are off are left out, as Detector.initialize leaves them out)
         self.reporter = ReportGenerator(list(scores_to_compute), gather_on_rank0=gather_on_rank0, pg=pg, node_name=node_name,
-                                        kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
-                                        robust_scores=robust_scores, asynchronous=asynchronous,
-                                        onset_detection=onset_detection, onset_min_segment=onset_min_segment,
-                                        onset_min_strength=onset_min_strength, period_detection=period_detection,
-                                        period_max=period_max, period_min_strength=period_min_strength,
-                                        episode_detection=episode_detection, episode_min_length=episode_min_length,
-                                        episode_min_strength=episode_min_strength, score_history=score_history,
-                                        persistence_min_reports=persistence_min_reports,
-                                        persistence_thresholds=persistence_thresholds, score_trends=score_trends,
-                                        trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
-                                        trend_horizon=trend_horizon, collective_slack=collective_slack,
-                                        slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                        slack_max_ratio=slack_max_ratio, peer_groups=peer_groups,
-                                        peer_min_ranks=peer_min_ranks, pace_scores=pace_scores,
-                                        pace_min_ranks=pace_min_ranks, pace_min_columns=pace_min_columns,
-                                        pace_min_effect=pace_min_effect, pace_min_breadth=pace_min_breadth,
-                                        **({"pace_peer_groups": True} if pace_peer_groups else {}),
-                                        **({"slack_peer_groups": True} if slack_peer_groups else {}),
-                                        **({"robust_peer_groups": True} if robust_peer_groups else {}),
-                                        **({"row_peer_groups": True} if row_peer_groups else {}),
-                                        **({"node_peer_groups": True} if node_peer_groups else {}),
-                                        **({"peer_attribution": peer_attribution} if peer_attribution else {}),
-                                        **({"ramp_detection": True, "ramp_min_segment": ramp_min_segment,
-                                            "ramp_min_strength": ramp_min_strength} if ramp_detection else {}),
-                                        **({"stall_detection": True, "stall_min_ratio": stall_min_ratio,
-                                            "stall_min_z": stall_min_z, "stall_min_share": stall_min_share}
-                                           if stall_detection else {}),
-                                        **({"peer_history": peer_history,
-                                            "peer_persistence_min_reports": peer_persistence_min_reports,
-                                            "peer_persistence_thresholds": peer_persistence_thresholds,
-                                            "peer_trends": peer_trends} if peer_history or peer_trends else {}),
-                                        **({"node_scores": True, "node_groups": node_groups,
-                                            "node_min_members": node_min_members, "node_min_nodes": node_min_nodes,
-                                            "node_min_columns": node_min_columns, "node_min_effect": node_min_effect,
-                                            "node_min_breadth": node_min_breadth, "node_min_agree": node_min_agree}
-                                           if node_scores else {}),
-                                        **({"work_groups": bool(work_groups), "work_count_tol": work_count_tol,
-                                            "work_max_unlike": work_max_unlike}
-                                           if work_groups or (isinstance(peer_groups, str) and peer_groups == "auto") else {}))
+                                        **report_options.forwarded(locals()))
         self.rows = {name: self.rings.row_for(_native.KIND_SECTION, name) for name in self.section_names}
         # (the same object every report so the reporter's cached plan stays valid)
         self._no_kernel_rows = {name: self.rings.row_for(_native.KIND_KERNEL, name) for name in self.kernel_names}

@@ -34,6 +34,7 @@ import numpy as np
 
 from . import backend as _backend_mod
 from . import dist_utils, row_families
+from . import report_options as opts
 from .name_mapper import NameMapper, name_digest
 from .statistics import NUM_COLUMN, STAT_KEYS, Statistic
 
@@ -2404,60 +2405,36 @@ class ReportGenerator:
             raise ValueError(f"kernel_attribution must be 0 (off) or 1..16 kernels per GPU score, got {kernel_attribution!r}")
         self.kernel_attribution = n
         if n:
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "attribute"):
-                raise RuntimeError(f"kernel_attribution={n}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no kernel attribution (backend.attribute)")
+            opts.needs_backend(f"kernel_attribution={n}", "kernel attribution", "attribute")
         self._attr_names_cache = (None, 0, ())  # (mapper, kernel ids covered, names by id)
         # tail scores: every ring report also carries the q-quantile of every row and relative scores built from them
         # (Report.tail_scores); 0 = off: no buffer, no launch, no collective, no backend call.  The step adds one collective
         # per report, so EVERY rank must pass the same value.
         self.tail_q_ppm = _backend_mod._native.tail_q_ppm(tail_quantile)
         if self.tail_q_ppm:
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"tail_quantile={tail_quantile!r} needs relative_perf_scores among scores_to_compute "
-                                 f"(got {scores_to_compute!r}): tail scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "tail_score"):
-                raise RuntimeError(f"tail_quantile={tail_quantile!r}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no tail scores (backend.tail_score)")
+            opts.needs_relative(f"tail_quantile={tail_quantile!r}", scores_to_compute, "tail scores are relative scores")
+            opts.needs_backend(f"tail_quantile={tail_quantile!r}", "tail scores", "tail_score")
         # robust scores: every report also rates each rank against the job's median and spread (Report.robust_scores); off: no
         # buffer, no launch, no backend call.  They read the exchanged table only: no collective, so a mismatch between ranks
         # cannot hang anything -- but every rank should pass the same value.
         self.robust_scores = bool(robust_scores)
         if self.robust_scores:
-            if isinstance(robust_min_ranks, bool) or not isinstance(robust_min_ranks, (int, np.integer)) or robust_min_ranks < 1:
-                raise ValueError(f"robust_min_ranks must be an integer >= 1, got {robust_min_ranks!r}")
-            try:
-                floor = float(robust_floor)
-            except (TypeError, ValueError):
-                raise ValueError(f"robust_floor must be a number within [0, 1], got {robust_floor!r}") from None
-            if not 0.0 <= floor <= 1.0:  # (NaN fails both comparisons)
-                raise ValueError(f"robust_floor must be within [0, 1], got {robust_floor!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"robust_scores needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "robust scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "robust_score"):
-                raise RuntimeError(f"robust_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no robust scores (backend.robust_score)")
-            self.robust_min_ranks, self.robust_floor = int(robust_min_ranks), floor
+            min_ranks = opts.integer("robust_min_ranks", robust_min_ranks, "an integer >= 1", 1)
+            floor = opts.share("robust_floor", robust_floor)
+            opts.needs_relative("robust_scores", scores_to_compute, "robust scores are relative scores")
+            opts.needs_backend("robust_scores", "robust scores", "robust_score")
+            self.robust_min_ranks, self.robust_floor = min_ranks, floor
         # peer-group scores: every report also rates each rank against the fastest rank of its own group -- the ranks doing the
         # same work (Report.peer_scores); None = off: no buffer, no launch, no backend call.  They read the exchanged table
         # only: no collective, so a mismatch between ranks cannot hang anything -- but every rank should pass the same value.
         self.peer_groups = _peer_spec(peer_groups)  # None, a backend._PeerRule or a tuple of labels, one per logical rank
         self._peer_resolved = None  # backend.PeerGroups for the R of the tables seen so far
-        if self.peer_groups is not None:
-            if isinstance(peer_min_ranks, bool) or not isinstance(peer_min_ranks, (int, np.integer)) or peer_min_ranks < 1:
-                raise ValueError(f"peer_min_ranks must be an integer >= 1, got {peer_min_ranks!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"peer_groups needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "peer-group scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "peer_score"):
-                raise RuntimeError(f"peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no peer-group scores (backend.peer_score)")
-            self.peer_min_ranks = int(peer_min_ranks)
+        peers_on = self.peer_groups is not None
+        if peers_on:
+            min_ranks = opts.integer("peer_min_ranks", peer_min_ranks, "an integer >= 1", 1)
+            opts.needs_relative("peer_groups", scores_to_compute, "peer-group scores are relative scores")
+            opts.needs_backend("peer_groups", "peer-group scores", "peer_score")
+            self.peer_min_ranks = min_ranks
         # work groups: every report also says which ranks do the same work, inferred from the table (Report.work_groups), and
         # peer_groups="auto" takes its groups from there; off: no buffer, no launch, no backend call.  The step reads the
         # exchanged table only: no collective, and every rank infers the same groups from the same table.  0.25 and 0.1 are
@@ -2466,23 +2443,13 @@ class ReportGenerator:
         self._work_handle = None  # this report's step (peer_groups="auto" waits for it: _peer_for)
         self._peer_auto_roots = None  # the root array _peer_resolved was built from
         if self.work_groups:
-            try:
-                tol, share = float(work_count_tol), float(work_max_unlike)
-            except (TypeError, ValueError):
-                raise ValueError(f"work_count_tol and work_max_unlike must be numbers, got {work_count_tol!r} and "
-                                 f"{work_max_unlike!r}") from None
-            if isinstance(work_count_tol, bool) or not 0.0 <= tol <= 16.0:  # (NaN fails both comparisons)
-                raise ValueError(f"work_count_tol must be within [0, 16], got {work_count_tol!r}")
-            if isinstance(work_max_unlike, bool) or not 0.0 <= share <= 1.0:
-                raise ValueError(f"work_max_unlike must be within [0, 1], got {work_max_unlike!r}")
+            tol, share = opts.floats((work_count_tol, work_max_unlike), "work_count_tol and work_max_unlike must be numbers, got "
+                                     f"{work_count_tol!r} and {work_max_unlike!r}")
+            opts.within("work_count_tol", work_count_tol, tol, "within [0, 16]", 0.0, 16.0, no_bool=True)
+            opts.within("work_max_unlike", work_max_unlike, share, "within [0, 1]", 0.0, 1.0, no_bool=True)
             option = "peer_groups='auto'" if self.peer_groups == "auto" else "work_groups"
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"{option} needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "work groups compare ranks")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "work_groups"):
-                raise RuntimeError(f"{option}: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no work groups (backend.work_groups)")
+            opts.needs_relative(option, scores_to_compute, "work groups compare ranks")
+            opts.needs_backend(option, "work groups", "work_groups")
             self.work_count_tol, self.work_max_unlike = tol, share
             self.work_max_unlike_ppm = int(round(share * 1e6))
         # pace scores: every report also says whether a rank is a little slower in nearly all of its kernels
@@ -2490,54 +2457,28 @@ class ReportGenerator:
         # so a mismatch between ranks cannot hang anything -- but every rank should pass the same value.
         self.pace_scores = bool(pace_scores)
         if self.pace_scores:
-            if isinstance(pace_min_ranks, bool) or not isinstance(pace_min_ranks, (int, np.integer)) or pace_min_ranks < 1:
-                raise ValueError(f"pace_min_ranks must be an integer >= 1, got {pace_min_ranks!r}")
-            if isinstance(pace_min_columns, bool) or not isinstance(pace_min_columns, (int, np.integer)) or pace_min_columns < 1:
-                raise ValueError(f"pace_min_columns must be an integer >= 1, got {pace_min_columns!r}")
-            try:
-                effect, breadth = float(pace_min_effect), float(pace_min_breadth)
-            except (TypeError, ValueError):
-                raise ValueError(f"pace_min_effect and pace_min_breadth must be numbers, got {pace_min_effect!r} and "
-                                 f"{pace_min_breadth!r}") from None
-            if not 0.0 <= effect < 1.0:
-                raise ValueError(f"pace_min_effect must be within [0, 1), got {pace_min_effect!r}")
-            if not 0.0 < breadth <= 1.0:
-                raise ValueError(f"pace_min_breadth must be within (0, 1], got {pace_min_breadth!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"pace_scores needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "pace scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "pace_score"):
-                raise RuntimeError(f"pace_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no pace scores (backend.pace_score)")
-            self.pace_min_ranks, self.pace_min_columns = int(pace_min_ranks), int(pace_min_columns)
+            min_ranks = opts.integer("pace_min_ranks", pace_min_ranks, "an integer >= 1", 1)
+            min_columns = opts.integer("pace_min_columns", pace_min_columns, "an integer >= 1", 1)
+            effect, breadth = opts.floats((pace_min_effect, pace_min_breadth), "pace_min_effect and pace_min_breadth must be "
+                                          f"numbers, got {pace_min_effect!r} and {pace_min_breadth!r}")
+            opts.within("pace_min_effect", pace_min_effect, effect, "within [0, 1)", 0.0, 1.0, hi_open=True)
+            opts.within("pace_min_breadth", pace_min_breadth, breadth, "within (0, 1]", 0.0, 1.0, lo_open=True)
+            opts.needs_relative("pace_scores", scores_to_compute, "pace scores are relative scores")
+            opts.needs_backend("pace_scores", "pace scores", "pace_score")
+            self.pace_min_ranks, self.pace_min_columns = min_ranks, min_columns
             self.pace_min_effect, self.pace_min_breadth = effect, breadth
         # pace scores per peer group: the pace step rates each rank against the lower median of its OWN group
         # (nvrx_pace_group_score); off: the pace step is the job-wide one, whatever peer_groups says
         self.pace_peer_groups = bool(pace_peer_groups)
         if self.pace_peer_groups:
-            if not self.pace_scores or self.peer_groups is None:
-                missing = [name for name, on in (("pace_scores", self.pace_scores), ("peer_groups", self.peer_groups is not None))
-                           if not on]
-                raise ValueError(f"pace_peer_groups needs pace_scores and peer_groups; {' and '.join(missing)} "
-                                 f"{'is' if len(missing) == 1 else 'are'} not set")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "pace_group_score"):
-                raise RuntimeError(f"pace_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no pace scores per peer group (backend.pace_group_score)")
+            opts.needs_with_peer_groups("pace_peer_groups", "pace_scores", self.pace_scores, peers_on)
+            opts.needs_backend("pace_peer_groups", "pace scores per peer group", "pace_group_score")
         # robust scores per peer group: the robust step rates each rank against the lower median and MAD of its OWN group
         # (nvrx_robust_group_score), behind the peer step; off: the robust step is the job-wide one, whatever peer_groups says
         self.robust_peer_groups = bool(robust_peer_groups)
         if self.robust_peer_groups:
-            if not self.robust_scores or self.peer_groups is None:
-                missing = [name for name, on in (("robust_scores", self.robust_scores), ("peer_groups", self.peer_groups is not None))
-                           if not on]
-                raise ValueError(f"robust_peer_groups needs robust_scores and peer_groups; {' and '.join(missing)} "
-                                 f"{'is' if len(missing) == 1 else 'are'} not set")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "robust_group_score"):
-                raise RuntimeError(f"robust_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no robust scores per peer group (backend.robust_group_score)")
+            opts.needs_with_peer_groups("robust_peer_groups", "robust_scores", self.robust_scores, peers_on)
+            opts.needs_backend("robust_peer_groups", "robust scores per peer group", "robust_group_score")
         # node scores: every report also says whether a NODE is a little slower in nearly all of its kernels (Report.node_scores);
         # off: nothing is allocated, resolved, launched or called.  They read the exchanged table and rank_to_node only: no
         # collective, so ranks need not agree on the option.
@@ -2546,65 +2487,36 @@ class ReportGenerator:
         self._node_resolved = None  # backend.PeerGroups of the nodes for the R (and rank_to_node) of the tables seen so far
         self._node_source = None    # the rank_to_node object _node_resolved was built from (node_groups=None)
         if self.node_scores:
-            for name, val in (("node_min_members", node_min_members), ("node_min_nodes", node_min_nodes),
-                              ("node_min_columns", node_min_columns)):
-                if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < 1:
-                    raise ValueError(f"{name} must be an integer >= 1, got {val!r}")
-            try:
-                effect, breadth, agree = float(node_min_effect), float(node_min_breadth), float(node_min_agree)
-            except (TypeError, ValueError):
-                raise ValueError(f"node_min_effect, node_min_breadth and node_min_agree must be numbers, got {node_min_effect!r}, "
-                                 f"{node_min_breadth!r} and {node_min_agree!r}") from None
-            if not 0.0 <= effect < 1.0:
-                raise ValueError(f"node_min_effect must be within [0, 1), got {node_min_effect!r}")
-            if not 0.0 < breadth <= 1.0:
-                raise ValueError(f"node_min_breadth must be within (0, 1], got {node_min_breadth!r}")
-            if not 0.0 < agree <= 1.0:
-                raise ValueError(f"node_min_agree must be within (0, 1], got {node_min_agree!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"node_scores needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "node scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "node_score"):
-                raise RuntimeError(f"node_scores: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no node scores (backend.node_score)")
+            min_members = opts.integer("node_min_members", node_min_members, "an integer >= 1", 1)
+            min_nodes = opts.integer("node_min_nodes", node_min_nodes, "an integer >= 1", 1)
+            min_columns = opts.integer("node_min_columns", node_min_columns, "an integer >= 1", 1)
+            effect, breadth, agree = opts.floats(
+                (node_min_effect, node_min_breadth, node_min_agree), "node_min_effect, node_min_breadth and node_min_agree must "
+                f"be numbers, got {node_min_effect!r}, {node_min_breadth!r} and {node_min_agree!r}")
+            opts.within("node_min_effect", node_min_effect, effect, "within [0, 1)", 0.0, 1.0, hi_open=True)
+            opts.within("node_min_breadth", node_min_breadth, breadth, "within (0, 1]", 0.0, 1.0, lo_open=True)
+            opts.within("node_min_agree", node_min_agree, agree, "within (0, 1]", 0.0, 1.0, lo_open=True)
+            opts.needs_relative("node_scores", scores_to_compute, "node scores are relative scores")
+            opts.needs_backend("node_scores", "node scores", "node_score")
             self.node_groups = _peer_spec(node_groups, "node_groups")  # None: the nodes are rank_to_node's
-            self.node_min_members, self.node_min_nodes = int(node_min_members), int(node_min_nodes)
-            self.node_min_columns = int(node_min_columns)
+            self.node_min_members, self.node_min_nodes, self.node_min_columns = min_members, min_nodes, min_columns
             self.node_min_effect, self.node_min_breadth, self.node_min_agree = effect, breadth, agree
         # node scores per peer group: the node step compares a node with the nodes doing the SAME work (nvrx_node_group_score),
         # behind the peer step; off: the node step is the job-wide one, whatever peer_groups says
         self.node_peer_groups = bool(node_peer_groups)
         self._cells_resolved = None  # backend.NodeCells of the (nodes, peer groups) pair the last report ran on
         if self.node_peer_groups:
-            if not self.node_scores or self.peer_groups is None:
-                missing = [name for name, on in (("node_scores", self.node_scores), ("peer_groups", self.peer_groups is not None))
-                           if not on]
-                raise ValueError(f"node_peer_groups needs node_scores and peer_groups; {' and '.join(missing)} "
-                                 f"{'is' if len(missing) == 1 else 'are'} not set")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "node_group_score"):
-                raise RuntimeError(f"node_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no node scores per peer group (backend.node_group_score)")
+            opts.needs_with_peer_groups("node_peer_groups", "node_scores", self.node_scores, peers_on)
+            opts.needs_backend("node_peer_groups", "node scores per peer group", "node_group_score")
         # onset scores: every ring report also carries, per row, the single step that explains most of the window's variance and
         # relative scores built from the shifts (Report.onset_scores); off: no buffer, no launch, no collective, no backend
         # call.  The step adds one collective per report, so EVERY rank must pass the same value.
         self.onset_seg_ppm = 0  # (0 = off)
         if onset_detection:
             seg_ppm = _backend_mod._native.onset_seg_ppm(onset_min_segment)
-            try:
-                strength = float(onset_min_strength)
-            except (TypeError, ValueError):
-                raise ValueError(f"onset_min_strength must be a number within [0, 1], got {onset_min_strength!r}") from None
-            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
-                raise ValueError(f"onset_min_strength must be within [0, 1], got {onset_min_strength!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"onset_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "onset scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "onset_score"):
-                raise RuntimeError(f"onset_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no onset scores (backend.onset_score)")
+            strength = opts.share("onset_min_strength", onset_min_strength)
+            opts.needs_relative("onset_detection", scores_to_compute, "onset scores are relative scores")
+            opts.needs_backend("onset_detection", "onset scores", "onset_score")
             self.onset_seg_ppm, self.onset_min_strength = seg_ppm, strength
         # period scores: every ring report also carries, per row, the period on which the row stalls, if any, and relative
         # scores built from the excesses (Report.period_scores); off: no buffer, no launch, no collective, no backend call.
@@ -2612,19 +2524,9 @@ class ReportGenerator:
         self.period_max = 0  # (0 = off)
         if period_detection:
             pmax = _backend_mod._native.period_max(period_max)
-            try:
-                strength = float(period_min_strength)
-            except (TypeError, ValueError):
-                raise ValueError(f"period_min_strength must be a number within [0, 1], got {period_min_strength!r}") from None
-            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
-                raise ValueError(f"period_min_strength must be within [0, 1], got {period_min_strength!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"period_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "period scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "period_score"):
-                raise RuntimeError(f"period_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no period scores (backend.period_score)")
+            strength = opts.share("period_min_strength", period_min_strength)
+            opts.needs_relative("period_detection", scores_to_compute, "period scores are relative scores")
+            opts.needs_backend("period_detection", "period scores", "period_score")
             self.period_max, self.period_min_strength = pmax, strength
         # episode scores: every ring report also carries, per row, the one stretch of the window that spent most time above
         # the row's mean, if any, and relative scores built from the excesses (Report.episode_scores); off: no buffer, no
@@ -2633,19 +2535,9 @@ class ReportGenerator:
         self.episode_len_ppm = 0  # (0 = off)
         if episode_detection:
             len_ppm = _backend_mod._native.episode_len_ppm(episode_min_length)
-            try:
-                strength = float(episode_min_strength)
-            except (TypeError, ValueError):
-                raise ValueError(f"episode_min_strength must be a number within [0, 1], got {episode_min_strength!r}") from None
-            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
-                raise ValueError(f"episode_min_strength must be within [0, 1], got {episode_min_strength!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"episode_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "episode scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "episode_score"):
-                raise RuntimeError(f"episode_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no episode scores (backend.episode_score)")
+            strength = opts.share("episode_min_strength", episode_min_strength)
+            opts.needs_relative("episode_detection", scores_to_compute, "episode scores are relative scores")
+            opts.needs_backend("episode_detection", "episode scores", "episode_score")
             self.episode_len_ppm, self.episode_min_strength = len_ppm, strength
         # ramp scores: every ring report also carries, per row, the hinge (flat, then linear to the window's end) that explains
         # most of the window's variance and relative scores built from the rises (Report.ramp_scores); off: no buffer, no
@@ -2654,19 +2546,9 @@ class ReportGenerator:
         self.ramp_seg_ppm = 0  # (0 = off)
         if ramp_detection:
             seg_ppm = _backend_mod._native.ramp_seg_ppm(ramp_min_segment)
-            try:
-                strength = float(ramp_min_strength)
-            except (TypeError, ValueError):
-                raise ValueError(f"ramp_min_strength must be a number within [0, 1], got {ramp_min_strength!r}") from None
-            if not 0.0 <= strength <= 1.0:  # (NaN fails both comparisons)
-                raise ValueError(f"ramp_min_strength must be within [0, 1], got {ramp_min_strength!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"ramp_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "ramp scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "ramp_score"):
-                raise RuntimeError(f"ramp_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no ramp scores (backend.ramp_score)")
+            strength = opts.share("ramp_min_strength", ramp_min_strength)
+            opts.needs_relative("ramp_detection", scores_to_compute, "ramp scores are relative scores")
+            opts.needs_backend("ramp_detection", "ramp scores", "ramp_score")
             self.ramp_seg_ppm, self.ramp_min_strength = seg_ppm, strength
         # stall scores: every ring report also carries, per row, the count, the timing and the cost of the samples far above the
         # row's pace and relative scores built from their excess (Report.stall_scores); off: no buffer, no launch, no
@@ -2675,22 +2557,12 @@ class ReportGenerator:
         self.stall_ratio_ppm = 0  # (0 = off)
         if stall_detection:
             ratio_ppm = _backend_mod._native.stall_ratio_ppm(stall_min_ratio)
-            try:
-                min_z, min_share = float(stall_min_z), float(stall_min_share)
-            except (TypeError, ValueError):
-                raise ValueError(f"stall_min_z must be a finite number >= 0 and stall_min_share a number within [0, 1), got "
-                                 f"{stall_min_z!r} and {stall_min_share!r}") from None
-            if not 0.0 <= min_z < float("inf"):  # (NaN fails both comparisons)
-                raise ValueError(f"stall_min_z must be a finite number >= 0, got {stall_min_z!r}")
-            if not 0.0 <= min_share < 1.0:
-                raise ValueError(f"stall_min_share must be within [0, 1), got {stall_min_share!r}")
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"stall_detection needs relative_perf_scores among scores_to_compute (got {scores_to_compute!r}): "
-                                 "stall scores are relative scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "stall_score"):
-                raise RuntimeError(f"stall_detection: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no stall scores (backend.stall_score)")
+            min_z, min_share = opts.floats((stall_min_z, stall_min_share), "stall_min_z must be a finite number >= 0 and "
+                                           f"stall_min_share a number within [0, 1), got {stall_min_z!r} and {stall_min_share!r}")
+            opts.within("stall_min_z", stall_min_z, min_z, "a finite number >= 0", 0.0, math.inf, hi_open=True)
+            opts.within("stall_min_share", stall_min_share, min_share, "within [0, 1)", 0.0, 1.0, hi_open=True)
+            opts.needs_relative("stall_detection", scores_to_compute, "stall scores are relative scores")
+            opts.needs_backend("stall_detection", "stall scores", "stall_score")
             self.stall_ratio_ppm, self.stall_min_z, self.stall_min_share = ratio_ppm, min_z, min_share
         # score history: every report also appends its scores to a device ring of the last H reports and says, per rank and
         # score, for how many reports in a row the score has been below its threshold (Report.score_history,
@@ -2698,30 +2570,13 @@ class ReportGenerator:
         # kernel wrote: no collective, so a mismatch between ranks cannot hang anything.  The history belongs to this generator
         # and dies with it.
         self._history = None  # (backend.ScoreHistory while the option is on)
-        depth = score_history
-        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not (
-                depth == 0 or 2 <= depth <= _backend_mod._native.HISTORY_MAX_DEPTH):
-            raise ValueError(f"score_history must be 0 (off) or an integer within [2, {_backend_mod._native.HISTORY_MAX_DEPTH}] "
-                             f"reports, got {score_history!r}")
-        self.score_history = int(depth)
+        self.score_history = opts.history_depth("score_history", score_history)
         if self.score_history:
-            m = persistence_min_reports
-            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= self.score_history:
-                raise ValueError(f"persistence_min_reports must be an integer within [1, score_history={self.score_history}], "
-                                 f"got {persistence_min_reports!r}")
-            try:
-                thr = self.thresholds if persistence_thresholds is None else tuple(float(t) for t in persistence_thresholds)
-            except (TypeError, ValueError):
-                raise ValueError(f"persistence_thresholds must be four finite numbers (gpu_rel, section_rel, gpu_indiv, "
-                                 f"section_indiv), got {persistence_thresholds!r}") from None
-            if len(thr) != 4 or not all(np.isfinite(thr)):
-                raise ValueError(f"persistence_thresholds must be four finite numbers (gpu_rel, section_rel, gpu_indiv, "
-                                 f"section_indiv), got {persistence_thresholds!r}")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "score_history"):
-                raise RuntimeError(f"score_history: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no score history (backend.score_history)")
-            self.persistence_min_reports, self.persistence_thresholds = int(m), thr
+            m, thr = opts.persistence_rule(
+                "score_history", self.score_history, "persistence_min_reports", persistence_min_reports, "persistence_thresholds",
+                persistence_thresholds, self.thresholds, 4, "four finite numbers (gpu_rel, section_rel, gpu_indiv, section_indiv)")
+            opts.needs_backend("score_history", "score history", "score_history")
+            self.persistence_min_reports, self.persistence_thresholds = m, thr
             self._history = _backend_mod.ScoreHistory(self.score_history)
         # score trends: behind the history step, every report also estimates per rank and score whether the ring's scores are
         # falling (Report.score_trends, Report.identify_declining_stragglers); off: no buffer, no launch, no backend call.  It
@@ -2729,138 +2584,63 @@ class ReportGenerator:
         # measurements.
         self.score_trends = bool(score_trends)
         if self.score_trends:
-            if self.score_history < 4:
-                raise ValueError(f"score_trends needs a score history of at least 4 reports (score_history within [4, "
-                                 f"{_backend_mod._native.HISTORY_MAX_DEPTH}]), got score_history={self.score_history!r}")
-            m = trend_min_reports
-            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 4 <= m <= self.score_history:
-                raise ValueError(f"trend_min_reports must be an integer within [4, score_history={self.score_history}], "
-                                 f"got {trend_min_reports!r}")
-            try:
-                tau = float(trend_min_tau)
-            except (TypeError, ValueError):
-                tau = float("nan")
-            if isinstance(trend_min_tau, bool) or not 0.0 < tau <= 1.0:
-                raise ValueError(f"trend_min_tau must be a number within (0, 1], got {trend_min_tau!r}")
-            hz = self.score_history if trend_horizon is None else trend_horizon
-            if isinstance(hz, bool) or not isinstance(hz, (int, np.integer)) or hz < 0:
-                raise ValueError(f"trend_horizon must be None (the history's depth) or an integer >= 0 reports, "
-                                 f"got {trend_horizon!r}")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "score_trend"):
-                raise RuntimeError(f"score_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no score trends (backend.score_trend)")
-            self.trend_min_reports, self.trend_min_tau, self.trend_horizon = int(m), tau, int(hz)
+            rule = opts.trend_rule("score_trends", "score_history", self.score_history, trend_min_reports, trend_min_tau,
+                                   trend_horizon)
+            opts.needs_backend("score_trends", "score trends", "score_trend")
+            self.trend_min_reports, self.trend_min_tau, self.trend_horizon = rule
         # peer-score history and trends: the two options above on the PEER scores (Report.peer_history,
         # Report.identify_persistent_peer_stragglers, Report.peer_trends, Report.identify_declining_peer_stragglers); 0 = off:
         # no buffer, no launch, no backend call.  The step runs directly behind the peer step and reads its rank part where
         # that step wrote it: no collective.  The history is per rank: it does not notice that a rank's peers changed.
         self._peer_history = None  # (backend.PeerHistory while the option is on)
-        depth = peer_history
-        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not (
-                depth == 0 or 2 <= depth <= _backend_mod._native.HISTORY_MAX_DEPTH):
-            raise ValueError(f"peer_history must be 0 (off) or an integer within [2, {_backend_mod._native.HISTORY_MAX_DEPTH}] "
-                             f"reports, got {peer_history!r}")
-        self.peer_history = int(depth)
+        self.peer_history = opts.history_depth("peer_history", peer_history)
         if self.peer_history:
-            if self.peer_groups is None:
+            if not peers_on:
                 raise ValueError("peer_history needs peer_groups: it is the history of the peer-group scores")
-            m = peer_persistence_min_reports
-            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= self.peer_history:
-                raise ValueError(f"peer_persistence_min_reports must be an integer within [1, peer_history={self.peer_history}], "
-                                 f"got {peer_persistence_min_reports!r}")
-            try:
-                thr = (0.75, 0.75) if peer_persistence_thresholds is None else tuple(float(t) for t in peer_persistence_thresholds)
-            except (TypeError, ValueError):
-                thr = ()
-            if len(thr) != 2 or not all(np.isfinite(thr)):
-                raise ValueError(f"peer_persistence_thresholds must be two finite numbers (gpu, section), "
-                                 f"got {peer_persistence_thresholds!r}")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "peer_history"):
-                raise RuntimeError(f"peer_history: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no peer-score history (backend.peer_history)")
-            self.peer_persistence_min_reports, self.peer_persistence_thresholds = int(m), thr
+            m, thr = opts.persistence_rule(
+                "peer_history", self.peer_history, "peer_persistence_min_reports", peer_persistence_min_reports,
+                "peer_persistence_thresholds", peer_persistence_thresholds, (0.75, 0.75), 2, "two finite numbers (gpu, section)")
+            opts.needs_backend("peer_history", "peer-score history", "peer_history")
+            self.peer_persistence_min_reports, self.peer_persistence_thresholds = m, thr
             self._peer_history = _backend_mod.PeerHistory(self.peer_history)
         self.peer_trends = bool(peer_trends)
         if self.peer_trends:
-            if self.peer_history < 4:
-                raise ValueError(f"peer_trends needs a peer history of at least 4 reports (peer_history within [4, "
-                                 f"{_backend_mod._native.HISTORY_MAX_DEPTH}]), got peer_history={self.peer_history!r}")
-            m = trend_min_reports
-            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 4 <= m <= self.peer_history:
-                raise ValueError(f"trend_min_reports must be an integer within [4, peer_history={self.peer_history}], "
-                                 f"got {trend_min_reports!r}")
-            try:
-                tau = float(trend_min_tau)
-            except (TypeError, ValueError):
-                tau = float("nan")
-            if isinstance(trend_min_tau, bool) or not 0.0 < tau <= 1.0:
-                raise ValueError(f"trend_min_tau must be a number within (0, 1], got {trend_min_tau!r}")
-            hz = self.peer_history if trend_horizon is None else trend_horizon
-            if isinstance(hz, bool) or not isinstance(hz, (int, np.integer)) or hz < 0:
-                raise ValueError(f"trend_horizon must be None (the history's depth) or an integer >= 0 reports, "
-                                 f"got {trend_horizon!r}")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "peer_trend"):
-                raise RuntimeError(f"peer_trends: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no peer-score trends (backend.peer_trend)")
-            self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon = int(m), tau, int(hz)
+            rule = opts.trend_rule("peer_trends", "peer_history", self.peer_history, trend_min_reports, trend_min_tau, trend_horizon)
+            opts.needs_backend("peer_trends", "peer-score trends", "peer_trend")
+            # (with score_trends on as well, trend_min_reports and trend_min_tau are what this block leaves)
+            self.trend_min_reports, self.trend_min_tau, self.peer_trend_horizon = rule
         # peer attribution: every report also names the top-N kernels behind each PEER GPU score
         # (Report.explain_peer_gpu_scores); 0 = off: no buffer, no launch, no backend call.  The step runs behind the peer
         # step and reads its column records where that step wrote them: no collective.  (peer_groups already makes
         # steps_behind_report say "table follow-ups", so the lane declines as it does for kernel_attribution.)
-        n = peer_attribution
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 16:
-            raise ValueError(f"peer_attribution must be 0 (off) or 1..16 kernels per peer GPU score, got {peer_attribution!r}")
-        self.peer_attribution = int(n)
+        self.peer_attribution = opts.integer("peer_attribution", peer_attribution, "0 (off) or 1..16 kernels per peer GPU score",
+                                             0, 16)
         if self.peer_attribution:
-            if self.peer_groups is None:  # (which in turn needs relative_perf_scores, and said so above)
+            if not peers_on:  # (which in turn needs relative_perf_scores, and said so above)
                 raise ValueError(f"peer_attribution={self.peer_attribution} needs peer_groups (and with it relative_perf_scores): "
                                  "it explains the peer-group scores")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "peer_attribute"):
-                raise RuntimeError(f"peer_attribution={self.peer_attribution}: the active backend "
-                                   f"({getattr(be, 'name', type(be).__name__)}) has no peer attribution (backend.peer_attribute)")
+            opts.needs_backend(f"peer_attribution={self.peer_attribution}", "peer attribution", "peer_attribute")
         # slack scores: every ring report also says whom the job waits for in collectives (Report.slack_scores,
         # Report.identify_slack_stragglers) from the statistics of the collective kernels' rows, which every other score drops;
         # off: no buffer, no launch, no collective, no backend call.  The step adds one collective per report, so EVERY rank
         # must pass the same value.  4 ranks, 0.05 and 0.25 are defaults, not measurements.
         self.collective_slack = bool(collective_slack)
         if self.collective_slack:
-            if isinstance(slack_min_ranks, bool) or not isinstance(slack_min_ranks, (int, np.integer)) or slack_min_ranks < 1:
-                raise ValueError(f"slack_min_ranks must be an integer >= 1, got {slack_min_ranks!r}")
-            rule = []
-            for name, v in (("slack_min_share", slack_min_share), ("slack_max_ratio", slack_max_ratio)):
-                try:
-                    x = float(v)
-                except (TypeError, ValueError):
-                    x = float("nan")
-                if isinstance(v, bool) or not (x >= 0.0 and math.isfinite(x)):
-                    raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
-                rule.append(x)
-            if not self.is_computing_rel_scores:
-                raise ValueError(f"collective_slack needs relative_perf_scores among scores_to_compute (got "
-                                 f"{scores_to_compute!r}): slack scores compare ranks")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "slack_score"):
-                raise RuntimeError(f"collective_slack: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no slack scores (backend.slack_score)")
-            self.slack_min_ranks, (self.slack_min_share, self.slack_max_ratio) = int(slack_min_ranks), rule
+            min_ranks = opts.integer("slack_min_ranks", slack_min_ranks, "an integer >= 1", 1)
+            min_share = opts.number("slack_min_share", slack_min_share, "a finite number >= 0", 0.0, math.inf, hi_open=True,
+                                    no_bool=True)
+            max_ratio = opts.number("slack_max_ratio", slack_max_ratio, "a finite number >= 0", 0.0, math.inf, hi_open=True,
+                                    no_bool=True)
+            opts.needs_relative("collective_slack", scores_to_compute, "slack scores compare ranks")
+            opts.needs_backend("collective_slack", "slack scores", "slack_score")
+            self.slack_min_ranks, self.slack_min_share, self.slack_max_ratio = min_ranks, min_share, max_ratio
         # slack scores per peer group: the score step of the slack scores takes a column's floor and the typical wait inside
         # the rank's OWN group (nvrx_slack_group_score); off: the step is the job-wide one, whatever peer_groups says.  The
         # local step and its collective are the same either way.
         self.slack_peer_groups = bool(slack_peer_groups)
         if self.slack_peer_groups:
-            if not self.collective_slack or self.peer_groups is None:
-                missing = [name for name, on in (("collective_slack", self.collective_slack),
-                                                 ("peer_groups", self.peer_groups is not None)) if not on]
-                raise ValueError(f"slack_peer_groups needs collective_slack and peer_groups; {' and '.join(missing)} "
-                                 f"{'is' if len(missing) == 1 else 'are'} not set")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            if be is not None and not hasattr(be, "slack_group_score"):
-                raise RuntimeError(f"slack_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   "has no slack scores per peer group (backend.slack_group_score)")
+            opts.needs_with_peer_groups("slack_peer_groups", "collective_slack", self.collective_slack, peers_on)
+            opts.needs_backend("slack_peer_groups", "slack scores per peer group", "slack_group_score")
         # the row families that are switched on, in the order their steps (and collectives) run in; and the first of them, if
         # any, that needs the ring-start snapshot
         self._row_families = tuple(f for f in row_families.ROW_STEPS if f.params(self))
@@ -2870,17 +2650,10 @@ class ReportGenerator:
         # kernels, the send rows and the collectives are the same either way.
         self.row_peer_groups = bool(row_peer_groups)
         if self.row_peer_groups:
-            if not self._row_families or self.peer_groups is None:
-                missing = [name for name, on in (("a row family (" + ", ".join(f.option for f in row_families.FAMILIES) + ")",
-                                                  bool(self._row_families)),
-                                                 ("peer_groups", self.peer_groups is not None)) if not on]
-                raise ValueError(f"row_peer_groups needs a row family and peer_groups; {' and '.join(missing)} "
-                                 f"{'is' if len(missing) == 1 else 'are'} not set")
-            be = _backend_mod._backend  # (an engine that does not exist yet is the HIP engine, which has it)
-            lacks = [f.name + "_group_score" for f in self._row_families if be is not None and not hasattr(be, f.name + "_group_score")]
-            if lacks:
-                raise RuntimeError(f"row_peer_groups: the active backend ({getattr(be, 'name', type(be).__name__)}) "
-                                   f"has no row-family scores per peer group (backend.{lacks[0]})")
+            opts.needs_with_peer_groups("row_peer_groups", "a row family", self._row_families, peers_on,
+                                        "a row family (" + ", ".join(f.option for f in row_families.FAMILIES) + ")")
+            opts.needs_backend("row_peer_groups", "row-family scores per peer group",
+                               *(f.name + "_group_score" for f in self._row_families))
         # what follows a report, decided here once (nothing assigns the options later): whether any table follow-up
         # (_follow_ups) is on, whether any ring step (_ring_steps) is, and what the one-call route needs of its rings
         self._table_steps_on, self._ring_steps_on = steps_behind_report(self)

@@ -39,6 +39,7 @@ from . import _native
 from . import backend as _backend_mod
 from . import dist_utils as _dist_utils
 from . import ktrace as _ktrace
+from . import report_options as opts
 from .cupti import CuptiManager
 from .interval_tracker import ReportIntervalTracker
 from .reporting import Report, ReportGenerator, _LiveBlock, _PendingBlock, _ScoreSource, steps_behind_report
@@ -712,182 +713,65 @@ class Detector(metaclass=_DeviceSideOnDemand):
                   "kernel, by kernel name" if per_kernel else "profiled region", _ktrace.timing_mode(), _ktrace.mode_note())
 
         # host side: who scores, and when
-        if asynchronous is None:
-            asynchronous = os.environ.get("NVRX_ASYNC_REPORT", "0") not in ("", "0")
-        if kernel_attribution is None:
-            try:
-                kernel_attribution = int(os.environ.get("NVRX_KERNEL_ATTRIBUTION", "0") or 0)
-            except ValueError:
-                raise ValueError("NVRX_KERNEL_ATTRIBUTION must be an integer: 0 (off) or 1..16") from None
+        asynchronous = opts.env_flag(asynchronous, "NVRX_ASYNC_REPORT")
+        kernel_attribution = opts.env_number(kernel_attribution, "NVRX_KERNEL_ATTRIBUTION", int, 0,
+                                             "NVRX_KERNEL_ATTRIBUTION must be an integer: 0 (off) or 1..16")
         if tail_quantile is None:
-            tail_quantile = os.environ.get("NVRX_TAIL_QUANTILE", "") or 0.0
-        if robust_scores is None:
-            robust_scores = os.environ.get("NVRX_ROBUST_SCORES", "0") not in ("", "0")
-        if onset_detection is None:
-            onset_detection = os.environ.get("NVRX_ONSET_DETECTION", "0") not in ("", "0")
-        if period_detection is None:
-            period_detection = os.environ.get("NVRX_PERIOD_DETECTION", "0") not in ("", "0")
-        if episode_detection is None:
-            episode_detection = os.environ.get("NVRX_EPISODE_DETECTION", "0") not in ("", "0")
-        if score_history is None:
-            try:
-                score_history = int(os.environ.get("NVRX_SCORE_HISTORY", "0") or 0)
-            except ValueError:
-                raise ValueError("NVRX_SCORE_HISTORY must be an integer: 0 (off) or 2..64 reports") from None
+            tail_quantile = os.environ.get("NVRX_TAIL_QUANTILE", "") or 0.0  # (the generator converts it, and says what it takes)
+        robust_scores = opts.env_flag(robust_scores, "NVRX_ROBUST_SCORES")
+        onset_detection = opts.env_flag(onset_detection, "NVRX_ONSET_DETECTION")
+        period_detection = opts.env_flag(period_detection, "NVRX_PERIOD_DETECTION")
+        episode_detection = opts.env_flag(episode_detection, "NVRX_EPISODE_DETECTION")
+        score_history = opts.env_number(score_history, "NVRX_SCORE_HISTORY", int, 0,
+                                        "NVRX_SCORE_HISTORY must be an integer: 0 (off) or 2..64 reports")
+        persistence_min_reports = opts.env_number(persistence_min_reports, "NVRX_PERSISTENCE_MIN_REPORTS", int, None,
+                                                  "NVRX_PERSISTENCE_MIN_REPORTS must be an integer within [1, NVRX_SCORE_HISTORY]")
         if persistence_min_reports is None:
-            from_env = os.environ.get("NVRX_PERSISTENCE_MIN_REPORTS", "")
-            if from_env:
-                try:
-                    persistence_min_reports = int(from_env)
-                except ValueError:
-                    raise ValueError("NVRX_PERSISTENCE_MIN_REPORTS must be an integer within [1, NVRX_SCORE_HISTORY]") from None
-            else:
-                persistence_min_reports = 3
-                if score_history == 2:
-                    persistence_min_reports = 2  # (a history of two reports cannot hold a streak of three)
-        if score_trends is None:
-            score_trends = os.environ.get("NVRX_SCORE_TRENDS", "0") not in ("", "0")
-        if collective_slack is None:
-            collective_slack = os.environ.get("NVRX_COLLECTIVE_SLACK", "0") not in ("", "0")
+            persistence_min_reports = 2 if score_history == 2 else 3  # (a history of two reports cannot hold a streak of three)
+        score_trends = opts.env_flag(score_trends, "NVRX_SCORE_TRENDS")
+        collective_slack = opts.env_flag(collective_slack, "NVRX_COLLECTIVE_SLACK")
         trend_min_reports_defaulted = trend_min_reports is None
         if trend_min_reports is None:
             trend_min_reports = 6
             if isinstance(score_history, int) and 4 <= score_history < 6:
                 trend_min_reports = score_history  # (a history of four reports cannot hold six)
-        peer_options = {}  # (off: the generator is built exactly as before)
         if peer_groups is None:
             peer_groups = _peer_groups_from_env(os.environ.get("NVRX_PEER_GROUPS", ""))
         if peer_groups is not None:
-            if peer_min_ranks is None:
-                try:
-                    peer_min_ranks = int(os.environ.get("NVRX_PEER_MIN_RANKS", "") or 2)
-                except ValueError:
-                    raise ValueError("NVRX_PEER_MIN_RANKS must be an integer >= 1") from None
-            peer_options = {"peer_groups": peer_groups, "peer_min_ranks": peer_min_ranks}
-        if peer_history is None:
-            try:
-                peer_history = int(os.environ.get("NVRX_PEER_HISTORY", "0") or 0)
-            except ValueError:
-                raise ValueError("NVRX_PEER_HISTORY must be an integer: 0 (off) or 2..64 reports") from None
-        if peer_trends is None:
-            peer_trends = os.environ.get("NVRX_PEER_TRENDS", "0") not in ("", "0")
-        if peer_history or peer_trends:  # (off: the generator is built exactly as before)
+            peer_min_ranks = opts.env_number(peer_min_ranks, "NVRX_PEER_MIN_RANKS", int, 2, "NVRX_PEER_MIN_RANKS must be an integer >= 1")
+        peer_history = opts.env_number(peer_history, "NVRX_PEER_HISTORY", int, 0,
+                                       "NVRX_PEER_HISTORY must be an integer: 0 (off) or 2..64 reports")
+        peer_trends = opts.env_flag(peer_trends, "NVRX_PEER_TRENDS")
+        if peer_history or peer_trends:
+            peer_persistence_min_reports = opts.env_number(
+                peer_persistence_min_reports, "NVRX_PEER_PERSISTENCE_MIN_REPORTS", int, None,
+                "NVRX_PEER_PERSISTENCE_MIN_REPORTS must be an integer within [1, NVRX_PEER_HISTORY]")
             if peer_persistence_min_reports is None:
-                from_env = os.environ.get("NVRX_PEER_PERSISTENCE_MIN_REPORTS", "")
-                if from_env:
-                    try:
-                        peer_persistence_min_reports = int(from_env)
-                    except ValueError:
-                        raise ValueError("NVRX_PEER_PERSISTENCE_MIN_REPORTS must be an integer within [1, NVRX_PEER_HISTORY]") from None
-                else:
-                    peer_persistence_min_reports = 2 if peer_history == 2 else 3  # (two reports cannot hold a streak of three)
+                peer_persistence_min_reports = 2 if peer_history == 2 else 3  # (two reports cannot hold a streak of three)
             if peer_trends and trend_min_reports_defaulted and isinstance(peer_history, int) and 4 <= peer_history < trend_min_reports:
                 trend_min_reports = peer_history  # (a history of four reports cannot hold six)
-            peer_options.update(peer_history=peer_history, peer_persistence_min_reports=peer_persistence_min_reports,
-                                peer_persistence_thresholds=peer_persistence_thresholds, peer_trends=peer_trends)
-        work_options = {}  # (off: the generator is built exactly as before)
-        if work_groups is None:
-            from_env = os.environ.get("NVRX_WORK_GROUPS", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_WORK_GROUPS must be 0 or 1, got {from_env!r}")
-            work_groups = from_env == "1"
+        work_groups = opts.env_strict_flag(work_groups, "NVRX_WORK_GROUPS")
         if work_groups or (isinstance(peer_groups, str) and peer_groups == "auto"):
-            for name, env, default in (("work_count_tol", "NVRX_WORK_COUNT_TOL", 0.25), ("work_max_unlike", "NVRX_WORK_MAX_UNLIKE", 0.1)):
-                value = work_count_tol if name == "work_count_tol" else work_max_unlike
-                if value is None:
-                    try:
-                        value = float(os.environ.get(env, "") or default)
-                    except ValueError:
-                        raise ValueError(f"{env} must be a number, got {os.environ.get(env)!r}") from None
-                work_options[name] = value
-            if work_groups:
-                work_options["work_groups"] = True
-        pace_options = {}  # (off: the generator is built exactly as before)
-        if pace_scores is None:
-            pace_scores = os.environ.get("NVRX_PACE_SCORES", "0") not in ("", "0")
-        if pace_scores:
-            pace_options = {"pace_scores": True, "pace_min_ranks": pace_min_ranks, "pace_min_columns": pace_min_columns,
-                            "pace_min_effect": pace_min_effect, "pace_min_breadth": pace_min_breadth}
-        if pace_peer_groups is None:
-            from_env = os.environ.get("NVRX_PACE_PEER_GROUPS", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_PACE_PEER_GROUPS must be 0 or 1, got {from_env!r}")
-            pace_peer_groups = from_env == "1"
-        if pace_peer_groups:
-            pace_options["pace_peer_groups"] = True  # (the generator says which of pace_scores and peer_groups it misses)
-        if robust_peer_groups is None:
-            from_env = os.environ.get("NVRX_ROBUST_PEER_GROUPS", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_ROBUST_PEER_GROUPS must be 0 or 1, got {from_env!r}")
-            robust_peer_groups = from_env == "1"
-        if robust_peer_groups:
-            pace_options["robust_peer_groups"] = True  # (the generator says which of robust_scores and peer_groups it misses)
-        if slack_peer_groups is None:
-            from_env = os.environ.get("NVRX_SLACK_PEER_GROUPS", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_SLACK_PEER_GROUPS must be 0 or 1, got {from_env!r}")
-            slack_peer_groups = from_env == "1"
-        if slack_peer_groups:
-            pace_options["slack_peer_groups"] = True  # (the generator says which of collective_slack and peer_groups it misses)
-        if row_peer_groups is None:
-            from_env = os.environ.get("NVRX_ROW_PEER_GROUPS", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_ROW_PEER_GROUPS must be 0 or 1, got {from_env!r}")
-            row_peer_groups = from_env == "1"
-        if row_peer_groups:
-            pace_options["row_peer_groups"] = True  # (the generator says which of a row family and peer_groups it misses)
-        node_options = {}  # (off: the generator is built exactly as before)
-        if node_scores is None:
-            from_env = os.environ.get("NVRX_NODE_SCORES", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_NODE_SCORES must be 0 or 1, got {from_env!r}")
-            node_scores = from_env == "1"
-        if node_scores:
-            if node_groups is None:
-                node_groups = _peer_groups_from_env(os.environ.get("NVRX_NODE_GROUPS", ""), "NVRX_NODE_GROUPS")
-            node_options = {"node_scores": True, "node_groups": node_groups, "node_min_members": node_min_members,
-                            "node_min_nodes": node_min_nodes, "node_min_columns": node_min_columns,
-                            "node_min_effect": node_min_effect, "node_min_breadth": node_min_breadth,
-                            "node_min_agree": node_min_agree}
-        if node_peer_groups is None:
-            from_env = os.environ.get("NVRX_NODE_PEER_GROUPS", "")
-            if from_env not in ("", "0", "1"):
-                raise ValueError(f"NVRX_NODE_PEER_GROUPS must be 0 or 1, got {from_env!r}")
-            node_peer_groups = from_env == "1"
-        if node_peer_groups:
-            node_options["node_peer_groups"] = True  # (the generator says which of node_scores and peer_groups it misses)
-        if peer_attribution is None:
-            try:
-                peer_attribution = int(os.environ.get("NVRX_PEER_ATTRIBUTION", "0") or 0)
-            except ValueError:
-                raise ValueError("NVRX_PEER_ATTRIBUTION must be an integer: 0 (off) or 1..16") from None
-        if peer_attribution:
-            node_options["peer_attribution"] = peer_attribution  # (the generator validates it and says what it misses)
-        ramp_options = {}  # (off: the generator is built exactly as before)
-        if ramp_detection is None:
-            ramp_detection = os.environ.get("NVRX_RAMP_DETECTION", "0") not in ("", "0")
-        if ramp_detection:
-            ramp_options = {"ramp_detection": True, "ramp_min_segment": ramp_min_segment, "ramp_min_strength": ramp_min_strength}
-        if stall_detection is None:
-            stall_detection = os.environ.get("NVRX_STALL_DETECTION", "0") not in ("", "0")
-        if stall_detection:
-            ramp_options.update(stall_detection=True, stall_min_ratio=stall_min_ratio, stall_min_z=stall_min_z,
-                                stall_min_share=stall_min_share)
+            work_count_tol = opts.env_number(work_count_tol, "NVRX_WORK_COUNT_TOL", float, 0.25,
+                                             "NVRX_WORK_COUNT_TOL must be a number, got {value!r}")
+            work_max_unlike = opts.env_number(work_max_unlike, "NVRX_WORK_MAX_UNLIKE", float, 0.1,
+                                              "NVRX_WORK_MAX_UNLIKE must be a number, got {value!r}")
+        pace_scores = opts.env_flag(pace_scores, "NVRX_PACE_SCORES")
+        pace_peer_groups = opts.env_strict_flag(pace_peer_groups, "NVRX_PACE_PEER_GROUPS")
+        robust_peer_groups = opts.env_strict_flag(robust_peer_groups, "NVRX_ROBUST_PEER_GROUPS")
+        slack_peer_groups = opts.env_strict_flag(slack_peer_groups, "NVRX_SLACK_PEER_GROUPS")
+        row_peer_groups = opts.env_strict_flag(row_peer_groups, "NVRX_ROW_PEER_GROUPS")
+        node_scores = opts.env_strict_flag(node_scores, "NVRX_NODE_SCORES")
+        if node_scores and node_groups is None:
+            node_groups = _peer_groups_from_env(os.environ.get("NVRX_NODE_GROUPS", ""), "NVRX_NODE_GROUPS")
+        node_peer_groups = opts.env_strict_flag(node_peer_groups, "NVRX_NODE_PEER_GROUPS")
+        peer_attribution = opts.env_number(peer_attribution, "NVRX_PEER_ATTRIBUTION", int, 0,
+                                           "NVRX_PEER_ATTRIBUTION must be an integer: 0 (off) or 1..16")
+        ramp_detection = opts.env_flag(ramp_detection, "NVRX_RAMP_DETECTION")
+        stall_detection = opts.env_flag(stall_detection, "NVRX_STALL_DETECTION")
+        # (report_options.GROUPS: the options that are off are left out, so the generator is built exactly as before they existed)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
-                                       node_name=node_name or socket.gethostname(), asynchronous=asynchronous,
-                                       kernel_attribution=kernel_attribution, tail_quantile=tail_quantile,
-                                       robust_scores=robust_scores, onset_detection=onset_detection,
-                                       onset_min_segment=onset_min_segment, onset_min_strength=onset_min_strength,
-                                       period_detection=period_detection, period_max=period_max,
-                                       period_min_strength=period_min_strength, episode_detection=episode_detection,
-                                       episode_min_length=episode_min_length, episode_min_strength=episode_min_strength,
-                                       score_history=score_history, persistence_min_reports=persistence_min_reports,
-                                       persistence_thresholds=persistence_thresholds, score_trends=score_trends,
-                                       trend_min_reports=trend_min_reports, trend_min_tau=trend_min_tau,
-                                       trend_horizon=trend_horizon, collective_slack=collective_slack,
-                                       slack_min_ranks=slack_min_ranks, slack_min_share=slack_min_share,
-                                       slack_max_ratio=slack_max_ratio, **peer_options, **pace_options, **node_options,
-                                       **work_options, **ramp_options)
+                                       node_name=node_name or socket.gethostname(), **opts.forwarded(locals()))
         cls.report_interval_tracker = ReportIntervalTracker(time_interval=report_time_interval,
                                                             profiling_interval=profiling_interval)
         cls.report_interval_tracker.also_max = cls._trace_every_needed  # (the tracing budget's number rides on the tracker's all-reduce)
