@@ -63,6 +63,12 @@ window, below ``stall_min_share``), with every row family on (``ReportGenerator(
 ``identify_*_stragglers`` names and what every family reads for rank 5 next to its stall record (``Report.stall_scores()``):
 how many events, how long ago the last one, what share of the window they cost.
 
+``--tail-profile`` needs no training loop: it plays one report of a job of 8 ranks (folded onto one GPU, 64 sections x 10 000
+samples, 1 % noise, seed 47) in which rank 5 is 1.4 x slower on 2 % of its samples at irregular positions, with every row
+family and the profile on (``ReportGenerator(tail_profile=(0.9, 0.99, 0.999))``), and prints whom each
+``identify_*_stragglers`` names, what every family reads for rank 5, and its quantiles side by side (``Report.tail_profile()``):
+from which quantile on the rank is slow, and so on what share of its samples.
+
 ``--persist`` needs no training loop: it plays 20 reports of a job of 8 ranks (folded onto one GPU, 1 % noise, seed 17) in which
 rank 2 is 1.6x slower in report 6 only and rank 5 is 1.45x slower from report 10 on, with a score history of 8 reports
 (``ReportGenerator(score_history=8, persistence_min_reports=3)``), and prints per report whom ``identify_stragglers`` flags and
@@ -575,6 +581,55 @@ def stall(stalled: int = 5, once: int = 2) -> None:
         job.close()
 
 
+PROFILE_QUANTILES = (0.9, 0.99, 0.999)
+
+
+def tail_profile_samples(ranks: int = 8, sections: int = 64, samples: int = 10000, slow: int = 5):
+    """The ``--tail-profile`` job: ``[ranks, sections, samples]`` f64 microseconds (NumPy only), 1000 us with 1 % noise; rank
+    ``slow`` is 1.4 x slower on 2 % of its samples, at positions drawn per row."""
+    import numpy as np
+
+    rng = np.random.default_rng(47)
+    x = 1000.0 * (1.0 + 0.01 * rng.standard_normal((ranks, sections, samples)))
+    for s in range(sections):
+        x[slow, s, rng.choice(samples, samples // 50, replace=False)] *= 1.4
+    return x
+
+
+def tail_profile(slow: int = 5) -> None:
+    """A rank that is 1.4 x slower on 2 % of its samples under every score that reads a window, next to its tail profile."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    x = tail_profile_samples(slow=slow)
+    ranks, sections, samples = x.shape
+    job = FoldedJob(total_ranks=ranks, sections=sections, ring_cap=samples, scores_to_compute=("relative_perf_scores",),
+                    tail_profile=PROFILE_QUANTILES, **STALL_OPTIONS)
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, x[r].astype(np.float32))
+        report = job.report()
+        name = job.section_names[0]
+        print(f"identify_stragglers(): {named_ranks({k: v for k, v in report.identify_stragglers().items() if 'relative' in k})}")
+        for family in STALL_FAMILIES:
+            print(f"identify_{family}_stragglers(): {named_ranks(getattr(report, f'identify_{family}_stragglers')())}")
+        found = report.identify_tail_profile_stragglers()
+        print(f"identify_tail_profile_stragglers(): {named_ranks({k: v for k, v in found.items() if k != 'slow_share'})}")
+        print(f"rank {slow}, {name}: relative {report.section_relative_perf_scores[name][slow]:.3f}, "
+              + ", ".join(f"{family} {getattr(report, family + '_scores')()['section_relative'][name][slow]:.3f}"
+                          for family in STALL_FAMILIES))
+        profile = report.tail_profile()
+        for q, t, score in zip(profile["quantiles"], profile["section_profile"][name][slow], profile["section_relative"][name][slow]):
+            print(f"  q = {q}: {t:.0f} us, score {score:.3f}")
+        shares = {share for by_rank in found["slow_share"]["sections"].values() for share in by_rank.values()}
+        for at_least, fewer_than in sorted(shares):
+            print(f"  rank {slow} is slow on at least {100 * at_least:g} % and on fewer than {100 * fewer_than:g} % of its samples")
+    finally:
+        job.close()
+
+
 def named_ranks(found) -> list:
     """The ranks an ``identify_*_stragglers()`` result names, in any of its mappings."""
     return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
@@ -1058,7 +1113,13 @@ def main() -> None:
     ap.add_argument("--ramp", action="store_true",
                     help="no training: play the ramp-score scenario (8 ranks, rank 5 rises by 50 %% over the last 40 %% of the "
                          "window, rank 2 stepped) under the relative, tail, onset, episode and ramp scores, and exit")
+    ap.add_argument("--tail-profile", action="store_true",
+                    help="no training: play the tail-profile scenario (8 ranks x 64 sections, rank 5 1.4 x slower on 2 %% of its "
+                         "samples) under the relative scores, every row family and the profile at 0.9 / 0.99 / 0.999, and exit")
     args = ap.parse_args()
+    if args.tail_profile:
+        tail_profile()
+        return
     if args.stall:
         stall()
         return

@@ -423,6 +423,36 @@ enum { NVRX_STALL_PLANES = 7 };
 int nvrx_stall_score(const float *d_stall, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                      float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Tail profile of timing rows: SEVERAL quantiles of every row in one launch.  Extends nvrx_row_quantile (straggler.py:172-197,
+ * above), which selects one: how OFTEN a row is slow shows only when its quantiles stand side by side, and each further
+ * nvrx_row_quantile launch reads the whole window three times again.  q_ppm[Q] (host memory, copied by the call): Q in
+ * 1..NVRX_PROFILE_MAX_Q quantiles, strictly ascending, each within nvrx_row_quantile's range [500000, 999999].  Per row and j
+ * the element of rank k_j = (q_ppm[j] * n + 999999) / 1000000 - 1 (64-bit integers) in nvrx_row_quantile's order: plane j is
+ * nvrx_row_quantile at q_ppm[j], bit for bit.
+ *   d_samples [rows][row_stride], 16-byte aligned, row_stride % 4 == 0, at most NVRX_MAX_RING_CAP; d_counts [rows];
+ *   d_out [Q][rows]: -1.0 in every plane where the row holds no sample.  Stateless, like nvrx_row_quantile.
+ * One workgroup per row selects all Q ranks together, MSB first, in three passes of 12 + 10 + 10 bits with one sweep over the
+ * keys per pass whatever Q is; the row is read from device memory ONCE: its order keys stay in LDS.  Rows of at most
+ * NVRX_PROFILE_LDS_SAMPLES samples stay there entirely; longer ones keep that many and take the rest from the L2 in passes two
+ * and three.  The cut: seven 1024-bin group histograms are 28 672 bytes (the first pass' 4096 bins live in them), the scan's
+ * wave sums and the picks 504; of the 64 KB of a workgroup's static LDS that leaves 36 360 bytes = 9090 keys; 8960 = 35 x 256.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched.
+ * (An enumerator, not a macro, as NVRX_RAMP_PLANES is: the number of planes is the run-time Q; seven are the most the
+ * row-family pipeline carries.) */
+enum { NVRX_PROFILE_MAX_Q = 7 };
+#define NVRX_PROFILE_LDS_SAMPLES 8960
+int nvrx_row_profile(const float *d_samples, const uint32_t *d_counts, int rows, int row_stride, const uint32_t *q_ppm, int Q,
+                     float *d_out, void *stream);
+/* Relative profile scores.  Extends _compute_section_relative_scores / _compute_gpu_perf_score (reporting.py:196-253) as
+ * nvrx_tail_score does, once per quantile: d_profile [R][Q][K+S] holds every rank's Q quantiles per kernel id and section id
+ * (-1.0: none).  Per plane q the reference of a column is the minimum over all R ranks, NaN if any rank has none, and per
+ * reported rank [first_rank, first_rank + n_ranks) and q exactly nvrx_tail_score's arithmetic on plane q:
+ *   d_out [n_ranks][Q][1 + S] = {GPU score, section score[S]} per quantile; weights from d_table [R][L] as there.
+ *   d_colmin_scratch  NVRX_ATTR_SCRATCH_FLOATS(Q * (K+S)) floats of device memory.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+int nvrx_profile_score(const float *d_profile, int Q, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                       float *d_colmin_scratch, float *d_out, void *stream);
+
 /* Robust scores: every rank against the job's median and spread. Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
@@ -1231,6 +1261,14 @@ int nvrx_ramp_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t min_se
  * snapshot is not enabled, or no report was issued through this descriptor. */
 int nvrx_stall_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t ratio_ppm, float min_z, float min_share,
                      float *d_stall_send, int K, int S, int rows_active, void *stream);
+/* Tail profile on the rings (straggler.py:172-197, above; reporting.py:196-253 follows with nvrx_profile_score):
+ * nvrx_row_profile on the rings as the report just issued saw them, packed by gid into d_send [local_ranks][Q][K+S] (plane j:
+ * the q_ppm[j]-quantile; kernel ids first, then section ids; every slot is written, -1.0 where no row with samples has that
+ * gid).  q_ppm and Q as for nvrx_row_profile.  No ring-start snapshot is needed: a quantile does not look at the order of the
+ * samples.  Ordering, desc, rows_active and the caller's duty to wait are those of nvrx_tail_local.  NVRX_ERR_STATE: no report
+ * was issued through this descriptor. */
+int nvrx_profile_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, const uint32_t *q_ppm, int Q, float *d_send, int K, int S,
+                       int rows_active, void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

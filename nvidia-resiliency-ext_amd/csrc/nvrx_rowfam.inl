@@ -35,16 +35,22 @@ int min_strength_check(float min_strength) {
 
 // nvrx_{tail,onset,period,episode}_score: relative scores from plane 0 of a gathered [R][planes][K+S] table -- a [R][K+S]
 // table with a pitch of planes * (K+S)
-int plane_score(const float *d_planes, int planes, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
-                float *d_colmin_scratch, float *d_out, void *stream) {
+int plane_score_check(const float *d_planes, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                      const float *d_colmin_scratch, const float *d_out) {
     if (R <= 0 || K < 0 || S < 0) return fail(NVRX_ERR_INVALID, "bad table shape R=%d K=%d S=%d", R, K, S);
     if (K > NVRX_MAX_ROWS) return fail(NVRX_ERR_RANGE, "K=%d kernel ids, at most %d", K, NVRX_MAX_ROWS);
     if (first_rank < 0 || n_ranks < 1 || first_rank > R - n_ranks)
         return fail(NVRX_ERR_RANGE, "ranks [%d,%d+%d) outside the table's %d", first_rank, first_rank, n_ranks, R);
     if (!d_planes || !d_table || !d_out) return fail(NVRX_ERR_INVALID, "null device pointer");
-    const int KS = K + S;
-    if (KS > 0 && !d_colmin_scratch) return fail(NVRX_ERR_INVALID, "d_colmin_scratch is null");
-    return tail_score_launch(d_planes, planes * KS, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out, as_stream(stream));
+    if (K + S > 0 && !d_colmin_scratch) return fail(NVRX_ERR_INVALID, "d_colmin_scratch is null");
+    return NVRX_OK;
+}
+
+int plane_score(const float *d_planes, int planes, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
+                float *d_colmin_scratch, float *d_out, void *stream) {
+    if (const int rc = plane_score_check(d_planes, d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out)) return rc;
+    return tail_score_launch(d_planes, planes * (K + S), d_table, R, K, S, first_rank, n_ranks, d_colmin_scratch, d_out,
+                             as_stream(stream));
 }
 
 // the window the context's last report read, as a family's ring kernel needs it (copied into the family's argument struct)

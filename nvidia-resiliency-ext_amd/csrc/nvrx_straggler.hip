@@ -4031,6 +4031,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_episode.inl"
 #include "nvrx_ramp.inl"
 #include "nvrx_stall.inl"
+#include "nvrx_profile.inl"
 #include "nvrx_peer.inl"
 #include "nvrx_rowfam_group.inl"
 #include "nvrx_pace.inl"

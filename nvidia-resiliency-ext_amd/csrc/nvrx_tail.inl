@@ -157,30 +157,26 @@ struct TailScoreArgs {
 
 constexpr int TAIL_SCORE_THREADS = 256;
 
-// one workgroup per reported rank: {gpu_tail, section_tail[S]}
-__global__ __launch_bounds__(TAIL_SCORE_THREADS) void k_tail_score(TailScoreArgs a) {
+// {gpu_tail, section_tail[S]} of one rank from its tails [KS], its weights [K] and the column minima [KS]; a whole workgroup
+// of TAIL_SCORE_THREADS threads
+__device__ __forceinline__ void tail_score_rank(const float *__restrict__ tail, const float *__restrict__ wrow,
+                                                const float *__restrict__ colmin, int K, int S, float *__restrict__ out) {
     constexpr int NW = TAIL_SCORE_THREADS / 64;
     __shared__ double s_sum[2][NW];
     __shared__ uint32_t s_cnt[NW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.K, S = a.S, KS = K + S;
-    const int L = NVRX_TABLE_LEN(K, S);
-    const int r = a.first_rank + (int)blockIdx.x;
-    const float *__restrict__ tail = a.tails + (size_t)r * (size_t)a.ld;
-    const float *__restrict__ wrow = a.table + (size_t)r * L + 2 * KS;
-    float *__restrict__ out = a.out + (size_t)blockIdx.x * (size_t)(1 + S);
     const float NaN = __builtin_nanf("");
 
     for (int s = tid; s < S; s += TAIL_SCORE_THREADS) {
         const float t = tail[K + s];
-        out[1 + s] = t >= 0.0f ? (float)((double)a.colmin[K + s] / (double)t) : NaN;
+        out[1 + s] = t >= 0.0f ? (float)((double)colmin[K + s] / (double)t) : NaN;
     }
     double ws = 0.0, ss = 0.0;
     uint32_t cnt = 0;
     for (int k = tid; k < K; k += TAIL_SCORE_THREADS) {
         const float t = tail[k];
         if (!(t >= 0.0f)) continue;
-        const float ref = a.colmin[k];
+        const float ref = colmin[k];
         if (!(ref == ref)) continue;
         const double w = (double)wrow[k];
         ss += ((double)ref / (double)t) * w;
@@ -208,6 +204,14 @@ __global__ __launch_bounds__(TAIL_SCORE_THREADS) void k_tail_score(TailScoreArgs
     }
 }
 
+// one workgroup per reported rank
+__global__ __launch_bounds__(TAIL_SCORE_THREADS) void k_tail_score(TailScoreArgs a) {
+    const int KS = a.K + a.S;
+    const int r = a.first_rank + (int)blockIdx.x;
+    tail_score_rank(a.tails + (size_t)r * (size_t)a.ld, a.table + (size_t)r * NVRX_TABLE_LEN(a.K, a.S) + 2 * KS, a.colmin, a.K,
+                    a.S, a.out + (size_t)blockIdx.x * (size_t)(1 + a.S));
+}
+
 int quantile_launch(const QuantArgs &a, int blocks, hipStream_t st) {
     if (blocks == 0) return NVRX_OK;
     if (a.row_stride <= 256 * 4 * 4)
@@ -218,24 +222,29 @@ int quantile_launch(const QuantArgs &a, int blocks, hipStream_t st) {
     return NVRX_OK;
 }
 
+// attr_colmin with the table's own pitch: the minimum of every column of a [R][KS] table whose rows are ld floats apart into
+// scratch[0, KS) (NaN where a rank has none); beyond 64 ranks in two stages through scratch[KS, 33 * KS)
+int colmin_launch(const float *d_table, int KS, int R, int ld, float *d_scratch, hipStream_t st) {
+    if (KS <= 0) return NVRX_OK;
+    if (R > 64) {
+        const int chunks = std::max(1, std::min(COLMIN_MAX_CHUNKS, (R + 63) / 64));
+        const int rows_per_chunk = (R + chunks - 1) / chunks;
+        float *part = d_scratch + KS;
+        hipLaunchKernelGGL(k_colmin_part, dim3((KS + 63) / 64, chunks), dim3(256), 0, st, d_table, R, KS, ld, rows_per_chunk, part);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_colmin_finish, dim3((KS + 255) / 256), dim3(256), 0, st, part, chunks, KS, d_scratch);
+    } else {
+        hipLaunchKernelGGL(k_colmin, dim3((KS + 255) / 256), dim3(256), 0, st, d_table, R, KS, ld, d_scratch);
+    }
+    HIP_TRY(hipGetLastError());
+    return NVRX_OK;
+}
+
 // column minima of a [R][KS] table whose rows are ld floats apart, then k_tail_score (arguments checked by the caller)
 int tail_score_launch(const float *d_tails, int ld, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                       float *d_colmin_scratch, float *d_out, hipStream_t st) {
     const int KS = K + S;
-    if (KS > 0) {
-        // attr_colmin with the tail table's own pitch: every column of a [R][KS] table
-        if (R > 64) {
-            const int chunks = std::max(1, std::min(COLMIN_MAX_CHUNKS, (R + 63) / 64));
-            const int rows_per_chunk = (R + chunks - 1) / chunks;
-            float *part = d_colmin_scratch + KS;
-            hipLaunchKernelGGL(k_colmin_part, dim3((KS + 63) / 64, chunks), dim3(256), 0, st, d_tails, R, KS, ld, rows_per_chunk, part);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_colmin_finish, dim3((KS + 255) / 256), dim3(256), 0, st, part, chunks, KS, d_colmin_scratch);
-        } else {
-            hipLaunchKernelGGL(k_colmin, dim3((KS + 255) / 256), dim3(256), 0, st, d_tails, R, KS, ld, d_colmin_scratch);
-        }
-        HIP_TRY(hipGetLastError());
-    }
+    if (const int rc = colmin_launch(d_tails, KS, R, ld, d_colmin_scratch, st)) return rc;
     TailScoreArgs a{};
     a.tails = d_tails, a.ld = ld, a.table = d_table, a.colmin = d_colmin_scratch;
     a.R = R, a.K = K, a.S = S, a.first_rank = first_rank, a.out = d_out;

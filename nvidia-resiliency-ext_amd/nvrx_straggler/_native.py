@@ -47,6 +47,8 @@ STALL_PLANES = 7  # NVRX_STALL_PLANES: {e, pace, level, share, events, last_ago,
 STALL_LDS_SAMPLES = 12032  # NVRX_STALL_LDS_SAMPLES: the longest row k_row_stall keeps in LDS next to its selection histogram
 STALL_MIN_SAMPLES = 8  # NVRX_STALL_MIN_SAMPLES: shorter rows have a pace, a spread and a cut, and no stalls
 STALL_RATIO_PPM_MIN, STALL_RATIO_PPM_MAX = 1000001, 1000000000  # the accepted range of a stall's minimum ratio to the pace
+PROFILE_MAX_Q = 7  # NVRX_PROFILE_MAX_Q: the most quantiles a tail profile selects in its one launch
+PROFILE_LDS_SAMPLES = 8960  # NVRX_PROFILE_LDS_SAMPLES: the longest row k_row_profile keeps in LDS next to its seven group histograms
 HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
 HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
 TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, family, slot)
@@ -109,6 +111,8 @@ SYMBOLS = [
     ("nvrx_ramp_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_stall", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     ("nvrx_stall_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_profile", c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_uint32), c_int, c_void_p, c_void_p]),
+    ("nvrx_profile_score", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -176,6 +180,7 @@ SYMBOLS = [
     ("nvrx_episode_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_ramp_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_stall_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_profile_local", c_int, [c_void_p, POINTER(ReportDesc), POINTER(c_uint32), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),
@@ -424,6 +429,30 @@ def tail_q_ppm(q) -> int:
     if ppm != 0 and not TAIL_Q_PPM_MIN <= ppm <= TAIL_Q_PPM_MAX:
         raise ValueError(f"tail_quantile must be 0 (off) or within [0.5, 0.999999], got {q!r}")
     return ppm
+
+
+def profile_q_ppm(quantiles) -> tuple:
+    """A tail profile's quantiles as the library carries them: ``round(q * 1e6)`` of each; None / ``()`` = off (``()``), else 1..7
+    strictly ascending numbers within [0.5, 0.999999].  ``ValueError`` for anything else."""
+    if quantiles is None:
+        return ()
+    text = "a sequence of 1..7 strictly ascending numbers within [0.5, 0.999999] (None or () = off)"
+    try:
+        ppm = tuple(int(round(float(q) * 1e6)) for q in quantiles)
+    except (TypeError, ValueError):
+        raise ValueError(f"tail_profile must be {text}, got {quantiles!r}") from None
+    if len(ppm) > PROFILE_MAX_Q:
+        raise ValueError(f"tail_profile takes at most {PROFILE_MAX_Q} quantiles, got {len(ppm)}: {quantiles!r}")
+    if not all(TAIL_Q_PPM_MIN <= q <= TAIL_Q_PPM_MAX for q in ppm):
+        raise ValueError(f"tail_profile quantiles must be within [0.5, 0.999999], got {quantiles!r}")
+    if any(b <= a for a, b in zip(ppm, ppm[1:])):
+        raise ValueError(f"tail_profile quantiles must strictly ascend, got {quantiles!r}")
+    return ppm
+
+
+def q_array(q_ppm):
+    """``(uint32 array, Q)`` as ``nvrx_row_profile`` and its siblings take a profile's quantiles."""
+    return (c_uint32 * len(q_ppm))(*q_ppm), len(q_ppm)
 
 
 def tail_rank(q_ppm: int, n: int) -> int:

@@ -321,6 +321,33 @@ class RowGroupScores(RowScores):
         return self._host
 
 
+class ProfileScores:
+    """The tail profile of one report (``nvrx_profile_local`` -> exchange -> ``nvrx_profile_score``), enqueued and not waited
+    for: once the score kernel has run, the workspace's profile buffer holds the gathered table ``[R][Q][K+S]`` and, behind it,
+    the scores ``[n_ranks][Q][1 + S]`` of the reported ranks.  ``records()`` waits for it and takes the private host copy (one
+    ordered D2H on the backend's stream), as ``RowScores.records`` does for a row family."""
+
+    __slots__ = ("backend", "d_ptr", "R", "Q", "K", "S", "first_rank", "n_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, Q: int, K: int, S: int, first_rank: int, n_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.R, self.Q, self.K, self.S = R, Q, K, S
+        self.first_rank, self.n_ranks = first_rank, n_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(quantiles [n_ranks, Q, K+S], scores [n_ranks, Q, 1 + S])`` f32 of the reported ranks (private copies); the first
+        call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.profile_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class _FamilyBuffers:
     """A workspace's device buffers of one row family, and the handle that may still be using them."""
 
@@ -838,9 +865,38 @@ class Workspace:
     def stall_settle(self) -> None:
         self.family_settle(STALL)
 
+    # ---- tail profile (off unless a ReportGenerator asks: nothing is allocated before) ---------------------------------
+    _profile_state = None  # (Q, buf, send, table, scratch) once the step has run on this workspace
+    _profile_last = None   # the ProfileScores whose kernels may still be reading the table / writing the buffer
+
+    def profile_buffers(self, Q: int):
+        """``(send, table, scores, scratch)`` of the tail profile of ``Q`` quantiles (cold: allocated on first use, and again
+        behind ``profile_settle`` should Q change): ONE buffer holds the gathered table ``[R][Q * (K+S)]`` and then the scores
+        ``[R][Q][1 + S]`` (one copy-out); ``send`` are this process' rows (the table's own without an exchange); ``scratch``
+        takes the minima of the ``Q * (K+S)`` columns."""
+        st = self._profile_state
+        if st is None or st[0] != Q:
+            self.profile_settle()
+            KS, R, dev = self.K + self.S, self.R, self._backend.device
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                buf = torch.empty(max(R * Q * KS + R * Q * (1 + self.S), 64), dtype=torch.float32, device=dev)
+                table = buf[: R * Q * KS].view(R, Q * KS)
+                send = table if R == self.local_ranks else torch.empty((self.local_ranks, Q * KS), dtype=torch.float32, device=dev)
+                scratch = torch.empty(max(33 * Q * KS, 64), dtype=torch.float32, device=dev)
+            st = self._profile_state = (Q, buf, send, table, scratch)
+        _, buf, send, table, scratch = st
+        return send, table, buf[table.numel():], scratch
+
+    def profile_settle(self) -> None:
+        """Before anything rewrites this workspace's table or the profile's buffers: the last profile step's kernels have run
+        and their results are on the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        last, self._profile_last = self._profile_last, None
+        if last is not None:
+            last.records()
+
     def settle_readers(self) -> None:
         """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
-        reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps, stalls -- has run and delivered; and so has the
+        reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps, stalls, the tail profile -- has run and delivered; and so has the
         score history's step, which read the result block and wrote the records buffer."""
         if self._attr_last is not None:
             self.attr_settle()
@@ -852,6 +908,8 @@ class Workspace:
         if self._family_state:
             for fam in ROW_STEPS[1:]:
                 self.family_settle(fam)
+        if self._profile_last is not None:
+            self.profile_settle()
         if self._history_last is not None:
             self.history_settle()
         if self._trend_last is not None:
@@ -1320,6 +1378,45 @@ class HipBackend:
 
     def stall_score(self, ws, stalls, table, first_rank: int = 0, n_ranks: Optional[int] = None) -> RowScores:
         return self._family_score(STALL, ws, stalls, table, first_rank, n_ranks)
+
+    def profile_score(self, ws, profile, table, first_rank: int = 0, n_ranks: Optional[int] = None, q_ppm: tuple = ()) -> ProfileScores:
+        """Relative scores per quantile for ranks ``[first_rank, first_rank + n_ranks)`` from the gathered profile ``profile``
+        ([R, Q * (K+S)], ``Rings.profile_local``'s) and the weights in ``table`` ([R, L]): ``nvrx_profile_score`` enqueued on
+        the backend's stream.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        Q = len(q_ppm)
+        _, prof_table, scores, scratch = ws.profile_buffers(Q)
+        assert profile is prof_table or (profile.data_ptr() == prof_table.data_ptr())
+        table_ptr = ws.table_ptr if table is ws.table else (ws.send_ptr if table is ws.send else table.data_ptr())
+        rc = self.lib.nvrx_profile_score(prof_table.data_ptr(), Q, table_ptr, ws.R, ws.K, ws.S, first_rank, n_ranks,
+                                         scratch.data_ptr(), scores.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._profile_last = ProfileScores(self, ws._profile_state[1], ws.R, Q, ws.K, ws.S, first_rank, n_ranks)
+        return out
+
+    def profile_copy_out(self, t: ProfileScores):
+        """The one wait of a report's tail profile: a D2H of its table and scores on the backend's stream, behind the kernels."""
+        KS, Q = t.K + t.S, t.Q
+        n = t.R * Q * KS + t.n_ranks * Q * (1 + t.S)
+        host = np.empty(max(n, 1), dtype=np.float32)
+        if n:
+            _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        quantiles = host[: t.R * Q * KS].reshape(t.R, Q, KS)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        return quantiles, host[t.R * Q * KS : n].reshape(t.n_ranks, Q, 1 + t.S).copy()
+
+    def row_profile(self, samples: torch.Tensor, counts: torch.Tensor, q_ppm) -> torch.Tensor:
+        """Stateless nearest-rank quantiles on caller tensors ([rows, stride] f32, [rows] u32/i32) -> [Q, rows] f32, -1.0 where
+        a row holds no sample: all of ``q_ppm`` in one launch (``nvrx_row_profile``)."""
+        rows, stride = samples.shape
+        q, Q = _native.q_array(q_ppm)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((max(Q, 1), max(rows, 1)), dtype=torch.float32, device=samples.device)
+            _native.check(self.lib.nvrx_row_profile(samples.data_ptr(), counts.data_ptr(), rows, stride, q, Q, out.data_ptr(),
+                                                    self.stream_handle))
+        self.stream.synchronize()
+        return out[:, :rows]
 
     def _row_op(self, fam: RowFamily, samples: torch.Tensor, counts: torch.Tensor, param: int,
                 starts: Optional[torch.Tensor]) -> torch.Tensor:
@@ -2190,6 +2287,21 @@ class HipRings:
 
     def stall_local(self, ws: Workspace, ratio_ppm: int, min_z: float, min_share: float, rows_active: int = 0, fused: bool = False):
         return self._family_local(STALL, ws, (ratio_ppm, min_z, min_share), rows_active, fused)
+
+    def profile_local(self, ws: Workspace, q_ppm: tuple, rows_active: int = 0, fused: bool = False):
+        """The tail profile's ring kernel over every ring row as the report just issued on ``ws`` saw it, packed by gid into
+        the workspace's profile rows (``nvrx_profile_local``; ``fused`` as for ``_family_local``).  Returns ``(send
+        [local_ranks, Q * (K+S)], table [R, Q * (K+S)])`` -- the same rows when nothing is exchanged.  Waits for the kernel,
+        as ``_family_local`` does and for its reason."""
+        ws.profile_settle()
+        q, Q = _native.q_array(q_ppm)
+        send, table, _, _ = ws.profile_buffers(Q)
+        rc = self.lib.nvrx_profile_local(self.ctx, ws.block.desc_ref if fused else None, q, Q, send.data_ptr(), ws.K, ws.S,
+                                         rows_active, self.backend._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        self.backend.stream.synchronize()
+        return send, table
 
     def peek_stats(self) -> np.ndarray:
         """Statistics of every used row right now ([rows_used, 8] on the host); exchanges nothing and

@@ -41,7 +41,8 @@ class FoldedJob:
                  slack_peer_groups: bool = False, row_peer_groups: bool = False, ramp_detection: bool = False,
                  ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5, robust_peer_groups: bool = False,
                  stall_detection: bool = False, stall_min_ratio: float = 1.5, stall_min_z: float = 6.0,
-                 stall_min_share: float = 0.01, node_peer_groups: bool = False, peer_attribution: int = 0):
+                 stall_min_share: float = 0.01, node_peer_groups: bool = False, peer_attribution: int = 0,
+                 tail_profile=None):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")

@@ -143,6 +143,19 @@ def env_number(given, name: str, kind: Callable[[str], Any], default, message: s
         raise ValueError(message.format(value=value)) from None
 
 
+def env_numbers(given, name: str, message: str):
+    """A tuple of comma-separated numbers; unset or "": None (off).  ``message`` may quote the text as ``{value!r}``."""
+    if given is not None:
+        return given
+    value = os.environ.get(name, "")
+    if not value.strip():
+        return None
+    try:
+        return tuple(float(v) for v in value.split(","))
+    except ValueError:
+        raise ValueError(message.format(value=value)) from None
+
+
 # ---- what Detector and FoldedJob hand to ReportGenerator ---------------------------------------------------------------------
 @dataclasses.dataclass(frozen=True)
 class OptionGroup:
@@ -179,6 +192,7 @@ GROUPS: Tuple[OptionGroup, ...] = (
     OptionGroup(("peer_attribution",)),  # (the generator validates it and says what it misses)
     OptionGroup(("ramp_detection", "ramp_min_segment", "ramp_min_strength")),
     OptionGroup(("stall_detection", "stall_min_ratio", "stall_min_z", "stall_min_share")),
+    OptionGroup(("tail_profile",)),  # (None and () are off)
 )
 
 

@@ -722,6 +722,42 @@ class _RowFamilySource:
         return self._built
 
 
+class _ProfileSource:
+    """What a report keeps of its tail profile: the backend's handle (``records()`` waits for the kernels and copies the
+    quantiles and scores out on first use), the ranks its rows stand for, the sections it shows with their ids, the kernel
+    names by id as the report's mapper had them at report time, and the quantiles in ppm."""
+
+    __slots__ = ("handle", "ranks", "sections", "kernels", "q_ppm", "_built")
+
+    def __init__(self, handle, ranks, sections, kernels, q_ppm: tuple):
+        self.handle, self.ranks, self.kernels, self.q_ppm = handle, tuple(ranks), kernels, q_ppm
+        self.sections = {n: g for n, g in sections.items() if g is not None}  # (a name whose id is still to be agreed has no column)
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            ranks, K = self.ranks, len(self.kernels)
+            quantiles, scores = self.handle.records()
+            o, sc = quantiles.tolist(), scores.tolist()
+            Q = range(len(self.q_ppm))
+
+            def present(col):  # (-1 in plane 0: the rank has no samples in this row, in any plane)
+                return {r: tuple(o[i][j][col] for j in Q) for i, r in enumerate(ranks) if o[i][0][col] != -1.0}
+
+            kernel_profile = {name: present(k) for k, name in enumerate(self.kernels)}
+            section_profile = {name: present(K + g) for name, g in self.sections.items()}
+            self._built = {
+                "quantiles": tuple(q / 1e6 for q in self.q_ppm),
+                "gpu_relative": {r: tuple(sc[i][j][0] for j in Q) for i, r in enumerate(ranks)},
+                "section_relative": {name: {r: tuple(sc[i][j][1 + g] for j in Q) for i, r in enumerate(ranks)}
+                                     for name, g in self.sections.items()},
+                "section_profile": {n: v for n, v in section_profile.items() if v},
+                "kernel_profile": {n: v for n, v in kernel_profile.items() if v},
+            }
+            self.handle = None
+        return self._built
+
+
 class _RowGroupFamilySource(_RowFamilySource):
     """What a report keeps of one row family's scores per peer group (``ReportGenerator(row_peer_groups=True)``):
     ``_RowFamilySource``'s, the resolved groups and ``min_peers``.  The handle's ``records()`` delivers the column records
@@ -1545,6 +1581,9 @@ class Report:
             scores = self.__dict__.get(fam.slot)
             if scores is not None:
                 state[fam.slot] = scores.build() if isinstance(scores, _RowFamilySource) else scores
+        profile = self.__dict__.get("_profile")
+        if profile is not None:
+            state["_profile"] = profile.build() if isinstance(profile, _ProfileSource) else profile
         return state
 
     def __setstate__(self, state) -> None:
@@ -1729,6 +1768,51 @@ class Report:
         set[StragglerId], 'straggler_sections_relative': {section: set}}``; a section appears only if somebody is flagged
         for it.  Empty sets when the report carries no stall scores."""
         return self._identify_relative(self.stall_scores(), gpu_rel_threshold, section_rel_threshold)
+
+    def tail_profile(self) -> Dict[str, Any]:
+        """The tail profile (``ReportGenerator(tail_profile=(0.9, 0.99, 0.999))``; ``{}`` when the report carries none): HOW OFTEN
+        a rank is slow.  ``tail_scores()`` looks at one quantile that has to be guessed in advance -- a rank slower on 2 % of
+        its samples is invisible at 0.95; here up to seven nearest-rank quantiles of every timing row stand side by side, all
+        selected by one kernel launch that reads the window once, each scored as a tail score is.
+
+        ``{"quantiles": (q_0, ...), "section_profile": {section: {rank: (t_0, ...)}}, "kernel_profile": {kernel: {rank: (t_0,
+        ...)}}, "section_relative": {section: {rank: (score_0, ...)}}, "gpu_relative": {rank: (score_0, ...)}}`` -- ``t_j``
+        is the ``q_j``-quantile of the rank's samples (an actual sample, ``tail_scores()``'s value at that quantile bit for
+        bit); ``score_j`` is the fastest rank's ``t_j`` over this rank's (NaN where a rank lacks the row), the GPU score the
+        weighted mean over the kernels as in ``gpu_relative_perf_scores``.  A rank whose scores fall from some ``q_j`` on is
+        slow on at least ``1 - q_j`` of its samples (``identify_tail_profile_stragglers()``).  Ranks and sections as in the
+        score mappings, rows without samples are left out.  Plain dicts, tuples and floats.  The first call waits for the
+        profile kernels and copies their results; ``generate_report`` does not."""
+        profile = self.__dict__.get("_profile")
+        if profile is None:
+            return {}
+        if isinstance(profile, _ProfileSource):
+            profile = self.__dict__["_profile"] = profile.build()
+        return _copy_scores(profile)
+
+    def identify_tail_profile_stragglers(self, threshold: float = 0.75) -> Dict[str, Any]:
+        """Ranks whose PROFILE score at ANY quantile falls strictly below ``threshold`` (NaN is never flagged), and how often
+        they are slow: ``{'straggler_gpus_relative': set[StragglerId], 'straggler_sections_relative': {section: set},
+        'slow_share': {'gpus': {rank: (at_least, fewer_than)}, 'sections': {section: {rank: (at_least, fewer_than)}}}}``.
+        With ``q_j`` the lowest flagged quantile, the rank is slow on ``at_least = 1 - q_j`` of its samples and on
+        ``fewer_than = 1 - q_{j-1}`` of them -- 1.0 when the profile's lowest quantile is flagged itself.  A section appears
+        only if somebody is flagged for it.  Empty when the report carries no tail profile."""
+        profile = self.tail_profile()
+        rest = [(1000000 - round(q * 1e6)) / 1e6 for q in profile.get("quantiles", ())]  # (1 - q in ppm: 0.01, not 0.01000000000000001)
+
+        def shares(scores: Mapping[int, tuple]) -> Dict[int, tuple]:
+            out = {}
+            for r, row in scores.items():
+                j = next((j for j, x in enumerate(row) if x < threshold), None)
+                if j is not None:
+                    out[r] = (rest[j], rest[j - 1] if j else 1.0)
+            return out
+
+        gpus = shares(profile.get("gpu_relative", {}))
+        sections = {n: found for n, found in ((n, shares(v)) for n, v in profile.get("section_relative", {}).items()) if found}
+        return {"straggler_gpus_relative": self._ids(gpus),
+                "straggler_sections_relative": {n: self._ids(found) for n, found in sections.items()},
+                "slow_share": {"gpus": gpus, "sections": sections}}
 
     def robust_scores(self) -> Dict[str, Any]:
         """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
@@ -2309,7 +2393,7 @@ def steps_behind_report(generator) -> tuple:
                  or getattr(generator, "pace_scores", False) or getattr(generator, "node_scores", False)
                  or getattr(generator, "score_history", 0))
     ring = bool(any(getattr(generator, fam.param_attrs[0], 0) for fam in row_families.ROW_STEPS)
-                or getattr(generator, "collective_slack", False))
+                or getattr(generator, "tail_profile_ppm", ()) or getattr(generator, "collective_slack", False))
     return table, ring
 
 
@@ -2354,7 +2438,7 @@ class ReportGenerator:
                  ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5,
                  robust_peer_groups: bool = False, stall_detection: bool = False, stall_min_ratio: float = 1.5,
                  stall_min_z: float = 6.0, stall_min_share: float = 0.01, node_peer_groups: bool = False,
-                 peer_attribution: int = 0) -> None:
+                 peer_attribution: int = 0, tail_profile: Optional[Sequence[float]] = None) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2654,6 +2738,13 @@ class ReportGenerator:
                                         "a row family (" + ", ".join(f.option for f in row_families.FAMILIES) + ")")
             opts.needs_backend("row_peer_groups", "row-family scores per peer group",
                                *(f.name + "_group_score" for f in self._row_families))
+        # tail profile: every ring report also carries up to seven quantiles of every row, selected in one launch, and relative
+        # scores built from each (Report.tail_profile); () = off: no buffer, no launch, no collective, no backend call.  The
+        # step adds one collective per report, so EVERY rank must pass the same value.  (Checked behind every other option.)
+        self.tail_profile_ppm = _backend_mod._native.profile_q_ppm(tail_profile)
+        if self.tail_profile_ppm:
+            opts.needs_relative(f"tail_profile={tail_profile!r}", scores_to_compute, "profile scores are relative scores")
+            opts.needs_backend(f"tail_profile={tail_profile!r}", "tail profile", "profile_score")
         # what follows a report, decided here once (nothing assigns the options later): whether any table follow-up
         # (_follow_ups) is on, whether any ring step (_ring_steps) is, and what the one-call route needs of its rings
         self._table_steps_on, self._ring_steps_on = steps_behind_report(self)
@@ -2738,7 +2829,7 @@ class ReportGenerator:
             # with one stay on that route as a whole (the option has the same value on every rank, so every rank decides alike
             # -- no collective here).  A row family that is on is the one named.
             option, what = ((self._row_families[0].option, self._row_families[0].name) if self._row_families
-                            else ("collective_slack", "slack"))
+                            else ("tail_profile", "profile") if self.tail_profile_ppm else ("collective_slack", "slack"))
             self._direct = None
             self.exchange_info = {"route": f"torch.distributed all-gather on the job's own process group ({option} is "
                                            f"set: reports with {what} scores do not use the in-stream routes)", "mode": "c10d"}
@@ -3387,13 +3478,34 @@ class ReportGenerator:
 
     def _ring_steps(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
         """The ring steps of one ``generate_report_from_rings`` call: the families that are switched on, in the table's order,
-        then slack -- the order of their collectives, the same on every rank whatever ``report`` is."""
+        then the tail profile, then slack -- the order of their collectives, the same on every rank whatever ``report`` is."""
         if not self._ring_steps_on:
             return
         for fam in self._row_families:
             self._family_step(fam, report, rings, ws, mapper, rows_active, fused, local_ranks)
+        if self.tail_profile_ppm:
+            self._profile_step(report, rings, ws, mapper, rows_active, fused, local_ranks)
         if self.collective_slack:
             self._slack_step(report, rings, ws, rows_active, fused, local_ranks)
+
+    def _profile_step(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The tail profile's step of a ring report, behind the row families' steps and ahead of slack, on the same workspace:
+        its ring kernel on the window the report saw -> [one all-gather of its rows] -> its score kernel for the ranks the
+        report covers, hung on ``report`` unread.  Like a family's step, every rank issues it at every report, whatever the
+        report found and whether or not it holds a report: same collectives everywhere.  (A step of its own and no
+        ``RowFamily`` record: those score plane 0 into one score per rank; this one scores every plane.)"""
+        be = _backend_mod.get_backend()
+        q_ppm = self.tail_profile_ppm
+        local, score = getattr(rings, "profile_local", None), getattr(be, "profile_score", None)
+        if local is None or score is None:
+            raise RuntimeError("tail_profile: the active backend has no tail profile (rings.profile_local / backend.profile_score)")
+        table = self._gather_step_rows(be, *local(ws, q_ppm, rows_active, fused))
+        if report is None or report is False:
+            return
+        lo, hi = self._covered(ws, local_ranks)
+        view = report.__dict__["_src"].view
+        handle = score(ws, table, ws.table, lo, hi - lo, q_ppm)
+        report.__dict__["_profile"] = _ProfileSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), q_ppm)
 
     def _gather_step_rows(self, be, send, table):
         """Exchange a ring step's rows behind its local kernel: its one collective, on the backend's stream."""

@@ -454,6 +454,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         stall_min_ratio: float = 1.5,
         stall_min_z: float = 6.0,
         stall_min_share: float = 0.01,
+        tail_profile=None,
     ):
         """
         Args:
@@ -641,6 +642,13 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 ``kernel_attribution`` names what the slow stage runs; this names what is slow on one rank and not on its
                 peers.  Needs ``peer_groups`` (``"auto"`` is allowed) and relative scores.  Default:
                 ``NVRX_PEER_ATTRIBUTION``, else 0.  Same value on every rank (no collective depends on it).
+            tail_profile: 1..7 strictly ascending quantiles within [0.5, 0.999999], e.g. ``(0.9, 0.99, 0.999)``: every report
+                also carries those quantiles of every section and kernel row side by side -- all selected by ONE kernel launch
+                that reads the window once -- and relative scores per quantile (``Report.tail_profile()``,
+                ``Report.identify_tail_profile_stragglers()``): HOW OFTEN a rank is slow.  ``tail_quantile`` answers that only
+                for the one quantile it was given: a rank 1.4 x slower on 2 % of its samples is invisible at 0.95.  Needs
+                ``relative_perf_scores``.  Default: ``NVRX_TAIL_PROFILE`` (comma-separated, ``0.9,0.99,0.999``), else off.
+                Pass the same values on EVERY rank (the step adds one collective per report).
             slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
                 peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
                 expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
@@ -769,6 +777,8 @@ class Detector(metaclass=_DeviceSideOnDemand):
                                            "NVRX_PEER_ATTRIBUTION must be an integer: 0 (off) or 1..16")
         ramp_detection = opts.env_flag(ramp_detection, "NVRX_RAMP_DETECTION")
         stall_detection = opts.env_flag(stall_detection, "NVRX_STALL_DETECTION")
+        tail_profile = opts.env_numbers(tail_profile, "NVRX_TAIL_PROFILE", "NVRX_TAIL_PROFILE must be comma-separated numbers "
+                                        "(0.9,0.99,0.999), got {value!r}")
         # (report_options.GROUPS: the options that are off are left out, so the generator is built exactly as before they existed)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), **opts.forwarded(locals()))
