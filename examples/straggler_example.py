@@ -69,6 +69,12 @@ family and the profile on (``ReportGenerator(tail_profile=(0.9, 0.99, 0.999))``)
 ``identify_*_stragglers`` names, what every family reads for rank 5, and its quantiles side by side (``Report.tail_profile()``):
 from which quantile on the rank is slow, and so on what share of its samples.
 
+``--timeline`` needs no training loop: it plays one report of a job of 8 ranks (folded onto one GPU, 120 kernels x 10 000
+samples, 1 % noise, seed 59) in which rank 5 is 4 % slower in ALL its kernels on samples 6000-6999 -- a clock step down for a
+tenth of the window -- with the robust and pace scores, every row family, the tail profile and the timeline on
+(``ReportGenerator(timeline_scores=True)``), and prints whom each ``identify_*_stragglers`` names and rank 5's timeline
+(``Report.timeline_scores()``): when the stretch began and ended, how much slower the rank was in it, in what share of its rows.
+
 ``--persist`` needs no training loop: it plays 20 reports of a job of 8 ranks (folded onto one GPU, 1 % noise, seed 17) in which
 rank 2 is 1.6x slower in report 6 only and rank 5 is 1.45x slower from report 10 on, with a score history of 8 reports
 (``ReportGenerator(score_history=8, persistence_min_reports=3)``), and prints per report whom ``identify_stragglers`` flags and
@@ -630,6 +636,52 @@ def tail_profile(slow: int = 5) -> None:
         job.close()
 
 
+def timeline_samples(ranks: int = 8, kernels: int = 120, samples: int = 10000, slow: int = 5, span=(6000, 7000)):
+    """The ``--timeline`` job: ``[ranks, kernels, samples]`` f64 microseconds (NumPy only), per-kernel levels around 100 us with
+    1 % noise; rank ``slow`` is 4 % slower in every kernel on the samples of ``span``."""
+    import numpy as np
+
+    rng = np.random.default_rng(59)
+    x = rng.lognormal(np.log(100.0), 0.5, kernels)[None, :, None] * (1.0 + 0.01 * rng.standard_normal((ranks, kernels, samples)))
+    x[slow, :, span[0]:span[1]] *= 1.04
+    return x
+
+
+def timeline(slow: int = 5) -> None:
+    """A rank that is 4 % slower in everything for a tenth of the window under every score of a report, next to its timeline."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    x = timeline_samples(slow=slow)
+    ranks, kernels, samples = x.shape
+    job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=samples, scores_to_compute=("relative_perf_scores",),
+                    kernel_names=[f"kernel_{k:03d}" for k in range(kernels)], robust_scores=True, pace_scores=True,
+                    tail_profile=PROFILE_QUANTILES, timeline_scores=True, **STALL_OPTIONS)
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            job.load(lr, x[r].sum(axis=0, keepdims=True).astype(np.float32))
+            job.load_kernels(lr, x[r].astype(np.float32))
+        report = job.report()
+        print(f"identify_stragglers(): {named_ranks({k: v for k, v in report.identify_stragglers().items() if 'relative' in k})}")
+        for family in ("robust", "pace") + STALL_FAMILIES + ("tail_profile",):
+            found = getattr(report, f"identify_{family}_stragglers")()
+            print(f"identify_{family}_stragglers(): {named_ranks({k: v for k, v in found.items() if k != 'slow_share'})}")
+        found = report.identify_timeline_stragglers()
+        t = report.timeline_scores()
+        print(f"identify_timeline_stragglers(): {named_ranks({k: v for k, v in found.items() if k != 'runs'})}; "
+              f"{t['buckets']} buckets, rule {t['params']}")
+        gpu = t["ranks"][slow]["gpu"]
+        print(f"rank {slow}: {gpu['slow_buckets']} slow buckets, the longest run from {gpu['began_at']} to {gpu['ended_at']} of the "
+              f"window ({gpu['ended_buckets_ago']} buckets ago), {gpu['excess']:.3f} x the fastest rank's level there")
+        for b, (rel, breadth, rows) in enumerate(zip(gpu["timeline"], gpu["breadth"], gpu["rows"])):
+            print(f"  bucket {b:2d}: level {rel:.3f}, {100 * breadth:3.0f} % of {rows} kernels more than "
+                  f"{100 * t['params']['min_effect']:g} % above their own typical bucket")
+    finally:
+        job.close()
+
+
 def named_ranks(found) -> list:
     """The ranks an ``identify_*_stragglers()`` result names, in any of its mappings."""
     return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
@@ -1116,7 +1168,13 @@ def main() -> None:
     ap.add_argument("--tail-profile", action="store_true",
                     help="no training: play the tail-profile scenario (8 ranks x 64 sections, rank 5 1.4 x slower on 2 %% of its "
                          "samples) under the relative scores, every row family and the profile at 0.9 / 0.99 / 0.999, and exit")
+    ap.add_argument("--timeline", action="store_true",
+                    help="no training: play the timeline scenario (8 ranks x 120 kernels, rank 5 4 %% slower in every kernel on "
+                         "a tenth of the window) under every score of a report and the timeline scores, and exit")
     args = ap.parse_args()
+    if args.timeline:
+        timeline()
+        return
     if args.tail_profile:
         tail_profile()
         return

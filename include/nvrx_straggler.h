@@ -453,6 +453,37 @@ int nvrx_row_profile(const float *d_samples, const uint32_t *d_counts, int rows,
 int nvrx_profile_score(const float *d_profile, int Q, const float *d_table, int R, int K, int S, int first_rank, int n_ranks,
                        float *d_colmin_scratch, float *d_out, void *stream);
 
+/* Timeline scores: WHEN, inside a window, a whole GPU ran slow.  Extends _compute_gpu_perf_score (reporting.py:196-253), which
+ * reads each row's median, and the row operators above, which each read one row alone: a card that loses 4 % on EVERY kernel
+ * for a tenth of the window moves no median and no single row's statistic beyond its noise; the rows' agreement in time is
+ * the evidence.  The pace scores' rule (nvrx_pace_score, below), resolved in time.
+ * 1. Row timeline (nvrx_row_timeline).  B buckets, B in [NVRX_TIMELINE_MIN_BUCKETS, NVRX_TIMELINE_MAX_BUCKETS].  A row with n
+ *    samples in time order (d_starts as for nvrx_row_stall) takes part iff n >= 4 * B.  Sample i lies in bucket i * B / n
+ *    (64-bit integers); m_b = (float)(f64 sum of the bucket / its count); c = the lower median of the B values m_b (rank
+ *    (B - 1) / 2 in nvrx_row_quantile's order); x_b = (float)((double)m_b / (double)c).  If c <= 0 or any m_b is not finite
+ *    the row does not take part.  d_out [B][rows]: x_b, or -1.0 in every plane where the row does not take part.  Stateless.
+ *    The sums' order depends on n and the time index alone: a rotated ring gives the same bits.
+ * 2. Rank timeline (nvrx_timeline_rank).  d_planes [ranks][B][K+S] holds x_b per column (kernel ids first, then section ids;
+ *    a slot takes part iff its value is >= 0: ratios of timings are never negative).  Per rank, bucket and family (kernel
+ *    columns [0, K), section columns [K, K+S)): rows = the slots that take part; level = the lower median of their values
+ *    (rank (rows - 1) / 2), -1.0 when rows == 0; slower = how many of them exceed (float)(1 + effect_ppm / 1e6).
+ *    d_out [ranks][2][3][B] floats, family-major, fields {rows, level, slower}: all a rank exchanges.
+ * 3. Score (nvrx_timeline_score).  d_blocks [R][2][3][B] are all ranks' blocks.  Per reported rank [first_rank, first_rank +
+ *    n_ranks), family and bucket: ref_b = the smallest level_b of any rank with rows_b >= min_rows; rel_b = (float)((double)
+ *    level_b / (double)ref_b), NaN where the rank's own rows_b < min_rows; the bucket is SLOW iff (double)rel_b >= 1 +
+ *    effect_ppm / 1e6 and slower_b * 1000000 >= breadth_ppm * rows_b (integers).  d_out [n_ranks][2][4 + B] 32-bit words:
+ *    {u32 slow_buckets, u32 run_first, u32 run_len, f32 excess, f32 rel[B]} -- the longest run of consecutive slow buckets,
+ *    among equal runs the most recent (0, 0 without one); excess = (float)(f64 mean of rel_b over the run), 1.0 without one.
+ *    A stretch every rank shares raises ref_b too and flags nobody; a job of one rank reads 1.0 wherever it is rated.
+ * effect_ppm at most 1e9, breadth_ppm at most 1e6, min_rows in [1, NVRX_MAX_ROWS]; K and S at most NVRX_MAX_ROWS each.
+ * Argument errors (NVRX_ERR_INVALID / NVRX_ERR_RANGE) are reported before any device is touched. */
+enum { NVRX_TIMELINE_MIN_BUCKETS = 4, NVRX_TIMELINE_MAX_BUCKETS = 64 };
+int nvrx_row_timeline(const float *d_samples, const uint32_t *d_counts, const uint32_t *d_starts, int rows, int row_stride, int B,
+                      float *d_out, void *stream);
+int nvrx_timeline_rank(const float *d_planes, int ranks, int B, int K, int S, uint32_t effect_ppm, float *d_out, void *stream);
+int nvrx_timeline_score(const float *d_blocks, int R, int B, int first_rank, int n_ranks, uint32_t min_rows, uint32_t effect_ppm,
+                        uint32_t breadth_ppm, void *d_out, void *stream);
+
 /* Robust scores: every rank against the job's median and spread. Extends _compute_section_relative_scores /
  * _compute_gpu_perf_score (reporting.py:196-253), whose reference point is the FASTEST rank's median: one anomalously fast
  * rank flags the whole job, the minimum over R ranks drifts with R, and a fixed threshold does not know the job's spread.
@@ -1269,6 +1300,14 @@ int nvrx_stall_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, uint32_t ratio
  * was issued through this descriptor. */
 int nvrx_profile_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, const uint32_t *q_ppm, int Q, float *d_send, int K, int S,
                        int rows_active, void *stream);
+/* Row timelines on the rings (step 1 of the timeline scores, above; nvrx_timeline_rank and nvrx_timeline_score follow):
+ * nvrx_row_timeline on the rings as the report just issued saw them, packed by gid into d_planes [local_ranks][B][K+S] (plane
+ * b: bucket b; kernel ids first, then section ids; every slot is written, -1.0 where no row that takes part has that gid).
+ * Needs the ring-start snapshot (nvrx_onset_enable), as nvrx_stall_local does.  Ordering, desc, rows_active and the caller's
+ * duty to wait are those of nvrx_tail_local.  NVRX_ERR_STATE: the snapshot is not enabled, or no report was issued through
+ * this descriptor. */
+int nvrx_timeline_local(nvrx_ctx *ctx, const nvrx_report_desc *desc, int B, float *d_planes, int K, int S, int rows_active,
+                        void *stream);
 /* nvrx_robust_score (reporting.py:196-253, above) on the table of the report LAST issued through `desc` on `ctx` (d_table,
  * or d_send without an exchange; shape from the descriptor).  Ordered behind that report's kernels exactly as
  * nvrx_report_attribute orders itself: the context's stream, with an event when the report's last kernel ran elsewhere.  The

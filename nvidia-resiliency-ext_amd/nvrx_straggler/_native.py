@@ -22,6 +22,7 @@ STATS_STRIDE = 8
 STAT_MIN, STAT_MAX, STAT_MED, STAT_AVG, STAT_STD, STAT_NUM, STAT_WEIGHT = range(7)
 KIND_SECTION, KIND_KERNEL = 0, 1
 MAX_RING_CAP = 65536
+MAX_ROWS = 65536  # NVRX_MAX_ROWS: the most kernel ids (and section ids) a table carries
 META_WORDS = 8
 ERR_TIMEOUT = -62
 ERR_RANGE = -34
@@ -49,6 +50,7 @@ STALL_MIN_SAMPLES = 8  # NVRX_STALL_MIN_SAMPLES: shorter rows have a pace, a spr
 STALL_RATIO_PPM_MIN, STALL_RATIO_PPM_MAX = 1000001, 1000000000  # the accepted range of a stall's minimum ratio to the pace
 PROFILE_MAX_Q = 7  # NVRX_PROFILE_MAX_Q: the most quantiles a tail profile selects in its one launch
 PROFILE_LDS_SAMPLES = 8960  # NVRX_PROFILE_LDS_SAMPLES: the longest row k_row_profile keeps in LDS next to its seven group histograms
+TIMELINE_MIN_BUCKETS, TIMELINE_MAX_BUCKETS = 4, 64  # NVRX_TIMELINE_{MIN,MAX}_BUCKETS: a timeline's buckets (one wave holds them)
 HISTORY_MAX_DEPTH = 64  # NVRX_HISTORY_MAX_DEPTH: the largest depth H of a score history (the smallest is 2)
 HISTORY_RECORD_WORDS = 8  # {latest, median, worst, best, streak, below, present, depth} per (rank, family, slot)
 TREND_RECORD_WORDS = 4  # {f32 slope, f32 level, i32 S, u32 usable} per (rank, family, slot)
@@ -113,6 +115,9 @@ SYMBOLS = [
     ("nvrx_stall_score", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("nvrx_row_profile", c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_uint32), c_int, c_void_p, c_void_p]),
     ("nvrx_profile_score", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("nvrx_row_timeline", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("nvrx_timeline_rank", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_timeline_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -181,6 +186,7 @@ SYMBOLS = [
     ("nvrx_ramp_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_stall_local", c_int, [c_void_p, POINTER(ReportDesc), c_uint32, c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_profile_local", c_int, [c_void_p, POINTER(ReportDesc), POINTER(c_uint32), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    ("nvrx_timeline_local", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_robust", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_float, c_void_p]),
     ("nvrx_report_peer", c_int, [c_void_p, POINTER(ReportDesc), c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("nvrx_report_pace", c_int, [c_void_p, POINTER(ReportDesc), c_int, c_int, c_int, c_void_p]),

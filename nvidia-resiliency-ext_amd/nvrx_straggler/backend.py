@@ -348,6 +348,32 @@ class ProfileScores:
         return self._host
 
 
+class TimelineScores:
+    """The timeline scores of one report (``nvrx_timeline_local`` -> ``nvrx_timeline_rank`` -> exchange ->
+    ``nvrx_timeline_score``), enqueued and not waited for: once the score kernel has run, the workspace's timeline buffer holds
+    the gathered blocks ``[R][2][3][B]`` and, behind them, the records ``[n_ranks][2][4 + B]`` of the reported ranks.
+    ``records()`` waits for it and takes the private host copy, as ``ProfileScores.records`` does."""
+
+    __slots__ = ("backend", "d_ptr", "R", "B", "first_rank", "n_ranks", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, B: int, first_rank: int, n_ranks: int):
+        self.backend, self.d_ptr = backend, buf.data_ptr()
+        self.R, self.B, self.first_rank, self.n_ranks = R, B, first_rank, n_ranks
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(blocks [n_ranks, 2, 3, B] f32, records [n_ranks, 2, 4 + B] u32)`` of the reported ranks (private copies; a
+        record's words from the fourth on are f32 bit patterns); the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.timeline_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class _FamilyBuffers:
     """A workspace's device buffers of one row family, and the handle that may still be using them."""
 
@@ -894,6 +920,35 @@ class Workspace:
         if last is not None:
             last.records()
 
+    # ---- timeline scores (off unless a ReportGenerator asks: nothing is allocated before) --------------------------------
+    _timeline_state = None  # (B, buf, planes, send, table) once the step has run on this workspace
+    _timeline_last = None   # the TimelineScores whose kernel may still be reading the blocks / writing the records
+
+    def timeline_buffers(self, B: int):
+        """``(planes, send, table, records)`` of the timeline scores with ``B`` buckets (cold: allocated on first use, and again
+        behind ``timeline_settle`` should B change): ``planes`` ``[local_ranks][B][K+S]`` are the row timelines, which stay on
+        this process; ONE buffer holds the gathered blocks ``[R][2 * 3 * B]`` and then the records ``[R][2][4 + B]`` (one
+        copy-out); ``send`` are this process' blocks (the table's own without an exchange)."""
+        st = self._timeline_state
+        if st is None or st[0] != B:
+            self.timeline_settle()
+            KS, R, dev = self.K + self.S, self.R, self._backend.device
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                buf = torch.empty(R * 6 * B + R * 2 * (4 + B), dtype=torch.float32, device=dev)
+                table = buf[: R * 6 * B].view(R, 6 * B)
+                send = table if R == self.local_ranks else torch.empty((self.local_ranks, 6 * B), dtype=torch.float32, device=dev)
+                planes = torch.empty(max(self.local_ranks * B * KS, 64), dtype=torch.float32, device=dev)
+            st = self._timeline_state = (B, buf, planes, send, table)
+        _, buf, planes, send, table = st
+        return planes, send, table, buf[table.numel():]
+
+    def timeline_settle(self) -> None:
+        """Before anything rewrites the timeline's buffers: the last timeline step's kernels have run and their results are on
+        the host (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        last, self._timeline_last = self._timeline_last, None
+        if last is not None:
+            last.records()
+
     def settle_readers(self) -> None:
         """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
         reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps, stalls, the tail profile -- has run and delivered; and so has the
@@ -910,6 +965,8 @@ class Workspace:
                 self.family_settle(fam)
         if self._profile_last is not None:
             self.profile_settle()
+        if self._timeline_last is not None:
+            self.timeline_settle()
         if self._history_last is not None:
             self.history_settle()
         if self._trend_last is not None:
@@ -1417,6 +1474,55 @@ class HipBackend:
                                                     self.stream_handle))
         self.stream.synchronize()
         return out[:, :rows]
+
+    def timeline_score(self, ws, table, first_rank: int = 0, n_ranks: Optional[int] = None, min_rows: int = 8,
+                       effect_ppm: int = 30000, breadth_ppm: int = 900000) -> TimelineScores:
+        """Timeline records for ranks ``[first_rank, first_rank + n_ranks)`` from the gathered blocks ``table`` ([R, 2 * 3 * B],
+        ``Rings.timeline_local``'s): ``nvrx_timeline_score`` enqueued on the backend's stream.  Nothing is waited for."""
+        n_ranks = ws.R - first_rank if n_ranks is None else n_ranks
+        B = table.shape[1] // 6
+        _, _, blocks, records = ws.timeline_buffers(B)
+        assert table.data_ptr() == blocks.data_ptr()
+        rc = self.lib.nvrx_timeline_score(blocks.data_ptr(), ws.R, B, first_rank, n_ranks, min_rows, effect_ppm, breadth_ppm,
+                                          records.data_ptr(), self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._timeline_last = TimelineScores(self, ws._timeline_state[1], ws.R, B, first_rank, n_ranks)
+        return out
+
+    def timeline_copy_out(self, t: TimelineScores):
+        """The one wait of a report's timeline scores: a D2H of its blocks and records on the backend's stream, behind the kernels."""
+        B = t.B
+        n = t.R * 6 * B + t.n_ranks * 2 * (4 + B)
+        host = np.empty(n, dtype=np.float32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, n * 4, self._stream_handle))
+        blocks = host[: t.R * 6 * B].reshape(t.R, 2, 3, B)[t.first_rank : t.first_rank + t.n_ranks].copy()
+        return blocks, host[t.R * 6 * B :].view(np.uint32).reshape(t.n_ranks, 2, 4 + B).copy()
+
+    def row_timeline(self, samples: torch.Tensor, counts: torch.Tensor, B: int, starts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Stateless row timelines on caller tensors ([rows, stride] f32, [rows] u32/i32 counts and ring starts) -> [B, rows]
+        f32 bucket ratios, -1.0 where a row does not take part (``nvrx_row_timeline``)."""
+        rows, stride = samples.shape
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((max(B, 1), max(rows, 1)), dtype=torch.float32, device=samples.device)
+            _native.check(self.lib.nvrx_row_timeline(samples.data_ptr(), counts.data_ptr(),
+                                                     starts.data_ptr() if starts is not None else None, rows, stride, B,
+                                                     out.data_ptr(), self.stream_handle))
+        self.stream.synchronize()
+        return out[:, :rows]
+
+    def timeline_rank(self, planes: torch.Tensor, K: int, S: int, effect_ppm: int) -> torch.Tensor:
+        """Stateless rank timelines on a caller tensor ([ranks, B, K+S] f32 bucket ratios, -1.0 = none) -> [ranks, 2, 3, B] f32
+        ``{rows, level, slower}`` per family (``nvrx_timeline_rank``)."""
+        ranks, B, _ = planes.shape
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((ranks, 2, 3, B), dtype=torch.float32, device=planes.device)
+            _native.check(self.lib.nvrx_timeline_rank(planes.data_ptr(), ranks, B, K, S, effect_ppm, out.data_ptr(),
+                                                      self.stream_handle))
+        self.stream.synchronize()
+        return out
 
     def _row_op(self, fam: RowFamily, samples: torch.Tensor, counts: torch.Tensor, param: int,
                 starts: Optional[torch.Tensor]) -> torch.Tensor:
@@ -2298,6 +2404,25 @@ class HipRings:
         send, table, _, _ = ws.profile_buffers(Q)
         rc = self.lib.nvrx_profile_local(self.ctx, ws.block.desc_ref if fused else None, q, Q, send.data_ptr(), ws.K, ws.S,
                                          rows_active, self.backend._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        self.backend.stream.synchronize()
+        return send, table
+
+    def timeline_local(self, ws: Workspace, B: int, effect_ppm: int, rows_active: int = 0, fused: bool = False):
+        """The timeline's two local kernels: the ring kernel over every ring row as the report just issued on ``ws`` saw it,
+        packed by gid into the workspace's planes (``nvrx_timeline_local``; ``fused`` as for ``_family_local``; needs
+        ``onset_enable``'s ring-start snapshot), then ``nvrx_timeline_rank`` on those planes.  Returns ``(send [local_ranks,
+        2 * 3 * B], table [R, 2 * 3 * B])`` -- the same rows when nothing is exchanged.  Waits for the kernels, as
+        ``_family_local`` does and for its reason."""
+        assert self.onset_enabled, "timeline_local() before onset_enable(): no ring-start snapshot"
+        ws.timeline_settle()
+        planes, send, table, _ = ws.timeline_buffers(B)
+        rc = self.lib.nvrx_timeline_local(self.ctx, ws.block.desc_ref if fused else None, B, planes.data_ptr(), ws.K, ws.S,
+                                          rows_active, self.backend._stream_handle)
+        if rc >= 0:
+            rc = self.lib.nvrx_timeline_rank(planes.data_ptr(), ws.local_ranks, B, ws.K, ws.S, effect_ppm, send.data_ptr(),
+                                             self.backend._stream_handle)
         if rc < 0:
             _native.check(rc)
         self.backend.stream.synchronize()

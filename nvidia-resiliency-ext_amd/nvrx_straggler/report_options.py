@@ -193,6 +193,8 @@ GROUPS: Tuple[OptionGroup, ...] = (
     OptionGroup(("ramp_detection", "ramp_min_segment", "ramp_min_strength")),
     OptionGroup(("stall_detection", "stall_min_ratio", "stall_min_z", "stall_min_share")),
     OptionGroup(("tail_profile",)),  # (None and () are off)
+    OptionGroup(("timeline_scores", "timeline_buckets", "timeline_min_rows", "timeline_min_effect", "timeline_min_breadth",
+                 "timeline_min_buckets")),
 )
 
 

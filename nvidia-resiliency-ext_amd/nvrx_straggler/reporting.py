@@ -758,6 +758,38 @@ class _ProfileSource:
         return self._built
 
 
+class _TimelineSource:
+    """What a report keeps of its timeline scores: the backend's handle (``records()`` waits for the kernels and copies the
+    ranks' blocks and records out on first use), the ranks its rows stand for, and the parameters."""
+
+    __slots__ = ("handle", "ranks", "params", "_built")
+
+    def __init__(self, handle, ranks, params: dict):
+        self.handle, self.ranks, self.params = handle, tuple(ranks), params
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            blocks, records = self.handle.records()
+            B = blocks.shape[3]
+            rel = np.ascontiguousarray(records[:, :, 4:]).view(np.float32).tolist()
+            excess = np.ascontiguousarray(records[:, :, 3]).view(np.float32).tolist()
+            head, blk = records[:, :, :3].tolist(), blocks.tolist()
+
+            def part(i, f):
+                slow, first, length = head[i][f]
+                rows, _, slower = blk[i][f]
+                return {"timeline": tuple(rel[i][f]), "breadth": tuple(s / n if n else math.nan for s, n in zip(slower, rows)),
+                        "rows": tuple(int(n) for n in rows), "slow_buckets": slow, "excess": excess[i][f],
+                        "began_at": first / B if length else None, "ended_at": (first + length) / B if length else None,
+                        "ended_buckets_ago": B - first - length if length else None}
+
+            self._built = {"buckets": B, "params": dict(self.params),
+                           "ranks": {r: {"gpu": part(i, 0), "sections": part(i, 1)} for i, r in enumerate(self.ranks)}}
+            self.handle = None
+        return self._built
+
+
 class _RowGroupFamilySource(_RowFamilySource):
     """What a report keeps of one row family's scores per peer group (``ReportGenerator(row_peer_groups=True)``):
     ``_RowFamilySource``'s, the resolved groups and ``min_peers``.  The handle's ``records()`` delivers the column records
@@ -1584,6 +1616,9 @@ class Report:
         profile = self.__dict__.get("_profile")
         if profile is not None:
             state["_profile"] = profile.build() if isinstance(profile, _ProfileSource) else profile
+        timeline = self.__dict__.get("_timeline")
+        if timeline is not None:
+            state["_timeline"] = timeline.build() if isinstance(timeline, _TimelineSource) else timeline
         return state
 
     def __setstate__(self, state) -> None:
@@ -1813,6 +1848,56 @@ class Report:
         return {"straggler_gpus_relative": self._ids(gpus),
                 "straggler_sections_relative": {n: self._ids(found) for n, found in sections.items()},
                 "slow_share": {"gpus": gpus, "sections": sections}}
+
+    def timeline_scores(self) -> Dict[str, Any]:
+        """Timeline scores (``ReportGenerator(timeline_scores=True)``; ``{}`` when the report carries none): WHEN, inside the
+        window, a whole rank ran slow.  The pace scores find a rank that is a little slower in nearly all its rows for the whole
+        window; a card that drops a clock step for a tenth of it moves no median, and no single row's quantile or stretch
+        leaves its noise.  Here every row is cut into ``buckets`` buckets of its own samples, a bucket's mean is divided by the
+        row's typical (lower-median) bucket, and per rank and bucket the lower median of those ratios across the rank's rows
+        is its ``level``; the reference of a bucket is the smallest level of any rank with at least ``min_rows`` rows there.
+
+        ``{"buckets": B, "params": {"min_rows", "min_effect", "min_breadth", "min_buckets"}, "ranks": {rank: {"gpu": {...},
+        "sections": {...}}}}``.  A part holds ``timeline`` (B values level / reference, NaN where the rank has fewer than
+        ``min_rows`` rows in the bucket), ``breadth`` (per bucket the share of its rows more than ``min_effect`` above their own
+        typical bucket; NaN without rows), ``rows`` (per bucket, how many took part: rows with fewer than four samples per
+        bucket do not), ``slow_buckets`` (buckets with ``timeline >= 1 + min_effect`` and ``breadth >= min_breadth``),
+        ``excess`` (the mean of ``timeline`` over the longest run of consecutive slow buckets, the most recent among equal
+        ones; 1.0 without a run), ``began_at`` / ``ended_at`` (that run as fractions of the window; None without one) and
+        ``ended_buckets_ago``.  A stretch every rank shares -- a checkpoint -- raises the reference too and shows nowhere.
+        Buckets are fractions of each row's OWN samples: rows line up in time only if they run evenly through the window, a
+        row whose ring wrapped covers the window's end only, and ranks line up bucket for bucket only in a lockstep job.
+        Plain dicts, tuples, floats and ints.  The first call waits for the timeline kernels and copies their results;
+        ``generate_report`` does not."""
+        timeline = self.__dict__.get("_timeline")
+        if timeline is None:
+            return {}
+        if isinstance(timeline, _TimelineSource):
+            timeline = self.__dict__["_timeline"] = timeline.build()
+        return _copy_scores(timeline)
+
+    def identify_timeline_stragglers(self, min_buckets: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks that ran slow in nearly everything for a stretch of the window: a part of a rank (its kernels, its sections)
+        is named iff its longest run of consecutive slow buckets is at least ``min_buckets`` long (the generator's
+        ``timeline_min_buckets`` unless told otherwise: 2, a default, not a measurement).  ``{'straggler_gpus_relative':
+        set[StragglerId], 'straggler_section_ranks_relative': set[StragglerId], 'runs': {'gpus': {rank: (first bucket,
+        buckets)}, 'sections': {rank: (first bucket, buckets)}}}``.  Empty when the report carries no timeline scores."""
+        t = self.timeline_scores()
+        B = t.get("buckets", 0)
+        least = t["params"]["min_buckets"] if t and min_buckets is None else min_buckets
+
+        def runs(part):
+            found = {}
+            for r, d in t.get("ranks", {}).items():
+                if d[part]["began_at"] is not None:
+                    first, end = round(d[part]["began_at"] * B), round(d[part]["ended_at"] * B)
+                    if end - first >= least:
+                        found[r] = (first, end - first)
+            return found
+
+        gpus, sections = runs("gpu"), runs("sections")
+        return {"straggler_gpus_relative": self._ids(gpus), "straggler_section_ranks_relative": self._ids(sections),
+                "runs": {"gpus": gpus, "sections": sections}}
 
     def robust_scores(self) -> Dict[str, Any]:
         """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
@@ -2393,7 +2478,8 @@ def steps_behind_report(generator) -> tuple:
                  or getattr(generator, "pace_scores", False) or getattr(generator, "node_scores", False)
                  or getattr(generator, "score_history", 0))
     ring = bool(any(getattr(generator, fam.param_attrs[0], 0) for fam in row_families.ROW_STEPS)
-                or getattr(generator, "tail_profile_ppm", ()) or getattr(generator, "collective_slack", False))
+                or getattr(generator, "tail_profile_ppm", ()) or getattr(generator, "timeline_b", 0)
+                or getattr(generator, "collective_slack", False))
     return table, ring
 
 
@@ -2415,6 +2501,8 @@ class ReportGenerator:
             on some rank enters the reports one report later (the name exchange is a host collective and runs at the
             start of the next ``generate_report``, when every rank is there).
     """
+
+    timeline_b = 0  # the timeline's buckets; a generator with timeline_scores on holds its own, and timeline_params
 
     def __init__(self, scores_to_compute, gather_on_rank0=True, pg=None, node_name="<notset>",
                  thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
@@ -2438,7 +2526,9 @@ class ReportGenerator:
                  ramp_detection: bool = False, ramp_min_segment: float = 0.05, ramp_min_strength: float = 0.5,
                  robust_peer_groups: bool = False, stall_detection: bool = False, stall_min_ratio: float = 1.5,
                  stall_min_z: float = 6.0, stall_min_share: float = 0.01, node_peer_groups: bool = False,
-                 peer_attribution: int = 0, tail_profile: Optional[Sequence[float]] = None) -> None:
+                 peer_attribution: int = 0, tail_profile: Optional[Sequence[float]] = None, timeline_scores: bool = False,
+                 timeline_buckets: int = 32, timeline_min_rows: int = 8, timeline_min_effect: float = 0.03,
+                 timeline_min_breadth: float = 0.9, timeline_min_buckets: int = 2) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2745,6 +2835,26 @@ class ReportGenerator:
         if self.tail_profile_ppm:
             opts.needs_relative(f"tail_profile={tail_profile!r}", scores_to_compute, "profile scores are relative scores")
             opts.needs_backend(f"tail_profile={tail_profile!r}", "tail profile", "profile_score")
+        # timeline scores: every ring report also says when, inside its window, a whole rank ran slow (Report.timeline_scores,
+        # Report.identify_timeline_stragglers); off (timeline_b == 0): no buffer, no launch, no collective, no backend call.
+        # The step adds one collective per report, so EVERY rank must pass the same values.  32 buckets, 8 rows, 0.03, 0.9 and
+        # 2 buckets are defaults, not measurements.  (Checked behind every other option.  Off, the generator holds no attribute
+        # of it: timeline_b is the class' 0.)
+        if timeline_scores:
+            B = opts.integer("timeline_buckets", timeline_buckets, "an integer within [4, 64]", 4, 64)
+            rows = opts.integer("timeline_min_rows", timeline_min_rows, "an integer within [1, 65536]", 1, 65536)
+            effect = opts.number("timeline_min_effect", timeline_min_effect, "a number within (0, 1]", 0.0, 1.0, lo_open=True,
+                                 no_bool=True)
+            breadth = opts.number("timeline_min_breadth", timeline_min_breadth, "a number within (0, 1]", 0.0, 1.0, lo_open=True,
+                                  no_bool=True)
+            least = opts.integer("timeline_min_buckets", timeline_min_buckets, f"an integer within [1, timeline_buckets={B}]", 1, B)
+            opts.needs_relative("timeline_scores", scores_to_compute, "timeline scores compare ranks")
+            opts.needs_backend("timeline_scores", "timeline scores", "timeline_score")
+            self.timeline_b = B
+            self.timeline_params = {"min_rows": rows, "min_effect": effect, "min_breadth": breadth, "min_buckets": least}
+        # what names the ring-start snapshot's user where the backend has none: a row family, else the timeline
+        self._starts_option = (self._starts_family.option if self._starts_family is not None
+                               else "timeline_scores" if self.timeline_b else None)
         # what follows a report, decided here once (nothing assigns the options later): whether any table follow-up
         # (_follow_ups) is on, whether any ring step (_ring_steps) is, and what the one-call route needs of its rings
         self._table_steps_on, self._ring_steps_on = steps_behind_report(self)
@@ -2829,7 +2939,8 @@ class ReportGenerator:
             # with one stay on that route as a whole (the option has the same value on every rank, so every rank decides alike
             # -- no collective here).  A row family that is on is the one named.
             option, what = ((self._row_families[0].option, self._row_families[0].name) if self._row_families
-                            else ("tail_profile", "profile") if self.tail_profile_ppm else ("collective_slack", "slack"))
+                            else ("tail_profile", "profile") if self.tail_profile_ppm
+                            else ("timeline_scores", "timeline") if self.timeline_b else ("collective_slack", "slack"))
             self._direct = None
             self.exchange_info = {"route": f"torch.distributed all-gather on the job's own process group ({option} is "
                                            f"set: reports with {what} scores do not use the in-stream routes)", "mode": "c10d"}
@@ -3478,13 +3589,15 @@ class ReportGenerator:
 
     def _ring_steps(self, report, rings, ws, mapper, rows_active: int, fused: bool, local_ranks: int) -> None:
         """The ring steps of one ``generate_report_from_rings`` call: the families that are switched on, in the table's order,
-        then the tail profile, then slack -- the order of their collectives, the same on every rank whatever ``report`` is."""
+        then the tail profile, then the timeline, then slack -- the order of their collectives, the same on every rank whatever ``report`` is."""
         if not self._ring_steps_on:
             return
         for fam in self._row_families:
             self._family_step(fam, report, rings, ws, mapper, rows_active, fused, local_ranks)
         if self.tail_profile_ppm:
             self._profile_step(report, rings, ws, mapper, rows_active, fused, local_ranks)
+        if self.timeline_b:
+            self._timeline_step(report, rings, ws, rows_active, fused, local_ranks)
         if self.collective_slack:
             self._slack_step(report, rings, ws, rows_active, fused, local_ranks)
 
@@ -3506,6 +3619,26 @@ class ReportGenerator:
         view = report.__dict__["_src"].view
         handle = score(ws, table, ws.table, lo, hi - lo, q_ppm)
         report.__dict__["_profile"] = _ProfileSource(handle, view.ranks, view.cols, self._attr_names(mapper, ws.K), q_ppm)
+
+    def _timeline_step(self, report, rings, ws, rows_active: int, fused: bool, local_ranks: int) -> None:
+        """The timeline's step of a ring report, behind the tail profile's and ahead of slack, on the same workspace: its ring
+        kernel on the window the report saw and its rank kernel -> [one all-gather of the ranks' blocks, 2 x 3 x B floats each]
+        -> its score kernel for the ranks the report covers, hung on ``report`` unread.  Like a family's step, every rank
+        issues it at every report, whatever the report found and whether or not it holds a report: same collectives
+        everywhere.  (A step of its own and no ``RowFamily`` record: what it exchanges is per rank, not per column.)"""
+        be = _backend_mod.get_backend()
+        local, score = getattr(rings, "timeline_local", None), getattr(be, "timeline_score", None)
+        if local is None or score is None:
+            raise RuntimeError("timeline_scores: the active backend has no timeline scores (rings.timeline_local / "
+                               "backend.timeline_score)")
+        p = self.timeline_params
+        effect_ppm, breadth_ppm = int(round(p["min_effect"] * 1e6)), int(round(p["min_breadth"] * 1e6))
+        table = self._gather_step_rows(be, *local(ws, self.timeline_b, effect_ppm, rows_active, fused))
+        if report is None or report is False:
+            return
+        lo, hi = self._covered(ws, local_ranks)
+        handle = score(ws, table, lo, hi - lo, p["min_rows"], effect_ppm, breadth_ppm)
+        report.__dict__["_timeline"] = _TimelineSource(handle, report.__dict__["_src"].view.ranks, p)
 
     def _gather_step_rows(self, be, send, table):
         """Exchange a ring step's rows behind its local kernel: its one collective, on the backend's stream."""
@@ -3620,9 +3753,9 @@ class ReportGenerator:
         """
         t0 = time.perf_counter_ns()
         self.world_size, self.rank = dist_utils.world_and_rank(self.group, self._wr_cache)
-        if self._starts_family is not None and not getattr(rings, "onset_enabled", False):
+        if self._starts_option is not None and not getattr(rings, "onset_enabled", False):
             if not hasattr(rings, "onset_enable"):
-                raise RuntimeError(f"{self._starts_family.option}: the active backend has no ring-start snapshot (rings.onset_enable)")
+                raise RuntimeError(f"{self._starts_option}: the active backend has no ring-start snapshot (rings.onset_enable)")
             rings.onset_enable(True)  # (before this window's report: it notes where every ring's oldest sample lives)
         if not self._direct_tried and self.world_size != 1:  # (a single process has no route to build)
             self._maybe_create_direct_exchange()

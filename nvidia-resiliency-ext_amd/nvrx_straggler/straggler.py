@@ -455,6 +455,12 @@ class Detector(metaclass=_DeviceSideOnDemand):
         stall_min_z: float = 6.0,
         stall_min_share: float = 0.01,
         tail_profile=None,
+        timeline_scores: Optional[bool] = None,
+        timeline_buckets: Optional[int] = None,
+        timeline_min_rows: int = 8,
+        timeline_min_effect: float = 0.03,
+        timeline_min_breadth: float = 0.9,
+        timeline_min_buckets: int = 2,
     ):
         """
         Args:
@@ -649,6 +655,24 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 for the one quantile it was given: a rank 1.4 x slower on 2 % of its samples is invisible at 0.95.  Needs
                 ``relative_perf_scores``.  Default: ``NVRX_TAIL_PROFILE`` (comma-separated, ``0.9,0.99,0.999``), else off.
                 Pass the same values on EVERY rank (the step adds one collective per report).
+            timeline_scores: every report also says WHEN, inside its window, a whole rank ran slow (a clock step down, a power
+                cap, a thermal excursion: 3-5 % on every kernel for part of the window).  Every section and kernel row is cut
+                into ``timeline_buckets`` buckets of its own samples, each bucket's mean is divided by the row's typical
+                bucket, and per rank and bucket the lower median across the rows is compared with the fastest rank's
+                (``Report.timeline_scores()``, ``Report.identify_timeline_stragglers()``).  No median moves in such a window,
+                and no single row's quantile, stretch or hinge leaves its noise: the evidence is that the rows agree in
+                time.  Needs ``relative_perf_scores``.  Default: ``NVRX_TIMELINE_SCORES`` (0 or 1), else off.  Pass the
+                same values on EVERY rank (the step adds one collective per report).
+            timeline_buckets: buckets per window, an integer within [4, 64]; rows with fewer than four samples per bucket
+                take no part.  Default: ``NVRX_TIMELINE_BUCKETS``, else 32 -- a default, not a measurement.
+            timeline_min_rows: a rank's bucket is rated where at least this many of its rows take part (>= 1).  8 is a
+                default, not a measurement.
+            timeline_min_effect: a bucket is slow where the rank's level is at least ``1 + timeline_min_effect`` times the
+                fastest rank's, within (0, 1].  0.03 is a default, not a measurement.
+            timeline_min_breadth: ... and at least this share of its rows are that much above their own typical bucket,
+                within (0, 1].  0.9 is a default, not a measurement.
+            timeline_min_buckets: a rank is named for a run of at least this many consecutive slow buckets (>= 1).  2 is a
+                default, not a measurement.
             slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
                 peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
                 expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
@@ -779,6 +803,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
         stall_detection = opts.env_flag(stall_detection, "NVRX_STALL_DETECTION")
         tail_profile = opts.env_numbers(tail_profile, "NVRX_TAIL_PROFILE", "NVRX_TAIL_PROFILE must be comma-separated numbers "
                                         "(0.9,0.99,0.999), got {value!r}")
+        timeline_scores = opts.env_strict_flag(timeline_scores, "NVRX_TIMELINE_SCORES")
+        if timeline_scores:
+            timeline_buckets = opts.env_number(timeline_buckets, "NVRX_TIMELINE_BUCKETS", int, 32,
+                                               "NVRX_TIMELINE_BUCKETS must be an integer within [4, 64], got {value!r}")
         # (report_options.GROUPS: the options that are off are left out, so the generator is built exactly as before they existed)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), **opts.forwarded(locals()))
