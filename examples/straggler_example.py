@@ -682,6 +682,57 @@ def timeline(slow: int = 5) -> None:
         job.close()
 
 
+def comove_samples(rank: int, ranks: int = 32, per_node: int = 8, kernels: int = 120, samples: int = 10000, dipped=(1, 2),
+                   span=(6000, 7000), alone: int = 5, alone_span=(2000, 3000)):
+    """One rank of the ``--comove`` job: ``[kernels, samples]`` f64 microseconds (NumPy only), per-kernel levels around 100 us
+    with 1 % noise; the ranks of the nodes ``dipped`` are 2 % slower in every kernel on the samples of ``span``, and rank
+    ``alone`` is 2 % slower on those of ``alone_span``, by itself."""
+    import numpy as np
+
+    levels = np.random.default_rng(61).lognormal(np.log(100.0), 0.5, kernels)
+    x = levels[:, None] * (1.0 + 0.01 * np.random.default_rng(6100 + rank).standard_normal((kernels, samples)))
+    if rank // per_node in dipped:
+        x[:, span[0]:span[1]] *= 1.02
+    if rank == alone:
+        x[:, alone_span[0]:alone_span[1]] *= 1.02
+    return x
+
+
+def comove(ranks: int = 32, per_node: int = 8) -> None:
+    """Two nodes whose sixteen ranks dip 2 % together for a tenth of the window, and one rank that dips alone, under the
+    timeline, pace and node scores -- none of which names anybody -- and the co-movement groups."""
+    import numpy as np
+
+    from nvrx_straggler.folded import FoldedJob
+
+    torch.cuda.set_device(0)
+    kernels, samples = comove_samples(0).shape
+    job = FoldedJob(total_ranks=ranks, section_names=["step"], ring_cap=samples, scores_to_compute=("relative_perf_scores",),
+                    kernel_names=[f"kernel_{k:03d}" for k in range(kernels)], pace_scores=True, node_scores=True,
+                    node_groups=f"block:{per_node}", timeline_scores=True, comovement_groups=True)
+    try:
+        for lr, r in enumerate(job.logical_ranks()):
+            x = comove_samples(r, ranks, per_node)
+            job.load(lr, x.sum(axis=0, keepdims=True).astype(np.float32))
+            job.load_kernels(lr, x.astype(np.float32))
+        report = job.report()
+        print(f"identify_pace_stragglers(): {named_ranks(report.identify_pace_stragglers())}")
+        print(f"identify_node_stragglers(): {sorted(report.identify_node_stragglers()['straggler_nodes'], key=str)}")
+        found = report.identify_timeline_stragglers()
+        print(f"identify_timeline_stragglers(): {named_ranks({k: v for k, v in found.items() if k != 'runs'})}")
+        found = report.identify_comoving_stragglers()
+        c = report.comovement_groups()
+        print(f"identify_comoving_stragglers(): {named_ranks({k: v for k, v in found.items() if k != 'groups'})}; rule {c['params']}")
+        for root, g in c["groups"]["gpu"].items():
+            print(f"group {root}: ranks {g['ranks']} (nodes {sorted({r // per_node for r in g['ranks']})}), "
+                  f"{'a chain' if g['loose'] else 'a clique'}, {100 * g['excess']:+.2f} % from {g['began_at']} to {g['ended_at']} "
+                  f"of the window")
+        alone = [r for r, d in c["ranks"].items() if d["gpu"]["active"] and d["gpu"]["size"] == 1]
+        print(f"active without a partner: {alone}")
+    finally:
+        job.close()
+
+
 def named_ranks(found) -> list:
     """The ranks an ``identify_*_stragglers()`` result names, in any of its mappings."""
     return sorted({s.rank for v in found.values() for group in (v.values() if isinstance(v, dict) else [v]) for s in group})
@@ -1171,7 +1222,14 @@ def main() -> None:
     ap.add_argument("--timeline", action="store_true",
                     help="no training: play the timeline scenario (8 ranks x 120 kernels, rank 5 4 %% slower in every kernel on "
                          "a tenth of the window) under every score of a report and the timeline scores, and exit")
+    ap.add_argument("--comove", action="store_true",
+                    help="no training: play the co-movement scenario (32 ranks on 4 nodes x 120 kernels, nodes 1 and 2 2 %% "
+                         "slower together on a tenth of the window, rank 5 alone on another) under the pace, node and "
+                         "timeline scores and the co-movement groups, and exit")
     args = ap.parse_args()
+    if args.comove:
+        comove()
+        return
     if args.timeline:
         timeline()
         return

@@ -1046,6 +1046,48 @@ size_t nvrx_rowfam_group_words(int G, int K, int S, int n_ranks);
 int nvrx_work_words(int R, int K, int S);
 int nvrx_work_groups(const float *d_table, int R, int K, int S, float count_tol, int max_unlike_ppm, void *d_out, void *stream);
 
+/* Co-movement groups: WHICH ranks ran slow (or fast) at the same times.  Every score above rates a rank, or a node it was told
+ * about; a cause above a node -- a PDU, a cooling loop, a rack switch, a shared mount -- moves many ranks a little at the same
+ * times, each below its own threshold.  The evidence is that the ranks agree with each other in time.  Everything is per
+ * family (0: kernel columns, 1: section columns) and from the timeline's gathered blocks d_blocks [R][2][3][B] alone
+ * (nvrx_timeline_rank: fields {rows, level, slower}); R <= NVRX_WORK_MAX_RANKS; T = ceil(R / 64).
+ * 1. Centre.  A rank is RATED at bucket b iff rows[r][b] >= min_rows.  n[b] = the rated ranks; c[b] = the lower median of
+ *    level[r][b] over them (rank (n - 1) / 2; +0.0 when n == 0).  A bucket is USABLE iff n[b] >= 3 and c[b] > 0.  The median
+ *    and not the timeline's fastest-rank reference: one rank's noise must not be imprinted on everybody as a shared pattern,
+ *    and a stretch the whole job shares (a checkpoint) cancels.
+ * 2. Deviation.  d[r][b] = (float)((double)level / (double)c - 1.0) where the bucket is usable and the rank rated, else 0.
+ *    peak[r] = max_b |d[r][b]|, peak_bucket the lowest such b.  A rank is ACTIVE iff peak >= (float)(amplitude_ppm / 1e6).
+ * 3. Unit timeline.  x[r][b] = (float)((double)d / sqrt(sum_b (double)d * (double)d)) for active ranks (the sum in f64, its
+ *    order unspecified: x is good to 1 ulp), all zeros for inactive ranks, zero in buckets B..63.  X [R][64] f32.
+ * 4. Similarity.  s[i][j] = sum_b x[i][b] * x[j][b] in f32 (64 multiply-adds, order unspecified, but s[i][j] and s[j][i] are the
+ *    same bits).  There is an EDGE between i != j iff both are active and s >= (float)(similarity_ppm / 1e6).  nvrx_comove_pairs
+ *    takes any X [R][64] of finite floats, 16-byte aligned; there a rank is active iff its row has a nonzero element.
+ * 5. Groups.  Connected components over the edges; the root is the component's lowest rank; an inactive rank is its own
+ *    component of size 1.
+ * d_out, 16-byte aligned, nvrx_comove_words(R, B) 32-bit words, every part on a 16-byte boundary:
+ *   centre  at 0            [2][64] f32 c, then [2][64] u32 n (zero from bucket B on)
+ *   rank    at 256          [2][R][8]  {i32 root, u32 size, u32 partners (edges), i32 best partner, f32 best s, f32 peak,
+ *                           u32 peak_bucket | 0x100 if active, i32 sign of d at peak_bucket}.  The best partner is the other
+ *                           active rank with the largest s, the lower rank on a tie, whether or not there is an edge; -1 and
+ *                           s = 0 for an inactive rank or without another active one.  A group is LOOSE iff some member has
+ *                           partners + 1 < size (a chain, not a clique).
+ *   dev     behind it       [2][R][64] f32 d
+ *   unit    behind it       [2][R][64] f32 x
+ *   adj     behind it       [2][R][T] u64: bit j % 64 of word j / 64 of row i is the edge (i, j); bits at or beyond R are clear
+ *   part    behind it       [2][R][T] {f32 s, i32 partner}: the best partner of rank i among the 64 ranks of tile t
+ * nvrx_comove_unit runs steps 1-3 (it writes centre, dev, unit and words 5..7 of the rank records); nvrx_comove_pairs runs steps
+ * 4-5 on the caller's d_x for family 0 (adj, part and the rank records of family 0, words 5..7 as 0; it neither reads nor
+ * writes unit); nvrx_comove_groups runs all of it for both families.  No float atomics, no atomics on global memory, no scratch.
+ * Argument errors, reported before any device is touched: NVRX_ERR_INVALID for R <= 0, then NVRX_ERR_RANGE for R >
+ * NVRX_WORK_MAX_RANKS, a B outside the timeline's range, min_rows outside [1, NVRX_MAX_ROWS], amplitude_ppm or similarity_ppm
+ * outside [1, 1000000], then NVRX_ERR_INVALID for a null pointer or a d_out (d_x) that is not 16-byte aligned.
+ * nvrx_comove_words returns the block's size, or the error for that shape. */
+int nvrx_comove_words(int R, int B);
+int nvrx_comove_unit(const float *d_blocks, int R, int B, uint32_t min_rows, uint32_t amplitude_ppm, void *d_out, void *stream);
+int nvrx_comove_pairs(const float *d_x, int R, uint32_t similarity_ppm, void *d_out, void *stream);
+int nvrx_comove_groups(const float *d_blocks, int R, int B, uint32_t min_rows, uint32_t amplitude_ppm, uint32_t similarity_ppm,
+                       void *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Context: device ring buffers + pinned staging + hipEvent timing for `local_ranks` logical ranks
  * of `rows_per_rank` rows each (one logical rank per GPU in production; several per GPU only when a

@@ -4036,6 +4036,7 @@ int nvrx_wait(nvrx_ctx *ctx) {
 #include "nvrx_rowfam_group.inl"
 #include "nvrx_pace.inl"
 #include "nvrx_timeline.inl"
+#include "nvrx_comove.inl"
 #include "nvrx_pace_group.inl"
 #include "nvrx_robust_group.inl"
 #include "nvrx_slack_group.inl"

@@ -21,7 +21,8 @@
 //   (non-returning LDS OR) and stored as plain 8-byte vector stores; each row's nearest of the tile is reduced from 16
 //   candidates in LDS.
 // k_work_groups  one workgroup of 1024: labels in LDS (16 KB at 4096 ranks), min-label propagation over the adjacency bits
-//   with pointer jumping until a block-wide "nothing changed" (at most R trips).  Thread r alone writes label r and labels
+//   with pointer jumping until a block-wide "nothing changed" (at most R trips; components_label in nvrx_comove.inl, which the
+//   co-movement groups share).  Thread r alone writes label r and labels
 //   only fall, towards the component's lowest rank, which is where every schedule ends.  Then sizes (LDS integer adds),
 //   {root, size} per rank and the job record.
 // k_work_rank    one wave per rank: the popcount of its adjacency row, the T partial nearest records reduced in the total
@@ -243,37 +244,8 @@ __global__ __launch_bounds__(WORK_GROUPS_THREADS) void k_work_groups(WorkArgs a)
     __shared__ int s_changed;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int R = a.R, T = a.T;
-    for (int r = tid; r < R; r += WORK_GROUPS_THREADS) s_label[r] = r, s_size[r] = 0u;
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
-    for (int trip = 0; trip < R; trip++) {  // block-uniform
-        bool changed = false;
-        for (int r = tid; r < R; r += WORK_GROUPS_THREADS) {
-            const int old = s_label[r];
-            int m = old;
-            const unsigned long long *__restrict__ row = a.adj + (size_t)r * (size_t)T;
-            for (int j = 0; j < T; j++) {
-                unsigned long long w = row[j];
-                while (w) {
-                    const int b = 64 * j + __builtin_ctzll(w);
-                    w &= w - 1;
-                    m = min(m, s_label[b]);  // (b < R: bits at or beyond R are clear)
-                }
-            }
-            if (m < old) s_label[r] = m, changed = true;
-        }
-        __syncthreads();
-        for (int r = tid; r < R; r += WORK_GROUPS_THREADS) {  // pointer jumping
-            const int l = s_label[r], ll = s_label[l];
-            if (ll < l) s_label[r] = ll, changed = true;
-        }
-        if (changed) s_changed = 1;
-        __syncthreads();
-        const int any = s_changed;
-        __syncthreads();
-        if (!any) break;
-        if (tid == 0) s_changed = 0;  // (read by nobody before the next trip's barriers)
-    }
+    for (int r = tid; r < R; r += WORK_GROUPS_THREADS) s_size[r] = 0u;
+    components_label<WORK_GROUPS_THREADS>(a.adj, R, T, s_label, &s_changed);  // (nvrx_comove.inl: the co-movement groups share it)
     for (int r = tid; r < R; r += WORK_GROUPS_THREADS) atomicAdd(&s_size[s_label[r]], 1u);
     __syncthreads();
     uint32_t groups = 0, single = 0, largest = 0, with_data = 0;

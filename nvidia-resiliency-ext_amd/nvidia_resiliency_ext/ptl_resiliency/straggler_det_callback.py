@@ -57,6 +57,7 @@ class StragglerDetectionCallback(Callback):
         min_consecutive_peer_reports: int = 1,
         slack_peer_groups: bool = False,
         node_peer_groups: bool = False,
+        warn_if_comoving: bool = False,
     ):
         """
         Args:
@@ -117,6 +118,10 @@ class StragglerDetectionCallback(Callback):
                 ``min_consecutive_reports`` does for a job without peer groups.  With ``peer_groups`` use this, not
                 ``min_consecutive_reports``: the job-wide history rates every healthy rank of a slower stage low in every
                 report and would name them all from the M-th report on.
+            warn_if_comoving: False (the default): nothing changes.  True: the detector also computes timeline scores and
+                co-movement groups (``Detector.initialize(timeline_scores=True, comovement_groups=True)``) and every report
+                logs one warning that names the groups of ranks that ran slow at the same times.  Needs
+                ``calc_relative_gpu_perf``.  Never a reason to halt.
             slack_peer_groups: False (the default): nothing changes.  True (needs ``warn_if_waited_for`` and ``peer_groups``):
                 the slack scores are taken inside each rank's own peer group
                 (``Detector.initialize(slack_peer_groups=True)``), so that a pipeline job is not warned about the healthy ranks
@@ -198,6 +203,9 @@ class StragglerDetectionCallback(Callback):
                 raise ValueError("node_peer_groups needs warn_if_node_off_pace=True: it changes what the node scores compare with")
             if peer_groups is None:
                 raise ValueError("node_peer_groups needs peer_groups: which ranks do the same work")
+        self.warn_if_comoving = bool(warn_if_comoving)
+        if self.warn_if_comoving and not calc_relative_gpu_perf:
+            raise ValueError("warn_if_comoving needs calc_relative_gpu_perf=True: co-movement groups compare ranks")
         self._unrated_said = False
         self.interval_est_was_reset = False
 
@@ -236,6 +244,8 @@ class StragglerDetectionCallback(Callback):
                 persistence["node_groups"] = self.node_groups
         if self.node_peer_groups:
             persistence["node_peer_groups"] = True
+        if self.warn_if_comoving:
+            persistence.update(timeline_scores=True, comovement_groups=True)
         straggler.Detector.initialize(
             scores_to_compute=self.scores_to_compute,
             gather_on_rank0=True,
@@ -268,6 +278,8 @@ class StragglerDetectionCallback(Callback):
             self._warn_off_pace(report)  # (likewise)
         if self.warn_if_node_off_pace and bool(report) and trainer.global_rank == 0:
             self._warn_node_off_pace(report)  # (likewise)
+        if self.warn_if_comoving and bool(report) and trainer.global_rank == 0:
+            self._warn_comoving(report)  # (likewise)
         if not detector.is_interval_elapsed():
             return  # no report was due this iteration
         if self.stop_if_detected and self._decision_of_rank0(found):
@@ -401,6 +413,22 @@ class StragglerDetectionCallback(Callback):
                          f"kernels, {d['members_off_pace']} of {d['members_rated']} GPUs off pace)")
         self.logger.warning("STRAGGLER DETECTION WARNING: Some nodes are a little slower in nearly all of their kernels on most "
                             "of their GPUs (host fault: cooling, power, host CPU?): " + "; ".join(parts))
+
+    def _warn_comoving(self, report) -> None:
+        """One warning per report that names the groups of ranks that ran slower than the job's typical rank at the same
+        times, with the stretch of the window and the nodes they sit on (``warn_if_comoving``).  Never a reason to halt."""
+        named = report.identify_comoving_stragglers()["groups"]
+        groups = report.comovement_groups().get("groups", {})
+        parts = []
+        for what, part in (("gpus", "gpu"), ("sections", "sections")):
+            for root, ranks in sorted(named[what].items()):
+                g = groups[part][root]
+                parts.append(f"{what} of ranks {ranks} ({100.0 * g['excess']:.1f} % slower from {g['began_at']:.2f} to "
+                             f"{g['ended_at']:.2f} of the window{', a chain' if g['loose'] else ''}; nodes: "
+                             f"{', '.join(map(str, g['nodes'])) or 'unknown'})")
+        if parts:
+            self.logger.warning("STRAGGLER DETECTION WARNING: Some ranks ran slow at the same times (a shared cause above the "
+                                "node: power, cooling, a switch, a mount?): " + "; ".join(parts))
 
     def _name_the_kernels(self, report, flagged) -> None:
         """Kernel attribution (``NVRX_KERNEL_ATTRIBUTION=N``, off by default: nothing is logged then): for every flagged GPU the

@@ -61,6 +61,8 @@ SLACK_GROUP_HEAD_WORDS = 8 + 4 * SLACK_COLS  # per group of nvrx_slack_group_sco
 WORK_MAX_RANKS = 4096  # NVRX_WORK_MAX_RANKS: the most ranks a work-group step compares pairwise
 WORK_RANK_WORDS = 8  # {i32 root, u32 size, degree, i32 nearest, u32 nearest_unlike, nearest_either, kernels, sections} per rank
 WORK_JOB_WORDS = 4  # {u32 groups, singletons, largest, ranks_with_data}
+COMOVE_WIDTH = 64  # floats of a unit timeline (buckets B..63 are zero)
+COMOVE_RANK_WORDS = 8  # {i32 root, u32 size, partners, i32 best partner, f32 best s, peak, u32 peak_bucket | 0x100 active, i32 sign}
 
 
 
@@ -118,6 +120,10 @@ SYMBOLS = [
     ("nvrx_row_timeline", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_timeline_rank", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("nvrx_timeline_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_comove_words", c_int, [c_int, c_int]),
+    ("nvrx_comove_unit", c_int, [c_void_p, c_int, c_int, c_uint32, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_comove_pairs", c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p]),
+    ("nvrx_comove_groups", c_int, [c_void_p, c_int, c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p]),
     ("nvrx_robust_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("nvrx_peer_score", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("nvrx_pace_score", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -421,6 +427,19 @@ def work_words(R: int, K: int, S: int) -> int:
     """``nvrx_work_words``: 32-bit words of a work-group block -- signatures | adjacency | partial nearest | ``R`` rank records |
     job record."""
     return work_offsets(R, K, S)[4]
+
+
+def comove_offsets(R: int):
+    """Where the parts of a co-movement block start, in 32-bit words -- ``(rank records, deviations, unit timelines, adjacency,
+    partial partners, size)``; the centre starts at 0 and every part on a 16-byte boundary.  The size is
+    ``nvrx_comove_words(R, B)``."""
+    T = -(-R // 64)
+    rank = 4 * COMOVE_WIDTH
+    dev = rank + 2 * COMOVE_RANK_WORDS * R
+    unit = dev + 2 * COMOVE_WIDTH * R
+    adj = unit + 2 * COMOVE_WIDTH * R
+    part = adj + 4 * R * T
+    return rank, dev, unit, adj, part, part + 4 * R * T
 
 
 def tail_q_ppm(q) -> int:

@@ -374,6 +374,31 @@ class TimelineScores:
         return self._host
 
 
+class ComovementScores:
+    """The co-movement groups of one report (``nvrx_comove_groups`` on the timeline's gathered blocks, behind
+    ``nvrx_timeline_score``), enqueued and not waited for: once the kernels have run, the workspace's co-movement block
+    (include/nvrx_straggler.h) holds the centre, the rank records and the deviations in front of what stays on the device.
+    ``records()`` waits for it and takes the private host copy, as ``TimelineScores.records`` does."""
+
+    __slots__ = ("backend", "d_ptr", "R", "B", "_host", "_lock", "_keep")
+
+    def __init__(self, backend: "HipBackend", buf: torch.Tensor, R: int, B: int):
+        self.backend, self.d_ptr, self.R, self.B = backend, buf.data_ptr(), R, B
+        self._host = None
+        self._lock = threading.Lock()
+        self._keep = buf  # the device buffer lives at least until the copy is taken
+
+    def records(self):
+        """``(center [2, B] f32, rated [2, B] u32, records [2, R, 8] u32, deviations [2, R, B] f32)`` of ALL ranks, family-major
+        (private copies); the first call waits for the kernels."""
+        if self._host is None:
+            with self._lock:
+                if self._host is None:
+                    self._host = self.backend.comovement_copy_out(self)
+                    self.backend = self._keep = None
+        return self._host
+
+
 class _FamilyBuffers:
     """A workspace's device buffers of one row family, and the handle that may still be using them."""
 
@@ -949,6 +974,25 @@ class Workspace:
         if last is not None:
             last.records()
 
+    # ---- co-movement groups (off unless a ReportGenerator asks: nothing is allocated before) ------------------------------
+    _comovement_buf = None   # device: the block of the last co-movement step (its size depends on R alone)
+    _comovement_last = None  # the ComovementScores whose kernels may still be writing _comovement_buf
+
+    def comovement_buffers(self):
+        """The co-movement block of this workspace's R ranks (cold: allocated on first use)."""
+        if self._comovement_buf is None:
+            words = _native.comove_offsets(self.R)[5]
+            with torch.cuda.stream(self._backend.stream):  # (allocated, written and read under the backend's stream)
+                self._comovement_buf = torch.empty(words, dtype=torch.int32, device=self._backend.device)
+        return self._comovement_buf
+
+    def comovement_settle(self) -> None:
+        """Before anything rewrites the co-movement block: the last step's kernels have run and their results are on the host
+        (a ``Report`` still alive keeps them; an unread one costs this one copy)."""
+        last, self._comovement_last = self._comovement_last, None
+        if last is not None:
+            last.records()
+
     def settle_readers(self) -> None:
         """Before a report rewrites this workspace's table: whatever follow-up kernel of the previous report may still be
         reading it -- attribution, tails, robust scores, onsets, periods, episodes, ramps, stalls, the tail profile -- has run and delivered; and so has the
@@ -967,6 +1011,8 @@ class Workspace:
             self.profile_settle()
         if self._timeline_last is not None:
             self.timeline_settle()
+        if self._comovement_last is not None:
+            self.comovement_settle()
         if self._history_last is not None:
             self.history_settle()
         if self._trend_last is not None:
@@ -1523,6 +1569,66 @@ class HipBackend:
                                                       self.stream_handle))
         self.stream.synchronize()
         return out
+
+    def comovement_score(self, ws, table, min_rows: int = 8, amplitude_ppm: int = 10000,
+                         similarity_ppm: int = 800000) -> ComovementScores:
+        """Co-movement groups of ALL ranks from the gathered blocks ``table`` ([R, 2 * 3 * B], the timeline step's, which stay
+        where they are): ``nvrx_comove_groups`` enqueued on the backend's stream behind ``nvrx_timeline_score``.  Nothing is
+        exchanged and nothing is waited for."""
+        B = table.shape[1] // 6
+        ws.comovement_settle()  # (the block is about to be rewritten)
+        buf = ws.comovement_buffers()
+        rc = self.lib.nvrx_comove_groups(table.data_ptr(), ws.R, B, min_rows, amplitude_ppm, similarity_ppm, buf.data_ptr(),
+                                         self._stream_handle)
+        if rc < 0:
+            _native.check(rc)
+        out = ws._comovement_last = ComovementScores(self, buf, ws.R, B)
+        return out
+
+    def comovement_copy_out(self, t: ComovementScores):
+        """The one wait of a report's co-movement groups: a D2H of the block's head -- centre, rank records, deviations -- on
+        the backend's stream, behind the kernels."""
+        rank, dev, unit = _native.comove_offsets(t.R)[:3]
+        host = np.empty(unit, dtype=np.uint32)
+        _native.check(self.lib.nvrx_d2h_sync(host.ctypes.data, t.d_ptr, host.nbytes, self._stream_handle))
+        W, B = _native.COMOVE_WIDTH, t.B
+        center = host[: 2 * W].view(np.float32).reshape(2, W)[:, :B].copy()
+        rated = host[2 * W : rank].reshape(2, W)[:, :B].copy()
+        records = host[rank:dev].reshape(2, t.R, _native.COMOVE_RANK_WORDS).copy()
+        return center, rated, records, host[dev:].view(np.float32).reshape(2, t.R, W)[:, :, :B].copy()
+
+    def _comove_block(self, R: int, launch) -> np.ndarray:
+        """A stateless co-movement entry on a fresh block: ``launch(d_out)`` on the backend's stream -> the block's words."""
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros(_native.comove_offsets(R)[5], dtype=torch.int32, device=self.device)
+            _native.check(launch(out.data_ptr()))
+        self.stream.synchronize()
+        return out.cpu().numpy().view(np.uint32)
+
+    def comove_unit(self, blocks: torch.Tensor, min_rows: int, amplitude_ppm: int):
+        """Stateless centre and unit timelines on a caller tensor ([R, 2, 3, B] f32 blocks) -> ``(center [2, 64] f32, rated
+        [2, 64] u32, records [2, R, 8] u32 (words 5..7), deviations [2, R, 64] f32, unit [2, R, 64] f32)``
+        (``nvrx_comove_unit``)."""
+        R, B = blocks.shape[0], blocks.shape[3]
+        host = self._comove_block(R, lambda d_out: self.lib.nvrx_comove_unit(blocks.data_ptr(), R, B, min_rows, amplitude_ppm,
+                                                                            d_out, self.stream_handle))
+        rank, dev, unit, adj = _native.comove_offsets(R)[:4]
+        W = _native.COMOVE_WIDTH
+        return (host[: 2 * W].view(np.float32).reshape(2, W), host[2 * W : rank].reshape(2, W),
+                host[rank:dev].reshape(2, R, _native.COMOVE_RANK_WORDS), host[dev:unit].view(np.float32).reshape(2, R, W),
+                host[unit:adj].view(np.float32).reshape(2, R, W))
+
+    def comove_pairs(self, x: torch.Tensor, similarity_ppm: int):
+        """Stateless similarity, edges and groups on a caller tensor ([R, 64] f32 unit timelines; a zero row is inactive) ->
+        ``(records [R, 8] u32, adjacency [R, T] u64, partial partners [R, T, 2] u32 {f32 s, i32 partner})``
+        (``nvrx_comove_pairs``)."""
+        R, T = x.shape[0], -(-x.shape[0] // 64)
+        host = self._comove_block(R, lambda d_out: self.lib.nvrx_comove_pairs(x.data_ptr(), R, similarity_ppm, d_out,
+                                                                             self.stream_handle))
+        rank, _, _, adj, part, _ = _native.comove_offsets(R)
+        return (host[rank : rank + _native.COMOVE_RANK_WORDS * R].reshape(R, _native.COMOVE_RANK_WORDS),
+                host[adj : adj + 2 * R * T].view(np.uint64).reshape(R, T), host[part : part + 2 * R * T].reshape(R, T, 2))
 
     def _row_op(self, fam: RowFamily, samples: torch.Tensor, counts: torch.Tensor, param: int,
                 starts: Optional[torch.Tensor]) -> torch.Tensor:

@@ -43,7 +43,9 @@ class FoldedJob:
                  stall_detection: bool = False, stall_min_ratio: float = 1.5, stall_min_z: float = 6.0,
                  stall_min_share: float = 0.01, node_peer_groups: bool = False, peer_attribution: int = 0,
                  tail_profile=None, timeline_scores: bool = False, timeline_buckets: int = 32, timeline_min_rows: int = 8,
-                 timeline_min_effect: float = 0.03, timeline_min_breadth: float = 0.9, timeline_min_buckets: int = 2):
+                 timeline_min_effect: float = 0.03, timeline_min_breadth: float = 0.9, timeline_min_buckets: int = 2,
+                 comovement_groups: bool = False, comovement_min_amplitude: float = 0.01, comovement_min_similarity: float = 0.8,
+                 comovement_min_ranks: int = 2):
         world = dist_utils.get_world_size(pg)
         if total_ranks % world:
             raise ValueError(f"total_ranks {total_ranks} must be a multiple of the world size {world}")

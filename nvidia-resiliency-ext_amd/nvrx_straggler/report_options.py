@@ -195,6 +195,7 @@ GROUPS: Tuple[OptionGroup, ...] = (
     OptionGroup(("tail_profile",)),  # (None and () are off)
     OptionGroup(("timeline_scores", "timeline_buckets", "timeline_min_rows", "timeline_min_effect", "timeline_min_breadth",
                  "timeline_min_buckets")),
+    OptionGroup(("comovement_groups", "comovement_min_amplitude", "comovement_min_similarity", "comovement_min_ranks")),
 )
 
 

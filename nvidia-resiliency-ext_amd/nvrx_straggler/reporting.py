@@ -790,6 +790,62 @@ class _TimelineSource:
         return self._built
 
 
+class _ComovementSource:
+    """What a report keeps of its co-movement groups: the backend's handle (``records()`` waits for the kernels and copies
+    the centre, every rank's record and the deviations out on first use), the table rows ``[lo, hi)`` the report covers, the
+    parameters, and ``rank_to_node`` as the generator had it."""
+
+    __slots__ = ("handle", "lo", "hi", "params", "rank_to_node", "_built")
+
+    def __init__(self, handle, lo: int, hi: int, params: dict, rank_to_node):
+        self.handle, self.lo, self.hi, self.params, self.rank_to_node = handle, lo, hi, params, rank_to_node
+        self._built: Optional[dict] = None
+
+    def build(self) -> dict:
+        if self._built is None:
+            center, rated, records, dev = self.handle.records()
+            B = center.shape[1]
+            amplitude = np.float32(self.params["min_amplitude_ppm"] / 1e6)  # (the kernels' own threshold)
+            r2n = self.rank_to_node
+            ranks: Dict[int, dict] = {r: {} for r in range(self.lo, self.hi)}
+            groups, centers = {}, {}
+            for f, part in enumerate(("gpu", "sections")):
+                rec = records[f]
+                root, size, partners = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64), rec[:, 2].astype(np.int64)
+                best, sign = rec[:, 3].view(np.int32).tolist(), rec[:, 7].view(np.int32).tolist()
+                best_s, peak = rec[:, 4].view(np.float32).tolist(), rec[:, 5].view(np.float32).tolist()
+                word = rec[:, 6].tolist()
+                usable = (rated[f] >= 3) & (center[f] > 0)
+                centers[part] = tuple(float(c) if ok else math.nan for c, ok in zip(center[f], usable))
+                found = {}
+                for g in np.flatnonzero((root == np.arange(len(root))) & (size >= 2)).tolist():
+                    members = np.flatnonzero(root == g)
+                    d = dev[f][members].astype(np.float64)
+                    on = np.abs(d).mean(axis=0) >= amplitude
+                    first, length, b = 0, 0, 0
+                    while b < B:  # the longest run of buckets where the members' mean |d| reaches the amplitude, the earliest among equals
+                        e = b
+                        while e < B and on[e]:
+                            e += 1
+                        if e - b > length:
+                            first, length = b, e - b
+                        b = e + 1
+                    found[g] = {"ranks": members.tolist(), "size": len(members),
+                                "loose": bool((partners[members] + 1 < len(members)).any()),
+                                "nodes": sorted({r2n[r] for r in members.tolist() if r in r2n}),
+                                "began_at": first / B if length else None, "ended_at": (first + length) / B if length else None,
+                                "excess": float(d[:, first:first + length].mean()) if length else 0.0}
+                groups[part] = found
+                for r in ranks:
+                    ranks[r][part] = {"root": int(root[r]), "size": int(size[r]), "partners": int(partners[r]),
+                                      "best_partner": best[r] if best[r] >= 0 else None, "best_similarity": best_s[r],
+                                      "peak": peak[r], "peak_bucket": word[r] & 0xFF, "active": bool(word[r] & 0x100),
+                                      "sign": sign[r]}
+            self._built = {"buckets": B, "params": dict(self.params), "center": centers, "ranks": ranks, "groups": groups}
+            self.handle = None
+        return self._built
+
+
 class _RowGroupFamilySource(_RowFamilySource):
     """What a report keeps of one row family's scores per peer group (``ReportGenerator(row_peer_groups=True)``):
     ``_RowFamilySource``'s, the resolved groups and ``min_peers``.  The handle's ``records()`` delivers the column records
@@ -1619,6 +1675,9 @@ class Report:
         timeline = self.__dict__.get("_timeline")
         if timeline is not None:
             state["_timeline"] = timeline.build() if isinstance(timeline, _TimelineSource) else timeline
+        comovement = self.__dict__.get("_comovement")
+        if comovement is not None:
+            state["_comovement"] = comovement.build() if isinstance(comovement, _ComovementSource) else comovement
         return state
 
     def __setstate__(self, state) -> None:
@@ -1898,6 +1957,54 @@ class Report:
         gpus, sections = runs("gpu"), runs("sections")
         return {"straggler_gpus_relative": self._ids(gpus), "straggler_section_ranks_relative": self._ids(sections),
                 "runs": {"gpus": gpus, "sections": sections}}
+
+    def comovement_groups(self) -> Dict[str, Any]:
+        """Co-movement groups (``ReportGenerator(timeline_scores=True, comovement_groups=True)``; ``{}`` when the report
+        carries none): WHICH ranks ran slow (or fast) at the same times.  Every other score rates a rank, or a node it was
+        told about; a cause above a node -- a PDU, a cooling loop, a rack switch, a shared mount -- moves many ranks a
+        little, each below its own threshold, and the evidence is that they agree with EACH OTHER in time.  Per family (a
+        rank's kernels, its sections) a rank's timeline levels are centred on the job's lower median per bucket (so a stretch
+        the whole job shares cancels), a rank is *active* where its largest deviation reaches ``min_amplitude``, active
+        timelines are scaled to unit length, two active ranks are joined where their similarity (the cosine) reaches
+        ``min_similarity``, and the groups are the connected components, named by their lowest rank.
+
+        ``{"buckets": B, "params": {"min_rows", "min_amplitude", "min_similarity", "min_ranks", ...}, "center": {"gpu": (B
+        levels; NaN where fewer than 3 ranks are rated), "sections": ...}, "ranks": {rank: {"gpu": {...}, "sections": {...}}},
+        "groups": {"gpu": {root: {...}}, "sections": {...}}}``.  A rank's part holds ``root``, ``size``, ``partners`` (ranks it
+        is joined to), ``best_partner`` (the other active rank most like it, joined or not; None without one),
+        ``best_similarity``, ``peak`` (its largest |deviation|), ``peak_bucket``, ``sign`` (+1: slower than the centre there) and
+        ``active``.  A group of two or more holds ``ranks``, ``size``, ``loose`` (some member is not joined to every other: a
+        chain, not a clique), ``nodes`` (from ``rank_to_node`` where the report has it), and ``began_at`` / ``ended_at`` /
+        ``excess``: the longest run of buckets where the members' mean |deviation| reaches ``min_amplitude``, as fractions of
+        the window, and the members' mean deviation over it (positive: slower; None, None and 0.0 without a run).
+        Limits: ranks line up bucket for bucket only in a lockstep job; the centre is the job's typical rank, so if half the
+        job or more moves together the OTHERS read as the group; single linkage can chain (``loose``); there is no history
+        of groups and none per peer group.  Plain dicts, lists, tuples, floats and ints.  The first call waits for the
+        kernels and copies their results; ``generate_report`` does not."""
+        comovement = self.__dict__.get("_comovement")
+        if comovement is None:
+            return {}
+        if isinstance(comovement, _ComovementSource):
+            comovement = self.__dict__["_comovement"] = comovement.build()
+        return _copy_peer(comovement)  # (nested dicts and lists, as the work groups)
+
+    def identify_comoving_stragglers(self, min_ranks: Optional[int] = None) -> Dict[str, Any]:
+        """Ranks that ran SLOWER than the job's centre together: the members of every co-movement group of at least
+        ``min_ranks`` ranks (the generator's ``comovement_min_ranks`` unless told otherwise: 2, a default, not a measurement)
+        whose ``excess`` is positive.  ``{'straggler_gpus_comoving': set[StragglerId], 'straggler_section_ranks_comoving':
+        set[StragglerId], 'groups': {'gpus': {root: [ranks]}, 'sections': {root: [ranks]}}}``.  Empty when the report carries
+        no co-movement groups."""
+        c = self.comovement_groups()
+        least = c["params"]["min_ranks"] if c and min_ranks is None else min_ranks
+
+        def slow(part):
+            return {g: list(v["ranks"]) for g, v in c.get("groups", {}).get(part, {}).items()
+                    if v["size"] >= least and v["excess"] > 0.0}
+
+        gpus, sections = slow("gpu"), slow("sections")
+        return {"straggler_gpus_comoving": self._ids(r for m in gpus.values() for r in m),
+                "straggler_section_ranks_comoving": self._ids(r for m in sections.values() for r in m),
+                "groups": {"gpus": gpus, "sections": sections}}
 
     def robust_scores(self) -> Dict[str, Any]:
         """Robust scores (``ReportGenerator(robust_scores=True)``; ``{}`` when the report carries none).  Every relative score
@@ -2503,6 +2610,7 @@ class ReportGenerator:
     """
 
     timeline_b = 0  # the timeline's buckets; a generator with timeline_scores on holds its own, and timeline_params
+    comovement_params = None  # the co-movement groups' parameters; a generator with comovement_groups on holds its own
 
     def __init__(self, scores_to_compute, gather_on_rank0=True, pg=None, node_name="<notset>",
                  thresholds: Sequence[float] = _backend_mod.DEFAULT_THRESHOLDS, asynchronous: bool = False,
@@ -2528,7 +2636,9 @@ class ReportGenerator:
                  stall_min_z: float = 6.0, stall_min_share: float = 0.01, node_peer_groups: bool = False,
                  peer_attribution: int = 0, tail_profile: Optional[Sequence[float]] = None, timeline_scores: bool = False,
                  timeline_buckets: int = 32, timeline_min_rows: int = 8, timeline_min_effect: float = 0.03,
-                 timeline_min_breadth: float = 0.9, timeline_min_buckets: int = 2) -> None:
+                 timeline_min_breadth: float = 0.9, timeline_min_buckets: int = 2, comovement_groups: bool = False,
+                 comovement_min_amplitude: float = 0.01, comovement_min_similarity: float = 0.8,
+                 comovement_min_ranks: int = 2) -> None:
         self.is_computing_rel_scores = "relative_perf_scores" in scores_to_compute
         self.is_computing_indiv_scores = "individual_perf_scores" in scores_to_compute
         self.gather_on_rank0 = gather_on_rank0
@@ -2852,6 +2962,23 @@ class ReportGenerator:
             opts.needs_backend("timeline_scores", "timeline scores", "timeline_score")
             self.timeline_b = B
             self.timeline_params = {"min_rows": rows, "min_effect": effect, "min_breadth": breadth, "min_buckets": least}
+        # co-movement groups: every ring report also says which ranks ran slow at the same times (Report.comovement_groups,
+        # Report.identify_comoving_stragglers); off (comovement_params is the class' None): no buffer, no launch, no backend
+        # call.  The step runs behind the timeline's score kernel on the blocks that step gathered: no collective.  0.01, 0.8
+        # and 2 ranks are defaults, not measurements.
+        if comovement_groups:
+            amplitude = opts.number("comovement_min_amplitude", comovement_min_amplitude, "a number within (0, 1]", 0.0, 1.0,
+                                    lo_open=True, no_bool=True)
+            similarity = opts.number("comovement_min_similarity", comovement_min_similarity, "a number within (0, 1]", 0.0, 1.0,
+                                     lo_open=True, no_bool=True)
+            least = opts.integer("comovement_min_ranks", comovement_min_ranks, "an integer >= 2", 2)
+            if not self.timeline_b:
+                raise ValueError("comovement_groups needs timeline_scores; timeline_scores is not set")
+            opts.needs_backend("comovement_groups", "co-movement groups", "comovement_score")
+            self.comovement_params = {"min_rows": self.timeline_params["min_rows"], "min_amplitude": amplitude,
+                                      "min_similarity": similarity, "min_ranks": least,
+                                      "min_amplitude_ppm": max(1, int(round(amplitude * 1e6))),
+                                      "min_similarity_ppm": max(1, int(round(similarity * 1e6)))}
         # what names the ring-start snapshot's user where the backend has none: a row family, else the timeline
         self._starts_option = (self._starts_family.option if self._starts_family is not None
                                else "timeline_scores" if self.timeline_b else None)
@@ -3639,6 +3766,17 @@ class ReportGenerator:
         lo, hi = self._covered(ws, local_ranks)
         handle = score(ws, table, lo, hi - lo, p["min_rows"], effect_ppm, breadth_ppm)
         report.__dict__["_timeline"] = _TimelineSource(handle, report.__dict__["_src"].view.ranks, p)
+        c = self.comovement_params
+        if c is not None:  # directly behind the score kernel, on the same blocks: no collective
+            self._comovement_refuse(ws.R)
+            handle = be.comovement_score(ws, table, c["min_rows"], c["min_amplitude_ppm"], c["min_similarity_ppm"])
+            report.__dict__["_comovement"] = _ComovementSource(handle, lo, hi, c, self._shared_rank_to_node())
+
+    def _comovement_refuse(self, R: int) -> None:
+        """The step compares every pair of ranks and takes at most ``NVRX_WORK_MAX_RANKS`` of them, as the work groups."""
+        cap = _backend_mod._native.WORK_MAX_RANKS
+        if R > cap:
+            raise ValueError(f"comovement_groups: the job has {R} logical ranks, co-movement groups are inferred for at most {cap}")
 
     def _gather_step_rows(self, be, send, table):
         """Exchange a ring step's rows behind its local kernel: its one collective, on the backend's stream."""

@@ -461,6 +461,10 @@ class Detector(metaclass=_DeviceSideOnDemand):
         timeline_min_effect: float = 0.03,
         timeline_min_breadth: float = 0.9,
         timeline_min_buckets: int = 2,
+        comovement_groups: Optional[bool] = None,
+        comovement_min_amplitude: float = 0.01,
+        comovement_min_similarity: float = 0.8,
+        comovement_min_ranks: int = 2,
     ):
         """
         Args:
@@ -673,6 +677,18 @@ class Detector(metaclass=_DeviceSideOnDemand):
                 within (0, 1].  0.9 is a default, not a measurement.
             timeline_min_buckets: a rank is named for a run of at least this many consecutive slow buckets (>= 1).  2 is a
                 default, not a measurement.
+            comovement_groups: every report also says WHICH ranks ran slow at the same times (``Report.comovement_groups()``,
+                ``Report.identify_comoving_stragglers()``): a cause above a node -- a PDU, a cooling loop, a rack switch, a
+                shared mount -- moves many ranks a little, each below ``timeline_min_effect``, and the evidence is that they
+                agree with each other in time.  Needs ``timeline_scores``, whose gathered blocks it reads: nothing more is
+                exchanged.  At most 4096 logical ranks.  Ranks line up bucket for bucket only in a lockstep job.  Default:
+                ``NVRX_COMOVEMENT_GROUPS`` ("1"; "0" or unset: off).
+            comovement_min_amplitude: a rank takes part where its level leaves the job's median by at least this share in
+                some bucket, within (0, 1].  0.01 is a default, not a measurement.
+            comovement_min_similarity: two ranks are joined where the cosine of their centred timelines reaches this, within
+                (0, 1].  0.8 is a default, not a measurement.
+            comovement_min_ranks: ``identify_comoving_stragglers`` names groups of at least this many ranks (>= 2).  2 is a
+                default, not a measurement.
             slack_peer_groups: the slack scores take a collective kernel's floor and the typical wait inside each rank's OWN
                 peer group instead of the whole job -- the right reference in a job of pipeline stages, tensor-parallel or
                 expert groups, where waits in collectives legitimately differ per stage and the job-wide rule names the
@@ -807,6 +823,7 @@ class Detector(metaclass=_DeviceSideOnDemand):
         if timeline_scores:
             timeline_buckets = opts.env_number(timeline_buckets, "NVRX_TIMELINE_BUCKETS", int, 32,
                                                "NVRX_TIMELINE_BUCKETS must be an integer within [4, 64], got {value!r}")
+        comovement_groups = opts.env_strict_flag(comovement_groups, "NVRX_COMOVEMENT_GROUPS")
         # (report_options.GROUPS: the options that are off are left out, so the generator is built exactly as before they existed)
         cls.reporter = ReportGenerator(scores_to_compute=cls.scores_to_compute, gather_on_rank0=gather_on_rank0,
                                        node_name=node_name or socket.gethostname(), **opts.forwarded(locals()))
